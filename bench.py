@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — the reference's headline metric on MI355X: Mray/s (primary + secondary rays) of the path-tracing
-hot path on the Cornell box at 2048x2048, depth 50 (BASELINE.json configs[3]; it fits one GPU), plus the dominant
-kernel's roofline block (VALU lane-slot fraction: the binding resource; physical HBM traffic; SURVEY 8(d)'s algorithmic bytes,
-labelled) and the CPU oracle timed on this box's host cores (all cores and one thread).
+hot path on the Cornell box at 2048x2048, depth 50 (BASELINE.json configs[3]; it fits one GPU).  With --full it also reports
+the dominant kernel's roofline block (VALU lane-slot fraction: the binding resource; physical HBM traffic; SURVEY 8(d)'s
+algorithmic bytes, labelled), the CPU oracle timed on the host's cores (all cores and one thread) with a pixel-for-pixel
+parity check against it, and short runs of the other BASELINE scenes.  A plain run sets up, warms up, times the steps and
+prints the headline line, nothing else.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1 without WORLD_SIZE: starts the line below as a child and relays it)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+  python bench.py ... --full                             (the roofline, CPU baseline, parity and other-scene blocks too)
+  python bench.py ... --dump-outputs DIR                 (after the timed steps: DIR/frame.npy, DIR/counters.npy; see dump_outputs)
 
 A "step" is one pass of --spp-per-step samples per pixel over the whole image, continuing the running f32 sums that
 stay resident in HBM (the full config's 4096 spp is 16 such steps of 256).  With N > 1 the image's 16-row bands are
@@ -333,6 +337,33 @@ def short_run(trt, torch, dev, scene_name, spheres, W, H, S, steps, warmup, dept
     return out
 
 
+DUMP_BYTES_MAX = 64_000_000     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, frame, counters, max_bytes=DUMP_BYTES_MAX):
+    """What the timed path hands its caller after the last timed step, as .npy files under `out_dir`:
+    frame.npy - the f32 running sums [H, W, 3] of the current frame up to the last step (every sample weighted 1 / 4096, imager.rs:50);
+    counters.npy - the device counters of the timed steps (all ranks summed), int64 as float64 (exact below 2**53).
+    A frame larger than the budget is replaced by a fixed sample of its pixels (seed 0): frame.npy [n, 3] and
+    frame_pixels.npy [n] (float64 flat pixel indices, row-major, ascending).  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(frame.detach().cpu().numpy(), dtype=np.float32)
+    arrays = {"counters": np.asarray(counters.detach().cpu().numpy(), dtype=np.float64)}
+    budget = max_bytes - arrays["counters"].nbytes
+    if img.nbytes <= budget:
+        arrays["frame"] = img
+    else:
+        pixels = img.reshape(-1, img.shape[-1])
+        n = budget // (pixels.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+        arrays["frame"] = pixels[idx]
+        arrays["frame_pixels"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -405,11 +436,18 @@ def main():
     ap.add_argument("--scene", default="cornell", choices=["cornell", "random_spheres", "sphere_grid", "sphere_field"])
     ap.add_argument("--spheres", type=int, default=0, help="sphere_grid (default 100000) / sphere_field (default 4000000): number of spheres")
     ap.add_argument("--tuning", default="", help="trt_tuning fields for the timed renders, e.g. dual_walk=1,stream_waves_per_simd=6 (scheduling only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline block (kernel timing, untimed counting passes), the CPU baseline with its "
+                         "parity check and the other BASELINE scenes; a plain run does none of it")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the cpu_baseline leg; 0 = measurement only: no CPU leg, no parity block, no other scenes (what the tools/ scripts use)")
-    ap.add_argument("--no-roofline-pass", action="store_true", help="skip the untimed counter pass")
-    ap.add_argument("--no-other-scenes", action="store_true", help="skip the short runs of the other two BASELINE scenes after the timed region")
+                    help="with --full: budget of the cpu_baseline leg; 0 = no CPU leg, no parity block, no other scenes")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="with --full: skip the untimed counter pass")
+    ap.add_argument("--no-other-scenes", action="store_true", help="with --full: skip the short runs of the other BASELINE scenes after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (frame sums, counters) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -459,7 +497,6 @@ def main():
     renderer = trt.Renderer(total_spp, 1, args.depth, False, desc["background"], seed=1, backend=backend)
     if args.tuning:
         renderer.tuning = {k: int(v) for k, v in (kv.split("=") for kv in args.tuning.split(","))}
-    kernel_name = trt.lib.trt_dominant_kernel(scene._h, C.byref(cam.pod), C.byref(renderer.params())).decode()      # what a kernel trace of a step shows
 
     lay = tiles.band_layout(H, world_size, rank)
     band = dict(band_rows=lay["band_rows"], band_stride=lay["band_stride"], band_offset=lay["band_offset"],
@@ -501,19 +538,24 @@ def main():
         gather(acc)
     barrier()
     ctr.zero_()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # per-step and per-launch HIP events only feed the roofline block: a plain run times the steps alone
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     barrier()
-    trt._lib.check(trt.lib.trt_kernel_timing_begin())   # HIP events around every dominant-kernel launch, on the launch stream
+    if args.full:
+        trt._lib.check(trt.lib.trt_kernel_timing_begin())   # HIP events around every dominant-kernel launch, on the launch stream
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record(stream)
+        if ev:
+            ev[k][0].record(stream)
         step(args.warmup + k)
-        ev[k][1].record(stream)
+        if ev:
+            ev[k][1].record(stream)
     frame = gather(acc)
     barrier()
     elapsed = time.perf_counter() - t0
     k_ms, k_n = C.c_double(0.0), C.c_uint32(0)
-    trt._lib.check(trt.lib.trt_kernel_timing_end(C.byref(k_ms), C.byref(k_n)))
+    if args.full:
+        trt._lib.check(trt.lib.trt_kernel_timing_end(C.byref(k_ms), C.byref(k_n)))
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     counts = ctr.clone()
     if world_size > 1:
@@ -522,133 +564,139 @@ def main():
     elapsed = float(t.item())
     total_rays = int(counts[1].item())
     total_samples = int(counts[0].item())
-    launch_ms = [a.elapsed_time(b) for a, b in ev]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame, counts)
 
-    # ---- roofline block of the dominant kernel, per rank ----
-    # Live part: the kernel's average launch time from HIP events on its own launch stream (trt_kernel_timing_*), this rank's
-    # rays per launch.  Stored part: VALU instruction and HBM byte counts PER RAY from the rocprofv3 PMC passes kept under
-    # profiles/ (tools/pmc_bench.sh; counters need their own runs), scaled by this rank's rays - so the block exists at any N.
-    # Nothing here can end the run: what does not add up goes into roofline["warnings"].
-    warnings = []
-    launches_per_step = 1
-    if args.backend == "streamed":
-        chunk = trt.lib.trt_streamed_chunk_spp(W, max(rows_local, 1))
-        launches_per_step = (S + chunk - 1) // chunk
-    if rows_local == 0:
-        launches_per_step = 0
-    n_launch = int(k_n.value)
-    if n_launch != launches_per_step * args.steps:
-        warnings.append(f"timed {n_launch} dominant-kernel launches, expected {launches_per_step * args.steps}")
-    avg_ms = k_ms.value / n_launch if n_launch else None
-    my_rays = int(ctr[1].item())
-    rays_per_launch = my_rays / n_launch if n_launch else 0.0
-    scene_tag = args.scene + (str(args.spheres) if args.spheres else "")
-    key = f"{scene_tag}_{W}x{H}_d{args.depth}_spp{S}_{args.backend}" + ("_" + args.tuning.replace(",", "_").replace("=", "") if args.tuning else "")
-    roofline = {"bound": "valu", "kernel": kernel_name, "achieved": None, "peak": round(VALU_PEAK_GINST * 64.0 / 1e3, 2),
-                "unit": "T f32 lane-instructions/s (VALU wave-instructions x active lanes)", "frac": None, "traffic": None,
-                "frac_is": "lane-slot fraction: VALU lane-instructions per second / (1024 SIMDs x 2.4 GHz / 2 cycles x 64 lanes); "
-                           "instruction counts per ray from a stored PMC profile of the same kernel sources, launch time measured live",
-                "avg_launch_ms": round(avg_ms, 4) if avg_ms else None, "launches_per_step": launches_per_step, "launches_timed": n_launch,
-                "rays_per_launch": int(rays_per_launch), "step_ms_by_events": round(sum(launch_ms) / len(launch_ms), 4), "rank": rank}
-    roofline.update(valu_roofline(key, avg_ms, rays_per_launch, warnings, single_gpu=world_size == 1))
-    if not args.no_roofline_pass and rows_local > 0:
-        # untimed: the same K launches with the counting kernel variant -> exact algorithmic bytes of those launches
-        sctr = torch.zeros(16, dtype=torch.int64, device=dev)
-        scratch = torch.zeros_like(acc)
-        for k in range(args.steps):
-            step(args.warmup + k, stats=True, counters=sctr, target=scratch)
-        torch.cuda.synchronize()
-        c = dict(zip(("samples", "rays", "node_tests", "sphere_tests", "quad_plane_tests", "quad_inside_tests", "shades"),
-                     [int(v) for v in sctr[:7].tolist()]))
-        if c["rays"] != my_rays:
-            warnings.append(f"counting variant traced {c['rays']} rays, the timed launches {my_rays}")
-        roofline["rays_per_sample"] = round(c["rays"] / max(c["samples"], 1), 3)
-        if avg_ms and n_launch:
-            bytes_per_launch = (algorithmic_bytes(c, 0) + 12 * rows_local * W * args.steps) / n_launch
-            gbps = bytes_per_launch / (avg_ms * 1e-3) / 1e9
-            roofline["algorithmic"] = {
-                "bytes_per_launch": int(bytes_per_launch), "GBps": round(gbps, 2), "ratio_to_hbm_peak": round(gbps / HBM_PEAK_GBPS, 5),
-                "bytes_per_ray": round(algorithmic_bytes(c, 0) / max(c["rays"], 1), 2),
-                "note": "SURVEY 8(d): bytes the reference-order traversal would read per launch / launch time.  NOT a physical "
-                        "fraction and not a roofline for this path: the scene is served from SGPRs / LDS / L2, so it exceeds 1 "
-                        "(DESIGN.md section 8); the physical HBM traffic is `traffic`"}
-    # ---- useful-work fraction: what the path's arithmetic NEEDS against the chip's lane-slots (frac counts every issued lane-instruction) ----
-    table, table_stale = isa_event_costs()
-    if not args.no_roofline_pass and rows_local > 0 and avg_ms and n_launch and table is not None and not table_stale:
-        # one untimed step with the counting variant on the CULLING tree (collect_stats = 2): the box tests the production walk performs
-        uctr = torch.zeros(16, dtype=torch.int64, device=dev)
-        uscratch = torch.zeros_like(acc)
-        step(args.warmup, stats=2, counters=uctr, target=uscratch)
-        torch.cuda.synchronize()
-        names = ("samples", "rays", "node_tests", "sphere_tests", "quad_plane_tests", "quad_inside_tests", "shades")
-        uc = dict(zip(names, [int(v) for v in uctr[:7].tolist()]))
-        uc.update(zip(("shade_lambertian", "shade_metal", "shade_dielectric", "shade_light"), [int(v) for v in uctr[12:16].tolist()]))
-        plan = renderer.launch_plan(cam, scene) if hasattr(renderer, "launch_plan") else None
-        walk = plan["walk"] if plan else 0
-        info = scene.info()
-        useful, parts, box_cost = useful_lane_instructions(uc, walk, info["num_quads"], info["num_spheres"], table)
-        per_ray = useful / max(uc["rays"], 1)
-        useful_rate = per_ray * rays_per_launch / (avg_ms * 1e-3) / 1e12             # T lane-instructions / s
-        roofline["useful_frac"] = round(useful_rate / (VALU_PEAK_GINST * 64.0 / 1e3), 4)
-        roofline["useful"] = {"lane_instructions_per_ray": round(per_ray, 1), "achieved_T_per_s": round(useful_rate, 2),
-                              "per_ray_by_event": {k: round(v / max(uc["rays"], 1), 1) for k, v in parts.items()},
-                              "box_tests_per_ray": round(uc["node_tests"] / max(uc["rays"], 1), 2), "valu_per_box_test": box_cost,
-                              "events_from": "one untimed step of the counting kernel on the culling tree (collect_stats = 2)",
-                              "costs_from": "profiles/isa_event_costs.json (tools/isa_event_costs.py: gfx950 ISA of the product's device functions)",
-                              "is": "lane-instructions the path's arithmetic needs (events x per-event VALU count) per second / peak lane-slots; "
-                                    "frac counts every lane-instruction ISSUED instead"}
-        if roofline.get("valu_wave_insts_per_ray") and roofline.get("mean_active_lanes"):
-            issued = roofline["valu_wave_insts_per_ray"] * roofline["mean_active_lanes"]
-            roofline["useful"]["issued_lane_instructions_per_ray"] = round(issued, 1)
-            roofline["useful"]["useful_over_issued"] = round(per_ray / issued, 3)
-    elif table is None or table_stale:
-        warnings.append("profiles/isa_event_costs.json is missing or was made from other kernel sources: no useful_frac (python tools/isa_event_costs.py)")
-    roofline["warnings"] = warnings
-    # per-rank summary on rank 0 (N > 1): launch time and rays of every rank
     per_rank = None
-    if world_size > 1:
-        mine = torch.tensor([avg_ms or 0.0, float(n_launch), float(my_rays), float(rows_local), roofline["frac"] or 0.0], dtype=torch.float64, device=dev)
-        table = [torch.zeros_like(mine) for _ in range(world_size)]
-        if rehearsal:
-            host = [t.cpu() for t in table]
-            dist.all_gather(host, mine.cpu())
-            table = host
-        else:
-            dist.all_gather(table, mine)
-        per_rank = [{"rank": r, "avg_launch_ms": round(float(t[0]), 4), "launches": int(t[1]), "rays": int(t[2]), "image_rows": int(t[3]),
-                     "frac": round(float(t[4]), 4) if float(t[4]) > 0 else None} for r, t in enumerate(table)]
+    if args.full:
+        kernel_name = trt.lib.trt_dominant_kernel(scene._h, C.byref(cam.pod), C.byref(renderer.params())).decode()      # what a kernel trace of a step shows
+        launch_ms = [a.elapsed_time(b) for a, b in ev]
 
-    # ---- outside the timed region, rank 0 at N = 1 only: the CPU oracle on this box's host cores, a pixel-for-pixel parity check of the
-    # GPU path against the frame that leg renders, and short runs of the other two BASELINE scenes.  None of it can end the run.
-    cpu = parity = None
-    other = []
-    if rank == 0 and world_size == 1 and args.cpu_seconds > 0:
-        cpu, cpu_frame, cpu_spp, cpu_rays = cpu_baseline(trt, desc, args.depth, args.cpu_seconds)
-        try:
-            import numpy as np
-            pctr = torch.zeros(16, dtype=torch.int64, device=dev)
-            pacc = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-            renderer.render_device(cam, scene, pacc.data_ptr(), stream.cuda_stream, pctr.data_ptr(), sample_begin=0, sample_end=cpu_spp, accumulate=0)
+        # ---- roofline block of the dominant kernel, per rank ----
+        # Live part: the kernel's average launch time from HIP events on its own launch stream (trt_kernel_timing_*), this rank's
+        # rays per launch.  Stored part: VALU instruction and HBM byte counts PER RAY from the rocprofv3 PMC passes kept under
+        # profiles/ (tools/pmc_bench.sh; counters need their own runs), scaled by this rank's rays - so the block exists at any N.
+        # Nothing here can end the run: what does not add up goes into roofline["warnings"].
+        warnings = []
+        launches_per_step = 1
+        if args.backend == "streamed":
+            chunk = trt.lib.trt_streamed_chunk_spp(W, max(rows_local, 1))
+            launches_per_step = (S + chunk - 1) // chunk
+        if rows_local == 0:
+            launches_per_step = 0
+        n_launch = int(k_n.value)
+        if n_launch != launches_per_step * args.steps:
+            warnings.append(f"timed {n_launch} dominant-kernel launches, expected {launches_per_step * args.steps}")
+        avg_ms = k_ms.value / n_launch if n_launch else None
+        my_rays = int(ctr[1].item())
+        rays_per_launch = my_rays / n_launch if n_launch else 0.0
+        scene_tag = args.scene + (str(args.spheres) if args.spheres else "")
+        key = f"{scene_tag}_{W}x{H}_d{args.depth}_spp{S}_{args.backend}" + ("_" + args.tuning.replace(",", "_").replace("=", "") if args.tuning else "")
+        roofline = {"bound": "valu", "kernel": kernel_name, "achieved": None, "peak": round(VALU_PEAK_GINST * 64.0 / 1e3, 2),
+                    "unit": "T f32 lane-instructions/s (VALU wave-instructions x active lanes)", "frac": None, "traffic": None,
+                    "frac_is": "lane-slot fraction: VALU lane-instructions per second / (1024 SIMDs x 2.4 GHz / 2 cycles x 64 lanes); "
+                               "instruction counts per ray from a stored PMC profile of the same kernel sources, launch time measured live",
+                    "avg_launch_ms": round(avg_ms, 4) if avg_ms else None, "launches_per_step": launches_per_step, "launches_timed": n_launch,
+                    "rays_per_launch": int(rays_per_launch), "step_ms_by_events": round(sum(launch_ms) / len(launch_ms), 4), "rank": rank}
+        roofline.update(valu_roofline(key, avg_ms, rays_per_launch, warnings, single_gpu=world_size == 1))
+        if not args.no_roofline_pass and rows_local > 0:
+            # untimed: the same K launches with the counting kernel variant -> exact algorithmic bytes of those launches
+            sctr = torch.zeros(16, dtype=torch.int64, device=dev)
+            scratch = torch.zeros_like(acc)
+            for k in range(args.steps):
+                step(args.warmup + k, stats=True, counters=sctr, target=scratch)
             torch.cuda.synchronize()
-            gpu_frame = pacc.cpu().numpy()
-            same = bool(np.array_equal(gpu_frame.view(np.uint32), np.ascontiguousarray(cpu_frame, np.float32).view(np.uint32)))
-            with np.errstate(invalid="ignore"):
-                delta = float(np.nanmax(np.abs(gpu_frame - cpu_frame)))
-            parity = {"against": "the oracle frame of the cpu_baseline leg (oracle/rt_oracle.c, the CPU restatement of cpu.rs:39-65 / imager.rs:50)",
-                      "workload": f"{args.scene} {W}x{H}, depth {args.depth}, samples [0, {cpu_spp}) of 4096, seed 1, whole frame",
-                      "spp": cpu_spp, "pixels": W * H, "bit_identical": same, "max_abs_delta": delta, "tolerance": 1e-3,
-                      "rays_gpu": int(pctr[1].item()), "rays_oracle": int(cpu_rays), "ray_counts_equal": int(pctr[1].item()) == int(cpu_rays)}
-            del pacc, gpu_frame
-        except Exception as e:                                   # noqa: BLE001 - the bench line must still be printed
-            parity = {"error": repr(e)}
-    if rank == 0 and world_size == 1 and args.cpu_seconds > 0 and not args.no_other_scenes:
-        for name, ospheres, ow, oh, ospp, osteps, owarm in OTHER_SCENES:
-            if name == args.scene and (ow, oh) == (W, H):
-                continue
+            c = dict(zip(("samples", "rays", "node_tests", "sphere_tests", "quad_plane_tests", "quad_inside_tests", "shades"),
+                         [int(v) for v in sctr[:7].tolist()]))
+            if c["rays"] != my_rays:
+                warnings.append(f"counting variant traced {c['rays']} rays, the timed launches {my_rays}")
+            roofline["rays_per_sample"] = round(c["rays"] / max(c["samples"], 1), 3)
+            if avg_ms and n_launch:
+                bytes_per_launch = (algorithmic_bytes(c, 0) + 12 * rows_local * W * args.steps) / n_launch
+                gbps = bytes_per_launch / (avg_ms * 1e-3) / 1e9
+                roofline["algorithmic"] = {
+                    "bytes_per_launch": int(bytes_per_launch), "GBps": round(gbps, 2), "ratio_to_hbm_peak": round(gbps / HBM_PEAK_GBPS, 5),
+                    "bytes_per_ray": round(algorithmic_bytes(c, 0) / max(c["rays"], 1), 2),
+                    "note": "SURVEY 8(d): bytes the reference-order traversal would read per launch / launch time.  NOT a physical "
+                            "fraction and not a roofline for this path: the scene is served from SGPRs / LDS / L2, so it exceeds 1 "
+                            "(DESIGN.md section 8); the physical HBM traffic is `traffic`"}
+        # ---- useful-work fraction: what the path's arithmetic NEEDS against the chip's lane-slots (frac counts every issued lane-instruction) ----
+        table, table_stale = isa_event_costs()
+        if not args.no_roofline_pass and rows_local > 0 and avg_ms and n_launch and table is not None and not table_stale:
+            # one untimed step with the counting variant on the CULLING tree (collect_stats = 2): the box tests the production walk performs
+            uctr = torch.zeros(16, dtype=torch.int64, device=dev)
+            uscratch = torch.zeros_like(acc)
+            step(args.warmup, stats=2, counters=uctr, target=uscratch)
+            torch.cuda.synchronize()
+            names = ("samples", "rays", "node_tests", "sphere_tests", "quad_plane_tests", "quad_inside_tests", "shades")
+            uc = dict(zip(names, [int(v) for v in uctr[:7].tolist()]))
+            uc.update(zip(("shade_lambertian", "shade_metal", "shade_dielectric", "shade_light"), [int(v) for v in uctr[12:16].tolist()]))
+            plan = renderer.launch_plan(cam, scene) if hasattr(renderer, "launch_plan") else None
+            walk = plan["walk"] if plan else 0
+            info = scene.info()
+            useful, parts, box_cost = useful_lane_instructions(uc, walk, info["num_quads"], info["num_spheres"], table)
+            per_ray = useful / max(uc["rays"], 1)
+            useful_rate = per_ray * rays_per_launch / (avg_ms * 1e-3) / 1e12             # T lane-instructions / s
+            roofline["useful_frac"] = round(useful_rate / (VALU_PEAK_GINST * 64.0 / 1e3), 4)
+            roofline["useful"] = {"lane_instructions_per_ray": round(per_ray, 1), "achieved_T_per_s": round(useful_rate, 2),
+                                  "per_ray_by_event": {k: round(v / max(uc["rays"], 1), 1) for k, v in parts.items()},
+                                  "box_tests_per_ray": round(uc["node_tests"] / max(uc["rays"], 1), 2), "valu_per_box_test": box_cost,
+                                  "events_from": "one untimed step of the counting kernel on the culling tree (collect_stats = 2)",
+                                  "costs_from": "profiles/isa_event_costs.json (tools/isa_event_costs.py: gfx950 ISA of the product's device functions)",
+                                  "is": "lane-instructions the path's arithmetic needs (events x per-event VALU count) per second / peak lane-slots; "
+                                        "frac counts every lane-instruction ISSUED instead"}
+            if roofline.get("valu_wave_insts_per_ray") and roofline.get("mean_active_lanes"):
+                issued = roofline["valu_wave_insts_per_ray"] * roofline["mean_active_lanes"]
+                roofline["useful"]["issued_lane_instructions_per_ray"] = round(issued, 1)
+                roofline["useful"]["useful_over_issued"] = round(per_ray / issued, 3)
+        elif table is None or table_stale:
+            warnings.append("profiles/isa_event_costs.json is missing or was made from other kernel sources: no useful_frac (python tools/isa_event_costs.py)")
+        roofline["warnings"] = warnings
+        # per-rank summary on rank 0 (N > 1): launch time and rays of every rank
+        per_rank = None
+        if world_size > 1:
+            mine = torch.tensor([avg_ms or 0.0, float(n_launch), float(my_rays), float(rows_local), roofline["frac"] or 0.0], dtype=torch.float64, device=dev)
+            table = [torch.zeros_like(mine) for _ in range(world_size)]
+            if rehearsal:
+                host = [t.cpu() for t in table]
+                dist.all_gather(host, mine.cpu())
+                table = host
+            else:
+                dist.all_gather(table, mine)
+            per_rank = [{"rank": r, "avg_launch_ms": round(float(t[0]), 4), "launches": int(t[1]), "rays": int(t[2]), "image_rows": int(t[3]),
+                         "frac": round(float(t[4]), 4) if float(t[4]) > 0 else None} for r, t in enumerate(table)]
+
+        # ---- outside the timed region, rank 0 at N = 1 only: the CPU oracle on this box's host cores, a pixel-for-pixel parity check of the
+        # GPU path against the frame that leg renders, and short runs of the other two BASELINE scenes.  None of it can end the run.
+        cpu = parity = None
+        other = []
+        if rank == 0 and world_size == 1 and args.cpu_seconds > 0:
+            cpu, cpu_frame, cpu_spp, cpu_rays = cpu_baseline(trt, desc, args.depth, args.cpu_seconds)
             try:
-                other.append(short_run(trt, torch, dev, name, ospheres, ow, oh, ospp, osteps, owarm, args.depth, args.backend, backend))
-            except Exception as e:                               # noqa: BLE001
-                other.append({"workload": name, "error": repr(e)})
+                import numpy as np
+                pctr = torch.zeros(16, dtype=torch.int64, device=dev)
+                pacc = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+                renderer.render_device(cam, scene, pacc.data_ptr(), stream.cuda_stream, pctr.data_ptr(), sample_begin=0, sample_end=cpu_spp, accumulate=0)
+                torch.cuda.synchronize()
+                gpu_frame = pacc.cpu().numpy()
+                same = bool(np.array_equal(gpu_frame.view(np.uint32), np.ascontiguousarray(cpu_frame, np.float32).view(np.uint32)))
+                with np.errstate(invalid="ignore"):
+                    delta = float(np.nanmax(np.abs(gpu_frame - cpu_frame)))
+                parity = {"against": "the oracle frame of the cpu_baseline leg (oracle/rt_oracle.c, the CPU restatement of cpu.rs:39-65 / imager.rs:50)",
+                          "workload": f"{args.scene} {W}x{H}, depth {args.depth}, samples [0, {cpu_spp}) of 4096, seed 1, whole frame",
+                          "spp": cpu_spp, "pixels": W * H, "bit_identical": same, "max_abs_delta": delta, "tolerance": 1e-3,
+                          "rays_gpu": int(pctr[1].item()), "rays_oracle": int(cpu_rays), "ray_counts_equal": int(pctr[1].item()) == int(cpu_rays)}
+                del pacc, gpu_frame
+            except Exception as e:                                   # noqa: BLE001 - the bench line must still be printed
+                parity = {"error": repr(e)}
+        if rank == 0 and world_size == 1 and args.cpu_seconds > 0 and not args.no_other_scenes:
+            for name, ospheres, ow, oh, ospp, osteps, owarm in OTHER_SCENES:
+                if name == args.scene and (ow, oh) == (W, H):
+                    continue
+                try:
+                    other.append(short_run(trt, torch, dev, name, ospheres, ow, oh, ospp, osteps, owarm, args.depth, args.backend, backend))
+                except Exception as e:                               # noqa: BLE001
+                    other.append({"workload": name, "error": repr(e)})
 
     if rank == 0:
         if frame is not None:
@@ -668,8 +716,9 @@ def main():
                        "collective_backend": (dist.get_backend() if world_size > 1 else None),
                        "launched_by": "bench.py itself (child torch.distributed.run)" if os.environ.get("TRT_BENCH_SELF_LAUNCHED") == "1"
                                       else ("external launcher" if world_size > 1 else "plain")},
-            "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "other_scenes": other,
         }
+        if args.full:
+            out.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity, "other_scenes": other})
         if per_rank is not None:
             out["roofline_per_rank"] = per_rank
         print(json.dumps(out), flush=True)

@@ -150,3 +150,34 @@ def test_useful_lane_instructions_adds_up(bench):
     assert abs(total - sum(parts.values())) < 1e-6 and parts["ray_setup"] == 70 * ev["ray_setup"]
     _, parts_s, box_s = bench.useful_lane_instructions(dict(c, sphere_tests=100, quad_plane_tests=0), 3, 0, 1000, table)
     assert box_s == loops["box_step_compact"] and parts_s["primitive_tests"] == 100 * ev["sphere_test"]
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(bench, tmp_path):
+    """--dump-outputs: float32 frame + float64 counters; a frame over the byte budget becomes the same seeded pixel sample every time."""
+    import numpy as np
+    import torch
+    frame = torch.arange(40 * 30 * 3, dtype=torch.float32).reshape(40, 30, 3)
+    counters = torch.arange(16, dtype=torch.int64) * (1 << 40)
+    assert bench.dump_outputs(str(tmp_path / "all"), frame, counters) == ["counters", "frame"]
+    assert np.array_equal(np.load(tmp_path / "all" / "frame.npy"), frame.numpy())
+    c = np.load(tmp_path / "all" / "counters.npy")
+    assert c.dtype == np.float64 and np.array_equal(c.astype(np.int64), counters.numpy())
+    budget = 4000
+    for name in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / name), frame, counters, max_bytes=budget) == ["counters", "frame", "frame_pixels"]
+        assert sum(os.path.getsize(tmp_path / name / f) - 128 for f in os.listdir(tmp_path / name)) <= budget    # 128: .npy header
+    for f in ("frame.npy", "frame_pixels.npy", "counters.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    px, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixels.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(px) == len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, frame.numpy().reshape(-1, 3)[idx.astype(np.int64)])
+
+
+def test_bench_options_full_and_dump_outputs_are_there():
+    """A plain run times the headline only; everything else is behind --full.  --steps below 1 is refused before any GPU work."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr

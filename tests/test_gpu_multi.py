@@ -181,7 +181,8 @@ def _bench_line(cmd, env, root):
     return json.loads(lines[-1])
 
 
-BENCH_N2_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "512", "--height", "500", "--spp-per-step", "64", "--cpu-seconds", "0"]
+BENCH_N2_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "512", "--height", "500", "--spp-per-step", "64", "--full",
+                 "--cpu-seconds", "0"]                               # --full: the roofline block and its per-rank summary are checked below
 
 
 def _check_n2_line(d):

@@ -5,7 +5,7 @@
 out=gpurun_out/r5/lds_compact; mkdir -p $out
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $out/suite.log 2>&1 || { echo "SUITE FAILED"; tail -40 $out/suite.log; exit 1; }
 tail -2 $out/suite.log
-run() { timeout -k 10 400 python3 bench.py --cpu-seconds 0 --no-roofline-pass "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f Mray/s %7.2f ms %s' % (d['value'], d['roofline']['avg_launch_ms'], d['config'].get('launch_plan', {}).get('walk', '')))"; }
+run() { timeout -k 10 400 python3 bench.py --full --cpu-seconds 0 --no-roofline-pass "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f Mray/s %7.2f ms %s' % (d['value'], d['roofline']['avg_launch_ms'], d['config'].get('launch_plan', {}).get('walk', '')))"; }
 R="--scene random_spheres --width 1920 --height 1080 --spp-per-step 256 --steps 3 --warmup 1"
 {
 for rep in 1 2 3; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The backends on the three BASELINE scenes, one box, one call (run on the GPU box).
 out=gpurun_out/matrix.jsonl; : > $out
-run() { timeout -k 10 400 python bench.py --cpu-seconds 0 "$@" 2>/dev/null | tail -1 >> $out; }
+run() { timeout -k 10 400 python bench.py --full --cpu-seconds 0 "$@" 2>/dev/null | tail -1 >> $out; }
 run --scene cornell --backend streamed
 run --scene cornell --backend megakernel
 run --scene cornell --spp-per-step 64 --backend wavefront

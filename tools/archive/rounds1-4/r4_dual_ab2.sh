@@ -7,7 +7,7 @@ for w in 4 6; do
   [ $rc -ne 0 ] && { tail -40 $out/dual2_parity_w$w.log; exit $rc; }
 done
 G="--scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 --steps 3 --warmup 1 --cpu-seconds 0 --no-roofline-pass"
-run() { timeout -k 10 300 python3 bench.py $G 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
+run() { timeout -k 10 300 python3 bench.py --full $G 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
 {
 echo "baseline (one path per lane, 8 waves):"; run; run
 for w in 4 5 6 7 8; do for st in 4 16; do

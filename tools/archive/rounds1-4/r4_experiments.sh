@@ -8,7 +8,7 @@ timeout -k 10 300 python3 tools/leaf_phase_budget.py > $out/leaf_phase_budget.tx
 TRT_LIB_PATH=$PWD/build/libtinyrt_ldssplit.so timeout -k 10 600 python3 -m pytest tests -x -q -m gpu -k "not full_baseline and not full_sample_count and not cfg5 and not c_example and not bench" > $out/ldssplit_parity.log 2>&1; rc=$?
 echo "ldssplit parity rc=$rc $(tail -1 $out/ldssplit_parity.log)"; [ $rc -ne 0 ] && { tail -40 $out/ldssplit_parity.log; exit $rc; }
 R="--scene random_spheres --width 1920 --height 1080 --spp-per-step 256 --steps 4 --warmup 1 --cpu-seconds 0 --no-roofline-pass"
-run() { TRT_LIB_PATH=$1 timeout -k 10 300 python3 bench.py $R 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f Mray/s %8.3f ms' % (d['value'], d['roofline']['avg_launch_ms']))"; }
+run() { TRT_LIB_PATH=$1 timeout -k 10 300 python3 bench.py --full $R 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f Mray/s %8.3f ms' % (d['value'], d['roofline']['avg_launch_ms']))"; }
 { for rep in 1 2 3; do echo "HEAD (32-byte nodes in LDS): $(run $PWD/tiny-raytracer_amd/libtinyrt.so)"; echo "two planes of 16-byte halves: $(run $PWD/build/libtinyrt_ldssplit.so)"; done; } | tee $out/ldssplit_ab.txt
 for v in head ldssplit; do
   lib=$PWD/tiny-raytracer_amd/libtinyrt.so; [ $v = ldssplit ] && lib=$PWD/build/libtinyrt_ldssplit.so

@@ -3,11 +3,11 @@
 # under rocprofv3 --kernel-trace --stats, and the two other scenes' own bench lines.
 export TMPDIR=/tmp
 out=gpurun_out/r4; mkdir -p $out
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r04_driver_command_bench.json 2> $out/r04_driver_command_bench.err; echo "driver command rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_driver -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r04_driver_command_bench_under_rocprof.json 2> $out/trace_driver.err || { tail -3 $out/trace_driver.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r04_driver_command_bench.json 2> $out/r04_driver_command_bench.err; echo "driver command rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_driver -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r04_driver_command_bench_under_rocprof.json 2> $out/trace_driver.err || { tail -3 $out/trace_driver.err; exit 1; }
 cp $out/trace_driver/*/*_kernel_stats.csv $out/r04_driver_command_kernel_stats.csv
-timeout -k 10 300 python3 bench.py --scene random_spheres --width 1920 --height 1080 --steps 4 --warmup 1 --cpu-seconds 0 > $out/r04_spheres1080_bench_line.json 2>/dev/null
-timeout -k 10 300 python3 bench.py --scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 --steps 4 --warmup 1 --cpu-seconds 0 > $out/r04_grid100k_bench_line.json 2>/dev/null
+timeout -k 10 300 python3 bench.py --full --scene random_spheres --width 1920 --height 1080 --steps 4 --warmup 1 --cpu-seconds 0 > $out/r04_spheres1080_bench_line.json 2>/dev/null
+timeout -k 10 300 python3 bench.py --full --scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 --steps 4 --warmup 1 --cpu-seconds 0 > $out/r04_grid100k_bench_line.json 2>/dev/null
 python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r4/r04_driver_command_bench.json").read().strip().splitlines()[-1])

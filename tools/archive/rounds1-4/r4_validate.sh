@@ -4,7 +4,7 @@
 out=gpurun_out/r4; mkdir -p $out
 timeout -k 10 1100 python3 -X faulthandler -m pytest tests -x -q -m gpu > $out/gputests_abi3.log 2>&1; rc=$?
 echo "pytest rc=$rc $(tail -1 $out/gputests_abi3.log)"; [ $rc -ne 0 ] && { tail -60 $out/gputests_abi3.log; exit $rc; }
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_abi3.json 2> $out/bench_driver_abi3.err; rc=$?
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_abi3.json 2> $out/bench_driver_abi3.err; rc=$?
 echo "bench rc=$rc"; python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r4/bench_driver_abi3.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ out=gpurun_out/r5/dualmix; mkdir -p $out
 L=$PWD/build/libtinyrt_dualmix.so
 TRT_LIB_PATH=$L TRT_DUAL_WALK=1 TRT_STREAM_MINW=6 timeout -k 10 600 python3 -m pytest tests -x -q -m gpu -k "cfg5 or global_memory or fuzz or fused_slab" > $out/parity.log 2>&1 || { echo "PARITY FAILED"; tail -30 $out/parity.log; exit 1; }
 tail -1 $out/parity.log
-run() { TRT_LIB_PATH=$L timeout -k 10 400 python3 bench.py --cpu-seconds 0 --no-roofline-pass "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f %s' % (d['value'], d['roofline']['kernel'][5:]))"; }
+run() { TRT_LIB_PATH=$L timeout -k 10 400 python3 bench.py --full --cpu-seconds 0 --no-roofline-pass "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f %s' % (d['value'], d['roofline']['kernel'][5:]))"; }
 G="--scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 --steps 3 --warmup 1"
 F1="--scene sphere_field --spheres 1000000 --width 3840 --height 2160 --spp-per-step 4 --steps 3 --warmup 1"
 F4="--scene sphere_field --spheres 4000000 --width 3840 --height 2160 --spp-per-step 4 --steps 3 --warmup 1"

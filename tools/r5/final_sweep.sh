@@ -5,7 +5,7 @@ out=gpurun_out/r5/final_sweep; mkdir -p $out
 C="--steps 3 --warmup 1 --cpu-seconds 0 --no-roofline-pass"
 G="--scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 $C"
 F="--scene sphere_field --spheres 4000000 --width 3840 --height 2160 --spp-per-step 4 $C"
-run() { timeout -k 10 300 python3 bench.py "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
+run() { timeout -k 10 300 python3 bench.py --full "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
 {
 echo "== 100 k spheres (one path per lane, 7 waves)"
 echo "default: $(run $G)"

@@ -3,7 +3,7 @@
 # (rounds 2-4 tuned them with ~70 whole-tree walks per launch stalling waves at random).  gpurun -- bash tools/r5/grid_sweep.sh
 out=gpurun_out/r5/grid_sweep; mkdir -p $out
 G="--scene sphere_grid --width 3840 --height 2160 --spp-per-step 16 --steps 3 --warmup 1 --cpu-seconds 0 --no-roofline-pass"
-run() { timeout -k 10 300 python3 bench.py $G "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
+run() { timeout -k 10 300 python3 bench.py --full $G "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%8.1f Mray/s %8.2f ms  %s' % (d['value'], d['roofline']['avg_launch_ms'], d['roofline']['kernel']))"; }
 {
 echo "default (one path, 8 waves, 3 slots, 8 stragglers): $(run)"
 echo "default again: $(run)"
