@@ -235,6 +235,7 @@ extern "C" {
     pub fn trt_scene_create(w: *const trt_world, out: *mut *mut trt_scene) -> c_int;
     pub fn trt_scene_options_default(out: *mut trt_scene_options);
     pub fn trt_scene_create_ex(w: *const trt_world, options: *const trt_scene_options, out: *mut *mut trt_scene) -> c_int;
+    pub fn trt_scene_create_on_device(w: *const trt_world, options: *const trt_scene_options, out: *mut *mut trt_scene) -> c_int;
     pub fn trt_tuning_default(out: *mut trt_tuning);
     pub fn trt_scene_destroy(s: *mut trt_scene);
     pub fn trt_scene_trim(s: *mut trt_scene) -> c_int;
@@ -242,6 +243,7 @@ extern "C" {
     pub fn trt_scene_get_nodes(s: *const trt_scene, bbox6: *mut f32, prim: *mut i32, skip: *mut i32, cap: u32) -> c_int;
     pub fn trt_scene_get_cull_nodes(s: *const trt_scene, bbox6: *mut f32, prim: *mut i32, skip: *mut i32, cap: u32) -> c_int;
     pub fn trt_scene_get_compact_nodes(s: *const trt_scene, words4: *mut u32, cap: u32) -> c_int;
+    pub fn trt_scene_get_packed(s: *const trt_scene, bytes: *mut u8, cap: u32) -> c_int;
 
     pub fn trt_camera_init(out: *mut trt_camera, focus_distance: f32, defocus_angle_deg: f32, position: trt_vec3,
                            look_at: trt_vec3, up: trt_vec3, vertical_fov_deg: f32, width: u32, height: u32) -> c_int;

@@ -36,7 +36,8 @@ extern "C" {
                              *              trt_scene_options + trt_scene_create_ex; trt_stats.gather_per_band
                              * 4 (round 5): + trt_world_add_spheres; trt_scene_options.top_nodes is ignored (the LDS cache of a large scene's upper
                              *              tree levels is gone: measured slower in every form); d_counters[12..15] = shades by material kind.
-                             *              No struct changed size or moved a field. */
+                             *              No struct changed size or moved a field.
+ *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -103,6 +104,11 @@ typedef struct {
 } trt_scene_options;
 void trt_scene_options_default(trt_scene_options *out);
 int trt_scene_create_ex(const trt_world *w, const trt_scene_options *options, trt_scene **out);
+/* Same scene as trt_scene_create_ex(w, options, out), compiled on the calling thread's current device
+ * (trt_set_device).  The packed scene, node dumps, info and launch plans are identical, byte for byte;
+ * the scene is already resident on that device.  TRT_ERR_NO_DEVICE without a gfx950 device, TRT_ERR_OOM
+ * if device scratch cannot be had (no silent fall-back to the host compiler). */
+int trt_scene_create_on_device(const trt_world *w, const trt_scene_options *options, trt_scene **out);
 /* Must not run while another host thread is inside a render call on this scene; renders enqueued with trt_render_device
  * that still run on the device are waited for. */
 void trt_scene_destroy(trt_scene *s);
@@ -135,6 +141,9 @@ int trt_scene_get_cull_nodes(const trt_scene *s, float *bbox6, int32_t *prim, in
  * inner node (the device copy keeps it as a byte offset, index x 16), or 0x80000000 | leaf sequence number.  Returns
  * TRT_ERR_NOT_FOUND if the scene has no such array. */
 int trt_scene_get_compact_nodes(const trt_scene *s, uint32_t *words4, uint32_t cap);
+/* Copies the packed scene (trt_scene_info.device_bytes bytes) as it is uploaded to a device.  TRT_ERR_INVALID_ARG if cap
+ * (bytes) is smaller. */
+int trt_scene_get_packed(const trt_scene *s, uint8_t *bytes, uint32_t cap);
 
 /* ---- Camera (camera.rs:4-14, 17-56) ---- */
 typedef struct {

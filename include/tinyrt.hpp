@@ -102,6 +102,7 @@ public:
         return options_;
     }
     int num_geometries() const { return trt_world_num_geometries(w_); }
+    const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).
     void trim() { if (scene_) check(trt_scene_trim(scene_)); }
 
@@ -111,6 +112,20 @@ private:
     trt_scene* scene_ = nullptr;
     trt_scene_options options_{};
     bool has_options_ = false;
+};
+
+// A scene compiled on the current device (trt_scene_create_on_device): the same bytes as World::get_bvh(), already resident there.
+// Owns its handle; render it through the C ABI (scene()).
+class DeviceScene {
+public:
+    explicit DeviceScene(const World& w, const trt_scene_options* options = nullptr) { check(trt_scene_create_on_device(w.handle(), options, &s_)); }
+    ~DeviceScene() { if (s_) trt_scene_destroy(s_); }
+    DeviceScene(const DeviceScene&) = delete;
+    DeviceScene& operator=(const DeviceScene&) = delete;
+    trt_scene* scene() const { return s_; }
+
+private:
+    trt_scene* s_ = nullptr;
 };
 
 class Camera {

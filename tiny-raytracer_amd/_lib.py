@@ -122,6 +122,7 @@ SIGNATURES = {
     "trt_scene_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "trt_scene_options_default": (None, [C.POINTER(SceneOptions)]),
     "trt_scene_create_ex": (C.c_int, [C.c_void_p, C.POINTER(SceneOptions), C.POINTER(C.c_void_p)]),
+    "trt_scene_create_on_device": (C.c_int, [C.c_void_p, C.POINTER(SceneOptions), C.POINTER(C.c_void_p)]),
     "trt_tuning_default": (None, [C.POINTER(Tuning)]),
     "trt_scene_destroy": (None, [C.c_void_p]),
     "trt_scene_trim": (C.c_int, [C.c_void_p]),
@@ -129,6 +130,7 @@ SIGNATURES = {
     "trt_scene_get_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "trt_scene_get_cull_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "trt_scene_get_compact_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "trt_scene_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "trt_camera_init": (C.c_int, [C.POINTER(CameraPOD), C.c_float, C.c_float, Vec3, Vec3, Vec3, C.c_float,
                                   C.c_uint32, C.c_uint32]),
     "trt_render": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_void_p, C.POINTER(Stats)]),

@@ -80,12 +80,14 @@ def tuning(**over):
 class Scene:
     """World::get_bvh(): the reference-order BVH, packed for the GPU (uploaded on first render)."""
 
-    def __init__(self, world, **options):
+    def __init__(self, world, on_device=False, **options):
         """options: fields of tinyrt.h trt_scene_options (cull_prune, flat_walk, compact_nodes, top_nodes, scratch_cap_bytes) - placement
-        only: whatever they are, the scene renders the same frames."""
+        only: whatever they are, the scene renders the same frames.  on_device: compile it on the current device
+        (trt_scene_create_on_device): the same bytes, already resident there."""
         self._h = C.c_void_p()
         opt = scene_options(**options)
-        check(lib.trt_scene_create_ex(world._h, C.byref(opt), C.byref(self._h)))
+        create = lib.trt_scene_create_on_device if on_device else lib.trt_scene_create_ex
+        check(create(world._h, C.byref(opt), C.byref(self._h)))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -112,6 +114,13 @@ class Scene:
         """The culling tree the kernels walk: same leaves in the same order, re-clustered inner nodes."""
         return self._dump(lib.trt_scene_get_cull_nodes, self.info()["num_cull_nodes"])
 
+
+    def packed(self):
+        """The packed scene as uploaded to a device: uint8[device_bytes]."""
+        n = self.info()["device_bytes"]
+        out = np.zeros(n, np.uint8)
+        check(lib.trt_scene_get_packed(self._h, out.ctypes.data, n))
+        return out
 
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
@@ -180,10 +189,10 @@ class World:
     def num_geometries(self):
         return lib.trt_world_num_geometries(self._h)
 
-    def get_bvh(self, **options):
-        """World::get_bvh (world.rs:43-45).  `options`: see Scene; a scene compiled with options is not cached."""
-        if options:
-            return Scene(self, **options)
+    def get_bvh(self, on_device=False, **options):
+        """World::get_bvh (world.rs:43-45).  `options`: see Scene; a scene compiled with options, or on the device, is not cached."""
+        if options or on_device:
+            return Scene(self, on_device=on_device, **options)
         if self._scene is None:
             self._scene = Scene(self, **self._scene_options)
         return self._scene

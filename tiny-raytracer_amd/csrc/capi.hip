@@ -35,6 +35,7 @@
 
 #include "kernels.h"
 #include "scene.h"
+#include "scene_adopt.h"
 
 using namespace trt;
 
@@ -586,6 +587,29 @@ void counters_to_stats(const unsigned long long* c, trt_stats* st) {
 
 }  // namespace
 
+// The device scene compiler's view of this layer (scene_adopt.h)
+namespace trt {
+int scene_options_check(const trt_scene_options& opt) {
+    if (!(opt.cull_prune > 0.0f && opt.cull_prune <= 1.0f)) return fail(TRT_ERR_INVALID_ARG, "cull_prune must be in (0, 1]");
+    return TRT_OK;
+}
+trt_scene_options scene_options_or_defaults(const trt_scene_options* options) { return options ? *options : defaults().scene; }
+int scene_fail(int code, const std::string& msg) { return fail(code, msg); }
+const World& world_of(const trt_world* w) { return w->w; }
+trt_scene* scene_adopt(SceneHost&& host, const trt_scene_options& opt, int device, void* d_blob) {
+    try {
+        trt_scene* s = new trt_scene();
+        s->host = std::move(host);
+        s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
+        if (d_blob) s->dev[device].blob = static_cast<float4*>(d_blob);      // the first render on `device` does not upload again
+        return s;
+    } catch (const std::bad_alloc&) {
+        fail(TRT_ERR_OOM, "out of memory");
+        return nullptr;
+    }
+}
+}  // namespace trt
+
 extern "C" {
 
 uint32_t trt_abi_version(void) { return TRT_ABI_VERSION; }
@@ -682,8 +706,8 @@ void trt_tuning_default(trt_tuning* out) { if (out) *out = defaults().tuning; }
 int trt_scene_create_ex(const trt_world* w, const trt_scene_options* options, trt_scene** out) {
     if (!w || !out) return fail(TRT_ERR_INVALID_ARG, "null argument");
     try {
-        const trt_scene_options opt = options ? *options : defaults().scene;
-        if (!(opt.cull_prune > 0.0f && opt.cull_prune <= 1.0f)) return fail(TRT_ERR_INVALID_ARG, "cull_prune must be in (0, 1]");
+        const trt_scene_options opt = scene_options_or_defaults(options);
+        if (scene_options_check(opt) != TRT_OK) return TRT_ERR_INVALID_ARG;
         trt_scene* s = new trt_scene();
         std::string msg;
         if (!compile_scene(w->w, opt, s->host, msg)) { delete s; return fail(TRT_ERR_INVALID_ARG, msg); }
@@ -773,6 +797,13 @@ int trt_scene_get_compact_nodes(const trt_scene* s, uint32_t* words4, uint32_t c
     memcpy(words4, s->host.blob.data() + 16u * (size_t)L.off_compact, 16u * (size_t)L.n_cull_nodes);
     for (uint32_t i = 0; i < L.n_cull_nodes; i++)                       // stored as byte offsets (the walk's cursor); reported as node indices
         if (!(words4[4u * (size_t)i + 3u] & 0x80000000u)) words4[4u * (size_t)i + 3u] >>= 4;
+    return TRT_OK;
+}
+int trt_scene_get_packed(const trt_scene* s, uint8_t* bytes, uint32_t cap) {
+    if (!s || !bytes) return fail(TRT_ERR_INVALID_ARG, "null argument");
+    const uint32_t n = s->host.layout.blob_bytes;
+    if (cap < n) return fail(TRT_ERR_INVALID_ARG, "cap is smaller than the packed scene (trt_scene_info.device_bytes)");
+    memcpy(bytes, s->host.blob.data(), n);
     return TRT_OK;
 }
 

@@ -106,6 +106,11 @@ struct SceneHost {
 // Builds the reference's BVH over `w`, derives the culling tree and packs both.  Returns false (with msg) on an empty world.
 // `opt`: trt_scene_options (tinyrt.h) - placement only, every value packs a scene that renders the same frames.
 bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out, std::string& msg);
+// The packed layout from the counts (shared by compile_scene and the device compiler); false (with msg) if it exceeds 4 GiB.
+bool scene_layout(const World& w, const trt_scene_options& opt, uint32_t ns, uint32_t nq, uint32_t nn, uint32_t nc, bool all_finite,
+                  SceneLayout& L, std::string& msg);
+// SceneHost::max_depth of the reference tree over n primitives (its shape depends on n alone).
+uint32_t reference_max_depth(uint32_t n);
 // The built-in defaults (cull_prune 0.5, flat_walk / compact_nodes automatic, no top-level cache, 32 GiB idle scratch).
 trt_scene_options scene_options_builtin();
 

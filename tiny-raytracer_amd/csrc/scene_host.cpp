@@ -3,6 +3,7 @@
 // -ffp-contract=off so the f32 values it precomputes (boxes, quad planes, camera basis) are the
 // ones the reference's constructors produce.
 #include "scene.h"
+#include "scene_common.h"
 #include "trt_pow.h"
 
 #include <math.h>
@@ -43,18 +44,10 @@ Box box_union(Box a, Box b) { return Box{hmin(a.lo, b.lo), hmax(a.hi, b.hi)}; } 
 
 // AABB::longest_axis (aabb.rs:63-78): ties go to the later axis.
 int box_longest_axis(const Box& b) {
-    float sx = b.hi.x - b.lo.x, sy = b.hi.y - b.lo.y, sz = b.hi.z - b.lo.z;
-    if (sx > sy) return sx > sz ? 0 : 2;
-    return sy > sz ? 1 : 2;
+    const float lo[3] = {b.lo.x, b.lo.y, b.lo.z}, hi[3] = {b.hi.x, b.hi.y, b.hi.z};
+    return box_longest_axis6(lo, hi);
 }
 inline float axis_of(H3 v, int axis) { return axis == 0 ? v.x : (axis == 1 ? v.y : v.z); }
-
-// f32::total_cmp as an integer key (aabb.rs:80-82)
-inline int32_t total_order_key(float f) {
-    int32_t bits;
-    memcpy(&bits, &f, 4);
-    return bits ^ (int32_t)((uint32_t)(bits >> 31) >> 1);
-}
 
 inline float bitsf(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
@@ -134,7 +127,7 @@ struct Builder {
                 uint32_t* in = in_small;
                 if (n > kSmall) { keyed_big.resize(n); in_big.resize(n); keyed = keyed_big.data(); in = in_big.data(); }
                 for (size_t i = 0; i < n; i++) {
-                    const uint32_t k = (uint32_t)total_order_key(axis_of(prim_box[objs[i]].lo, axis)) ^ 0x80000000u;    // signed order -> unsigned order
+                    const uint32_t k = total_order_key_u32(axis_of(prim_box[objs[i]].lo, axis));    // signed order -> unsigned order
                     keyed[i] = (uint64_t)k << 32 | (uint64_t)i;
                     in[i] = objs[i];
                 }
@@ -161,15 +154,11 @@ inline unsigned host_threads() {
     return hc == 0 ? 1u : (hc > 16u ? 16u : hc);
 }
 
-inline bool tame(float v) { return fabsf(v) < 1e30f; }
 inline bool tame3(H3 v) { return tame(v.x) && tame(v.y) && tame(v.z); }
 
 inline double surface_area(const Box& b) {
-    double dx = (double)b.hi.x - b.lo.x, dy = (double)b.hi.y - b.lo.y, dz = (double)b.hi.z - b.lo.z;
-    if (!(dx > 0)) dx = 0;
-    if (!(dy > 0)) dy = 0;
-    if (!(dz > 0)) dz = 0;
-    return 2.0 * (dx * dy + dy * dz + dz * dx);
+    const float lo[3] = {b.lo.x, b.lo.y, b.lo.z}, hi[3] = {b.hi.x, b.hi.y, b.hi.z};
+    return surface_area6(lo, hi);
 }
 
 // Culling tree: a second hierarchy over the reference tree's LEAF SEQUENCE (scene.h explains why any such
@@ -177,51 +166,6 @@ inline double surface_area(const Box& b) {
 // SA(left)*n_left + SA(right)*n_right is smallest; an inner node whose box is at least `kPrune` of its nearest
 // emitted ancestor's is not emitted at all (its children hang directly off that ancestor), since a ray that
 // passed the ancestor almost surely passes it too.  Boxes are exact f32 unions of leaf boxes.
-// f32 -> f16 bits rounded toward -inf (up = false) or +inf (up = true): the nearest-even conversion, stepped by one
-// f16 if it landed on the wrong side.  |x| beyond the f16 range becomes +-inf or +-65504, whichever is conservative.
-float f16_bits_to_f32(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
-    uint32_t out;
-    if (e == 0u) {
-        if (m == 0u) out = sign;
-        else {                                              // subnormal: m * 2^-24
-            float v = (float)m * 5.9604644775390625e-08f;
-            uint32_t b; memcpy(&b, &v, 4); out = b | sign;
-        }
-    } else if (e == 31u) out = sign | 0x7F800000u | (m << 13);
-    else out = sign | ((e + 112u) << 23) | (m << 13);
-    float f; memcpy(&f, &out, 4); return f;
-}
-uint16_t f32_to_f16_nearest(float x) {
-    uint32_t b; memcpy(&b, &x, 4);
-    const uint32_t sign = (b >> 16) & 0x8000u;
-    const uint32_t a = b & 0x7FFFFFFFu;
-    if (a >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (a > 0x7F800000u ? 0x200u : 0u));
-    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);            // >= 65520 rounds to inf
-    if (a < 0x33000001u) return (uint16_t)sign;                           // <= 2^-25 rounds to zero
-    int32_t e = (int32_t)(a >> 23) - 127;
-    uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
-    uint32_t shift = e < -14 ? (uint32_t)(13 + (-14 - e)) : 13u;          // subnormal results lose more bits
-    uint32_t half = m >> shift, rem = m & ((1u << shift) - 1u), mid = 1u << (shift - 1u);
-    if (rem > mid || (rem == mid && (half & 1u))) half++;
-    uint32_t he = e < -14 ? 0u : (uint32_t)(e + 15);
-    uint32_t out = e < -14 ? half : ((he << 10) + (half - 0x400u));       // a mantissa carry rolls into the exponent
-    return (uint16_t)(sign | out);
-}
-uint16_t f32_to_f16_dir(float x, bool up) {
-    if (x != x) return up ? 0x7C00u : 0xFC00u;                            // NaN: the conservative infinity
-    uint16_t h = f32_to_f16_nearest(x);
-    const float back = f16_bits_to_f32(h);
-    if (up ? back >= x : back <= x) return h;
-    // step one f16 toward the wanted side
-    if (up) {
-        if (h & 0x8000u) return (h & 0x7FFFu) == 0u ? (uint16_t)0x0001u : (uint16_t)(h - 1u);   // negative: smaller magnitude
-        return (uint16_t)(h + 1u);                                                           // positive: larger magnitude (0x7BFF -> inf)
-    }
-    if (h & 0x8000u) return (uint16_t)(h + 1u);
-    return (h & 0x7FFFu) == 0u ? (uint16_t)0x8001u : (uint16_t)(h - 1u);
-}
-
 struct CullBuilder {
     double kPrune;                           // trt_scene_options.cull_prune: 0.5 measured best on MI355X (round 3, profiles/r03_defaults_sweep.txt: random-spheres
                                              // 0.4-0.5 beat 0.7 by 3 %, the 100 k-sphere scene is flat from 0.3 to 0.7); any value gives the same hits
@@ -358,6 +302,62 @@ trt_scene_options scene_options_builtin() {
     return o;
 }
 
+// The packed scene's layout from the counts (compile_scene and the device compiler share it).  Returns false (with msg) if the
+// scene would not fit the layout's 32-bit offsets.  compact_origin_limit is left to the caller (it needs the culling root).
+bool scene_layout(const World& w, const trt_scene_options& opt, uint32_t ns, uint32_t nq, uint32_t nn, uint32_t nc, bool all_finite,
+                  SceneLayout& L, std::string& msg) {
+    const uint32_t nm = (uint32_t)w.materials.size();
+    L.n_nodes = nn; L.n_cull_nodes = nc; L.n_spheres = ns; L.n_quads = nq; L.n_materials = nm;
+    L.off_sphere = 2 * nc;
+    L.off_quad = L.off_sphere + ns;
+    L.off_material = L.off_quad + 5 * nq;
+    uint32_t n_f4 = L.off_material + nm;
+    L.off_sphere_mat = n_f4 * 4;
+    L.off_material_kind = L.off_sphere_mat + ns;
+    uint32_t n_u32 = L.off_material_kind + nm;
+    L.hot_bytes = ((n_u32 * 4u) + 15u) & ~15u;
+    L.off_ref_nodes = L.hot_bytes / 16u;
+    L.n_leaves = ns + nq;                                                      // one primitive per leaf
+    L.off_leaf_list = L.off_ref_nodes + 2u * nn;
+    L.blob_bytes = L.hot_bytes + 32u * nn + 32u * (L.n_leaves + kLeafListPad);     // the leaf list is followed by kLeafListPad copies of its last entry
+    L.off_compact = 0u;
+    bool want_compact = L.hot_bytes > kLdsSceneMaxBytes;                      // scenes walked from global memory
+    if (opt.compact_nodes >= 0) want_compact = opt.compact_nodes != 0;                        // tuning / tests; same frames either way
+    if (nc >= (1u << 27)) want_compact = false;                                               // (its links are byte offsets below 2^31)
+    if (want_compact) {
+        L.off_compact = L.blob_bytes / 16u;
+        L.blob_bytes += 16u * nc;
+    }
+    {   // every offset and size of the layout is 32 bits wide: refuse scenes that do not fit instead of wrapping around
+        const uint64_t prims = (uint64_t)ns + 5ull * nq + nm;
+        const uint64_t total = 16ull * (2ull * nc + prims) + 4ull * ((uint64_t)ns + nm) + 16ull                 // hot part
+                               + 32ull * nn + 32ull * ((uint64_t)L.n_leaves + kLeafListPad)                          // reference tree, leaf list
+                               + (want_compact ? 16ull * nc : 0ull);
+        if (total > 0xFFFFFFFFull) { msg = "scene too large: the packed scene would exceed 4 GiB"; return false; }
+    }
+    L.all_finite = all_finite ? 1u : 0u;
+    // cpu.rs:49-50 adds `attenuation * emission` at EVERY hit, emission = 0 for everything but lights: the sum stays +0 as long as
+    // the attenuation is finite (x * 0 = +-0, 0 + +-0 = +0), which |albedo| <= 1 guarantees (NaN fails the comparison)
+    bool lazy = true;
+    for (const trt_material& m : w.materials) {
+        if (m.kind == TRT_LIGHT) continue;
+        lazy = lazy && fabsf(m.albedo.x) <= 1.0f && fabsf(m.albedo.y) <= 1.0f && fabsf(m.albedo.z) <= 1.0f;
+    }
+    L.lazy_color = lazy ? 1u : 0u;
+    L.flat_walk = L.n_leaves <= kFlatWalkMaxLeaves ? 1u : 0u;
+    if (opt.flat_walk >= 0) L.flat_walk = opt.flat_walk ? 1u : 0u;                           // tuning / tests; same frames either way
+    L.reserved0 = 0u;
+    L.compact_origin_limit[0] = L.compact_origin_limit[1] = L.compact_origin_limit[2] = 0.0f;
+    return true;
+}
+
+uint32_t reference_max_depth(uint32_t n) {
+    // Builder::build: a leaf at depth 1 (the root), the two leaves of a 2-object node one deeper; the halves' sizes differ by at
+    // most one and the depth grows with the size, so the larger (right) half decides
+    if (n <= 2) return n;
+    return 1u + reference_max_depth(n - n / 2);
+}
+
 bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out, std::string& msg) {
     const size_t ng = w.geometries.size();
     if (ng == 0) { msg = "world has no geometry"; return false; }
@@ -420,47 +420,9 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
     std::vector<int32_t> cull_prim_geo(nc);
     for (uint32_t i = 0; i < nc; i++) cull_prim_geo[i] = cb.node_leaf[i] >= 0 ? leaf_geo[(size_t)cb.node_leaf[i]] : -1;
 
-    const uint32_t ns = (uint32_t)spheres.size(), nq = (uint32_t)q0.size(), nm = (uint32_t)w.materials.size();
+    const uint32_t ns = (uint32_t)spheres.size(), nq = (uint32_t)q0.size();
     SceneLayout& L = out.layout;
-    L.n_nodes = nn; L.n_cull_nodes = nc; L.n_spheres = ns; L.n_quads = nq; L.n_materials = nm;
-    L.off_sphere = 2 * nc;
-    L.off_quad = L.off_sphere + ns;
-    L.off_material = L.off_quad + 5 * nq;
-    uint32_t n_f4 = L.off_material + nm;
-    L.off_sphere_mat = n_f4 * 4;
-    L.off_material_kind = L.off_sphere_mat + ns;
-    uint32_t n_u32 = L.off_material_kind + nm;
-    L.hot_bytes = ((n_u32 * 4u) + 15u) & ~15u;
-    L.off_ref_nodes = L.hot_bytes / 16u;
-    L.n_leaves = (uint32_t)leaf_box.size();
-    L.off_leaf_list = L.off_ref_nodes + 2u * nn;
-    L.blob_bytes = L.hot_bytes + 32u * nn + 32u * (L.n_leaves + kLeafListPad);     // the leaf list is followed by kLeafListPad copies of its last entry
-    L.off_compact = 0u;
-    bool want_compact = L.hot_bytes > kLdsSceneMaxBytes;                      // scenes walked from global memory
-    if (opt.compact_nodes >= 0) want_compact = opt.compact_nodes != 0;                        // tuning / tests; same frames either way
-    if (nc >= (1u << 27)) want_compact = false;                                               // (its links are byte offsets below 2^31)
-    if (want_compact) {
-        L.off_compact = L.blob_bytes / 16u;
-        L.blob_bytes += 16u * nc;
-    }
-    {   // every offset and size of the layout is 32 bits wide: refuse scenes that do not fit instead of wrapping around
-        const uint64_t prims = (uint64_t)ns + 5ull * nq + nm;
-        const uint64_t total = 16ull * (2ull * nc + prims) + 4ull * ((uint64_t)ns + nm) + 16ull                 // hot part
-                               + 32ull * nn + 32ull * ((uint64_t)L.n_leaves + kLeafListPad)                          // reference tree, leaf list
-                               + (want_compact ? 16ull * nc : 0ull);
-        if (total > 0xFFFFFFFFull) { msg = "scene too large: the packed scene would exceed 4 GiB"; return false; }
-    }
-    L.all_finite = all_finite ? 1u : 0u;
-    // cpu.rs:49-50 adds `attenuation * emission` at EVERY hit, emission = 0 for everything but lights: the sum stays +0 as long as
-    // the attenuation is finite (x * 0 = +-0, 0 + +-0 = +0), which |albedo| <= 1 guarantees (NaN fails the comparison)
-    bool lazy = true;
-    for (const trt_material& m : w.materials) {
-        if (m.kind == TRT_LIGHT) continue;
-        lazy = lazy && fabsf(m.albedo.x) <= 1.0f && fabsf(m.albedo.y) <= 1.0f && fabsf(m.albedo.z) <= 1.0f;
-    }
-    L.lazy_color = lazy ? 1u : 0u;
-    L.flat_walk = L.n_leaves <= kFlatWalkMaxLeaves ? 1u : 0u;
-    if (opt.flat_walk >= 0) L.flat_walk = opt.flat_walk ? 1u : 0u;                           // tuning / tests; same frames either way
+    if (!scene_layout(w, opt, ns, nq, nn, nc, all_finite, L, msg)) return false;
 
     out.blob.assign(L.blob_bytes, 0);
     F4* f4 = reinterpret_cast<F4*>(out.blob.data());
@@ -489,7 +451,6 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
     std::vector<uint32_t> cull_place(nc), ref_place(nn);                  // both trees are packed in pre-order
     for (uint32_t i = 0; i < nc; i++) cull_place[i] = i;
     for (uint32_t i = 0; i < nn; i++) ref_place[i] = i;
-    L.reserved0 = 0u;
     pack_nodes(f4, cb.node_box, cull_prim_geo, cb.node_skip, cull_place);
     pack_nodes(f4 + L.off_ref_nodes, b.node_box, b.node_prim, b.node_skip, ref_place);
     {   // leaf list: the leaves alone, in walk order
@@ -506,7 +467,6 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
             dst[0] = last[0]; dst[1] = last[1];
         }
     }
-    L.compact_origin_limit[0] = L.compact_origin_limit[1] = L.compact_origin_limit[2] = 0.0f;
     if (L.off_compact) {   // compact culling tree: f16 boxes rounded outward (any superset box keeps the hits: DESIGN.md 4.1), pre-order
         // Round 5: the hand-written walk over these nodes evaluates a plane's distance as fma(x, 1/d, -fl(o * 1/d)) - one instruction instead of the
         // reference's fl(fl(x - o) * 1/d), two - which is NOT the reference's value: it may err by u (|x| + 2.001 |o|) |1/d|, u = 2^-24, and the
@@ -518,14 +478,8 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
         float eps[3];
         {
             const Box& root = cb.node_box[0];
-            const float b3[3] = {fmaxf(fabsf(root.lo.x), fabsf(root.hi.x)), fmaxf(fabsf(root.lo.y), fabsf(root.hi.y)), fmaxf(fabsf(root.lo.z), fabsf(root.hi.z))};
-            for (int a = 0; a < 3; a++) {
-                const bool ok = all_finite && b3[a] <= 1.0e12f;                           // (products with 1/d <= 2^60 and 4 B stay far from overflow)
-                eps[a] = ok ? b3[a] * 1.9073486328125e-06f : 0.0f;                       // 2^-19 B
-                L.compact_origin_limit[a] = ok ? 4.0f * b3[a] : 0.0f;
-            }
-            if (!(L.compact_origin_limit[0] > 0.0f && L.compact_origin_limit[1] > 0.0f && L.compact_origin_limit[2] > 0.0f))
-                L.compact_origin_limit[0] = L.compact_origin_limit[1] = L.compact_origin_limit[2] = 0.0f;
+            const float lo[3] = {root.lo.x, root.lo.y, root.lo.z}, hi[3] = {root.hi.x, root.hi.y, root.hi.z};
+            compact_eps_rule(lo, hi, all_finite, eps, L.compact_origin_limit);
         }
         uint32_t* c = u32 + 4u * (size_t)L.off_compact;
         std::vector<int32_t> leaf_seq(nc, -1);
@@ -535,13 +489,9 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
         }
         for (uint32_t i = 0; i < nc; i++) {
             const Box& bx = cb.node_box[i];
-            const uint32_t lx = f32_to_f16_dir(bx.lo.x - eps[0], false), ly = f32_to_f16_dir(bx.lo.y - eps[1], false), lz = f32_to_f16_dir(bx.lo.z - eps[2], false);
-            const uint32_t hx = f32_to_f16_dir(bx.hi.x + eps[0], true), hy = f32_to_f16_dir(bx.hi.y + eps[1], true), hz = f32_to_f16_dir(bx.hi.z + eps[2], true);
-            c[4 * i + 0] = lx | ly << 16;
-            c[4 * i + 1] = lz | hx << 16;
-            c[4 * i + 2] = hy | hz << 16;
+            const float lo[3] = {bx.lo.x, bx.lo.y, bx.lo.z}, hi[3] = {bx.hi.x, bx.hi.y, bx.hi.z};
             // an inner node's link is its skip node's BYTE offset in this array: the walk's cursor is the offset its load takes (box_loop_compact)
-            c[4 * i + 3] = cb.node_leaf[i] >= 0 ? (0x80000000u | (uint32_t)cb.node_leaf[i]) : (uint32_t)cb.node_skip[i] << 4;
+            compact_node_words(lo, hi, eps, cb.node_leaf[i] >= 0 ? (0x80000000u | (uint32_t)cb.node_leaf[i]) : (uint32_t)cb.node_skip[i] << 4, c + 4 * (size_t)i);
         }
     }
     dump_tree(out.reference, b.node_box, b.node_prim, b.node_skip);
@@ -551,7 +501,7 @@ bool compile_scene(const World& w, const trt_scene_options& opt, SceneHost& out,
         F4* q = f4 + L.off_quad + 5u * (size_t)i;                 // one record of five elements per quad
         q[0] = q0[i]; q[1] = q1[i]; q[2] = q2[i]; q[3] = q3[i]; q[4] = q4[i];
     }
-    for (uint32_t i = 0; i < nm; i++) {
+    for (uint32_t i = 0; i < L.n_materials; i++) {
         const trt_material& m = w.materials[i];
         f4[L.off_material + i] = F4{m.albedo.x, m.albedo.y, m.albedo.z, m.param};
         u32[L.off_material_kind + i] = m.kind;
