@@ -33,6 +33,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "flat_reuse.h"
 #include "kernels.h"
 #include "scene.h"
 #include "scene_adopt.h"
@@ -121,6 +122,7 @@ struct DeviceCache {
 
 struct trt_scene {
     SceneHost host;
+    FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h), derived once from host.blob
     std::mutex mu;
     std::condition_variable cv;
     std::unordered_map<int, DeviceCache> dev;     // device ordinal -> cached device resources
@@ -150,6 +152,7 @@ int fail_hip(hipError_t e, const char* what) {
 struct Defaults {
     trt_tuning tuning;
     trt_scene_options scene;
+    bool flat_reuse = true;                       // TRT_FLAT_REUSE=0: the lock-step leaf walk computes every leaf box in full (A/B runs, tests)
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -171,6 +174,7 @@ const Defaults& defaults() {
             if (v > 0.0f && v <= 1.0f) o.cull_prune = v;
         }
         if (const char* e = env("TRT_FLAT_WALK")) o.flat_walk = atoi(e) ? 1 : 0;
+        if (const char* e = env("TRT_FLAT_REUSE")) x.flat_reuse = atoi(e) != 0;
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -486,6 +490,7 @@ int to_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs
     ra.xcd_aware = tn.xcd_remap ? 1u : 0u;                 // off: contiguous image regions per XCD measured 2x slower (load imbalance)
     ra.stragglers = tn.stragglers;                         // profiles/r03_stragglers_sweep.txt
     ra.ref_tree = p->collect_stats == 1 ? 1u : 0u;      // 1: counters comparable with the CPU path; 2: count the culling tree's own tests
+    ra.flat_reuse = FlatReuse{0u, 0u, 0u};                 // the scene's schedule is filled in by enqueue_render
     return TRT_OK;
 }
 
@@ -502,6 +507,7 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
     if (rc != TRT_OK) return rc;
     CameraDev cd;
     to_camera_dev(*cam, cd);
+    ra.flat_reuse = s->flat_reuse;
     const size_t bytes = (size_t)rows * cam->width * 3 * sizeof(float);
     if (rows == 0 || ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64)
@@ -585,6 +591,16 @@ void counters_to_stats(const unsigned long long* c, trt_stats* st) {
     st->gather_per_band = 0;
 }
 
+// The reuse schedule of a flat-walk scene's leaf list, from the host copy of its blob (both scene compilers leave one).
+void set_flat_reuse(trt_scene* s) {
+    const SceneLayout& L = s->host.layout;
+    const size_t end = 16u * ((size_t)L.off_leaf_list + 2u * (size_t)L.n_leaves);
+    const bool have = L.flat_walk != 0u && L.n_leaves > 0u && s->host.blob.size() >= end;
+    uint32_t m[3];
+    flat_reuse_masks(have ? s->host.blob.data() + 16u * (size_t)L.off_leaf_list : nullptr, L.n_leaves, have && defaults().flat_reuse, m);
+    s->flat_reuse = FlatReuse{m[0], m[1], m[2]};
+}
+
 }  // namespace
 
 // The device scene compiler's view of this layer (scene_adopt.h)
@@ -600,6 +616,7 @@ trt_scene* scene_adopt(SceneHost&& host, const trt_scene_options& opt, int devic
     try {
         trt_scene* s = new trt_scene();
         s->host = std::move(host);
+        set_flat_reuse(s);
         s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
         if (d_blob) s->dev[device].blob = static_cast<float4*>(d_blob);      // the first render on `device` does not upload again
         return s;
@@ -711,6 +728,7 @@ int trt_scene_create_ex(const trt_world* w, const trt_scene_options* options, tr
         trt_scene* s = new trt_scene();
         std::string msg;
         if (!compile_scene(w->w, opt, s->host, msg)) { delete s; return fail(TRT_ERR_INVALID_ARG, msg); }
+        set_flat_reuse(s);
         s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
         *out = s;
     } catch (const std::bad_alloc&) {

@@ -18,6 +18,12 @@ struct CameraDev {               // camera.rs:4-14, the fields get_ray reads
     uint32_t width, height;
 };
 
+// Reuse schedule of the lock-step leaf walk (flat_reuse.h): bit i of x / y / z = leaf i's interval on that axis is leaf i-1's.  All zero:
+// every leaf box is computed in full.
+struct FlatReuse {
+    uint32_t x, y, z;
+};
+
 struct RenderArgs {
     float background[3];
     float inv_spp;               // 1/spp: Imager's color_multiplier (imager.rs:35)
@@ -33,6 +39,7 @@ struct RenderArgs {
     uint32_t ref_tree;           // 1: walk the reference tree (counting kernels: counters comparable with the oracle)
     uint32_t stragglers;         // streamed walks of scenes in global memory: a round's walk phase ends once at most this many lanes of the wave still walk
                                  // (they carry their walk into the next round); 0 = every walk runs to its end (rt_path.h walk_compact)
+    FlatReuse flat_reuse;        // lock-step leaf walk: per-axis intervals kept from the previous leaf (rt_path.h box_loop_flat); zero = none
 };
 
 // The built-in scheduling defaults (tinyrt.h trt_tuning; each a measured optimum, DESIGN.md "Tuning").  They live in THIS header -

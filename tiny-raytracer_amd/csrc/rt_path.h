@@ -468,25 +468,40 @@ TRT_DEV bool walk_fast_lds(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, C
 // The box-step loop of walk_flat by hand (round 3; conventions of box_loop_lds).  The leaf pair under test lives in s[36:51] - sixteen fixed
 // SGPRs, because a 64-byte scalar load needs an aligned tuple and inline-asm operands cannot be taken apart - and the next pair is requested
 // as soon as the last value of the current one has been read (the link of the second leaf is copied out first); the wave's other lanes'
-// work covers the rest of that load's latency.  25 vector instructions per box (23 for the slab test + the link copy and the stack-top add
-// under the push mask) and 6.5 scalar ones, against 26 + 12.5 from the C++ loop below.  `i` is the next leaf to test (wave-uniform, in and out);
-// the loop ends when i == n or when some lane cannot hold another pair of leaves.  Returns the lane's new stack top.
+// work covers the rest of that load's latency.  A box is three per-axis intervals (6 vector instructions each: 2 sub, 2 mul, and the
+// x axis' two medians with t_min / t_best or the y / z axis' min and max), then max3 / min3 / compare (3) and the push (2 under the
+// push mask).  `i` is the next leaf to test (wave-uniform, in and out); the loop ends when i == n or when some lane cannot hold another
+// pair of leaves.  Returns the lane's new stack top.
+//
+// Interval reuse: the three intervals stay in VGPRs from box to box, and an axis whose bit `i` is set in `reuse` (flat_reuse.h: leaf i's
+// two planes on that axis are leaf i-1's, bit for bit) is not computed again - one s_bitcmp1 + s_cbranch per axis on the wave-uniform
+// bit, no vector instruction.  The kept interval is what the skipped instructions would produce: the same operations on the same
+// operands (the ray, the two plane bit patterns, t_min, and t_best, which changes only in the leaf phase, outside this loop).  The first
+// box of every call computes all three axes whatever its bits say, so no interval outlives the t_best it was folded with.  Cornell:
+// 15 of the 54 intervals of its 18 leaves are the previous leaf's.
 #define TRT_FLAT_BOX(LOX, LOY, LOZ, HIX, HIY, HIZ)                                                                                        \
-    "v_sub_f32_e32 %[t0], " LOX ", %[ox]\n v_sub_f32_e32 %[t1], " HIX ", %[ox]\n v_sub_f32_e32 %[t2], " LOY ", %[oy]\n"                   \
-    "v_sub_f32_e32 %[t3], " HIY ", %[oy]\n v_mul_f32_e32 %[t0], %[ix], %[t0]\n v_mul_f32_e32 %[t1], %[ix], %[t1]\n"                       \
-    "v_mul_f32_e32 %[t2], %[iy], %[t2]\n v_mul_f32_e32 %[t3], %[iy], %[t3]\n v_sub_f32_e32 %[t4], " LOZ ", %[oz]\n"                      \
-    "v_sub_f32_e32 %[t5], " HIZ ", %[oz]\n v_mul_f32_e32 %[t4], %[iz], %[t4]\n v_mul_f32_e32 %[t5], %[iz], %[t5]\n"                      \
-    "v_med3_f32 %[st], %[t0], %[t1], %[tmin]\n v_med3_f32 %[t0], %[t0], %[t1], %[tb]\n v_min_f32_e32 %[t1], %[t2], %[t3]\n"              \
-    "v_max_f32_e32 %[t2], %[t2], %[t3]\n v_min_f32_e32 %[t3], %[t4], %[t5]\n v_max_f32_e32 %[t4], %[t4], %[t5]\n"                        \
-    "v_max3_f32 %[st], %[st], %[t1], %[t3]\n v_min3_f32 %[t0], %[t0], %[t2], %[t4]\n v_cmp_nle_f32_e32 vcc, %[t0], %[st]\n"
+    "s_bitcmp1_b32 %[rx], %[i]\n s_cbranch_scc1 10f\n"                                                                                  \
+    "v_sub_f32_e32 %[t0], " LOX ", %[ox]\n v_sub_f32_e32 %[t1], " HIX ", %[ox]\n v_mul_f32_e32 %[t0], %[ix], %[t0]\n"                  \
+    "v_mul_f32_e32 %[t1], %[ix], %[t1]\n v_med3_f32 %[xe], %[t0], %[t1], %[tmin]\n v_med3_f32 %[xx], %[t0], %[t1], %[tb]\n"              \
+    "10:\n s_bitcmp1_b32 %[ry], %[i]\n s_cbranch_scc1 11f\n"                                                                            \
+    "v_sub_f32_e32 %[t0], " LOY ", %[oy]\n v_sub_f32_e32 %[t1], " HIY ", %[oy]\n v_mul_f32_e32 %[t0], %[iy], %[t0]\n"                  \
+    "v_mul_f32_e32 %[t1], %[iy], %[t1]\n v_min_f32_e32 %[ye], %[t0], %[t1]\n v_max_f32_e32 %[yx], %[t0], %[t1]\n"                        \
+    "11:\n s_bitcmp1_b32 %[rz], %[i]\n s_cbranch_scc1 12f\n"                                                                            \
+    "v_sub_f32_e32 %[t0], " LOZ ", %[oz]\n v_sub_f32_e32 %[t1], " HIZ ", %[oz]\n v_mul_f32_e32 %[t0], %[iz], %[t0]\n"                  \
+    "v_mul_f32_e32 %[t1], %[iz], %[t1]\n v_min_f32_e32 %[ze], %[t0], %[t1]\n v_max_f32_e32 %[zx], %[t0], %[t1]\n"                        \
+    "12:\n v_max3_f32 %[st], %[xe], %[ye], %[ze]\n v_min3_f32 %[t0], %[xx], %[yx], %[zx]\n v_cmp_nle_f32_e32 vcc, %[t0], %[st]\n"
 
-TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restrict__ leaf_list, uint32_t& i, uint32_t n, float2* stk, float2* limit) {
+TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restrict__ leaf_list, uint32_t& i, uint32_t n, float2* stk, float2* limit,
+                              FlatReuse reuse) {
     const uint32_t stk_off = lds_offset(stk);
     uint32_t top = stk_off;
     const uint32_t lim = lds_offset(limit);
+    // the first box of this call computes every axis (i < n <= 32 wherever a mask has bits: flat_reuse.h)
+    const uint32_t first = ~(1u << (i & 31u));
+    const uint32_t rx = reuse.x & first, ry = reuse.y & first, rz = reuse.z & first;
     unsigned long long m;
     uint32_t off;
-    float t0, t1, t2, t3, t4, t5, st, lk;
+    float t0, t1, xe, xx, ye, yx, ze, zx, st, lk;
     asm volatile(
         "s_lshl_b32 %[off], %[i], 5\n"                              // a leaf is 32 bytes: (lo.x lo.y lo.z hi.x) (hi.y hi.z skip link)
         "s_load_dwordx16 s[36:51], %[list], %[off]\n"               // leaves i and i + 1 (the list is padded: scene.h kLeafListPad)
@@ -517,12 +532,34 @@ TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restr
         "s_cbranch_scc1 1b\n"
         "2:\n"
         "s_waitcnt lgkmcnt(0)\n"                                    // nothing may land in s[36:51] after the block
-        : [i] "+s"(i), [top] "+v"(top), [m] "=&s"(m), [off] "=&s"(off), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3),
-          [t4] "=&v"(t4), [t5] "=&v"(t5), [st] "=&v"(st), [lk] "=&v"(lk)
+        : [i] "+s"(i), [top] "+v"(top), [m] "=&s"(m), [off] "=&s"(off), [t0] "=&v"(t0), [t1] "=&v"(t1), [xe] "=&v"(xe), [xx] "=&v"(xx),
+          [ye] "=&v"(ye), [yx] "=&v"(yx), [ze] "=&v"(ze), [zx] "=&v"(zx), [st] "=&v"(st), [lk] "=&v"(lk)
         : [n] "s"(n), [list] "s"(leaf_list), [lim] "v"(lim), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(tr.inv.x), [iy] "v"(tr.inv.y),
-          [iz] "v"(tr.inv.z), [tb] "v"(tr.t_best), [tmin] "s"(kTMin)
+          [iz] "v"(tr.inv.z), [tb] "v"(tr.t_best), [tmin] "s"(kTMin), [rx] "s"(rx), [ry] "s"(ry), [rz] "s"(rz)
         : "vcc", "scc", "memory", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51");
     return stk + ((top - stk_off) >> 3);
+}
+
+// One leaf box of walk_flat's C++ loop with box_loop_flat's interval reuse: the axes whose bit is clear in `fresh` are computed (min / max
+// of the two plane distances), the others are kept from the previous leaf; then slab_fast_entry's combination, operation for operation.
+struct FlatIntervals {
+    float xe, xx, ye, yx, ze, zx;
+};
+TRT_DEV bool flat_box(FlatIntervals& c, float4 na, float4 nb, V3 o, V3 inv, uint32_t axes, float start, float end, float& start_out) {
+    if (axes & 1u) { const float x0 = (na.x - o.x) * inv.x, x1 = (na.w - o.x) * inv.x; c.xe = __builtin_fminf(x0, x1); c.xx = __builtin_fmaxf(x0, x1); }
+    if (axes & 2u) { const float y0 = (na.y - o.y) * inv.y, y1 = (nb.x - o.y) * inv.y; c.ye = __builtin_fminf(y0, y1); c.yx = __builtin_fmaxf(y0, y1); }
+    if (axes & 4u) { const float z0 = (na.z - o.z) * inv.z, z1 = (nb.y - o.z) * inv.z; c.ze = __builtin_fminf(z0, z1); c.zx = __builtin_fmaxf(z0, z1); }
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(c.xe, c.ye), c.ze);
+    const float tf = __builtin_fminf(__builtin_fminf(c.xx, c.yx), c.zx);
+    start = __builtin_fmaxf(start, tn);
+    end = __builtin_fminf(end, tf);
+    start_out = start;
+    return !(end <= start);
+}
+// Which axes leaf i computes (bit 0 x, 1 y, 2 z): those whose reuse bit is clear (wave-uniform).
+TRT_DEV uint32_t flat_axes(const FlatReuse& r, uint32_t i) {
+    const uint32_t b = 1u << (i & 31u);
+    return ((r.x & b) ? 0u : 1u) | ((r.y & b) ? 0u : 2u) | ((r.z & b) ? 0u : 4u);
 }
 
 // Scenes with a handful of primitives (SceneLayout::flat_walk): no tree at all.  Every lane of the wave steps the SAME
@@ -538,13 +575,13 @@ TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restr
 // `s_load_dwordx4; s_waitcnt lgkmcnt(0)`, once per box step, and spends 3 branches and ~10 scalar instructions per step).
 template <int MODE, bool STATS>
 TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf_list, const Ray& ray, Trav& tr, Counters<STATS>& ctr,
-                       float2* stk, uint32_t slots) {
+                       float2* stk, uint32_t slots, FlatReuse reuse) {
     const uint32_t n = sc.L.n_leaves;                    // >= 1
     uint32_t i = 0;                                      // wave-uniform
     if constexpr (kAsmBoxLoop && !STATS) {
         float2* const lim = stk + 64u * (slots - 2u);
         do {
-            float2* const top = box_loop_flat(tr, ray.o, leaf_list, i, n, stk, lim);
+            float2* const top = box_loop_flat(tr, ray.o, leaf_list, i, n, stk, lim, reuse);
             TRT_CLK(ctr, 1);
             leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr); });
             TRT_CLK(ctr, 2);
@@ -555,21 +592,24 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
                                                          // reading one pair ahead needs no clamping: ONE 64-byte scalar load per trip
     float4 a0 = pair[0], b0 = pair[1], a1 = pair[2], b1 = pair[3];
     float2* const limit = stk + 64u * (slots - 2u);      // a lane whose top is beyond it cannot hold another pair (slots >= 2)
+    FlatIntervals iv;
     do {
         float2* top = stk;
+        bool first = true;                               // box_loop_flat's rule: the first box after every leaf phase computes all three axes
         for (; i < n;) {
             // request the next pair
             pair += 4;
             const float4 na0 = pair[0], nb0 = pair[1], na1 = pair[2], nb1 = pair[3];
             if constexpr (STATS) { ctr.node++; if (first_active_lane()) ctr.w_steps++; }
             float start;
-            if (slab_fast_entry(a0, b0, ray.o, tr.inv, kTMin, tr.t_best, start)) {
+            if (flat_box(iv, a0, b0, ray.o, tr.inv, first ? 7u : flat_axes(reuse, i), kTMin, tr.t_best, start)) {
                 *top = make_float2(b0.w, start);
                 top += 64;
             }
+            first = false;
             if (i + 1u < n) {
                 if constexpr (STATS) { ctr.node++; if (first_active_lane()) ctr.w_steps++; }
-                if (slab_fast_entry(a1, b1, ray.o, tr.inv, kTMin, tr.t_best, start)) {
+                if (flat_box(iv, a1, b1, ray.o, tr.inv, flat_axes(reuse, i + 1u), kTMin, tr.t_best, start)) {
                     *top = make_float2(b1.w, start);
                     top += 64;
                 }
@@ -864,7 +904,7 @@ enum { WALK_RUNTIME = 0, WALK_LDS_STACK = 1, WALK_FLAT = 2, WALK_COMPACT = 3, WA
 template <int MODE, bool STATS, int WALK = WALK_RUNTIME>
 TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_tree, float& t_hit, Counters<STATS>& ctr,
                              uint32_t leaf_slots = 4u, float2* lds_stack = nullptr, const float4* __restrict__ leaf_list = nullptr,
-                             const uint4* __restrict__ nodes16 = nullptr) {
+                             const uint4* __restrict__ nodes16 = nullptr, FlatReuse flat_reuse = FlatReuse{0u, 0u, 0u}) {
     // (a general kernel reaches walk_compact's loop whenever it is handed the 16-byte nodes and an LDS stack: same domain as the specialised ones)
     const bool fused_loop = kAsmBoxLoop && !STATS && (WALK == WALK_COMPACT || (WALK == WALK_RUNTIME && lds_stack != nullptr && nodes16 != nullptr));
     Trav tr = trav_begin<MODE>(sc, ray, ref_tree, fused_loop);
@@ -872,14 +912,14 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
         if constexpr (WALK == WALK_COMPACT) {
             walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
         } else if constexpr (WALK == WALK_FLAT) {
-            walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
+            walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
         } else if constexpr (WALK == WALK_LDS_STACK) {
             walk_fast_lds<MODE, STATS>(sc, ray, tr, ctr, lds_stack, leaf_slots);
         } else if constexpr (WALK == WALK_REGS) {
             walk_fast<MODE, STATS, 4>(sc, ray, tr, ctr);
         } else {
             if (lds_stack != nullptr && nodes16 != nullptr) walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
-            else if (lds_stack != nullptr && leaf_list != nullptr) walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
+            else if (lds_stack != nullptr && leaf_list != nullptr) walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
             else if (lds_stack != nullptr) walk_fast_lds<MODE, STATS>(sc, ray, tr, ctr, lds_stack, leaf_slots);
             else if (leaf_slots >= 4u || leaf_slots == 0u) walk_fast<MODE, STATS, 4>(sc, ray, tr, ctr);
             else if (leaf_slots >= 2u) walk_fast<MODE, STATS, 2>(sc, ray, tr, ctr);

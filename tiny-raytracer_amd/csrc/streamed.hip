@@ -138,7 +138,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
             } else {
                 n_rays++;
                 float t;
-                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16);
+                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.flat_reuse);
                 if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
                     radiance_store(colors, out_idx, p.color);
                     has_path = false;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
             } else {
                 n_rays++;
                 float t;
-                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16);
+                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.flat_reuse);
                 if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
                     radiance_store(colors, out_idx, p.color);
                     has_path = false;
