@@ -89,6 +89,9 @@ def _load():
         "orc_world_build": (None, [C.c_void_p]),
         "orc_world_bvh_dump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
         "orc_world_hit": (C.c_int, [C.c_void_p, P(Ray), C.c_float, C.c_float, P(HitRecord), P(Stats)]),
+        "orc_world_hit_index": (C.c_int, [C.c_void_p, P(Ray), C.c_float, C.c_float, P(HitRecord), P(C.c_int32), P(Stats)]),
+        "orc_world_hit_index_batch": (None, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "orc_world_hit_bruteforce_batch": (None, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
         "orc_world_hit_bruteforce": (C.c_int, [C.c_void_p, P(Ray), C.c_float, C.c_float, P(HitRecord)]),
         "orc_camera_new": (None, [P(CameraPOD), C.c_float, C.c_float, Vec3, Vec3, Vec3, C.c_float, C.c_uint32, C.c_uint32]),
         "orc_render": (None, [C.c_void_p, P(CameraPOD), P(RenderParams), C.c_void_p, P(Stats), C.c_int]),
@@ -177,6 +180,27 @@ class World:
         rec, st = HitRecord(), Stats()
         ok = lib.orc_world_hit(self._h, C.byref(ray), t0, t1, C.byref(rec), C.byref(st))
         return (rec if ok else None), st.as_dict()
+
+    def hit_index(self, ray, t0=0.001, t1=float("inf")):
+        """hit(), and the geometry insertion index of the primitive that won (-1 on a miss): (record or None, index)."""
+        rec, idx = HitRecord(), C.c_int32(-1)
+        ok = lib.orc_world_hit_index(self._h, C.byref(ray), t0, t1, C.byref(rec), C.byref(idx), None)
+        return (rec if ok else None), idx.value
+
+    def hit_index_batch(self, rays, t0=0.001, t1=float("inf")):
+        """hit_index() for rays float32 [n, 6] (origin, direction; used as given): (hit bool[n], t float32[n] - inf on a miss, index int32[n])."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = len(r)
+        hit, t, idx = np.zeros(n, np.int32), np.full(n, np.inf, np.float32), np.zeros(n, np.int32)
+        lib.orc_world_hit_index_batch(self._h, r.ctypes.data, n, t0, t1, hit.ctypes.data, t.ctypes.data, idx.ctypes.data)
+        return hit != 0, t, idx
+
+    def hit_bruteforce_batch(self, rays, t0=0.001, t1=float("inf")):
+        """hit_bruteforce() for rays float32 [n, 6]: (hit bool[n], t float32[n] - inf on a miss)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        hit, t = np.zeros(len(r), np.int32), np.full(len(r), np.inf, np.float32)
+        lib.orc_world_hit_bruteforce_batch(self._h, r.ctypes.data, len(r), t0, t1, hit.ctypes.data, t.ctypes.data)
+        return hit != 0, t
 
     def hit_bruteforce(self, ray, t0=0.001, t1=float("inf")):
         rec = HitRecord()

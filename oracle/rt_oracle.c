@@ -503,6 +503,28 @@ static int node_hit(const orc_world *w, const node *nd, const orc_ray *ray, floa
     return node_hit(w, nd->right, ray, t0, t1, rec, st);
 }
 
+/* node_hit that also says which geometry won (insertion index): the same recursion, the same tests in the same order. */
+static int node_hit_index(const orc_world *w, const node *nd, const orc_ray *ray, float t0, float t1,
+                          orc_hit_record *rec, int32_t *index, orc_stats *st) {
+    if (st) st->node_tests++;
+    if (!aabb_intersect(&nd->bbox, ray, t0, t1)) return 0;
+    if (nd->hittable >= 0) {
+        if (!geometry_hit(&w->geos[nd->hittable], ray, t0, t1, rec, st)) return 0;
+        *index = nd->hittable;
+        return 1;
+    }
+    orc_hit_record left_rec;
+    int32_t left_index;
+    if (node_hit_index(w, nd->left, ray, t0, t1, &left_rec, &left_index, st)) {
+        orc_hit_record right_rec;
+        int32_t right_index;
+        if (node_hit_index(w, nd->right, ray, t0, left_rec.t, &right_rec, &right_index, st)) { *rec = right_rec; *index = right_index; }
+        else { *rec = left_rec; *index = left_index; }
+        return 1;
+    }
+    return node_hit_index(w, nd->right, ray, t0, t1, rec, index, st);
+}
+
 /* ------------------------------------------------------------------------------------------
  * World (hittable/world.rs:16-45)
  * ---------------------------------------------------------------------------------------- */
@@ -602,6 +624,24 @@ int orc_world_hit(orc_world *w, const orc_ray *ray, float t0, float t1, orc_hit_
     if (st) st->rays++;
     return node_hit(w, w->root, ray, t0, t1, out, st);                              /* bvh.rs:25-27 */
 }
+int orc_world_hit_index(orc_world *w, const orc_ray *ray, float t0, float t1, orc_hit_record *out, int32_t *index, orc_stats *st) {
+    *index = -1;
+    orc_world_build(w);
+    if (!w->root) return 0;
+    if (st) st->rays++;
+    int32_t idx = -1;
+    int hit = node_hit_index(w, w->root, ray, t0, t1, out, &idx, st);
+    *index = hit ? idx : -1;
+    return hit;
+}
+/* n rays at once (24 bytes each: origin, direction): hit[i], t[i] (untouched on a miss) and index[i] as orc_world_hit_index gives them */
+void orc_world_hit_index_batch(orc_world *w, const orc_ray *rays, int n, float t0, float t1, int32_t *hit, float *t, int32_t *index) {
+    for (int i = 0; i < n; i++) {
+        orc_hit_record rec;
+        hit[i] = orc_world_hit_index(w, &rays[i], t0, t1, &rec, &index[i], NULL);
+        if (hit[i]) t[i] = rec.t;
+    }
+}
 int orc_world_hit_bruteforce(orc_world *w, const orc_ray *ray, float t0, float t1, orc_hit_record *out) {
     int hit = 0;
     for (int i = 0; i < w->ngeo; i++) {
@@ -609,6 +649,13 @@ int orc_world_hit_bruteforce(orc_world *w, const orc_ray *ray, float t0, float t
         if (geometry_hit(&w->geos[i], ray, t0, t1, &rec, NULL)) { *out = rec; t1 = rec.t; hit = 1; }
     }
     return hit;
+}
+void orc_world_hit_bruteforce_batch(orc_world *w, const orc_ray *rays, int n, float t0, float t1, int32_t *hit, float *t) {
+    for (int i = 0; i < n; i++) {
+        orc_hit_record rec;
+        hit[i] = orc_world_hit_bruteforce(w, &rays[i], t0, t1, &rec);
+        if (hit[i]) t[i] = rec.t;
+    }
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -91,8 +91,13 @@ int orc_world_bvh_dump(orc_world *, float *bbox6, int32_t *prim, int32_t *subtre
 
 /* ---- closest hit through the BVH (bvh.rs:24-27,88-107); 1 = hit ---- */
 int orc_world_hit(orc_world *, const orc_ray *, float t0, float t1, orc_hit_record *out, orc_stats *stats);
+/* orc_world_hit, and which primitive won: *index = geometry insertion index of the winning leaf, -1 on a miss */
+int orc_world_hit_index(orc_world *, const orc_ray *, float t0, float t1, orc_hit_record *out, int32_t *index, orc_stats *stats);
+/* the same for n rays: hit[n], t[n] (left as it was on a miss), index[n] */
+void orc_world_hit_index_batch(orc_world *, const orc_ray *rays, int n, float t0, float t1, int32_t *hit, float *t, int32_t *index);
 /* brute force over all geometries in insertion order, strict '<' narrowing (no BVH) */
 int orc_world_hit_bruteforce(orc_world *, const orc_ray *, float t0, float t1, orc_hit_record *out);
+void orc_world_hit_bruteforce_batch(orc_world *, const orc_ray *rays, int n, float t0, float t1, int32_t *hit, float *t);   /* t[i] left as it was on a miss */
 
 /* ---- Camera (camera.rs:17-66) ---- */
 void orc_camera_new(orc_camera *out, float focus_distance, float defocus_angle_deg, orc_vec3 position,
