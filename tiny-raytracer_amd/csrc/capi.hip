@@ -33,6 +33,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "axis_quads.h"
 #include "flat_reuse.h"
 #include "kernels.h"
 #include "scene.h"
@@ -122,7 +123,7 @@ struct DeviceCache {
 
 struct trt_scene {
     SceneHost host;
-    FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h), derived once from host.blob
+    FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h) and axis-exact-quads switch (axis_quads.h), derived once from host.blob
     std::mutex mu;
     std::condition_variable cv;
     std::unordered_map<int, DeviceCache> dev;     // device ordinal -> cached device resources
@@ -153,6 +154,7 @@ struct Defaults {
     trt_tuning tuning;
     trt_scene_options scene;
     bool flat_reuse = true;                       // TRT_FLAT_REUSE=0: the lock-step leaf walk computes every leaf box in full (A/B runs, tests)
+    bool axis_quads = true;                       // TRT_AXIS_QUADS=0: the lock-step kernel keeps the generic quad test on axis-exact scenes too (A/B runs, tests)
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -175,6 +177,7 @@ const Defaults& defaults() {
         }
         if (const char* e = env("TRT_FLAT_WALK")) o.flat_walk = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_FLAT_REUSE")) x.flat_reuse = atoi(e) != 0;
+        if (const char* e = env("TRT_AXIS_QUADS")) x.axis_quads = atoi(e) != 0;
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -591,14 +594,19 @@ void counters_to_stats(const unsigned long long* c, trt_stats* st) {
     st->gather_per_band = 0;
 }
 
-// The reuse schedule of a flat-walk scene's leaf list, from the host copy of its blob (both scene compilers leave one).
+// The reuse schedule of a flat-walk scene's leaf list and its axis-exact-quads switch, from the host copy of its blob (both scene compilers leave one).
 void set_flat_reuse(trt_scene* s) {
     const SceneLayout& L = s->host.layout;
     const size_t end = 16u * ((size_t)L.off_leaf_list + 2u * (size_t)L.n_leaves);
     const bool have = L.flat_walk != 0u && L.n_leaves > 0u && s->host.blob.size() >= end;
     uint32_t m[3];
     flat_reuse_masks(have ? s->host.blob.data() + 16u * (size_t)L.off_leaf_list : nullptr, L.n_leaves, have && defaults().flat_reuse, m);
-    s->flat_reuse = FlatReuse{m[0], m[1], m[2]};
+    // ... and whether every quad is axis-exact (axis_quads.h): the lock-step kernel then runs the two-dot-product inside test
+    const size_t qend = 16u * ((size_t)L.off_quad + 5u * (size_t)L.n_quads);
+    const bool have_quads = have && L.n_quads > 0u && s->host.blob.size() >= qend;
+    const uint32_t aq = axis_quads_flag(have_quads ? s->host.blob.data() + 16u * (size_t)L.off_quad : nullptr, L.n_quads, L.n_leaves, L.flat_walk != 0u,
+                                        scene_mode(L) == 1, defaults().axis_quads);
+    s->flat_reuse = FlatReuse{m[0], m[1], m[2], aq};
 }
 
 }  // namespace

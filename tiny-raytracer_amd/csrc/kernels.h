@@ -20,8 +20,12 @@ struct CameraDev {               // camera.rs:4-14, the fields get_ray reads
 
 // Reuse schedule of the lock-step leaf walk (flat_reuse.h): bit i of x / y / z = leaf i's interval on that axis is leaf i-1's.  All zero:
 // every leaf box is computed in full.
+// axis_quads (axis_quads.h): 1 = every quad of the scene is axis-exact; the lock-step kernel then rewrites the quad records of its LDS copy
+// and runs the two-dot-product inside test (rt_path.h axis_quads_to_lds, trav_leaf).  Zero, also where it is left out of the braces: the
+// generic test on the packed records.
 struct FlatReuse {
     uint32_t x, y, z;
+    uint32_t axis_quads = 0u;
 };
 
 struct RenderArgs {

@@ -5,6 +5,7 @@
 // and its callees, plus primary-ray generation (renderer/pointgen.rs:37-52, camera.rs:58-66).
 #pragma once
 
+#include "axis_quads.h"
 #include "kernels.h"
 #include "rt_device.h"
 
@@ -162,10 +163,36 @@ TRT_DEV uint32_t trav_box_step(const SceneAcc<MODE>& sc, const Ray& ray, Trav& t
 }
 
 // Primitive test with the interval the leaf's box was tested with (bvh.rs:93-94).
+// `axis_quads` (wave-uniform: a launch argument; non-zero only in a kernel that has run axis_quads_to_lds): the quad records hold the
+// constants of axis_quads.h and the inside test is its two dot products.  One choice on the uniform flag, each side the whole
+// branch-free test; no per-lane select.  (The compiler lowers the choice to an exec-mask region whose other side is skipped by
+// s_cbranch_execz.  Forcing a scalar branch with readfirstlane, and compiling the kernel's tracing loop once per value of the flag, were
+// both measured: +0.1 % and +1.8 % against this form's +1.8 to +1.9 % - 47 and 21 spilled SGPRs against 26, the second with 69 VGPRs:
+// profiles/aq_axis_quads_ab.txt.)
 template <int MODE, bool STATS>
-TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint32_t leaf, Counters<STATS>& ctr) {
+TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint32_t leaf, Counters<STATS>& ctr, uint32_t axis_quads = 0u) {
     const uint32_t idx = leaf & PRIM_INDEX_MASK;
-    if (leaf & PRIM_QUAD_BIT) {                                        // Quad::hit, quad.rs:33-54
+    if (axis_quads != 0u && (leaf & PRIM_QUAD_BIT)) {
+        // Axis-exact quads (axis_quads.h has the argument and its case table): alpha = fl(w_a dot(p, A)), beta = fl(w_a dot(p, B)) are the
+        // generic test's dot(cross(p, v), w) and dot(cross(u, p), w) up to the sign of a zero, and a non-finite p is rejected by both
+        // forms.  Elements 2 and 3 of the record are (A.xyz, w_a) (B.xyz, 0) here; 0, 1 and 4 are the packed ones (shade_hit reads them).
+        // t, in_range and the assignment are the generic test's, operation for operation.  Four elements instead of five, 12 vector
+        // instructions instead of 28 for the inside test; nothing is fused (-ffp-contract=off).
+        if constexpr (STATS) ctr.quad_plane++;
+        const float4 q0 = sc.quad(0, idx), q1 = sc.quad(1, idx), q2 = sc.quad(2, idx), q3 = sc.quad(3, idx);
+        const V3 nrm = v3(q0.x, q0.y, q0.z);
+        const float dir_norm = dot(ray.d, nrm);
+        const float t = (q0.w - dot(ray.o, nrm)) / dir_norm;
+        const bool in_range = (kTMin <= t) & (t < tr.t_best);
+        if constexpr (STATS) { if (in_range) ctr.quad_inside++; }
+        const V3 p = ray_at(ray, t) - v3(q1.x, q1.y, q1.z);
+        const float planar_x = q2.w * dot(p, v3(q2.x, q2.y, q2.z));
+        const float planar_y = q2.w * dot(p, v3(q3.x, q3.y, q3.z));
+        if (in_range & (0.0f <= planar_x) & (planar_x < 1.0f) & (0.0f <= planar_y) & (planar_y < 1.0f)) {
+            tr.t_best = t;
+            tr.prim_best = leaf;
+        }
+    } else if (leaf & PRIM_QUAD_BIT) {                                 // Quad::hit, quad.rs:33-54
         if constexpr (STATS) ctr.quad_plane++;
         // Branch-free: all five planes are requested at once and the inside test is evaluated whatever the plane stage says.
         // Nearly every quad whose box still passes also passes the plane stage (Cornell: 1.08 plane tests and 0.97 inside
@@ -212,7 +239,7 @@ TRT_DEV bool ray_has_nan(const Ray& r) {
 // The rare walks: reference tree (counting kernels) and rays whose slab arithmetic needs the reference's
 // compare-and-assign form.  Runs the walk `tr` to its end.
 template <int MODE, bool STATS>
-TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr) {
+TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr, uint32_t axis_quads = 0u) {
     if constexpr (!STATS) {
         if (ray_has_nan(ray)) { tr.i = tr.n; return; }              // nothing can be hit (see ray_has_nan): t_best = inf, prim_best = PRIM_NONE
     }
@@ -224,7 +251,7 @@ TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr,
         }
         if (leaf == PRIM_NONE) break;
         if constexpr (STATS) { if (first_active_lane()) ctr.w_leaf++; }
-        trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr);
+        trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, axis_quads);
     }
 }
 
@@ -583,7 +610,7 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
         do {
             float2* const top = box_loop_flat(tr, ray.o, leaf_list, i, n, stk, lim, reuse);
             TRT_CLK(ctr, 1);
-            leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr); });
+            leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
             TRT_CLK(ctr, 2);
         } while (i < n);
         return;
@@ -620,7 +647,7 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
         }
         TRT_CLK(ctr, 1);
         if constexpr (STATS) ctr.pend += (uint32_t)(top - stk) >> 6;
-        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr); });
+        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
         TRT_CLK(ctr, 2);
     } while (i < n);
 }
@@ -898,6 +925,38 @@ constexpr uint32_t kLdsLeafSlotsMax = 16; // most slots per lane of the LDS leaf
 // 6849 lines of ISA, 44 spilled SGPRs and 16 spilled VGPRs with the runtime choice).
 enum { WALK_RUNTIME = 0, WALK_LDS_STACK = 1, WALK_FLAT = 2, WALK_COMPACT = 3, WALK_REGS = 5 };
 
+// Axis-exact quads (axis_quads.h).  Only the production lock-step kernel on an LDS scene copy takes the switch: the counting kernels,
+// the kernels that choose their walk at run time, the megakernel and the wavefront backend keep the generic test on the packed records
+// (their frames are what the specialised kernel's are compared with).
+template <int MODE, bool STATS, int WALK>
+constexpr bool kAxisQuadsKernel = MODE == MODE_LDS && !STATS && WALK == WALK_FLAT;
+
+// Called by the whole workgroup right after stage_scene_to_lds, with the launch's schedule.  Where the kernel takes the switch and the
+// scene has it (FlatReuse::axis_quads, derived on the host: EVERY quad is axis-exact), elements 2 and 3 of every quad record of the LDS
+// copy - (v.xyz, w.x) (w.y, w.z, u.x, u.y) - are overwritten in place with (A.xyz, w_a) (B.xyz, 0); a thread reads and writes one
+// record, elements 0, 1 and 4 stay (shade_hit, prim_material), one barrier follows.  No extra LDS.  Returns the schedule the kernel
+// hands to closest_hit: its axis_quads is non-zero exactly when the records were rewritten, so that the rewrite and the test that
+// reads it cannot disagree - from here on EVERY quad test on this LDS copy is the two-dot-product form (closest_hit_ref included).
+template <int MODE, bool STATS, int WALK>
+TRT_DEV FlatReuse axis_quads_to_lds(const SceneDev& sc, FlatReuse reuse) {
+    if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) {
+        reuse.axis_quads = 0u;
+    } else if (reuse.axis_quads != 0u) {
+        for (uint32_t k = threadIdx.x; k < sc.L.n_quads; k += blockDim.x) {
+            float4* const q = g_lds + sc.L.off_quad + 5u * k;
+            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+            const float rec[20] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, 0.0f, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, q4.z, q4.w};
+            float c[8];
+            if (axis_quad_constants(rec, c)) {                         // (always: the host set the flag for this very blob)
+                q[2] = make_float4(c[0], c[1], c[2], c[3]);
+                q[3] = make_float4(c[4], c[5], c[6], c[7]);
+            }
+        }
+        __syncthreads();
+    }
+    return reuse;
+}
+
 // Whole walk for one lane.  Returns the primitive reference (PRIM_NONE on a miss) and its t.  Postponed leaves go to
 // `lds_stack` (this lane's slot 0 of a `leaf_slots`-deep LDS stack) if the kernel has one, else into registers:
 // `leaf_slots` = 4 (also for 0 = default), 2 or 1 (tuning and tests; wave-uniform).
@@ -908,6 +967,7 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
     // (a general kernel reaches walk_compact's loop whenever it is handed the 16-byte nodes and an LDS stack: same domain as the specialised ones)
     const bool fused_loop = kAsmBoxLoop && !STATS && (WALK == WALK_COMPACT || (WALK == WALK_RUNTIME && lds_stack != nullptr && nodes16 != nullptr));
     Trav tr = trav_begin<MODE>(sc, ray, ref_tree, fused_loop);
+    if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) flat_reuse.axis_quads = 0u;      // (axis_quads_to_lds: no other kernel rewrites its records)
     if (__builtin_expect(!tr.ref, 1)) {
         if constexpr (WALK == WALK_COMPACT) {
             walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
@@ -926,7 +986,7 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
             else walk_fast<MODE, STATS, 1>(sc, ray, tr, ctr);
         }
     } else {
-        closest_hit_ref<MODE, STATS>(sc, ray, tr, ctr);
+        closest_hit_ref<MODE, STATS>(sc, ray, tr, ctr, flat_reuse.axis_quads);
     }
     t_hit = tr.t_best;
     return tr.prim_best;

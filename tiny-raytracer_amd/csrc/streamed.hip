@@ -40,6 +40,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
                                                                              const float4* __restrict__ leaf_list,
                                                                              const uint4* __restrict__ nodes16) {
     stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, STATS, WALK>(scd, ra.flat_reuse);      // axis-exact quads: the LDS copy's records rewritten (rt_path.h)
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
             } else {
                 n_rays++;
                 float t;
-                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.flat_reuse);
+                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, flat_reuse);
                 if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
                     radiance_store(colors, out_idx, p.color);
                     has_path = false;
@@ -172,6 +173,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                                                                            const float4* __restrict__ leaf_list,
                                                                            const uint4* __restrict__ nodes16) {
     stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, STATS, WALK>(scd, ra.flat_reuse);      // axis-exact quads: the LDS copy's records rewritten (rt_path.h)
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
@@ -275,7 +277,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
             } else {
                 n_rays++;
                 float t;
-                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.flat_reuse);
+                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, flat_reuse);
                 if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
                     radiance_store(colors, out_idx, p.color);
                     has_path = false;

@@ -61,6 +61,20 @@ extern "C" __global__ void ev_quad_test(const EvIn* in, EvOut* out, SceneDev scd
     EV_EPILOGUE
 }
 
+// the same test on an axis-exact quad's rewritten record (axis_quads.h: four elements, the inside test as two dot products).  For the
+// record only: bench.py's useful_frac keeps counting a quad test at the generic cost above.
+extern "C" __global__ void ev_quad_test_axis(const EvIn* in, EvOut* out, SceneDev scd) {
+    EV_PROLOGUE
+    const SceneAcc<MODE_GLOBAL> sc{scd.blob, scd.L};
+    const Ray ray = load_ray(v);
+    Trav tr;
+    tr.t_best = v.f[14]; tr.prim_best = v.u[1];
+    Counters<false> ctr;
+    trav_leaf<MODE_GLOBAL, false>(sc, ray, tr, PRIM_QUAD_BIT | (v.u[0] & 0xFFFFu), ctr, 1u);
+    o.f[0] = tr.t_best; o.u[0] = tr.prim_best;
+    EV_EPILOGUE
+}
+
 // Sphere::hit (sphere.rs:29-54)
 extern "C" __global__ void ev_sphere_test(const EvIn* in, EvOut* out, SceneDev scd) {
     EV_PROLOGUE

@@ -3,13 +3,14 @@
 #   tools/pmc_bench.sh <tag> [bench.py args...]      e.g.  tools/pmc_bench.sh r02_cornell2048
 #                                                           tools/pmc_bench.sh r02_spheres1080 --scene random_spheres --width 1920 --height 1080
 # Counters are collected in passes of their own (never combined with tracing); every pass profiles
-# `python3 bench.py --steps 2 --warmup 1` directly (no wrapper between rocprofv3 and the program).
+# `python3 bench.py --steps 2 --warmup 1` directly (no wrapper between rocprofv3 and the program), under a time limit of its own; the first
+# pass that fails ends the script.
 # Output: gpurun_out/prof/<tag>/pmc_summary.json = per-launch means of the dominant kernel + the digest of the kernel
 # sources they were taken from; tools/pmc_collect.py merges such summaries into profiles/pmc_kernels.json.
 export TMPDIR=/tmp
 tag=$1; shift
 base=gpurun_out/prof/$tag; mkdir -p $base
-pass() { name=$1; shift; rocprofv3 --pmc "$@" --output-format csv -d $base/$name -- python3 bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-roofline-pass $BENCH_ARGS > $base/$name.json 2> $base/$name.err || { echo "pass $name failed"; tail -3 $base/$name.err; exit 1; }; echo "pass $name ok"; }
+pass() { name=$1; shift; timeout -k 10 600 rocprofv3 --pmc "$@" --output-format csv -d $base/$name -- python3 bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-roofline-pass $BENCH_ARGS > $base/$name.json 2> $base/$name.err || { echo "pass $name failed"; tail -3 $base/$name.err; exit 1; }; echo "pass $name ok"; }
 BENCH_ARGS="$*"
 pass sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_SALU SQ_INST_CYCLES_SALU
 pass sq2 SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_VALU_TRANS_F32
@@ -18,8 +19,8 @@ pass fetch FETCH_SIZE
 pass write WRITE_SIZE
 pass grbm GRBM_GUI_ACTIVE
 pass tcc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum
-rocprofv3 --kernel-trace --stats --output-format csv -d $base/trace -- python3 bench.py --full --steps 4 --warmup 1 --cpu-seconds 0 $BENCH_ARGS > $base/trace.json 2> $base/trace.err || { echo "trace failed"; tail -3 $base/trace.err; exit 1; }
-python3 bench.py --full --steps 4 --warmup 1 --cpu-seconds 0 $BENCH_ARGS > $base/bench_plain.json 2> $base/bench_plain.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $base/trace -- python3 bench.py --full --steps 4 --warmup 1 --cpu-seconds 0 $BENCH_ARGS > $base/trace.json 2> $base/trace.err || { echo "trace failed"; tail -3 $base/trace.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full --steps 4 --warmup 1 --cpu-seconds 0 $BENCH_ARGS > $base/bench_plain.json 2> $base/bench_plain.err || { echo "plain run failed"; tail -3 $base/bench_plain.err; exit 1; }
 python3 - "$base" "$tag" <<'PY'
 import csv, glob, collections, json, sys, os
 sys.path.insert(0, os.getcwd())
