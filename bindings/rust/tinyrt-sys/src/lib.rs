@@ -59,6 +59,17 @@ pub struct trt_sampled_color {
     pub color: trt_vec3,
 }
 
+/// The answer of a closest-hit query (28 bytes).  A miss: `t` = +inf, `geometry` = `material` = 0xFFFFFFFF, the rest 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_hit {
+    pub t: f32,
+    pub geometry: u32,
+    pub material: u32,
+    pub front_face: u32,
+    pub normal: trt_vec3,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct trt_material {
@@ -262,6 +273,12 @@ extern "C" {
                              d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;
+    pub fn trt_occluded(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, occluded: *mut u8) -> c_int;
+    pub fn trt_intersect_device(s: *mut trt_scene, d_rays: *const trt_ray, d_t_max: *const f32, n: u32, d_hits: *mut trt_hit,
+                                stream: *mut c_void) -> c_int;
+    pub fn trt_occluded_device(s: *mut trt_scene, d_rays: *const trt_ray, d_t_max: *const f32, n: u32, d_occluded: *mut u8,
+                               stream: *mut c_void) -> c_int;
     pub fn trt_tonemap_u8(accum: *const f32, npixels: u32, gamma: f32, rgb: *mut u8) -> c_int;
     pub fn trt_tonemap_u8_device(d_accum: *const f32, npixels: u32, gamma: f32, d_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn trt_streamed_chunk_spp(width: u32, rows: u32) -> u32;

@@ -37,7 +37,8 @@ extern "C" {
                              * 4 (round 5): + trt_world_add_spheres; trt_scene_options.top_nodes is ignored (the LDS cache of a large scene's upper
                              *              tree levels is gone: measured slower in every form); d_counters[12..15] = shades by material kind.
                              *              No struct changed size or moved a field.
- *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed. */
+ *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed; trt_hit, trt_intersect, trt_occluded,
+ *              trt_intersect_device, trt_occluded_device. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -280,6 +281,39 @@ int trt_render_device(trt_scene *s, const trt_camera *cam, const trt_render_para
  * (reference-order walk of the reference tree: its counters equal the CPU path's); with NULL the production walk. */
 int trt_sample_batch(trt_scene *s, const trt_sample_point *in, uint32_t n, trt_sampled_color *out,
                      uint32_t max_bounces, trt_vec3 background, uint32_t seed, trt_stats *stats);
+
+/* ---- Ray queries: BVH::hit (hittable/bvh.rs:24-27,88-107) for caller-supplied rays ----
+ * What does ray i hit, and is the segment blocked: picking, visibility between two points, occlusion and shadow probes, depth / normal /
+ * material buffers, collision probes.  No shading, no random numbers.
+ *  - Query.  Ray i is queried over [0.001, t_max[i]); t_max == NULL means +inf for every ray.  The lower end is the reference's own
+ *    constant (renderer/sampler/cpu.rs:48) and is compiled into every walk: a caller-supplied t_min is NOT offered.
+ *  - The ray is used as given: the direction is not normalised (trt_ray is the POD, not Ray::new, ray.rs:12-14), and t counts in units
+ *    of the direction's length.
+ *  - Exactness.  The answer is BVH::hit's, bit for bit: the same primitive, the same t, the same HitRecord (hittable/mod.rs:28-48) as the
+ *    reference returns for Range { 0.001..t_max }.  That includes the part the leaf BOXES play: a primitive is tested only where the ray
+ *    passes its box in the current interval, so the answer can differ from a brute-force loop over the primitives.
+ *  - A ray with a NaN component hits nothing.  A ray whose t_max is not > 0.001 (NaN included) is a miss and is not walked.
+ *  - trt_occluded: occluded[i] is 1 if trt_intersect reports a hit for the same ray and t_max, else 0.  It does not pay for the closest
+ *    hit: its walk ends at the first primitive accepted (a prefix of trt_intersect's walk, hence exact: DESIGN.md 6).
+ *  - Order and coherence.  Answer i belongs to ray i.  A wave of the GPU works through a contiguous run of the caller's rays; nothing is
+ *    sorted, so neighbouring rays that travel together (image order, not a random permutation) are the caller's to arrange.
+ *  - Errors.  A NULL scene, or a NULL buffer with n > 0, is TRT_ERR_INVALID_ARG before any device work; then TRT_ERR_NO_DEVICE, as in
+ *    trt_sample_batch.  n == 0 then succeeds and touches nothing.
+ *  - Concurrency: as for the render entry points.  The scene is immutable; several threads and streams may query and render it at once. */
+typedef struct {
+    float t;                      /* +inf on a miss */
+    uint32_t geometry;            /* insertion index of the primitive (order of the trt_world_add_* calls); 0xFFFFFFFF on a miss */
+    uint32_t material;            /* index into the world's material table; 0xFFFFFFFF on a miss */
+    uint32_t front_face;          /* HitRecord::front_face (hittable/mod.rs:35); 0 on a miss */
+    trt_vec3 normal;              /* HitRecord::normal (mod.rs:36-40): unit, facing the ray; 0,0,0 on a miss */
+} trt_hit;                        /* 28 B */
+/* HOST buffers, synchronous: n rays (and n t_max, or NULL) in, n records / n bytes out. */
+int trt_intersect(trt_scene *s, const trt_ray *rays, const float *t_max, uint32_t n, trt_hit *hits);
+int trt_occluded(trt_scene *s, const trt_ray *rays, const float *t_max, uint32_t n, uint8_t *occluded);
+/* The same on buffers resident in HBM, on the calling thread's current device (trt_set_device), asynchronous on `stream` (a hipStream_t,
+ * NULL = default): returns after enqueueing; the caller synchronises the stream. */
+int trt_intersect_device(trt_scene *s, const trt_ray *d_rays, const float *d_t_max, uint32_t n, trt_hit *d_hits, void *stream);
+int trt_occluded_device(trt_scene *s, const trt_ray *d_rays, const float *d_t_max, uint32_t n, uint8_t *d_occluded, void *stream);
 
 /* Imager finalisation + Image -> RgbImage (imager.rs:52-53; utils/image.rs:92-111): c^(1/gamma),
  * clamp to [0, 0.999], *255, truncate; NaN -> 0.  HOST buffers, npixels*3 each. */

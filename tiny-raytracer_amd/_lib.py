@@ -40,6 +40,11 @@ class SampledColor(C.Structure):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("color", Vec3)]
 
 
+class Hit(C.Structure):
+    """tinyrt.h trt_hit: the answer of a closest-hit query (28 bytes)."""
+    _fields_ = [("t", C.c_float), ("geometry", C.c_uint32), ("material", C.c_uint32), ("front_face", C.c_uint32), ("normal", Vec3)]
+
+
 class Material(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("albedo", Vec3), ("param", C.c_float)]
 
@@ -147,6 +152,10 @@ SIGNATURES = {
                                     C.c_void_p]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
+    "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "trt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "trt_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "trt_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "trt_streamed_chunk_spp": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "trt_tonemap_u8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "trt_tonemap_u8_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),

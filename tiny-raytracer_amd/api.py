@@ -55,6 +55,24 @@ class Quad:
         self.corner, self.u, self.v, self.material = _v(corner), _v(u), _v(v), int(material)
 
 
+# tinyrt.h trt_hit as a numpy record (28 bytes, no padding)
+HIT_DTYPE = np.dtype([("t", np.float32), ("geometry", np.uint32), ("material", np.uint32), ("front_face", np.uint32), ("normal", np.float32, (3,))])
+assert HIT_DTYPE.itemsize == C.sizeof(_lib.Hit) == 28
+
+
+def _rays_and_t_max(rays, t_max):
+    """float32 [n, 6] (origin, direction: used as given) and float32 [n] or None, contiguous."""
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("rays must be [n, 6]: origin, direction")
+    if t_max is None:
+        return r, None
+    t = np.ascontiguousarray(t_max, np.float32).reshape(-1)
+    if len(t) != len(r):
+        raise ValueError("one t_max per ray")
+    return r, t
+
+
 def scene_options(**over):
     """The library's default trt_scene_options with `over` applied."""
     opt = SceneOptions()
@@ -121,6 +139,34 @@ class Scene:
         out = np.zeros(n, np.uint8)
         check(lib.trt_scene_get_packed(self._h, out.ctypes.data, n))
         return out
+
+    # ---- ray queries (tinyrt.h trt_intersect / trt_occluded): BVH::hit over [0.001, t_max) for caller-supplied rays ----
+    def intersect(self, rays, t_max=None):
+        """Closest hit of rays float32 [n, 6] (origin, direction; used as given, never normalised) over [0.001, t_max[i]) (None = inf):
+        a record array with the trt_hit fields t, geometry (insertion index), material, front_face, normal; a miss has t = inf and
+        geometry = material = 0xFFFFFFFF.  Answer i belongs to ray i; rays that travel together should be neighbours."""
+        r, t = _rays_and_t_max(rays, t_max)
+        out = np.zeros(len(r), HIT_DTYPE)
+        check(lib.trt_intersect(self._h, r.ctypes.data if len(r) else None, t.ctypes.data if t is not None and len(r) else None, len(r),
+                                out.ctypes.data if len(r) else None))
+        return out
+
+    def occluded(self, rays, t_max=None):
+        """bool [n]: does ray i hit anything in [0.001, t_max[i]) - intersect()'s `hit?` without paying for the closest hit."""
+        r, t = _rays_and_t_max(rays, t_max)
+        out = np.zeros(len(r), np.uint8)
+        check(lib.trt_occluded(self._h, r.ctypes.data if len(r) else None, t.ctypes.data if t is not None and len(r) else None, len(r),
+                               out.ctypes.data if len(r) else None))
+        return out.view(np.bool_)
+
+    def intersect_device(self, d_rays_ptr, n, d_hits_ptr, d_t_max_ptr=0, stream_ptr=0):
+        """Enqueue intersect() on buffers already in HBM (device pointers as integers: n x 24 bytes of rays, n floats or 0, n x 28 bytes
+        of records) on the current device; asynchronous on the stream."""
+        check(lib.trt_intersect_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_t_max_ptr), int(n), C.c_void_p(d_hits_ptr), C.c_void_p(stream_ptr)))
+
+    def occluded_device(self, d_rays_ptr, n, d_occluded_ptr, d_t_max_ptr=0, stream_ptr=0):
+        """Enqueue occluded() on buffers already in HBM (n bytes out, each 0 or 1); asynchronous on the stream."""
+        check(lib.trt_occluded_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_t_max_ptr), int(n), C.c_void_p(d_occluded_ptr), C.c_void_p(stream_ptr)))
 
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:

@@ -38,6 +38,7 @@
 #include "kernels.h"
 #include "scene.h"
 #include "scene_adopt.h"
+#include "scene_query.h"
 
 using namespace trt;
 
@@ -116,6 +117,8 @@ constexpr size_t kMaxWorkspacesPerDevice = 8;      // beyond that, renders queue
 struct DeviceCache {
     float4* blob = nullptr;                       // packed scene in HBM
     bool blob_busy = false;                       // a thread is uploading it
+    uint32_t* geo_index = nullptr;                // trt_scene::geo_index in HBM (uploaded by the first ray query on the device)
+    bool geo_index_busy = false;                  // a thread is uploading it
     std::vector<Workspace*> ws;
     std::vector<RenderCtx*> ctx;
     uint32_t short_samples = 0;                   // != 0: the last streamed render of a full-size launch was granted scratch for this many samples only
@@ -124,6 +127,8 @@ struct DeviceCache {
 struct trt_scene {
     SceneHost host;
     FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h) and axis-exact-quads switch (axis_quads.h), derived once from host.blob
+    std::vector<uint32_t> geo_index;              // ray queries: geometry insertion index of sphere k at [k], of quad k at [n_spheres + k] (the kernels know a
+                                                  // primitive as kind bit | index within its kind); derived once from the reference tree, outside the packed scene
     std::mutex mu;
     std::condition_variable cv;
     std::unordered_map<int, DeviceCache> dev;     // device ordinal -> cached device resources
@@ -609,7 +614,60 @@ void set_flat_reuse(trt_scene* s) {
     s->flat_reuse = FlatReuse{m[0], m[1], m[2], aq};
 }
 
+// The per-kind -> insertion-index table of the ray queries, from what both scene compilers leave on the handle: leaf i of the reference tree's
+// dump names its geometry (prim_geo), the packed node's link names the same primitive the kernels' way.
+void set_geo_index(trt_scene* s) {
+    const SceneLayout& L = s->host.layout;
+    const std::vector<int32_t>& geo = s->host.reference.prim_geo;
+    s->geo_index.assign((size_t)L.n_spheres + L.n_quads, 0xFFFFFFFFu);
+    const size_t end = 16u * ((size_t)L.off_ref_nodes + 2u * (size_t)L.n_nodes);
+    if (geo.size() < L.n_nodes || s->host.blob.size() < end) return;
+    for (uint32_t i = 0; i < L.n_nodes; i++) {
+        if (geo[i] < 0) continue;
+        uint32_t link;
+        memcpy(&link, s->host.blob.data() + 16u * ((size_t)L.off_ref_nodes + 2u * (size_t)i + 1u) + 12u, 4);
+        const size_t slot = (size_t)(link & PRIM_INDEX_MASK) + ((link & PRIM_QUAD_BIT) ? L.n_spheres : 0u);
+        if (!(link & NODE_INNER_BIT) && slot < s->geo_index.size()) s->geo_index[slot] = (uint32_t)geo[i];
+    }
+}
+
 }  // namespace
+
+// The ray-query unit's view of this layer (scene_query.h)
+namespace trt {
+int query_fail(int code, const std::string& msg) { return fail(code, msg); }
+int query_fail_hip(hipError_t e, const char* what) { return fail_hip(e, what); }
+int query_require_device() { return require_device(); }
+// The scene and its index table on the current device, both uploaded on first use (one thread uploads, the others wait: scene_on_device).
+int query_scene_on_device(trt_scene* s, QueryScene& out) {
+    int rc = scene_on_device(s, out.scene);
+    if (rc != TRT_OK) return rc;
+    int dev = 0;
+    TRT_HIP(hipGetDevice(&dev));
+    std::unique_lock<std::mutex> lock(s->mu);
+    DeviceCache& dc = s->dev[dev];
+    while (dc.geo_index == nullptr && dc.geo_index_busy) s->cv.wait(lock);
+    if (dc.geo_index == nullptr) {
+        dc.geo_index_busy = true;
+        lock.unlock();
+        uint32_t* d = nullptr;
+        const size_t bytes = s->geo_index.size() * sizeof(uint32_t);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), bytes ? bytes : sizeof(uint32_t));
+        if (e == hipSuccess && bytes) {
+            e = hipMemcpy(d, s->geo_index.data(), bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(d); d = nullptr; }
+        }
+        lock.lock();
+        dc.geo_index_busy = false;
+        dc.geo_index = d;
+        s->cv.notify_all();
+        if (e != hipSuccess) return fail_hip(e, "geometry index upload");
+    }
+    out.geo_index = dc.geo_index;
+    out.flat_reuse = s->flat_reuse;
+    return TRT_OK;
+}
+}  // namespace trt
 
 // The device scene compiler's view of this layer (scene_adopt.h)
 namespace trt {
@@ -625,6 +683,7 @@ trt_scene* scene_adopt(SceneHost&& host, const trt_scene_options& opt, int devic
         trt_scene* s = new trt_scene();
         s->host = std::move(host);
         set_flat_reuse(s);
+        set_geo_index(s);
         s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
         if (d_blob) s->dev[device].blob = static_cast<float4*>(d_blob);      // the first render on `device` does not upload again
         return s;
@@ -737,6 +796,7 @@ int trt_scene_create_ex(const trt_world* w, const trt_scene_options* options, tr
         std::string msg;
         if (!compile_scene(w->w, opt, s->host, msg)) { delete s; return fail(TRT_ERR_INVALID_ARG, msg); }
         set_flat_reuse(s);
+        set_geo_index(s);
         s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
         *out = s;
     } catch (const std::bad_alloc&) {
@@ -784,6 +844,7 @@ void trt_scene_destroy(trt_scene* s) {
         }
         for (RenderCtx* c : dc.ctx) context_destroy(c);               // after the workspaces: their events were recorded on these streams
         if (dc.blob) (void)hipFree(dc.blob);
+        if (dc.geo_index) (void)hipFree(dc.geo_index);
     }
     if (have_prev) (void)hipSetDevice(prev);
     (void)hipGetLastError();

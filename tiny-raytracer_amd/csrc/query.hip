@@ -1,0 +1,319 @@
+// query.hip — ray queries (tinyrt.h trt_intersect / trt_occluded and their device forms), written for gfx950 (CDNA4) only.
+//
+// The question a BVH is built to answer, for caller-supplied rays: what does ray i hit in [0.001, t_max[i]) - BVH::hit
+// (hittable/bvh.rs:24-27,88-107), bit for bit - or, for the occlusion form, whether it hits anything there at all.  There is no walk code
+// in this file: the kernels call the entry points of rt_path.h the way streamed.hip does (stage_scene_to_lds, axis_quads_to_lds,
+// trav_begin, closest_hit, closest_hit_resume, trav_unpark) with the dynamic LDS laid out as streamed.hip lays it out (scene copy | leaf
+// stack: threads x slots x 8 bytes), and run the walk the streamed launch plan picks for the scene (query_plan below).
+//
+// Work: a wave owns a contiguous run of the caller's rays, in the caller's order - nothing is sorted or compacted, coherence is the
+// caller's business.  With the two resumable walks (LDS tree, 16-byte nodes) the wave works in the rounds of stream_sample_kernel: a lane
+// whose walk completed writes its answer and takes the next ray of the run, a lane whose walk is still under way when at most
+// `stragglers` lanes walk parks it in its leaf stack and resumes beside the fresh rays, so one long walk does not hold 63 lanes.  The
+// other walks (lock-step list, register slots) run to their end, 64 rays of the run at a time.
+//
+// The occlusion kernels are the same template with the walks' ANY switch (rt_path.h closest_hit_ref): the walk ends after the leaf phase in
+// which a primitive was first accepted, and one byte is written per ray instead of a 28-byte record.
+#include "kernels.h"
+#include "rt_path.h"
+#include "scene_query.h"
+
+namespace trt {
+
+static_assert(sizeof(trt_hit) == 28 && offsetof(trt_hit, normal) == 16, "trt_hit layout (tinyrt.h)");
+
+TRT_DEV uint32_t q_rank(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+TRT_DEV Ray q_load_ray(const float* __restrict__ rays, uint32_t idx) {
+    const float* r = rays + 6ull * idx;
+    Ray ray;
+    ray.o = v3(r[0], r[1], r[2]);
+    ray.d = v3(r[3], r[4], r[5]);
+    return ray;
+}
+
+// The answer of one ray.  ANY: one byte.  Else the record of HitRecord::new (hittable/mod.rs:28-48) for the winning primitive, restated
+// from the lines of rt_path.h shade_hit that compute front_face, normal and the material index, in their operation order; `geometry` is
+// the primitive's insertion index (scene_query.h geo_index).  A miss: t = +inf, geometry = material = 0xFFFFFFFF, everything else 0.
+template <int MODE, bool ANY>
+TRT_DEV void q_store(const SceneAcc<MODE>& sc, const uint32_t* __restrict__ geo_index, void* __restrict__ out, uint32_t idx, const Ray& ray,
+                     uint32_t prim, float t) {
+    if constexpr (ANY) {
+        static_cast<uint8_t*>(out)[idx] = prim != PRIM_NONE ? 1u : 0u;
+    } else {
+        uint32_t* const rec = reinterpret_cast<uint32_t*>(static_cast<trt_hit*>(out) + idx);
+        if (prim == PRIM_NONE) {
+            rec[0] = __float_as_uint(__builtin_inff()); rec[1] = 0xFFFFFFFFu; rec[2] = 0xFFFFFFFFu; rec[3] = 0u;
+            rec[4] = 0u; rec[5] = 0u; rec[6] = 0u;
+            return;
+        }
+        const uint32_t k = prim & PRIM_INDEX_MASK;
+        V3 normal;
+        bool front_face;
+        uint32_t mat;
+        if (prim & PRIM_QUAD_BIT) {
+            const float4 q0 = sc.quad(0, k), q1 = sc.quad(1, k), q4 = sc.quad(4, k);
+            front_face = dot(ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;          // outward normal = n, un-normalised (quad.rs:45)
+            const V3 nu = v3(q4.y, q4.z, q4.w);                            // n.normalized(), precomputed on the host
+            normal = front_face ? nu : -nu;
+            mat = __float_as_uint(q1.w);
+        } else {
+            const float4 sp = sc.sphere(k);
+            const V3 outward = ray_at(ray, t) - v3(sp.x, sp.y, sp.z);      // sphere.rs:47-51 (p = ray.at(t))
+            front_face = dot(ray.d, outward) < 0.0f;
+            const V3 nu = normalized(outward);
+            normal = front_face ? nu : -nu;
+            mat = sc.sphere_material(k);
+        }
+        rec[0] = __float_as_uint(t);
+        rec[1] = geo_index[k + ((prim & PRIM_QUAD_BIT) ? sc.L.n_spheres : 0u)];
+        rec[2] = mat;
+        rec[3] = front_face ? 1u : 0u;
+        rec[4] = __float_as_uint(normal.x); rec[5] = __float_as_uint(normal.y); rec[6] = __float_as_uint(normal.z);
+    }
+}
+
+struct QueryArgs {
+    const float* rays;               // n x (origin, direction), used as given
+    const float* t_max;              // n, or nullptr = +inf for every ray
+    void* out;                       // n x trt_hit, or n bytes (ANY)
+    const uint32_t* geo_index;
+    uint32_t n, rays_per_wave;       // wave w owns rays [w * rays_per_wave, ...)
+    uint32_t slots, stragglers;      // leaf stack depth per lane; resumable walks: lanes that may carry a walk into the next round
+    FlatReuse flat_reuse;
+};
+
+template <int MODE, int WALK, bool ANY, int THREADS, int MINW>
+__global__ __launch_bounds__(THREADS, MINW) void query_kernel(SceneDev scd, QueryArgs qa, const float4* __restrict__ leaf_list,
+                                                                   const uint4* __restrict__ nodes16) {
+    stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, qa.flat_reuse);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const float* __restrict__ const rays = qa.rays;
+    const float* __restrict__ const t_max = qa.t_max;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    const unsigned long long begin64 = (unsigned long long)wave * qa.rays_per_wave;
+    if (begin64 >= qa.n) return;                                            // (after the barriers above)
+    const uint32_t begin = (uint32_t)begin64;
+    const uint32_t count = qa.n - begin < qa.rays_per_wave ? qa.n - begin : qa.rays_per_wave;
+    // postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave (streamed.hip)
+    float2* const stack = WALK != WALK_REGS
+        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * qa.slots) + lane
+        : nullptr;
+    Counters<false> ctr;
+    constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
+
+    if constexpr (kResumable) {
+        uint32_t cursor = 0;                                                // wave-uniform
+        bool has = false, walking = false;
+        uint32_t idx = 0;
+        float tm = 0.0f;
+        Ray ray;
+        ray.o = v3(0.0f, 0.0f, 0.0f); ray.d = v3(0.0f, 0.0f, 0.0f);
+        for (;;) {
+            const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
+            if (need != 0ull && cursor < count) {
+                const uint32_t item = cursor + q_rank(need);
+                if (!has && item < count) {
+                    idx = begin + item;
+                    ray = q_load_ray(rays, idx);
+                    tm = t_max ? t_max[idx] : __builtin_inff();
+                    if (tm > kTMin) has = true;
+                    else q_store<MODE, ANY>(sc, qa.geo_index, qa.out, idx, ray, PRIM_NONE, 0.0f);      // an empty or NaN range: a miss, not walked
+                }
+                cursor += (uint32_t)__builtin_popcountll(need);
+                if (cursor > count) cursor = count;
+            }
+            if (__builtin_amdgcn_ballot_w64(has) == 0ull) {
+                if (cursor >= count) break;
+                continue;                                                   // every ray taken in this round had an empty range
+            }
+            if (has) {
+                Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, ray, false);      // a new walk, or the frame of a parked one
+                if (walking) trav_unpark(stack, tr); else tr.t_best = tm;
+                const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+                walking = !closest_hit_resume<MODE, false, WALK, ANY>(sc, ray, tr, ctr, qa.slots, stack, leaf_list, nodes16, qa.stragglers, entered);
+                if (!walking) {
+                    q_store<MODE, ANY>(sc, qa.geo_index, qa.out, idx, ray, tr.prim_best, tr.t_best);
+                    has = false;
+                }
+            }
+        }
+    } else {
+        for (uint32_t base = 0; base < count; base += 64u) {
+            if (base + lane < count) {
+                const uint32_t idx = begin + base + lane;
+                const Ray ray = q_load_ray(rays, idx);
+                const float tm = t_max ? t_max[idx] : __builtin_inff();
+                float t = 0.0f;
+                uint32_t prim = PRIM_NONE;
+                if (tm > kTMin) prim = closest_hit<MODE, false, WALK, ANY>(sc, ray, false, t, ctr, qa.slots, stack, leaf_list, nodes16, flat_reuse, tm);
+                q_store<MODE, ANY>(sc, qa.geo_index, qa.out, idx, ray, prim, t);
+            }
+        }
+    }
+}
+
+namespace {
+
+constexpr size_t kQueryLdsPerCu = 160u * 1024u;
+inline size_t q_align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+struct QueryKernel {
+    const void* closest;
+    const void* any;
+    int mode, walk, threads, minw;
+};
+#define TRT_QUERY(MODE, WALK, THREADS, MINW)                                                                      \
+    QueryKernel{reinterpret_cast<const void*>(&query_kernel<MODE, WALK, false, THREADS, MINW>),                 \
+                reinterpret_cast<const void*>(&query_kernel<MODE, WALK, true, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// one instantiation per (scene mode, walk, workgroup shape) the streamed launch plan produces under the default tuning, plus the
+// register-slot walk for a scene in global memory whose 16-byte nodes a scene option has removed
+const QueryKernel kQueryKernels[] = {
+    TRT_QUERY(MODE_LDS, WALK_FLAT, 256, 8),
+    TRT_QUERY(MODE_LDS, WALK_LDS_STACK, 256, 8),
+    TRT_QUERY(MODE_LDS, WALK_LDS_STACK, 768, 6),
+    TRT_QUERY(MODE_LDS, WALK_REGS, 512, 6),
+    TRT_QUERY(MODE_GLOBAL, WALK_COMPACT, 256, 8),
+    TRT_QUERY(MODE_GLOBAL, WALK_REGS, 256, 8),
+};
+#undef TRT_QUERY
+
+// How a query batch is launched on this scene: the walk, workgroup shape and leaf-stack depth of the streamed launch plan under the
+// built-in tuning (streamed.hip streamed_launch_plan: the rule lives there and is not restated), without the ray pool.
+struct QueryPlan {
+    const QueryKernel* k;
+    uint32_t slots, stragglers, wg_per_cu;
+    size_t lds_bytes;
+};
+QueryPlan query_plan(const SceneLayout& L) {
+    const trt_tuning tn = tuning_builtin();
+    RenderArgs ra{};
+    ra.lds_leaf_stack = tn.lds_leaf_stack;
+    ra.leaf_slots = tn.leaf_slots;
+    const StreamLaunchPlan pl = streamed_launch_plan(L, ra, tn, false);
+    QueryPlan q{};
+    int walk = pl.walk, threads = pl.threads;
+    auto find = [&] {
+        for (const QueryKernel& k : kQueryKernels)
+            if (k.mode == pl.mode && k.walk == walk && k.threads == threads) return &k;
+        return static_cast<const QueryKernel*>(nullptr);
+    };
+    q.k = find();
+    if (!q.k) {
+        // a plan only scene options reach (16-byte nodes switched off, the lock-step list forced on a large scene, ...): the
+        // register-slot walk, which every scene has
+        walk = WALK_REGS;
+        threads = pl.mode == MODE_LDS ? 512 : 256;
+        q.k = find();
+    }
+    if (!q.k) return q;
+    q.slots = walk == WALK_REGS ? 0u : pl.slots;
+    q.stragglers = walk == WALK_LDS_STACK ? tn.lds_stragglers : walk == WALK_COMPACT ? tn.stragglers : 0u;
+    if (q.slots < 2u) q.stragglers = 0u;                                            // a parked walk occupies two slots (rt_path.h trav_park)
+    const size_t scene_b = pl.scene_lds_bytes;
+    q.lds_bytes = q.slots ? q_align16(scene_b) + (size_t)threads * q.slots * sizeof(float2) : scene_b;
+    q.wg_per_cu = (uint32_t)(q.k->minw * 4 * 64 / q.k->threads);
+    if (q.lds_bytes) { const uint32_t by_lds = (uint32_t)(kQueryLdsPerCu / q.lds_bytes); if (by_lds < q.wg_per_cu) q.wg_per_cu = by_lds ? by_lds : 1u; }
+    return q;
+}
+
+hipError_t launch_query(const QueryScene& qs, const float* d_rays, const float* d_t_max, uint32_t n, void* d_out, bool any, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const SceneLayout& L = qs.scene.L;
+    const QueryPlan q = query_plan(L);
+    if (q.k == nullptr) return hipErrorInvalidDeviceFunction;                       // no instantiation for this plan: a bug, never a fallback
+    const bool flat = q.k->walk == WALK_FLAT, compact = q.k->walk == WALK_COMPACT;
+    // what the walks assume, checked where the launch is made
+    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.slots < 2u) || (compact && L.off_compact == 0u) ||
+        (q.k->walk != WALK_REGS && (q.slots < 1u || q.slots > kLdsLeafSlotsMax)))
+        return hipErrorInvalidConfiguration;
+    int dev = 0, cus = 256;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    // a wave's run: 256 rays (four refills of a wave, so that stragglers resume beside fresh rays) unless that makes more than four waves
+    // per resident wave slot - a workgroup of an LDS scene pays for its scene copy once, whatever the length of its runs
+    const uint32_t waves_per_wg = (uint32_t)q.k->threads / 64u;
+    const unsigned long long wave_slots = 4ull * (unsigned long long)cus * q.wg_per_cu * waves_per_wg;
+    unsigned long long per_wave = 256ull;
+    if (((unsigned long long)n + per_wave - 1ull) / per_wave > wave_slots) per_wave = (((unsigned long long)n + wave_slots - 1ull) / wave_slots + 63ull) & ~63ull;
+    const unsigned long long waves = ((unsigned long long)n + per_wave - 1ull) / per_wave;
+    const uint32_t grid = (uint32_t)((waves + waves_per_wg - 1ull) / waves_per_wg);
+    const void* fn = any ? q.k->any : q.k->closest;
+    if (q.lds_bytes > 48u * 1024u) {
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    SceneDev scd = qs.scene;
+    QueryArgs qa{d_rays, d_t_max, d_out, qs.geo_index, n, (uint32_t)per_wave, q.slots, q.stragglers, qs.flat_reuse};
+    const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
+    const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
+    void* args[] = {&scd, &qa, &leaf_list, &nodes16};
+    return hipLaunchKernel(fn, dim3(grid), dim3((uint32_t)q.k->threads), args, q.lds_bytes, stream);
+}
+
+// Argument checks shared by the four entry points: TRT_ERR_INVALID_ARG before any device work, then TRT_ERR_NO_DEVICE (trt_sample_batch's order).
+int query_check(const trt_scene* s, const void* rays, uint32_t n, const void* out) {
+    if (!s) return query_fail(TRT_ERR_INVALID_ARG, "scene is null");
+    if (n && (!rays || !out)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
+    return query_require_device();
+}
+
+int query_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, void* d_out, bool any, void* stream) {
+    int rc = query_check(s, d_rays, n, d_out);
+    if (rc != TRT_OK || n == 0) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = launch_query(qs, reinterpret_cast<const float*>(d_rays), d_t_max, n, d_out, any, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return query_fail_hip(e, "ray query launch");
+    return TRT_OK;
+}
+
+// Host buffers: device copies of the call's own, one stream-ordered sequence on the default stream, complete when the call returns.
+int query_host(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, void* out, size_t out_stride, bool any) {
+    int rc = query_check(s, rays, n, out);
+    if (rc != TRT_OK || n == 0) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const size_t rays_b = (size_t)n * sizeof(trt_ray), tmax_b = t_max ? (size_t)n * sizeof(float) : 0u, out_b = (size_t)n * out_stride;
+    const size_t off_tmax = q_align16(rays_b), off_out = off_tmax + q_align16(tmax_b);
+    char* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), off_out + out_b);
+    if (e != hipSuccess) { (void)hipGetLastError(); return query_fail(TRT_ERR_OOM, std::string("ray query buffers: ") + hipGetErrorString(e)); }
+    const char* what = "hipMemcpy of the rays";
+    e = hipMemcpy(d, rays, rays_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess && t_max) { what = "hipMemcpy of t_max"; e = hipMemcpy(d + off_tmax, t_max, tmax_b, hipMemcpyHostToDevice); }
+    if (e == hipSuccess) {
+        what = "ray query launch";
+        e = launch_query(qs, reinterpret_cast<const float*>(d), t_max ? reinterpret_cast<const float*>(d + off_tmax) : nullptr, n, d + off_out, any, nullptr);
+    }
+    if (e == hipSuccess) { what = "hipMemcpy of the answers"; e = hipMemcpy(out, d + off_out, out_b, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
+    (void)hipFree(d);
+    if (e != hipSuccess) return query_fail_hip(e, what);
+    return TRT_OK;
+}
+
+}  // namespace
+}  // namespace trt
+
+extern "C" {
+
+int trt_intersect(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, trt_hit* hits) {
+    return trt::query_host(s, rays, t_max, n, hits, sizeof(trt_hit), false);
+}
+int trt_occluded(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, uint8_t* occluded) {
+    return trt::query_host(s, rays, t_max, n, occluded, 1u, true);
+}
+int trt_intersect_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, trt_hit* d_hits, void* stream) {
+    return trt::query_device(s, d_rays, d_t_max, n, d_hits, false, stream);
+}
+int trt_occluded_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, uint8_t* d_occluded, void* stream) {
+    return trt::query_device(s, d_rays, d_t_max, n, d_occluded, true, stream);
+}
+
+}  // extern "C"

@@ -238,7 +238,10 @@ TRT_DEV bool ray_has_nan(const Ray& r) {
 
 // The rare walks: reference tree (counting kernels) and rays whose slab arithmetic needs the reference's
 // compare-and-assign form.  Runs the walk `tr` to its end.
-template <int MODE, bool STATS>
+// ANY (every walk below has the switch; false in every render kernel): an any-hit query - the walk ends after the leaf phase in which a
+// primitive was first accepted.  Up to that acceptance t_best is still the caller's t_max, so the shortened walk is a prefix of the full
+// one, and a first acceptance exists exactly when a final hit does: tr.prim_best != PRIM_NONE is the full walk's "hit?".
+template <int MODE, bool STATS, bool ANY = false>
 TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr, uint32_t axis_quads = 0u) {
     if constexpr (!STATS) {
         if (ray_has_nan(ray)) { tr.i = tr.n; return; }              // nothing can be hit (see ray_has_nan): t_best = inf, prim_best = PRIM_NONE
@@ -252,6 +255,7 @@ TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr,
         if (leaf == PRIM_NONE) break;
         if constexpr (STATS) { if (first_active_lane()) ctr.w_leaf++; }
         trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, axis_quads);
+        if constexpr (ANY) { if (tr.prim_best != PRIM_NONE) { tr.i = tr.n; break; } }
     }
 }
 
@@ -271,7 +275,7 @@ TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr,
 //    `start` kept beside the postponed leaf.  That is bit for bit the reference's box test at the moment the
 //    reference stands on this leaf (same operands, same t_best), and the leaf's ancestors pass whenever the leaf does
 //    (DESIGN.md 4.1), so the primitive is tested exactly when the reference tests it.
-template <int MODE, bool STATS, int SLOTS>
+template <int MODE, bool STATS, int SLOTS, bool ANY = false>
 TRT_DEV void walk_fast(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr) {
     const uint32_t n = sc.L.n_cull_nodes;
     for (;;) {
@@ -309,6 +313,7 @@ TRT_DEV void walk_fast(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Count
             for (int k = 0; k + 1 < SLOTS; k++) { pend[k] = pend[k + 1]; entry[k] = entry[k + 1]; }
             pend[SLOTS - 1] = PRIM_NONE;
         }
+        if constexpr (ANY) { if (tr.prim_best != PRIM_NONE) { tr.i = n; break; } }
     }
 }
 
@@ -452,7 +457,7 @@ TRT_DEV float2* box_loop_lds(Trav& tr, const V3& o, float2* stk, float2* limit, 
 // 64 rays are spread widely (random-spheres: mean 26 box steps, 95th percentile 47, longest of 64 about 55), and a round runs as many trips
 // as its longest walk: carrying the few long ones into the next round cuts the trips per ray by a third in the model
 // (tools/proto/cull_tree_model.c + the walk-length replay in profiles/r03_stragglers_model.txt).
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, bool ANY = false>
 TRT_DEV bool walk_fast_lds(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr, float2* stk, uint32_t slots,
                            uint32_t stragglers = 0u, uint32_t entered = 64u) {
     const uint32_t n = sc.L.n_cull_nodes;
@@ -487,6 +492,7 @@ TRT_DEV bool walk_fast_lds(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, C
         if (top == stk && tr.i >= n) return true;
         if (top != stk) leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr); });
         TRT_CLK(ctr, 2);
+        if constexpr (ANY) { if (tr.prim_best != PRIM_NONE) tr.i = n; }                   // any-hit: the walk is over (the leaf stack is empty here)
         if (tr.i >= n) return true;
         if ((uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true)) <= few) { trav_park(stk, tr); return false; }
     }
@@ -600,7 +606,7 @@ TRT_DEV uint32_t flat_axes(const FlatReuse& r, uint32_t i) {
 // The loop is software-pipelined by hand: a trip tests TWO leaves, and the scalar loads of the next trip's pair are
 // issued before this trip's boxes are tested (the compiler otherwise waits for each node right after requesting it,
 // `s_load_dwordx4; s_waitcnt lgkmcnt(0)`, once per box step, and spends 3 branches and ~10 scalar instructions per step).
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, bool ANY = false>
 TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf_list, const Ray& ray, Trav& tr, Counters<STATS>& ctr,
                        float2* stk, uint32_t slots, FlatReuse reuse) {
     const uint32_t n = sc.L.n_leaves;                    // >= 1
@@ -612,6 +618,9 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
             TRT_CLK(ctr, 1);
             leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
             TRT_CLK(ctr, 2);
+            // any-hit: the lanes step the list together, so the wave leaves once every lane has accepted a primitive (a lane that has one
+            // goes on testing with its shrunken t_best, which cannot take its hit away)
+            if constexpr (ANY) { if (__builtin_amdgcn_ballot_w64(tr.prim_best == PRIM_NONE) == 0ull) return; }
         } while (i < n);
         return;
     }
@@ -649,6 +658,7 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
         if constexpr (STATS) ctr.pend += (uint32_t)(top - stk) >> 6;
         leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
         TRT_CLK(ctr, 2);
+        if constexpr (ANY) { if (__builtin_amdgcn_ballot_w64(tr.prim_best == PRIM_NONE) == 0ull) return; }
     } while (i < n);
 }
 
@@ -756,7 +766,7 @@ TRT_DEV float2* box_loop_compact(Trav& tr, const V3& o, const uint4* __restrict_
 // last third of the trips behind a few long walks (100 k spheres: 324 trips per round for 222 box steps per ray).  Measured:
 // +10 % on that scene in round 2; since round 3 (exit test inside the box-step loop, walk state parked in the leaf stack) the
 // LDS-resident tree walk is resumable too (walk_fast_lds: random-spheres +10 %).
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, bool ANY = false>
 TRT_DEV bool walk_compact(const SceneAcc<MODE>& sc, const uint4* __restrict__ nodes16, const float4* __restrict__ leaf_list,
                           const Ray& ray, Trav& tr, Counters<STATS>& ctr, float2* stk, uint32_t slots, uint32_t stragglers = 0u,
                           uint32_t entered = 64u) {
@@ -795,6 +805,7 @@ TRT_DEV bool walk_compact(const SceneAcc<MODE>& sc, const uint4* __restrict__ no
         // reference's leaf-box test on the exact f32 box, at the leaf's turn.
         if (top != stk) leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { compact_leaf_test<MODE, STATS>(sc, leaf_list, ray, tr, leaf, ctr); });
         TRT_CLK(ctr, 2);
+        if constexpr (ANY) { if (tr.prim_best != PRIM_NONE) tr.i = n; }                   // any-hit: the walk is over (the leaf stack is empty here)
         if (tr.i >= n) return true;
         if ((uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true)) <= few) { trav_park(stk, tr); return false; }      // resumable: see walk_fast_lds
     }
@@ -960,33 +971,36 @@ TRT_DEV FlatReuse axis_quads_to_lds(const SceneDev& sc, FlatReuse reuse) {
 // Whole walk for one lane.  Returns the primitive reference (PRIM_NONE on a miss) and its t.  Postponed leaves go to
 // `lds_stack` (this lane's slot 0 of a `leaf_slots`-deep LDS stack) if the kernel has one, else into registers:
 // `leaf_slots` = 4 (also for 0 = default), 2 or 1 (tuning and tests; wave-uniform).
-template <int MODE, bool STATS, int WALK = WALK_RUNTIME>
+// `t_max`: the exclusive end of the query, the walk's first t_best (the render kernels' cpu.rs:48 range ends at +inf); ANY: see closest_hit_ref.
+template <int MODE, bool STATS, int WALK = WALK_RUNTIME, bool ANY = false>
 TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_tree, float& t_hit, Counters<STATS>& ctr,
                              uint32_t leaf_slots = 4u, float2* lds_stack = nullptr, const float4* __restrict__ leaf_list = nullptr,
-                             const uint4* __restrict__ nodes16 = nullptr, FlatReuse flat_reuse = FlatReuse{0u, 0u, 0u}) {
+                             const uint4* __restrict__ nodes16 = nullptr, FlatReuse flat_reuse = FlatReuse{0u, 0u, 0u},
+                             float t_max = __builtin_inff()) {
     // (a general kernel reaches walk_compact's loop whenever it is handed the 16-byte nodes and an LDS stack: same domain as the specialised ones)
     const bool fused_loop = kAsmBoxLoop && !STATS && (WALK == WALK_COMPACT || (WALK == WALK_RUNTIME && lds_stack != nullptr && nodes16 != nullptr));
     Trav tr = trav_begin<MODE>(sc, ray, ref_tree, fused_loop);
+    tr.t_best = t_max;
     if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) flat_reuse.axis_quads = 0u;      // (axis_quads_to_lds: no other kernel rewrites its records)
     if (__builtin_expect(!tr.ref, 1)) {
         if constexpr (WALK == WALK_COMPACT) {
-            walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
+            walk_compact<MODE, STATS, ANY>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
         } else if constexpr (WALK == WALK_FLAT) {
-            walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
+            walk_flat<MODE, STATS, ANY>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
         } else if constexpr (WALK == WALK_LDS_STACK) {
-            walk_fast_lds<MODE, STATS>(sc, ray, tr, ctr, lds_stack, leaf_slots);
+            walk_fast_lds<MODE, STATS, ANY>(sc, ray, tr, ctr, lds_stack, leaf_slots);
         } else if constexpr (WALK == WALK_REGS) {
-            walk_fast<MODE, STATS, 4>(sc, ray, tr, ctr);
+            walk_fast<MODE, STATS, 4, ANY>(sc, ray, tr, ctr);
         } else {
-            if (lds_stack != nullptr && nodes16 != nullptr) walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
-            else if (lds_stack != nullptr && leaf_list != nullptr) walk_flat<MODE, STATS>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
-            else if (lds_stack != nullptr) walk_fast_lds<MODE, STATS>(sc, ray, tr, ctr, lds_stack, leaf_slots);
-            else if (leaf_slots >= 4u || leaf_slots == 0u) walk_fast<MODE, STATS, 4>(sc, ray, tr, ctr);
-            else if (leaf_slots >= 2u) walk_fast<MODE, STATS, 2>(sc, ray, tr, ctr);
-            else walk_fast<MODE, STATS, 1>(sc, ray, tr, ctr);
+            if (lds_stack != nullptr && nodes16 != nullptr) walk_compact<MODE, STATS, ANY>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
+            else if (lds_stack != nullptr && leaf_list != nullptr) walk_flat<MODE, STATS, ANY>(sc, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, flat_reuse);
+            else if (lds_stack != nullptr) walk_fast_lds<MODE, STATS, ANY>(sc, ray, tr, ctr, lds_stack, leaf_slots);
+            else if (leaf_slots >= 4u || leaf_slots == 0u) walk_fast<MODE, STATS, 4, ANY>(sc, ray, tr, ctr);
+            else if (leaf_slots >= 2u) walk_fast<MODE, STATS, 2, ANY>(sc, ray, tr, ctr);
+            else walk_fast<MODE, STATS, 1, ANY>(sc, ray, tr, ctr);
         }
     } else {
-        closest_hit_ref<MODE, STATS>(sc, ray, tr, ctr, flat_reuse.axis_quads);
+        closest_hit_ref<MODE, STATS, ANY>(sc, ray, tr, ctr, flat_reuse.axis_quads);
     }
     t_hit = tr.t_best;
     return tr.prim_best;
@@ -995,15 +1009,15 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
 // The per-lane tree walks in resumable form (WALK_COMPACT: 16-byte nodes from global memory; WALK_LDS_STACK: the culling tree in LDS): `tr`
 // is set up by the caller (trav_begin) when the ray starts its walk and kept while the function returns false.  Returns true when the
 // walk is complete (tr.t_best / tr.prim_best).
-template <int MODE, bool STATS, int WALK>
+template <int MODE, bool STATS, int WALK, bool ANY = false>
 TRT_DEV bool closest_hit_resume(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, Counters<STATS>& ctr, uint32_t leaf_slots, float2* lds_stack,
                                 const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16, uint32_t stragglers, uint32_t entered) {
     static_assert(WALK == WALK_COMPACT || WALK == WALK_LDS_STACK, "only the per-lane tree walks with an LDS leaf stack can be left and resumed");
     if (__builtin_expect(!tr.ref, 1)) {
-        if constexpr (WALK == WALK_COMPACT) return walk_compact<MODE, STATS>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, stragglers, entered);
-        else return walk_fast_lds<MODE, STATS>(sc, ray, tr, ctr, lds_stack, leaf_slots, stragglers, entered);
+        if constexpr (WALK == WALK_COMPACT) return walk_compact<MODE, STATS, ANY>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots, stragglers, entered);
+        else return walk_fast_lds<MODE, STATS, ANY>(sc, ray, tr, ctr, lds_stack, leaf_slots, stragglers, entered);
     }
-    closest_hit_ref<MODE, STATS>(sc, ray, tr, ctr);
+    closest_hit_ref<MODE, STATS, ANY>(sc, ray, tr, ctr);
     return true;
 }
 

@@ -1,0 +1,25 @@
+// scene_query.h - what the ray-query unit (query.hip) needs from the C ABI layer (capi.hip): the thread-local error message, the device
+// check and the device view of a scene handle - the packed scene plus the queries' index table, both uploaded on first use and freed
+// with the scene.  capi.hip calls nothing in query.hip, so the host-only build of capi.hip links without it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "kernels.h"
+
+namespace trt {
+struct QueryScene {
+    SceneDev scene;
+    const uint32_t* geo_index;       // geometry insertion index of sphere k at [k], of quad k at [n_spheres + k]
+    FlatReuse flat_reuse;            // the lock-step walk's schedule for this scene (kernels.h)
+};
+// sets the thread-local message trt_last_error returns; returns `code`
+int query_fail(int code, const std::string& msg);
+int query_fail_hip(hipError_t e, const char* what);
+// TRT_OK, or TRT_ERR_NO_DEVICE (message set)
+int query_require_device();
+// the scene on the calling thread's current device
+int query_scene_on_device(trt_scene* s, QueryScene& out);
+}  // namespace trt
