@@ -209,6 +209,29 @@ pub struct trt_launch_plan {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_query_plan {
+    pub scene_mode: u32,
+    pub walk: u32,
+    pub threads_per_workgroup: u32,
+    pub kernel_waves_per_simd: u32,
+    pub workgroups_per_cu: u32,
+    pub leaf_slots: u32,
+    pub stragglers: u32,
+    pub lds_bytes: u32,
+    pub scene_lds_bytes: u32,
+    pub has_kernel: u32,
+    pub fallback: u32,
+    pub streamed_walk: u32,
+    pub streamed_threads: u32,
+    pub compute_units: u32,
+    pub rays_per_wave: u32,
+    pub workgroups: u32,
+    pub wave_slots: u64,
+    pub waves: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct trt_stats {
     pub samples: u64,
     pub rays: u64,
@@ -279,6 +302,7 @@ extern "C" {
                                 stream: *mut c_void) -> c_int;
     pub fn trt_occluded_device(s: *mut trt_scene, d_rays: *const trt_ray, d_t_max: *const f32, n: u32, d_occluded: *mut u8,
                                stream: *mut c_void) -> c_int;
+    pub fn trt_query_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_tonemap_u8(accum: *const f32, npixels: u32, gamma: f32, rgb: *mut u8) -> c_int;
     pub fn trt_tonemap_u8_device(d_accum: *const f32, npixels: u32, gamma: f32, d_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn trt_streamed_chunk_spp(width: u32, rows: u32) -> u32;

@@ -38,7 +38,7 @@ extern "C" {
                              *              tree levels is gone: measured slower in every form); d_counters[12..15] = shades by material kind.
                              *              No struct changed size or moved a field.
  *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed; trt_hit, trt_intersect, trt_occluded,
- *              trt_intersect_device, trt_occluded_device. */
+ *              trt_intersect_device, trt_occluded_device; trt_query_plan, trt_query_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -314,6 +314,28 @@ int trt_occluded(trt_scene *s, const trt_ray *rays, const float *t_max, uint32_t
  * NULL = default): returns after enqueueing; the caller synchronises the stream. */
 int trt_intersect_device(trt_scene *s, const trt_ray *d_rays, const float *d_t_max, uint32_t n, trt_hit *d_hits, void *stream);
 int trt_occluded_device(trt_scene *s, const trt_ray *d_rays, const float *d_t_max, uint32_t n, uint8_t *d_occluded, void *stream);
+
+/* How a query batch of n rays is launched on this scene (host arithmetic only, the one copy of the rule: the four entry points above take
+ * their numbers from it).  The kernel follows the streamed launch plan of the scene under the built-in tuning (streamed_walk,
+ * streamed_threads); a plan without a query instantiation runs the register-slot walk instead (fallback = 1).  A wave owns rays_per_wave
+ * consecutive rays: 256, or more - a multiple of 64 - once ceil(n / 256) exceeds wave_slots = 4 x compute_units x workgroups_per_cu x
+ * waves per workgroup.  compute_units == 0: the count of the calling thread's current device (TRT_ERR_NO_DEVICE without one); any other
+ * value needs no device, so the invariants can be checked for every scene, option and batch size without a GPU (tests/test_query_abi.py). */
+typedef struct {
+    uint32_t scene_mode;              /* 0 scene read from global memory, 1 whole hot scene copied into LDS */
+    uint32_t walk;                    /* numbered as trt_launch_plan.walk: 1 LDS tree, 2 lock-step list, 3 16-byte nodes, 5 register slots */
+    uint32_t threads_per_workgroup, kernel_waves_per_simd, workgroups_per_cu;
+    uint32_t leaf_slots, stragglers;  /* LDS leaf-stack depth per lane (0: register slots); lanes that may carry a walk into the next round */
+    uint32_t lds_bytes, scene_lds_bytes;      /* dynamic LDS per workgroup; the scene copy's share */
+    uint32_t has_kernel;              /* 0 would be a bug: the launch then fails */
+    uint32_t fallback;                /* 1: the streamed plan has no query instantiation, the register-slot walk answers */
+    uint32_t streamed_walk, streamed_threads; /* the streamed launch plan's walk and workgroup shape for this scene */
+    uint32_t compute_units;           /* as given, or the current device's */
+    uint32_t rays_per_wave;           /* wave w owns rays [w * rays_per_wave, ...) */
+    uint32_t workgroups;              /* the grid: ceil(waves / (threads_per_workgroup / 64)); 0 for n == 0 (nothing is launched) */
+    uint64_t wave_slots, waves;
+} trt_query_plan;
+int trt_query_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* Imager finalisation + Image -> RgbImage (imager.rs:52-53; utils/image.rs:92-111): c^(1/gamma),
  * clamp to [0, 0.999], *255, truncate; NaN -> 0.  HOST buffers, npixels*3 each. */

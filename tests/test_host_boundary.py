@@ -542,20 +542,22 @@ def test_band_copy_plan_places_every_row_exactly_once(trt, height, ndev):
 
 # ---- round 4 (ABI v3): configuration as data ----
 def test_abi3_pod_layouts_match_the_c_compiler(trt, tmp_path):
-    """trt_tuning, trt_scene_options, trt_render_params (with its pointer member), trt_stats and trt_launch_plan as ctypes lays them out against
+    """trt_tuning, trt_scene_options, trt_render_params (with its pointer member), trt_stats, trt_launch_plan and trt_query_plan as ctypes lays them out against
     what gcc makes of include/tinyrt.h: sizes and the offsets that an alignment rule could move."""
     import subprocess
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tinyrt.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", '
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tinyrt.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", '
                    'sizeof(trt_tuning), sizeof(trt_scene_options), offsetof(trt_scene_options, scratch_cap_bytes), sizeof(trt_render_params), '
                    'offsetof(trt_render_params, tuning), sizeof(trt_stats), offsetof(trt_stats, gather_per_band), sizeof(trt_launch_plan), '
-                   'offsetof(trt_launch_plan, workspace_bytes)); return 0; }\n')
+                   'offsetof(trt_launch_plan, workspace_bytes), sizeof(trt_query_plan), offsetof(trt_query_plan, rays_per_wave), '
+                   'offsetof(trt_query_plan, wave_slots), offsetof(trt_query_plan, waves)); return 0; }\n')
     exe = str(tmp_path / "sz")
     subprocess.run(["gcc", "-std=c11", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
     got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     L = trt._lib
     want = [C.sizeof(L.Tuning), C.sizeof(L.SceneOptions), L.SceneOptions.scratch_cap_bytes.offset, C.sizeof(L.RenderParams), L.RenderParams.tuning.offset,
-            C.sizeof(L.Stats), L.Stats.gather_per_band.offset, C.sizeof(L.LaunchPlan), L.LaunchPlan.workspace_bytes.offset]
+            C.sizeof(L.Stats), L.Stats.gather_per_band.offset, C.sizeof(L.LaunchPlan), L.LaunchPlan.workspace_bytes.offset,
+            C.sizeof(L.QueryPlan), L.QueryPlan.rays_per_wave.offset, L.QueryPlan.wave_slots.offset, L.QueryPlan.waves.offset]
     assert got == want, (got, want)
     assert C.sizeof(L.Tuning) == 96 and C.sizeof(L.SceneOptions) == 48
 

@@ -44,7 +44,7 @@ def scene_names():
 
 
 def scene(trt, name):
-    """The description (tiny-raytracer_amd.scenes format) of one of scene_names()."""
+    """The description (tiny-raytracer_amd.scenes format) of one of scene_names(), or of prims600 (the ray queries' tests only)."""
     import test_gpu_flat_reuse as fr
     from test_gpu_fuzz import random_scene
     if name == "cornell":
@@ -62,6 +62,8 @@ def scene(trt, name):
         return trt.scenes.random_spheres(8, 8)
     if name == "mixed400":
         return random_scene(1100, n_prims=400)
+    if name == "prims600":                                                  # an LDS copy of 59 680 B: planned as LDS tree / 512 lanes (queries: register slots)
+        return random_scene(1100, n_prims=600)
     if name == "mixed2600":
         return random_scene(11, n_prims=2600)
     if name == "degenerate":

@@ -77,6 +77,17 @@ class LaunchPlan(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class QueryPlan(C.Structure):
+    """tinyrt.h trt_query_plan: how a batch of n rays is launched on a scene."""
+    _fields_ = [(n, C.c_uint32) for n in
+                ("scene_mode", "walk", "threads_per_workgroup", "kernel_waves_per_simd", "workgroups_per_cu", "leaf_slots", "stragglers",
+                 "lds_bytes", "scene_lds_bytes", "has_kernel", "fallback", "streamed_walk", "streamed_threads", "compute_units",
+                 "rays_per_wave", "workgroups")] + [("wave_slots", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -156,6 +167,7 @@ SIGNATURES = {
     "trt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trt_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "trt_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "trt_query_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_streamed_chunk_spp": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "trt_tonemap_u8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "trt_tonemap_u8_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),

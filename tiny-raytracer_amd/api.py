@@ -168,6 +168,13 @@ class Scene:
         """Enqueue occluded() on buffers already in HBM (n bytes out, each 0 or 1); asynchronous on the stream."""
         check(lib.trt_occluded_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_t_max_ptr), int(n), C.c_void_p(d_occluded_ptr), C.c_void_p(stream_ptr)))
 
+    def query_plan(self, n, compute_units=0):
+        """trt_query_launch_plan: how intersect() / occluded() launch a batch of n rays on this scene, as a dict (host arithmetic only;
+        compute_units = 0: the current device's count, which needs a device)."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_query_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""

@@ -638,6 +638,7 @@ namespace trt {
 int query_fail(int code, const std::string& msg) { return fail(code, msg); }
 int query_fail_hip(hipError_t e, const char* what) { return fail_hip(e, what); }
 int query_require_device() { return require_device(); }
+const SceneLayout& query_scene_layout(const trt_scene* s) { return s->host.layout; }
 // The scene and its index table on the current device, both uploaded on first use (one thread uploads, the others wait: scene_on_device).
 int query_scene_on_device(trt_scene* s, QueryScene& out) {
     int rc = scene_on_device(s, out.scene);

@@ -169,8 +169,15 @@ struct QueryKernel {
 #define TRT_QUERY(MODE, WALK, THREADS, MINW)                                                                      \
     QueryKernel{reinterpret_cast<const void*>(&query_kernel<MODE, WALK, false, THREADS, MINW>),                 \
                 reinterpret_cast<const void*>(&query_kernel<MODE, WALK, true, THREADS, MINW>), MODE, WALK, THREADS, MINW}
-// one instantiation per (scene mode, walk, workgroup shape) the streamed launch plan produces under the default tuning, plus the
-// register-slot walk for a scene in global memory whose 16-byte nodes a scene option has removed
+// one instantiation per (scene mode, walk, workgroup shape) the streamed launch plan produces for the scenes the tuning was measured on:
+// lock-step list in LDS / 256 lanes (up to 32 primitives), LDS tree with the leaf stack in LDS at 256 and at 768 lanes, 16-byte nodes from
+// global memory; and the register-slot walk for LDS scenes (512 lanes) and for scenes in global memory (256 lanes).  The table does NOT
+// hold every plan the default tuning produces: an LDS scene too large for two 768-lane workgroups per CU but whose leaf stack still costs
+// no resident 512-lane workgroup (scene copies of roughly 56 to 64 KB) is planned as LDS tree / 512 lanes, which is not here, and
+// neither are the plans only scene options reach (a tree walk from global memory with the 16-byte nodes switched off; the lock-step
+// list forced on a scene of more than 32 primitives that is in LDS at 768 lanes or in global memory).  Those run the register-slot
+// instantiation of their scene mode (plan_query: fallback), which walks the culling tree every compiled scene carries and needs neither
+// the leaf list nor the 16-byte nodes.
 const QueryKernel kQueryKernels[] = {
     TRT_QUERY(MODE_LDS, WALK_FLAT, 256, 8),
     TRT_QUERY(MODE_LDS, WALK_LDS_STACK, 256, 8),
@@ -181,78 +188,87 @@ const QueryKernel kQueryKernels[] = {
 };
 #undef TRT_QUERY
 
-// How a query batch is launched on this scene: the walk, workgroup shape and leaf-stack depth of the streamed launch plan under the
-// built-in tuning (streamed.hip streamed_launch_plan: the rule lives there and is not restated), without the ray pool.
-struct QueryPlan {
-    const QueryKernel* k;
-    uint32_t slots, stragglers, wg_per_cu;
-    size_t lds_bytes;
-};
-QueryPlan query_plan(const SceneLayout& L) {
+// How a batch of n rays is launched on this scene with `cus` compute units (what trt_query_launch_plan reports and launch_query launches:
+// the one copy of the rule).  The walk, workgroup shape and leaf-stack depth are those of the streamed launch plan under the built-in
+// tuning (streamed.hip streamed_launch_plan: that rule lives there and is not restated), without the ray pool.  Returns the instantiation,
+// nullptr if there is none.
+const QueryKernel* plan_query(const SceneLayout& L, uint32_t n, uint32_t cus, trt_query_plan& q) {
     const trt_tuning tn = tuning_builtin();
     RenderArgs ra{};
     ra.lds_leaf_stack = tn.lds_leaf_stack;
     ra.leaf_slots = tn.leaf_slots;
     const StreamLaunchPlan pl = streamed_launch_plan(L, ra, tn, false);
-    QueryPlan q{};
+    q = trt_query_plan{};
+    q.scene_mode = (uint32_t)pl.mode;
+    q.streamed_walk = (uint32_t)pl.walk;
+    q.streamed_threads = (uint32_t)pl.threads;
+    q.scene_lds_bytes = (uint32_t)pl.scene_lds_bytes;
+    q.compute_units = cus;
     int walk = pl.walk, threads = pl.threads;
     auto find = [&] {
         for (const QueryKernel& k : kQueryKernels)
             if (k.mode == pl.mode && k.walk == walk && k.threads == threads) return &k;
         return static_cast<const QueryKernel*>(nullptr);
     };
-    q.k = find();
-    if (!q.k) {
-        // a plan only scene options reach (16-byte nodes switched off, the lock-step list forced on a large scene, ...): the
-        // register-slot walk, which every scene has
+    const QueryKernel* k = find();
+    if (!k) {
+        // a plan without an instantiation (see kQueryKernels): the register-slot walk, which every scene has
         walk = WALK_REGS;
         threads = pl.mode == MODE_LDS ? 512 : 256;
-        q.k = find();
+        q.fallback = 1u;
+        k = find();
     }
-    if (!q.k) return q;
-    q.slots = walk == WALK_REGS ? 0u : pl.slots;
+    if (!k) return nullptr;
+    q.has_kernel = 1u;
+    q.walk = (uint32_t)walk;
+    q.threads_per_workgroup = (uint32_t)threads;
+    q.kernel_waves_per_simd = (uint32_t)k->minw;
+    q.leaf_slots = walk == WALK_REGS ? 0u : pl.slots;
     q.stragglers = walk == WALK_LDS_STACK ? tn.lds_stragglers : walk == WALK_COMPACT ? tn.stragglers : 0u;
-    if (q.slots < 2u) q.stragglers = 0u;                                            // a parked walk occupies two slots (rt_path.h trav_park)
+    if (q.leaf_slots < 2u) q.stragglers = 0u;                                       // a parked walk occupies two slots (rt_path.h trav_park)
     const size_t scene_b = pl.scene_lds_bytes;
-    q.lds_bytes = q.slots ? q_align16(scene_b) + (size_t)threads * q.slots * sizeof(float2) : scene_b;
-    q.wg_per_cu = (uint32_t)(q.k->minw * 4 * 64 / q.k->threads);
-    if (q.lds_bytes) { const uint32_t by_lds = (uint32_t)(kQueryLdsPerCu / q.lds_bytes); if (by_lds < q.wg_per_cu) q.wg_per_cu = by_lds ? by_lds : 1u; }
-    return q;
+    const size_t lds_bytes = q.leaf_slots ? q_align16(scene_b) + (size_t)threads * q.leaf_slots * sizeof(float2) : scene_b;
+    q.lds_bytes = (uint32_t)lds_bytes;
+    q.workgroups_per_cu = (uint32_t)(k->minw * 4 * 64 / k->threads);
+    if (lds_bytes) { const uint32_t by_lds = (uint32_t)(kQueryLdsPerCu / lds_bytes); if (by_lds < q.workgroups_per_cu) q.workgroups_per_cu = by_lds ? by_lds : 1u; }
+    // a wave's run: 256 rays (four refills of a wave, so that stragglers resume beside fresh rays) unless that makes more than four waves
+    // per resident wave slot - a workgroup of an LDS scene pays for its scene copy once, whatever the length of its runs
+    const uint32_t waves_per_wg = (uint32_t)threads / 64u;
+    q.wave_slots = 4ull * (unsigned long long)cus * q.workgroups_per_cu * waves_per_wg;
+    unsigned long long per_wave = 256ull;
+    if (((unsigned long long)n + per_wave - 1ull) / per_wave > q.wave_slots) per_wave = (((unsigned long long)n + q.wave_slots - 1ull) / q.wave_slots + 63ull) & ~63ull;
+    q.rays_per_wave = (uint32_t)per_wave;
+    q.waves = ((unsigned long long)n + per_wave - 1ull) / per_wave;
+    q.workgroups = (uint32_t)((q.waves + waves_per_wg - 1ull) / waves_per_wg);
+    return k;
 }
 
 hipError_t launch_query(const QueryScene& qs, const float* d_rays, const float* d_t_max, uint32_t n, void* d_out, bool any, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const SceneLayout& L = qs.scene.L;
-    const QueryPlan q = query_plan(L);
-    if (q.k == nullptr) return hipErrorInvalidDeviceFunction;                       // no instantiation for this plan: a bug, never a fallback
-    const bool flat = q.k->walk == WALK_FLAT, compact = q.k->walk == WALK_COMPACT;
-    // what the walks assume, checked where the launch is made
-    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.slots < 2u) || (compact && L.off_compact == 0u) ||
-        (q.k->walk != WALK_REGS && (q.slots < 1u || q.slots > kLdsLeafSlotsMax)))
-        return hipErrorInvalidConfiguration;
     int dev = 0, cus = 256;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // a wave's run: 256 rays (four refills of a wave, so that stragglers resume beside fresh rays) unless that makes more than four waves
-    // per resident wave slot - a workgroup of an LDS scene pays for its scene copy once, whatever the length of its runs
-    const uint32_t waves_per_wg = (uint32_t)q.k->threads / 64u;
-    const unsigned long long wave_slots = 4ull * (unsigned long long)cus * q.wg_per_cu * waves_per_wg;
-    unsigned long long per_wave = 256ull;
-    if (((unsigned long long)n + per_wave - 1ull) / per_wave > wave_slots) per_wave = (((unsigned long long)n + wave_slots - 1ull) / wave_slots + 63ull) & ~63ull;
-    const unsigned long long waves = ((unsigned long long)n + per_wave - 1ull) / per_wave;
-    const uint32_t grid = (uint32_t)((waves + waves_per_wg - 1ull) / waves_per_wg);
-    const void* fn = any ? q.k->any : q.k->closest;
+    trt_query_plan q;
+    const QueryKernel* const k = plan_query(L, n, (uint32_t)cus, q);
+    if (k == nullptr) return hipErrorInvalidDeviceFunction;                         // no instantiation for this plan: a bug, never a fallback
+    const bool flat = k->walk == WALK_FLAT, compact = k->walk == WALK_COMPACT;
+    // what the walks assume, checked where the launch is made
+    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.leaf_slots < 2u) || (compact && L.off_compact == 0u) ||
+        (k->walk != WALK_REGS && (q.leaf_slots < 1u || q.leaf_slots > kLdsLeafSlotsMax)))
+        return hipErrorInvalidConfiguration;
+    const void* fn = any ? k->any : k->closest;
     if (q.lds_bytes > 48u * 1024u) {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes);
         if (e != hipSuccess) return e;
     }
     SceneDev scd = qs.scene;
-    QueryArgs qa{d_rays, d_t_max, d_out, qs.geo_index, n, (uint32_t)per_wave, q.slots, q.stragglers, qs.flat_reuse};
+    QueryArgs qa{d_rays, d_t_max, d_out, qs.geo_index, n, q.rays_per_wave, q.leaf_slots, q.stragglers, qs.flat_reuse};
     const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
     const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
     void* args[] = {&scd, &qa, &leaf_list, &nodes16};
-    return hipLaunchKernel(fn, dim3(grid), dim3((uint32_t)q.k->threads), args, q.lds_bytes, stream);
+    return hipLaunchKernel(fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
 }
 
 // Argument checks shared by the four entry points: TRT_ERR_INVALID_ARG before any device work, then TRT_ERR_NO_DEVICE (trt_sample_batch's order).
@@ -314,6 +330,21 @@ int trt_intersect_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_m
 }
 int trt_occluded_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, uint8_t* d_occluded, void* stream) {
     return trt::query_device(s, d_rays, d_t_max, n, d_occluded, true, stream);
+}
+// How launch_query would launch n rays on this scene (host arithmetic only: works without a GPU when the CU count is given).
+int trt_query_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    if (!s || !out) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (compute_units == 0u) {
+        const int rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        int dev = 0, cus = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess || cus <= 0) return trt::query_fail_hip(e, "compute unit count of the current device");
+        compute_units = (uint32_t)cus;
+    }
+    (void)trt::plan_query(trt::query_scene_layout(s), n, compute_units, *out);     // no instantiation: has_kernel = 0 says so
+    return TRT_OK;
 }
 
 }  // extern "C"

@@ -20,6 +20,8 @@ int query_fail(int code, const std::string& msg);
 int query_fail_hip(hipError_t e, const char* what);
 // TRT_OK, or TRT_ERR_NO_DEVICE (message set)
 int query_require_device();
+// the layout of the packed scene behind a handle (host memory: no device needed)
+const SceneLayout& query_scene_layout(const trt_scene* s);
 // the scene on the calling thread's current device
 int query_scene_on_device(trt_scene* s, QueryScene& out);
 }  // namespace trt
