@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "axis_quads.h"
+#include "nearest_first.h"
 #include "flat_reuse.h"
 #include "kernels.h"
 #include "scene.h"
@@ -160,6 +161,7 @@ struct Defaults {
     trt_scene_options scene;
     bool flat_reuse = true;                       // TRT_FLAT_REUSE=0: the lock-step leaf walk computes every leaf box in full (A/B runs, tests)
     bool axis_quads = true;                       // TRT_AXIS_QUADS=0: the lock-step kernel keeps the generic quad test on axis-exact scenes too (A/B runs, tests)
+    bool nearest_first = true;                    // TRT_NEAREST_FIRST=0: the lock-step kernel keeps the walk-order leaf phase on all-axis-exact-quad scenes too (A/B runs, tests)
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -183,6 +185,7 @@ const Defaults& defaults() {
         if (const char* e = env("TRT_FLAT_WALK")) o.flat_walk = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_FLAT_REUSE")) x.flat_reuse = atoi(e) != 0;
         if (const char* e = env("TRT_AXIS_QUADS")) x.axis_quads = atoi(e) != 0;
+        if (const char* e = env("TRT_NEAREST_FIRST")) x.nearest_first = atoi(e) != 0;
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -611,7 +614,12 @@ void set_flat_reuse(trt_scene* s) {
     const bool have_quads = have && L.n_quads > 0u && s->host.blob.size() >= qend;
     const uint32_t aq = axis_quads_flag(have_quads ? s->host.blob.data() + 16u * (size_t)L.off_quad : nullptr, L.n_quads, L.n_leaves, L.flat_walk != 0u,
                                         scene_mode(L) == 1, defaults().axis_quads);
-    s->flat_reuse = FlatReuse{m[0], m[1], m[2], aq};
+    // ... and whether the leaf phase may test the nearest pending leaf first, with the planes its margin is built from (nearest_first.h)
+    float planes[3];
+    const uint32_t nf = nearest_first_flag(have ? s->host.blob.data() + 16u * (size_t)L.off_leaf_list : nullptr, L.n_leaves,
+                                           have_quads ? s->host.blob.data() + 16u * (size_t)L.off_quad : nullptr, L.n_quads, L.n_spheres, aq,
+                                           defaults().nearest_first, planes);
+    s->flat_reuse = FlatReuse{m[0], m[1], m[2], aq, nf, planes[0], planes[1], planes[2]};
 }
 
 // The per-kind -> insertion-index table of the ray queries, from what both scene compilers leave on the handle: leaf i of the reference tree's

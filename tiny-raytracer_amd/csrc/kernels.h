@@ -23,9 +23,13 @@ struct CameraDev {               // camera.rs:4-14, the fields get_ray reads
 // axis_quads (axis_quads.h): 1 = every quad of the scene is axis-exact; the lock-step kernel then rewrites the quad records of its LDS copy
 // and runs the two-dot-product inside test (rt_path.h axis_quads_to_lds, trav_leaf).  Zero, also where it is left out of the braces: the
 // generic test on the packed records.
+// nearest_first (nearest_first.h): 1 = the leaf phase tests the nearest pending leaf first and skips the others by the margin built from
+// px / py / pz, the largest |leaf-box plane| per axis; only with axis_quads, and never in a scene with a sphere.  Zero: leaf_phase as it was.
 struct FlatReuse {
     uint32_t x, y, z;
     uint32_t axis_quads = 0u;
+    uint32_t nearest_first = 0u;
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
 };
 
 struct RenderArgs {

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "axis_quads.h"
+#include "nearest_first.h"
 #include "kernels.h"
 #include "rt_device.h"
 
@@ -344,6 +345,57 @@ TRT_DEV void leaf_phase(const float2* stk, const float2* top, Trav& tr, Counters
     }
 }
 
+// trav_leaf's axis-exact branch, operation for operation, as the quad's OWN hit: whether t_min <= t and the point is inside, and t.  The
+// caller compares t with t_best (the conjunction trav_leaf forms in one go).  Only where axis_quads_to_lds has rewritten the records.
+template <int MODE>
+TRT_DEV bool axis_quad_hit(const SceneAcc<MODE>& sc, const Ray& ray, uint32_t leaf, float& t) {
+    const uint32_t idx = leaf & PRIM_INDEX_MASK;
+    const float4 q0 = sc.quad(0, idx), q1 = sc.quad(1, idx), q2 = sc.quad(2, idx), q3 = sc.quad(3, idx);
+    const V3 nrm = v3(q0.x, q0.y, q0.z);
+    const float dir_norm = dot(ray.d, nrm);
+    t = (q0.w - dot(ray.o, nrm)) / dir_norm;
+    const V3 p = ray_at(ray, t) - v3(q1.x, q1.y, q1.z);
+    const float planar_x = q2.w * dot(p, v3(q2.x, q2.y, q2.z));
+    const float planar_y = q2.w * dot(p, v3(q3.x, q3.y, q3.z));
+    return (kTMin <= t) & (0.0f <= planar_x) & (planar_x < 1.0f) & (0.0f <= planar_y) & (planar_y < 1.0f);
+}
+
+// Steps 4 and 5 of the nearest-first leaf phase (nearest_first.h) for the lanes that need them: cold code behind the wave's ballot.  (Out of
+// line it would take the scene accessor and the ray by address, through scratch.)
+template <int MODE>
+TRT_DEV void leaf_phase_nearest_cold(const SceneAcc<MODE>& sc, const Ray& ray, const float2* stk, const float2* top, Trav& tr,
+                                     bool residual, uint32_t leaf_s, float E, float t0, uint32_t p0, float win_start) {
+    nf_cold_phase((uint32_t)(top - stk) >> 6,
+                  [&](uint32_t k, uint32_t& leaf, float& start) { const float2 e = stk[64u * k]; leaf = __float_as_uint(e.x); start = e.y; },
+                  [&](uint32_t leaf, float& t) { return axis_quad_hit<MODE>(sc, ray, leaf, t); }, residual, leaf_s, E, t0, p0, win_start, tr.t_best, tr.prim_best);
+}
+
+// Leaf phase of the lock-step walk on a scene of axis-exact quads only (FlatReuse::nearest_first): the nearest pending leaf is tested
+// first and the others are skipped WITHOUT a test where their box entry lies beyond the new t_best by the margin E (nearest_first.h has
+// the rule and why the result is the walk-order phase's, bit for bit).  One scan of the slots (one 8-byte LDS read, two compares and four
+// selects per trip of the busiest lane; two slots per trip with both reads in flight was measured slower), ONE quad test for the wave, one
+// ballot; the residual loop and the walk-order re-run are behind it.  Cornell: +4.5 % same-box (profiles/nf_nearest_first_ab.txt).
+template <int MODE>
+TRT_DEV void leaf_phase_nearest(const SceneAcc<MODE>& sc, const Ray& ray, const float2* stk, const float2* top, Trav& tr, float E) {
+    NfScan s = nf_scan_begin();
+    for (const float2* slot = stk; slot != top; slot += 64) {
+        const unsigned long long e = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(slot));
+        nf_scan_step(s, (uint32_t)e, __uint_as_float((uint32_t)(e >> 32)));
+    }
+    const float t0 = tr.t_best;
+    const uint32_t p0 = tr.prim_best;
+    bool cold = false, residual = false;
+    if (top != stk) {
+        float t;
+        if (axis_quad_hit<MODE>(sc, ray, s.leaf, t) & (t < tr.t_best)) { tr.t_best = t; tr.prim_best = s.leaf; }
+        residual = nf_needs_more(s.start2, E, tr.t_best);
+        cold = residual | nf_unsafe(tr.prim_best, p0, s.smallest, tr.t_best);
+    }
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(cold) != 0ull, 0)) {
+        if (cold) leaf_phase_nearest_cold<MODE>(sc, ray, stk, top, tr, residual, s.leaf, E, t0, p0, s.smallest);
+    }
+}
+
 // A walk that is left unfinished (resumable walks below) parks its cursor, its t_best and its best primitive in the lane's leaf stack,
 // which is empty at that moment; the caller sets the walk up again from the ray (trav_begin: the three 1/d are recomputed, in the same
 // instruction stream in which the wave's other lanes start their new walks) and takes the three values back.  Nothing of the walk is then
@@ -611,12 +663,21 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
                        float2* stk, uint32_t slots, FlatReuse reuse) {
     const uint32_t n = sc.L.n_leaves;                    // >= 1
     uint32_t i = 0;                                      // wave-uniform
+    // nearest-first leaf phase (nearest_first.h; wave-uniform flag, only where axis_quads is set too): its margin, once per walk
+    const bool nearest = !STATS && !ANY && reuse.nearest_first != 0u;
+    const float margin = nearest ? nf_margin(reuse.px, reuse.py, reuse.pz, ray.o.x, ray.o.y, ray.o.z, tr.inv.x, tr.inv.y, tr.inv.z) : 0.0f;
+    auto phase = [&](const float2* top) {
+        if constexpr (!STATS && !ANY) {
+            if (nearest) { leaf_phase_nearest<MODE>(sc, ray, stk, top, tr, margin); return; }
+        }
+        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
+    };
     if constexpr (kAsmBoxLoop && !STATS) {
         float2* const lim = stk + 64u * (slots - 2u);
         do {
             float2* const top = box_loop_flat(tr, ray.o, leaf_list, i, n, stk, lim, reuse);
             TRT_CLK(ctr, 1);
-            leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
+            phase(top);
             TRT_CLK(ctr, 2);
             // any-hit: the lanes step the list together, so the wave leaves once every lane has accepted a primitive (a lane that has one
             // goes on testing with its shrunken t_best, which cannot take its hit away)
@@ -656,7 +717,7 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
         }
         TRT_CLK(ctr, 1);
         if constexpr (STATS) ctr.pend += (uint32_t)(top - stk) >> 6;
-        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
+        phase(top);
         TRT_CLK(ctr, 2);
         if constexpr (ANY) { if (__builtin_amdgcn_ballot_w64(tr.prim_best == PRIM_NONE) == 0ull) return; }
     } while (i < n);
@@ -952,6 +1013,7 @@ template <int MODE, bool STATS, int WALK>
 TRT_DEV FlatReuse axis_quads_to_lds(const SceneDev& sc, FlatReuse reuse) {
     if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) {
         reuse.axis_quads = 0u;
+        reuse.nearest_first = 0u;
     } else if (reuse.axis_quads != 0u) {
         for (uint32_t k = threadIdx.x; k < sc.L.n_quads; k += blockDim.x) {
             float4* const q = g_lds + sc.L.off_quad + 5u * k;
@@ -981,7 +1043,11 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
     const bool fused_loop = kAsmBoxLoop && !STATS && (WALK == WALK_COMPACT || (WALK == WALK_RUNTIME && lds_stack != nullptr && nodes16 != nullptr));
     Trav tr = trav_begin<MODE>(sc, ray, ref_tree, fused_loop);
     tr.t_best = t_max;
-    if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) flat_reuse.axis_quads = 0u;      // (axis_quads_to_lds: no other kernel rewrites its records)
+    if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) { flat_reuse.axis_quads = 0u; flat_reuse.nearest_first = 0u; }      // (axis_quads_to_lds: no other kernel rewrites its records)
+    if constexpr (kAxisQuadsKernel<MODE, STATS, WALK> && !ANY) {
+        // the nearest-first leaf phase's margin holds for 2^-60 <= |1/d| <= 2^60 (nearest_first.h); any other ray walks the reference tree
+        if (flat_reuse.nearest_first != 0u && !nf_in_domain(tr.inv.x, tr.inv.y, tr.inv.z)) { tr.ref = true; tr.n = sc.L.n_nodes; }
+    }
     if (__builtin_expect(!tr.ref, 1)) {
         if constexpr (WALK == WALK_COMPACT) {
             walk_compact<MODE, STATS, ANY>(sc, nodes16, leaf_list, ray, tr, ctr, lds_stack, leaf_slots);
