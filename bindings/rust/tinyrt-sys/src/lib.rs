@@ -230,6 +230,24 @@ pub struct trt_query_plan {
     pub waves: u64,
 }
 
+/// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct trt_aov_buffers {
+    pub albedo: *mut f32,
+    pub normal: *mut f32,
+    pub depth: *mut f32,
+    pub coverage: *mut f32,
+    pub geometry: *mut u32,
+    pub material: *mut u32,
+}
+impl Default for trt_aov_buffers {
+    fn default() -> Self {
+        // all-null: no buffer wanted yet
+        unsafe { std::mem::zeroed() }
+    }
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct trt_stats {
@@ -303,6 +321,13 @@ extern "C" {
     pub fn trt_occluded_device(s: *mut trt_scene, d_rays: *const trt_ray, d_t_max: *const f32, n: u32, d_occluded: *mut u8,
                                stream: *mut c_void) -> c_int;
     pub fn trt_query_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_primary_rays(cam: *const trt_camera, p: *const trt_render_params, s: u32, rays: *mut trt_ray) -> c_int;
+    pub fn trt_primary_rays_device(cam: *const trt_camera, p: *const trt_render_params, s: u32, d_rays: *mut trt_ray,
+                                   stream: *mut c_void) -> c_int;
+    pub fn trt_render_aov(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, buffers: *const trt_aov_buffers) -> c_int;
+    pub fn trt_render_aov_device(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params,
+                                 d_buffers: *const trt_aov_buffers, stream: *mut c_void) -> c_int;
+    pub fn trt_aov_launch_plan(s: *const trt_scene, n_pixels: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_tonemap_u8(accum: *const f32, npixels: u32, gamma: f32, rgb: *mut u8) -> c_int;
     pub fn trt_tonemap_u8_device(d_accum: *const f32, npixels: u32, gamma: f32, d_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn trt_streamed_chunk_spp(width: u32, rows: u32) -> u32;

@@ -226,6 +226,29 @@ impl Camera {
     pub fn get_image_size(&self) -> (usize, usize) {
         (self.pod.width as usize, self.pod.height as usize) // camera.rs:68-70
     }
+
+    /// The rays `Renderer::render` traces for sample `sample` of every pixel under `seed` (trt_primary_rays): width * height rays,
+    /// row-major, each (origin, direction) as six floats.
+    pub fn primary_rays(&self, sample: u32, samples_per_pixel: u32, seed: u32) -> Result<Vec<[Float; 6]>, Error> {
+        let (width, height) = self.get_image_size();
+        let params = sys::trt_render_params { samples_per_pixel, seed, ..Default::default() };
+        let mut rays = vec![[0.0 as Float; 6]; width * height];
+        check(unsafe { sys::trt_primary_rays(&self.pod, &params, sample, rays.as_mut_ptr() as *mut sys::trt_ray) })?;
+        Ok(rays)
+    }
+}
+
+/// The first-hit feature buffers of a frame (trt_render_aov): sums over the samples in the imager's order, indices of sample 0
+/// (0xFFFFFFFF on a miss).  Row-major, width * height pixels each.
+pub struct FeatureBuffers {
+    pub width: usize,
+    pub height: usize,
+    pub albedo: Vec<Float>,   // 3 per pixel
+    pub normal: Vec<Float>,   // 3 per pixel; not renormalised
+    pub depth: Vec<Float>,
+    pub coverage: Vec<Float>,
+    pub geometry: Vec<u32>,
+    pub material: Vec<u32>,
 }
 
 /// utils/image.rs Image with gamma 2.2 as the Imager builds it (imager.rs:37-41); holds the linear sums.
@@ -318,6 +341,39 @@ impl Renderer {
         let mut data = vec![0.0 as Float; width * height * 3];
         check(unsafe { sys::trt_render(scene, &camera.pod, &params, data.as_mut_ptr(), ptr::null_mut()) })?;
         Ok(Image { width, height, gamma: 2.2, data })
+    }
+
+    /// All six feature buffers of the frame `render` would trace: same seed, same samples, same primary rays.
+    pub fn render_aov(&self, camera: &Camera, world: &mut World) -> Result<FeatureBuffers, Error> {
+        let (width, height) = camera.get_image_size();
+        let scene = world.get_bvh()?;
+        let params = sys::trt_render_params {
+            samples_per_pixel: self.samples_per_pixel as u32,
+            background: self.background_color.raw(),
+            seed: self.seed,
+            ..Default::default()
+        };
+        let n = width * height;
+        let mut out = FeatureBuffers {
+            width,
+            height,
+            albedo: vec![0.0; n * 3],
+            normal: vec![0.0; n * 3],
+            depth: vec![0.0; n],
+            coverage: vec![0.0; n],
+            geometry: vec![0; n],
+            material: vec![0; n],
+        };
+        let buffers = sys::trt_aov_buffers {
+            albedo: out.albedo.as_mut_ptr(),
+            normal: out.normal.as_mut_ptr(),
+            depth: out.depth.as_mut_ptr(),
+            coverage: out.coverage.as_mut_ptr(),
+            geometry: out.geometry.as_mut_ptr(),
+            material: out.material.as_mut_ptr(),
+        };
+        check(unsafe { sys::trt_render_aov(scene, &camera.pod, &params, &buffers) })?;
+        Ok(out)
     }
 
     /// The same call over `ndev` GPUs of the node (0 = every visible device): the image's 16-row bands are dealt round-robin

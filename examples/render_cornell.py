@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The reference binary (src/main.rs) through the Python mirror: Cornell box -> output.png.
-   python examples/render_cornell.py [width height spp]"""
+   python examples/render_cornell.py [width height spp] [--aov DIR]
+--aov DIR also writes the frame's first-hit feature buffers (Renderer.render_aov: same seed, samples and primary rays as the render) to
+DIR: albedo.png, normal.png ((n + 1) / 2), depth.png (scaled to the farthest hit), coverage.png, and all six as arrays in aov.npz."""
 import os
 import sys
 import time
@@ -8,7 +10,13 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tinyrt_amd as trt
 
-w, h, spp = (int(a) for a in sys.argv[1:4]) if len(sys.argv) > 3 else (300, 300, 300)
+argv = sys.argv[1:]
+aov_dir = None
+if "--aov" in argv:
+    at = argv.index("--aov")
+    aov_dir = argv[at + 1]
+    del argv[at:at + 2]
+w, h, spp = (int(a) for a in argv[:3]) if len(argv) >= 3 else (300, 300, 300)
 world, camera = trt.world_from_description(trt.scenes.cornell(w, h))          # build_world + Camera::new, src/main.rs:7-16
 instance = trt.Renderer(spp, 8, 20, True, (0.001, 0.001, 0.001))             # Renderer::new(300, 8, 20, true, Some(0.001))
 t0 = time.perf_counter()
@@ -18,3 +26,15 @@ image.save("output.png")
 st = instance.last_stats
 print(f"{w}x{h}, {spp} spp: {st['rays']} rays, kernel {st['kernel_ms']:.1f} ms ({st['rays'] / st['kernel_ms'] / 1e3:.0f} Mray/s), "
       f"call {dt * 1e3:.1f} ms -> output.png")
+if aov_dir:
+    import numpy as np
+    os.makedirs(aov_dir, exist_ok=True)
+    aov = instance.render_aov(camera, world)
+    np.savez(os.path.join(aov_dir, "aov.npz"), **aov)
+    grey = lambda a: np.repeat(a[:, :, None], 3, axis=2)                         # noqa: E731
+    far = float(aov["depth"].max()) or 1.0
+    for name, linear in (("albedo", aov["albedo"]), ("normal", (aov["normal"] + 1.0) * 0.5), ("depth", grey(aov["depth"] / far)),
+                         ("coverage", grey(aov["coverage"]))):
+        trt.Image(np.ascontiguousarray(linear, np.float32), gamma=1.0).save(os.path.join(aov_dir, name + ".png"))
+    hit = aov["geometry"] != 0xFFFFFFFF
+    print(f"feature buffers -> {aov_dir}: coverage {float(aov['coverage'].mean()):.3f}, {len(np.unique(aov['geometry'][hit]))} geometries seen by sample 0")

@@ -38,7 +38,8 @@ extern "C" {
                              *              tree levels is gone: measured slower in every form); d_counters[12..15] = shades by material kind.
                              *              No struct changed size or moved a field.
  *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed; trt_hit, trt_intersect, trt_occluded,
- *              trt_intersect_device, trt_occluded_device; trt_query_plan, trt_query_launch_plan. */
+ *              trt_intersect_device, trt_occluded_device; trt_query_plan, trt_query_launch_plan; trt_primary_rays,
+ *              trt_primary_rays_device; trt_aov_buffers, trt_render_aov, trt_render_aov_device, trt_aov_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -336,6 +337,44 @@ typedef struct {
     uint64_t wave_slots, waves;
 } trt_query_plan;
 int trt_query_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- The camera's own rays: primary-ray export and first-hit feature buffers (AOVs) ----
+ * Primary rays.  Entry (r, x) of `rays` - row-major, rows x width, rows = p->rows_local, or height when p->band_rows == 0 - is the ray the
+ * render entry points trace for sample s of image pixel (x, image row of local row r): RNG stream (p->seed, pixel y * width + x,
+ * sample s), then SamplePointGenerator::generate (pointgen.rs:41-43) and Camera::get_ray (camera.rs:58-66), normalised by Ray::new.
+ * Handed to trt_intersect it gives that sample's first hit.  Of `p` only seed, samples_per_pixel (s must be below it) and the band
+ * fields are read.  trt_primary_rays: HOST buffer, synchronous.  trt_primary_rays_device: buffer in HBM on the calling thread's current
+ * device, asynchronous on `stream`.  Errors: TRT_ERR_INVALID_ARG (a NULL pointer, s >= samples_per_pixel, bad bands) before any device
+ * work, then TRT_ERR_NO_DEVICE: the rays are made by the device code that renders, there is no CPU path. */
+int trt_primary_rays(const trt_camera *cam, const trt_render_params *p, uint32_t s, trt_ray *rays);
+int trt_primary_rays_device(const trt_camera *cam, const trt_render_params *p, uint32_t s, trt_ray *d_rays, void *stream);
+
+/* Feature buffers of a frame: what the first hit of every camera ray says, folded per pixel over the samples - the guides a denoiser
+ * takes, an alpha matte, a picking buffer.  "First hit of sample s" is BVH::hit over [0.001, +inf) for the primary ray above: bit for bit
+ * the trt_hit record trt_intersect gives for that ray (a ray with a NaN component hits nothing).  Each pointer may be NULL (not wanted);
+ * all six NULL is TRT_ERR_INVALID_ARG.  Every buffer holds rows x width pixels, row-major, rows as above.
+ *  - Sums run in sample order with the imager's rule, acc = acc + value * (1 / samples_per_pixel) (imager.rs:35,50): with
+ *    samples_per_pixel equal, the result does not depend on how [sample_begin, sample_end) is split over calls.  p->accumulate as in
+ *    trt_render: 0 starts the sums at 0, 1 continues the ones in the buffers.  The two index buffers are written only by a call whose
+ *    sample range contains sample 0.
+ *  - Bands (band_rows, band_stride, band_offset, rows_local) as in trt_render.
+ *  - max_bounces, backend, collect_stats and tuning are ignored.
+ * One kernel makes the ray, walks and folds; neither rays nor hit records go through memory.  trt_render_aov: HOST buffers, synchronous.
+ * trt_render_aov_device: buffers in HBM (the struct itself is read on the host, during the call), asynchronous on `stream`.  Errors and
+ * concurrency as for the ray queries: TRT_ERR_INVALID_ARG before any device work, then TRT_ERR_NO_DEVICE. */
+typedef struct {
+    float *albedo;                /* 3 f32 per pixel: sum of a_s / spp; a_s = albedo of the first hit's material (the emitted colour for TRT_LIGHT), p->background on a miss */
+    float *normal;                /* 3 f32: sum of n_s / spp; n_s = trt_hit.normal of the first hit (unit, facing the ray), 0 on a miss; not renormalised */
+    float *depth;                 /* f32: sum of t_s / spp over the samples that hit; a miss adds nothing */
+    float *coverage;              /* f32: sum of hit_s / spp: the alpha of the geometry */
+    uint32_t *geometry;           /* insertion index of the first hit of sample 0; 0xFFFFFFFF on a miss */
+    uint32_t *material;           /* material index of the first hit of sample 0; 0xFFFFFFFF on a miss */
+} trt_aov_buffers;                /* 48 B */
+int trt_render_aov(trt_scene *s, const trt_camera *cam, const trt_render_params *p, const trt_aov_buffers *buffers);
+int trt_render_aov_device(trt_scene *s, const trt_camera *cam, const trt_render_params *p, const trt_aov_buffers *d_buffers, void *stream);
+/* How trt_render_aov[_device] launches a local image of n_pixels on this scene: trt_query_launch_plan's rule and fields with pixels in
+ * place of rays (rays_per_wave = pixels a wave owns, each for all of its samples), over the feature-buffer kernels' own table. */
+int trt_aov_launch_plan(const trt_scene *s, uint32_t n_pixels, uint32_t compute_units, trt_query_plan *out);
 
 /* Imager finalisation + Image -> RgbImage (imager.rs:52-53; utils/image.rs:92-111): c^(1/gamma),
  * clamp to [0, 0.999], *255, truncate; NaN -> 0.  HOST buffers, npixels*3 each. */

@@ -135,7 +135,25 @@ public:
         check(trt_camera_init(&pod, focus_distance, defocus_angle, position, look_at, up, vertical_fov, width, height));
     }
     std::pair<uint32_t, uint32_t> get_image_size() const { return {pod.width, pod.height}; }   // camera.rs:68-70
+    // The rays Renderer::render traces for sample `sample` of every pixel under `seed` (trt_primary_rays): width * height rays, row-major.
+    std::vector<trt_ray> primary_rays(uint32_t sample, uint32_t samples_per_pixel, uint32_t seed = 1) const {
+        trt_render_params p{};
+        p.samples_per_pixel = samples_per_pixel;
+        p.seed = seed;
+        std::vector<trt_ray> rays((size_t)pod.width * pod.height);
+        check(trt_primary_rays(&pod, &p, sample, rays.data()));
+        return rays;
+    }
     trt_camera pod;
+};
+
+// The first-hit feature buffers of a frame (trt_render_aov): sums over the samples in the imager's order, indices of sample 0
+// (0xFFFFFFFF on a miss).  Row-major, width * height pixels each.
+struct FeatureBuffers {
+    uint32_t width = 0, height = 0;
+    std::vector<float> albedo, normal;          // 3 per pixel; the normal is not renormalised
+    std::vector<float> depth, coverage;
+    std::vector<uint32_t> geometry, material;
 };
 
 // Minimal PNG writer (8-bit RGB, zlib "stored" blocks: valid for every decoder, no compression) so that
@@ -243,6 +261,20 @@ public:
         Image img(camera.pod.width, camera.pod.height);
         check(trt_render(world.get_bvh(), &camera.pod, &params_, img.linear(), stats));
         return img;
+    }
+    // All six feature buffers of the frame render() would trace: same seed, same samples, same primary rays.
+    FeatureBuffers render_aov(const Camera& camera, World& world) const {
+        FeatureBuffers out;
+        out.width = camera.pod.width;
+        out.height = camera.pod.height;
+        const size_t n = (size_t)out.width * out.height;
+        out.albedo.assign(n * 3, 0.0f); out.normal.assign(n * 3, 0.0f);
+        out.depth.assign(n, 0.0f); out.coverage.assign(n, 0.0f);
+        out.geometry.assign(n, 0u); out.material.assign(n, 0u);
+        const trt_aov_buffers b{out.albedo.data(), out.normal.data(), out.depth.data(), out.coverage.data(), out.geometry.data(),
+                                out.material.data()};
+        check(trt_render_aov(world.get_bvh(), &camera.pod, &params_, &b));
+        return out;
     }
     // The same call over several GPUs of the node (trt_render_multi): `devices` empty = every visible device.
     Image render_multi(const Camera& camera, World& world, const std::vector<int>& devices = {}, trt_stats* stats = nullptr) const {

@@ -6,7 +6,7 @@ importlib.import_module("tiny-raytracer_amd") or through the top-level alias mod
 from . import scenes  # noqa: F401
 from ._lib import (BACKEND_AUTO, BACKEND_MEGAKERNEL, BACKEND_STREAMED, BACKEND_WAVEFRONT, DIELECTRIC, LAMBERTIAN, LIGHT, METAL, CameraPOD,  # noqa: F401
                    Hit, Material, Ray, RenderParams, SampledColor, SamplePoint, SceneOptions, Stats, TinyRTError, Tuning, Vec3, lib)
-from .api import (HIT_DTYPE, Camera, Dielectric, Image, Lambertian, Light, Metal, Quad, Renderer, Scene, Sphere, World,  # noqa: F401
+from .api import (AOV_CHANNELS, HIT_DTYPE, Camera, Dielectric, Image, Lambertian, Light, Metal, Quad, Renderer, Scene, Sphere, World,  # noqa: F401
                   sample_batch, scene_options, tonemap_u8_device, tuning)
 
 _MATERIAL_CTORS = {LAMBERTIAN: lambda a, p: Lambertian(a), METAL: Metal, DIELECTRIC: Dielectric,

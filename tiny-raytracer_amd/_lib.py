@@ -88,6 +88,12 @@ class QueryPlan(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AovBuffers(C.Structure):
+    """tinyrt.h trt_aov_buffers: the six feature buffers of trt_render_aov, each a pointer or NULL (not wanted)."""
+    FIELDS = ("albedo", "normal", "depth", "coverage", "geometry", "material")
+    _fields_ = [(n, C.c_void_p) for n in FIELDS]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -168,6 +174,11 @@ SIGNATURES = {
     "trt_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "trt_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "trt_query_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_primary_rays": (C.c_int, [C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_uint32, C.c_void_p]),
+    "trt_primary_rays_device": (C.c_int, [C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "trt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
+    "trt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.POINTER(AovBuffers), C.c_void_p]),
+    "trt_aov_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_streamed_chunk_spp": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "trt_tonemap_u8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "trt_tonemap_u8_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),

@@ -60,6 +60,12 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("geometry", np.uint32), ("material", n
 assert HIT_DTYPE.itemsize == C.sizeof(_lib.Hit) == 28
 
 
+# tinyrt.h trt_aov_buffers: channel -> (numpy type, values per pixel)
+AOV_CHANNELS = {"albedo": (np.float32, 3), "normal": (np.float32, 3), "depth": (np.float32, 1), "coverage": (np.float32, 1),
+                "geometry": (np.uint32, 1), "material": (np.uint32, 1)}
+assert tuple(AOV_CHANNELS) == _lib.AovBuffers.FIELDS and C.sizeof(_lib.AovBuffers) == 48
+
+
 def _rays_and_t_max(rays, t_max):
     """float32 [n, 6] (origin, direction: used as given) and float32 [n] or None, contiguous."""
     r = np.ascontiguousarray(rays, np.float32)
@@ -175,6 +181,13 @@ class Scene:
         check(lib.trt_query_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    def aov_plan(self, n, compute_units=0):
+        """trt_aov_launch_plan: how Renderer.render_aov launches a local image of n pixels on this scene, as a dict with query_plan()'s
+        fields (rays_per_wave = pixels a wave owns)."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_aov_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""
@@ -259,6 +272,30 @@ class Camera:
 
     def get_image_size(self):
         return (self.pod.width, self.pod.height)
+
+    @staticmethod
+    def _ray_params(samples_per_pixel, seed, bands):
+        p = RenderParams()
+        p.samples_per_pixel, p.seed = int(samples_per_pixel), int(seed)
+        for k, v in bands.items():
+            if k not in ("band_rows", "band_stride", "band_offset", "rows_local"):
+                raise TypeError(f"unknown band field {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def primary_rays(self, sample, samples_per_pixel, seed=1, **bands):
+        """trt_primary_rays: float32 [rows, width, 6] (origin, direction) - the rays the render traces for sample `sample` of every pixel
+        under this seed; `bands`: band_rows, band_stride, band_offset, rows_local as in trt_render_params (none: all rows)."""
+        p = self._ray_params(samples_per_pixel, seed, bands)
+        rows = p.rows_local if p.band_rows else self.pod.height
+        out = np.zeros((rows, self.pod.width, 6), np.float32)
+        check(lib.trt_primary_rays(C.byref(self.pod), C.byref(p), int(sample), out.ctypes.data if out.size else None))
+        return out
+
+    def primary_rays_device(self, sample, samples_per_pixel, d_rays_ptr, seed=1, stream_ptr=0, **bands):
+        """Enqueue primary_rays() into a buffer already in HBM (rows x width x 24 bytes); asynchronous on the stream."""
+        p = self._ray_params(samples_per_pixel, seed, bands)
+        check(lib.trt_primary_rays_device(C.byref(self.pod), C.byref(p), int(sample), C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr)))
 
 
 class Image:
@@ -368,6 +405,39 @@ class Renderer:
         p = self.params(**over)
         check(lib.trt_render_device(scene._h, C.byref(camera.pod), C.byref(p), C.c_void_p(d_accum_ptr),
                                     C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+
+    def render_aov(self, camera, world, channels=tuple(AOV_CHANNELS), buffers=None, **over):
+        """trt_render_aov: the first-hit feature buffers of this renderer's frame (same seed, samples and rays as render()), as a dict
+        channel -> array [rows, width, 3] or [rows, width] for the `channels` asked (albedo, normal, depth, coverage: float32 sums over the
+        samples; geometry, material: uint32 of sample 0, 0xFFFFFFFF on a miss).  `buffers`: the dict of an earlier pass to continue
+        (over["accumulate"] = 1); `over`: sample range, bands."""
+        scene = world.get_bvh() if isinstance(world, World) else world
+        p = self.params(**over)
+        w, h = camera.get_image_size()
+        rows = p.rows_local if p.band_rows else h
+        out = {}
+        pod = _lib.AovBuffers()
+        for name in channels:
+            dtype, k = AOV_CHANNELS[name]                                  # KeyError: no such channel
+            shape = (rows, w, 3) if k == 3 else (rows, w)
+            a = buffers[name] if buffers is not None else np.zeros(shape, dtype)
+            assert a.dtype == dtype and a.flags.c_contiguous and a.shape == shape
+            out[name] = a
+            setattr(pod, name, a.ctypes.data if a.size else None)
+        check(lib.trt_render_aov(scene._h, C.byref(camera.pod), C.byref(p), C.byref(pod)))
+        return out
+
+    def render_aov_device(self, camera, scene, d_buffer_ptrs, stream_ptr=0, **over):
+        """Enqueue render_aov() on buffers already in HBM: d_buffer_ptrs is a dict channel -> device pointer (as an integer) for the
+        channels wanted; asynchronous on the stream."""
+        p = self.params(**over)
+        pod = _lib.AovBuffers()
+        for name, ptr in d_buffer_ptrs.items():
+            if name not in AOV_CHANNELS:
+                raise KeyError(name)
+            setattr(pod, name, ptr or None)
+        check(lib.trt_render_aov_device(scene._h, C.byref(camera.pod), C.byref(p), C.byref(pod), C.c_void_p(stream_ptr)))
 
 
 def tonemap_u8_device(d_accum_ptr, npixels, d_rgb_ptr, gamma=2.2, stream_ptr=0):

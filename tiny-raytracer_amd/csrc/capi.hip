@@ -676,6 +676,14 @@ int query_scene_on_device(trt_scene* s, QueryScene& out) {
     out.flat_reuse = s->flat_reuse;
     return TRT_OK;
 }
+int query_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs& ra, uint32_t& rows) {
+    trt_render_params q = *p;
+    q.backend = TRT_BACKEND_AUTO;
+    q.tuning = nullptr;
+    trt_tuning tn;
+    return to_render_args(cam, &q, ra, rows, tn);
+}
+void query_camera_dev(const trt_camera& cam, CameraDev& out) { to_camera_dev(cam, out); }
 }  // namespace trt
 
 // The device scene compiler's view of this layer (scene_adopt.h)

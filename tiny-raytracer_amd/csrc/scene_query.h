@@ -1,4 +1,4 @@
-// scene_query.h - what the ray-query unit (query.hip) needs from the C ABI layer (capi.hip): the thread-local error message, the device
+// scene_query.h - what the ray-query unit (query.hip) and the feature-buffer unit (aov.hip) need from the C ABI layer (capi.hip): the thread-local error message, the device
 // check and the device view of a scene handle - the packed scene plus the queries' index table, both uploaded on first use and freed
 // with the scene.  capi.hip calls nothing in query.hip, so the host-only build of capi.hip links without it.
 #pragma once
@@ -24,4 +24,8 @@ int query_require_device();
 const SceneLayout& query_scene_layout(const trt_scene* s);
 // the scene on the calling thread's current device
 int query_scene_on_device(trt_scene* s, QueryScene& out);
+// The kernel arguments of a camera and of the render parameters the feature-buffer unit (aov.hip) reads - seed, 1/spp, background, sample
+// range, accumulate, bands - validated as trt_render validates them (backend and tuning are not looked at).  rows = rows the call owns.
+int query_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs& ra, uint32_t& rows);
+void query_camera_dev(const trt_camera& cam, CameraDev& out);
 }  // namespace trt
