@@ -248,6 +248,33 @@ impl Default for trt_aov_buffers {
     }
 }
 
+/// Passes and edge stops of `trt_denoise`; take the defaults from `trt_denoise_params_default`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_denoise_params {
+    pub iterations: u32,
+    pub normal_power_log2: u32,
+    pub sigma_albedo: f32,
+    pub sigma_depth: f32,
+    pub reserved: [u32; 4],
+}
+
+/// The frame and its guides for `trt_denoise`; a null guide switches its term off.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct trt_denoise_inputs {
+    pub color: *const f32,
+    pub albedo: *const f32,
+    pub normal: *const f32,
+    pub depth: *const f32,
+}
+impl Default for trt_denoise_inputs {
+    fn default() -> Self {
+        // all-null: no buffer given yet
+        unsafe { std::mem::zeroed() }
+    }
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct trt_stats {
@@ -328,6 +355,11 @@ extern "C" {
     pub fn trt_render_aov_device(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params,
                                  d_buffers: *const trt_aov_buffers, stream: *mut c_void) -> c_int;
     pub fn trt_aov_launch_plan(s: *const trt_scene, n_pixels: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_denoise_params_default(out: *mut trt_denoise_params);
+    pub fn trt_denoise_scratch_bytes(width: u32, height: u32, params: *const trt_denoise_params) -> u64;
+    pub fn trt_denoise(input: *const trt_denoise_inputs, width: u32, height: u32, params: *const trt_denoise_params, out: *mut f32) -> c_int;
+    pub fn trt_denoise_device(d_in: *const trt_denoise_inputs, width: u32, height: u32, params: *const trt_denoise_params,
+                              d_out: *mut f32, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> c_int;
     pub fn trt_tonemap_u8(accum: *const f32, npixels: u32, gamma: f32, rgb: *mut u8) -> c_int;
     pub fn trt_tonemap_u8_device(d_accum: *const f32, npixels: u32, gamma: f32, d_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn trt_streamed_chunk_spp(width: u32, rows: u32) -> u32;

@@ -376,6 +376,20 @@ impl Renderer {
         Ok(out)
     }
 
+    /// The frame denoised by its own feature buffers (`trt_denoise`: the edge-avoiding a-trous filter of tinyrt.h guided by albedo,
+    /// normal and depth, default parameters): `frame` as `render` returned it, `aov` as `render_aov` returned it for the same camera.
+    pub fn denoise(frame: &Image, aov: &FeatureBuffers) -> Result<Image, Error> {
+        let input = sys::trt_denoise_inputs {
+            color: frame.data.as_ptr(),
+            albedo: aov.albedo.as_ptr(),
+            normal: aov.normal.as_ptr(),
+            depth: aov.depth.as_ptr(),
+        };
+        let mut data = vec![0.0 as Float; aov.width * aov.height * 3];
+        check(unsafe { sys::trt_denoise(&input, aov.width as u32, aov.height as u32, ptr::null(), data.as_mut_ptr()) })?;
+        Ok(Image { width: aov.width, height: aov.height, gamma: frame.gamma, data })
+    }
+
     /// The same call over `ndev` GPUs of the node (0 = every visible device): the image's 16-row bands are dealt round-robin
     /// over the devices and every finished band is copied to its place in the frame (trt_render_multi).
     pub fn render_multi(&self, camera: &Camera, world: &mut World, ndev: u32) -> Result<Image, Error> {

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """The reference binary (src/main.rs) through the Python mirror: Cornell box -> output.png.
-   python examples/render_cornell.py [width height spp] [--aov DIR]
+   python examples/render_cornell.py [width height spp] [--aov DIR] [--denoise]
 --aov DIR also writes the frame's first-hit feature buffers (Renderer.render_aov: same seed, samples and primary rays as the render) to
-DIR: albedo.png, normal.png ((n + 1) / 2), depth.png (scaled to the farthest hit), coverage.png, and all six as arrays in aov.npz."""
+DIR: albedo.png, normal.png ((n + 1) / 2), depth.png (scaled to the farthest hit), coverage.png, and all six as arrays in aov.npz.
+--denoise also writes denoised.png beside output.png: the frame through trt.denoise (the a-trous filter of tinyrt.h, default parameters)
+guided by the albedo, normal and depth buffers of the same seed and samples."""
 import os
 import sys
 import time
@@ -16,6 +18,9 @@ if "--aov" in argv:
     at = argv.index("--aov")
     aov_dir = argv[at + 1]
     del argv[at:at + 2]
+denoise = "--denoise" in argv
+if denoise:
+    argv.remove("--denoise")
 w, h, spp = (int(a) for a in argv[:3]) if len(argv) >= 3 else (300, 300, 300)
 world, camera = trt.world_from_description(trt.scenes.cornell(w, h))          # build_world + Camera::new, src/main.rs:7-16
 instance = trt.Renderer(spp, 8, 20, True, (0.001, 0.001, 0.001))             # Renderer::new(300, 8, 20, true, Some(0.001))
@@ -38,3 +43,11 @@ if aov_dir:
         trt.Image(np.ascontiguousarray(linear, np.float32), gamma=1.0).save(os.path.join(aov_dir, name + ".png"))
     hit = aov["geometry"] != 0xFFFFFFFF
     print(f"feature buffers -> {aov_dir}: coverage {float(aov['coverage'].mean()):.3f}, {len(np.unique(aov['geometry'][hit]))} geometries seen by sample 0")
+if denoise:
+    guides = instance.render_aov(camera, world, channels=("albedo", "normal", "depth"))
+    t0 = time.perf_counter()
+    clean = trt.denoise(image.data, guides["albedo"], guides["normal"], guides["depth"])
+    dt = time.perf_counter() - t0
+    trt.Image(clean).save("denoised.png")
+    p = trt.denoise_params()
+    print(f"denoised ({p.iterations} passes, call {dt * 1e3:.1f} ms with its copies) -> denoised.png")

@@ -39,7 +39,9 @@ extern "C" {
                              *              No struct changed size or moved a field.
  *              Later under 4 (new symbols only): trt_scene_create_on_device, trt_scene_get_packed; trt_hit, trt_intersect, trt_occluded,
  *              trt_intersect_device, trt_occluded_device; trt_query_plan, trt_query_launch_plan; trt_primary_rays,
- *              trt_primary_rays_device; trt_aov_buffers, trt_render_aov, trt_render_aov_device, trt_aov_launch_plan. */
+ *              trt_primary_rays_device; trt_aov_buffers, trt_render_aov, trt_render_aov_device, trt_aov_launch_plan;
+ *              trt_denoise_params, trt_denoise_params_default, trt_denoise_inputs, trt_denoise_scratch_bytes, trt_denoise,
+ *              trt_denoise_device. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -375,6 +377,57 @@ int trt_render_aov_device(trt_scene *s, const trt_camera *cam, const trt_render_
 /* How trt_render_aov[_device] launches a local image of n_pixels on this scene: trt_query_launch_plan's rule and fields with pixels in
  * place of rays (rays_per_wave = pixels a wave owns, each for all of its samples), over the feature-buffer kernels' own table. */
 int trt_aov_launch_plan(const trt_scene *s, uint32_t n_pixels, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
+ * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`
+ * and `normal` 3 f32, `depth` 1 f32; each optional, NULL switches its term off), all row-major height x width, and writes `out`
+ * (3 f32 per pixel).  The weights come from the guides only.  Every output bit is determined: all arithmetic is f32, one IEEE operation
+ * per operator below, nothing fused, division correctly rounded, f32 denormals kept (0.5^128 is a denormal weight and occurs).
+ *
+ * Pass i = 0 .. iterations-1 has step = 1 << i, reads image c_i (c_0 = color) and writes c_{i+1}; the last one is `out`.  For pixel
+ * p = (x, y) the 25 taps are q = (x + dx*step, y + dy*step), dy = -2..2 outer, dx = -2..2 inner, h = {0.0625, 0.25, 0.375, 0.25, 0.0625}.
+ * A tap outside the image is skipped.  w = h[dy+2] * h[dx+2]; then, for every tap but the centre (dx == dy == 0), in this order:
+ *   normal given:    d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  d = d > 0 ? d : 0;  normal_power_log2 times d = d*d;  w = w*d
+ *   albedo term on:  da = a_p - a_q;  e = (da.r*da.r + da.g*da.g) + da.b*da.b;  m = 1 - e*inv_a;  m = m > 0 ? m : 0;  w = w*(m*m)
+ *                    with inv_a = 1 / (sigma_albedo*sigma_albedo), computed once
+ *   depth term on:   dz = z_p - z_q;  m = 1 - ((dz*dz) * inv_z(p)) * (1.0f / float(dx*dx + dy*dy));  m = m > 0 ? m : 0;  w = w*(m*m)
+ *                    with inv_z(p) = 1 / (s*s), s = (sigma_depth * z_p) * float(step): one division per pixel and pass - a relative
+ *                    depth change per pixel of tap distance; a miss pixel (z_p = 0) gives inf / NaN, which the comparison turns into 0
+ * A tap is taken only if w > 0 (a zero or NaN weight adds nothing, not 0 * c): acc.c = acc.c + w * c_q.c per channel, ws = ws + w.  The
+ * centre tap is always taken, so ws > 0; r = 1 / ws, out.c = acc.c * r.  A term is on when its buffer is given and, for albedo and
+ * depth, its sigma is > 0.
+ * Consequences: a pixel whose normal is 0 (every sample missed) keeps its colour (to the rounding of (w*c) * (1/w)); a NaN guide removes its taps and never poisons the
+ * frame; a NaN colour spreads only through taps with positive weight.  The weights do not depend on the colour (no colour edge-stop:
+ * with unknown variance it made a 4-spp frame worse) and the albedo is not divided out (it is constant per material here).
+ * Whole frames only: a band of a sharded render has no neighbours across its seams, so bands and several GPUs are out of scope - gather
+ * the frame and its buffers first.  width and height are at most 65536.
+ *
+ * trt_denoise: HOST buffers, synchronous; uploads, runs the device kernels, downloads.  There is no CPU path.
+ * trt_denoise_device: buffers in HBM on the calling thread's current device (the struct itself is read on the host, during the call),
+ * asynchronous on `stream`; allocates nothing - the ping-pong images and the packed guides live in `d_scratch`, at least
+ * trt_denoise_scratch_bytes(width, height, params) bytes (host arithmetic, needs no device; 0 for invalid arguments); any alignment.  The
+ * inputs are not written.  params == NULL means the defaults.  Both take no scene handle, like trt_tonemap_u8_device.
+ * Errors: TRT_ERR_INVALID_ARG before any device work - a NULL `in`, `color` or `out`, width or height 0 (or above 65536), iterations
+ * outside 1..8, normal_power_log2 above 10, a NaN sigma, a non-zero reserved word, an output that overlaps an input, for the device form
+ * a NULL scratch or one smaller than required - then TRT_ERR_NO_DEVICE or TRT_ERR_OOM. */
+typedef struct {
+    uint32_t iterations;          /* 1..8 (default 4): passes, steps 1, 2, 4, ... */
+    uint32_t normal_power_log2;   /* 0..10 (default 7): the normal stop is max(n_p . n_q, 0)^(2^this) */
+    float sigma_albedo;           /* default 0.1; <= 0 switches the albedo term off */
+    float sigma_depth;            /* default 0.05; <= 0 switches the depth term off */
+    uint32_t reserved[4];         /* zero */
+} trt_denoise_params;             /* 32 B */
+void trt_denoise_params_default(trt_denoise_params *out);
+typedef struct {
+    const float *color;           /* 3 f32 per pixel: the frame (required) */
+    const float *albedo;          /* 3 f32 per pixel, or NULL */
+    const float *normal;          /* 3 f32 per pixel, or NULL */
+    const float *depth;           /* 1 f32 per pixel, or NULL */
+} trt_denoise_inputs;             /* 32 B */
+uint64_t trt_denoise_scratch_bytes(uint32_t width, uint32_t height, const trt_denoise_params *params);
+int trt_denoise(const trt_denoise_inputs *in, uint32_t width, uint32_t height, const trt_denoise_params *params, float *out);
+int trt_denoise_device(const trt_denoise_inputs *d_in, uint32_t width, uint32_t height, const trt_denoise_params *params,
+                       float *d_out, void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /* Imager finalisation + Image -> RgbImage (imager.rs:52-53; utils/image.rs:92-111): c^(1/gamma),
  * clamp to [0, 0.999], *255, truncate; NaN -> 0.  HOST buffers, npixels*3 each. */

@@ -276,6 +276,14 @@ public:
         check(trt_render_aov(world.get_bvh(), &camera.pod, &params_, &b));
         return out;
     }
+    // The frame denoised by its own feature buffers (trt_denoise: the a-trous filter of tinyrt.h guided by albedo, normal and depth):
+    // `frame` as render() returned it, `aov` as render_aov() returned it for the same camera.
+    static Image denoise(const Image& frame, const FeatureBuffers& aov, const trt_denoise_params* params = nullptr) {
+        Image out(aov.width, aov.height);
+        const trt_denoise_inputs in{frame.linear(), aov.albedo.data(), aov.normal.data(), aov.depth.data()};
+        check(trt_denoise(&in, aov.width, aov.height, params, out.linear()));
+        return out;
+    }
     // The same call over several GPUs of the node (trt_render_multi): `devices` empty = every visible device.
     Image render_multi(const Camera& camera, World& world, const std::vector<int>& devices = {}, trt_stats* stats = nullptr) const {
         Image img(camera.pod.width, camera.pod.height);

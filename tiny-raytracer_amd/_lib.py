@@ -94,6 +94,22 @@ class AovBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FIELDS]
 
 
+class DenoiseParams(C.Structure):
+    """tinyrt.h trt_denoise_params: passes and edge stops of trt_denoise (32 bytes)."""
+    FIELDS = ("iterations", "normal_power_log2", "sigma_albedo", "sigma_depth")
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in self.FIELDS}
+
+
+class DenoiseInputs(C.Structure):
+    """tinyrt.h trt_denoise_inputs: the frame and its guides, each guide a pointer or NULL (term off)."""
+    FIELDS = ("color", "albedo", "normal", "depth")
+    _fields_ = [(n, C.c_void_p) for n in FIELDS]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -179,6 +195,11 @@ SIGNATURES = {
     "trt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
     "trt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.POINTER(AovBuffers), C.c_void_p]),
     "trt_aov_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "trt_denoise_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]),
+    "trt_denoise": (C.c_int, [C.POINTER(DenoiseInputs), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p]),
+    "trt_denoise_device": (C.c_int, [C.POINTER(DenoiseInputs), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p]),
     "trt_streamed_chunk_spp": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "trt_tonemap_u8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "trt_tonemap_u8_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),

@@ -446,6 +446,57 @@ def tonemap_u8_device(d_accum_ptr, npixels, d_rgb_ptr, gamma=2.2, stream_ptr=0):
                                     C.c_void_p(stream_ptr)))
 
 
+def denoise_params(**over):
+    """The library's default trt_denoise_params (iterations 4, normal_power_log2 7, sigma_albedo 0.1, sigma_depth 0.05) with `over`
+    applied."""
+    p = _lib.DenoiseParams()
+    lib.trt_denoise_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in _lib.DenoiseParams.FIELDS:
+            raise TypeError(f"unknown denoise parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_scratch_bytes(width, height, **params):
+    """trt_denoise_scratch_bytes: what denoise_device needs as scratch for a width x height frame (host arithmetic; 0 = invalid)."""
+    return int(lib.trt_denoise_scratch_bytes(int(width), int(height), C.byref(denoise_params(**params))))
+
+
+def denoise(color, albedo=None, normal=None, depth=None, **params):
+    """trt_denoise: the edge-avoiding a-trous filter of tinyrt.h over a frame (float32 [H, W, 3], as Renderer.render leaves it) guided by
+    the feature buffers of Renderer.render_aov - albedo and normal [H, W, 3], depth [H, W]; None switches a term off.  `params`:
+    iterations, normal_power_log2, sigma_albedo, sigma_depth.  Returns float32 [H, W, 3]; the inputs are not changed."""
+    c = np.ascontiguousarray(color, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("color must be [H, W, 3]")
+    h, w = c.shape[:2]
+    pod = _lib.DenoiseInputs()
+    keep = [c]
+    pod.color = c.ctypes.data if c.size else None
+    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, np.float32)
+        if a.shape != shape:
+            raise ValueError(f"{name} must be {list(shape)}")
+        keep.append(a)
+        setattr(pod, name, a.ctypes.data if a.size else None)
+    out = np.zeros((h, w, 3), np.float32)
+    check(lib.trt_denoise(C.byref(pod), w, h, C.byref(denoise_params(**params)), out.ctypes.data if out.size else None))
+    return out
+
+
+def denoise_device(d_color_ptr, width, height, d_out_ptr, d_scratch_ptr, scratch_bytes, d_albedo_ptr=0, d_normal_ptr=0, d_depth_ptr=0,
+                   stream_ptr=0, **params):
+    """Enqueue denoise() on buffers already in HBM (device pointers as integers; a guide pointer of 0 switches its term off): nothing is
+    allocated, `d_scratch_ptr` holds at least denoise_scratch_bytes(width, height) bytes; asynchronous on the stream."""
+    pod = _lib.DenoiseInputs()
+    pod.color, pod.albedo, pod.normal, pod.depth = (d_color_ptr or None, d_albedo_ptr or None, d_normal_ptr or None, d_depth_ptr or None)
+    check(lib.trt_denoise_device(C.byref(pod), int(width), int(height), C.byref(denoise_params(**params)), C.c_void_p(d_out_ptr),
+                                 C.c_void_p(d_scratch_ptr), int(scratch_bytes), C.c_void_p(stream_ptr)))
+
+
 def sample_batch(scene, points, max_bounces, background, seed=1, collect_stats=True):
     """trait Sampler in batch form: ctypes array of SamplePoint -> SampledColor.  collect_stats=False runs the production walk
     (no traversal counters) instead of the counting kernel on the reference tree."""
