@@ -275,6 +275,21 @@ impl Default for trt_denoise_inputs {
     }
 }
 
+/// The variance image and sigma of `trt_denoise_ex`'s colour stop; take the default sigma from `trt_denoise_color_default`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct trt_denoise_color {
+    pub variance: *const f32,
+    pub sigma_color: f32,
+    pub reserved: [u32; 5],
+}
+impl Default for trt_denoise_color {
+    fn default() -> Self {
+        // null variance, sigma 0: the term is off
+        unsafe { std::mem::zeroed() }
+    }
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct trt_stats {
@@ -339,6 +354,13 @@ extern "C" {
                                     out: *mut trt_launch_plan) -> c_int;
     pub fn trt_render_device(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, d_accum: *mut f32,
                              d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_render_moments(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, accum: *mut f32,
+                              moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_render_moments_device(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, d_accum: *mut f32,
+                                     d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_variance(accum: *const f32, moment2: *const f32, npixels: u32, samples_per_pixel: u32, variance: *mut f32) -> c_int;
+    pub fn trt_variance_device(d_accum: *const f32, d_moment2: *const f32, npixels: u32, samples_per_pixel: u32,
+                               d_variance: *mut f32, stream: *mut c_void) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;
@@ -360,6 +382,12 @@ extern "C" {
     pub fn trt_denoise(input: *const trt_denoise_inputs, width: u32, height: u32, params: *const trt_denoise_params, out: *mut f32) -> c_int;
     pub fn trt_denoise_device(d_in: *const trt_denoise_inputs, width: u32, height: u32, params: *const trt_denoise_params,
                               d_out: *mut f32, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> c_int;
+    pub fn trt_denoise_color_default(out: *mut trt_denoise_color);
+    pub fn trt_denoise_ex(input: *const trt_denoise_inputs, color: *const trt_denoise_color, width: u32, height: u32,
+                          params: *const trt_denoise_params, out: *mut f32) -> c_int;
+    pub fn trt_denoise_ex_device(d_in: *const trt_denoise_inputs, color: *const trt_denoise_color, width: u32, height: u32,
+                                 params: *const trt_denoise_params, d_out: *mut f32, d_scratch: *mut c_void, scratch_bytes: u64,
+                                 stream: *mut c_void) -> c_int;
     pub fn trt_tonemap_u8(accum: *const f32, npixels: u32, gamma: f32, rgb: *mut u8) -> c_int;
     pub fn trt_tonemap_u8_device(d_accum: *const f32, npixels: u32, gamma: f32, d_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn trt_streamed_chunk_spp(width: u32, rows: u32) -> u32;

@@ -343,6 +343,29 @@ impl Renderer {
         Ok(Image { width, height, gamma: 2.2, data })
     }
 
+    /// `render` that also returns the per-pixel second moments (`trt_render_moments`; streamed backend) and the variance of every pixel's
+    /// estimate (`trt_variance`: 1 value per pixel, +inf at 1 spp): `(frame, moment2, variance)`.  The frame is `render`'s, bit for bit.
+    pub fn render_moments(&self, camera: &Camera, world: &mut World) -> Result<(Image, Vec<Float>, Vec<Float>), Error> {
+        let (width, height) = camera.get_image_size();
+        let scene = world.get_bvh()?;
+        let params = sys::trt_render_params {
+            samples_per_pixel: self.samples_per_pixel as u32,
+            max_bounces: self.max_bounces as u32,
+            background: self.background_color.raw(),
+            seed: self.seed,
+            backend: self.backend,
+            tuning: self.tuning.as_ref().map_or(ptr::null(), |t| t as *const sys::trt_tuning),
+            ..Default::default()
+        };
+        let n = width * height;
+        let mut data = vec![0.0 as Float; n * 3];
+        let mut moment2 = vec![0.0 as Float; n * 3];
+        let mut variance = vec![0.0 as Float; n];
+        check(unsafe { sys::trt_render_moments(scene, &camera.pod, &params, data.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut()) })?;
+        check(unsafe { sys::trt_variance(data.as_ptr(), moment2.as_ptr(), n as u32, self.samples_per_pixel as u32, variance.as_mut_ptr()) })?;
+        Ok((Image { width, height, gamma: 2.2, data }, moment2, variance))
+    }
+
     /// All six feature buffers of the frame `render` would trace: same seed, same samples, same primary rays.
     pub fn render_aov(&self, camera: &Camera, world: &mut World) -> Result<FeatureBuffers, Error> {
         let (width, height) = camera.get_image_size();
@@ -387,6 +410,25 @@ impl Renderer {
         };
         let mut data = vec![0.0 as Float; aov.width * aov.height * 3];
         check(unsafe { sys::trt_denoise(&input, aov.width as u32, aov.height as u32, ptr::null(), data.as_mut_ptr()) })?;
+        Ok(Image { width: aov.width, height: aov.height, gamma: frame.gamma, data })
+    }
+
+    /// `denoise` with the variance-guided colour stop (`trt_denoise_ex`, default sigma): `variance` as `render_moments` returned it.
+    pub fn denoise_with_variance(frame: &Image, aov: &FeatureBuffers, variance: &[Float]) -> Result<Image, Error> {
+        if variance.len() != aov.width * aov.height {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "one variance per pixel".to_string() });
+        }
+        let input = sys::trt_denoise_inputs {
+            color: frame.data.as_ptr(),
+            albedo: aov.albedo.as_ptr(),
+            normal: aov.normal.as_ptr(),
+            depth: aov.depth.as_ptr(),
+        };
+        let mut color = sys::trt_denoise_color::default();
+        unsafe { sys::trt_denoise_color_default(&mut color) };
+        color.variance = variance.as_ptr();
+        let mut data = vec![0.0 as Float; aov.width * aov.height * 3];
+        check(unsafe { sys::trt_denoise_ex(&input, &color, aov.width as u32, aov.height as u32, ptr::null(), data.as_mut_ptr()) })?;
         Ok(Image { width: aov.width, height: aov.height, gamma: frame.gamma, data })
     }
 

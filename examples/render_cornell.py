@@ -4,7 +4,9 @@
 --aov DIR also writes the frame's first-hit feature buffers (Renderer.render_aov: same seed, samples and primary rays as the render) to
 DIR: albedo.png, normal.png ((n + 1) / 2), depth.png (scaled to the farthest hit), coverage.png, and all six as arrays in aov.npz.
 --denoise also writes denoised.png beside output.png: the frame through trt.denoise (the a-trous filter of tinyrt.h, default parameters)
-guided by the albedo, normal and depth buffers of the same seed and samples."""
+guided by the albedo, normal and depth buffers of the same seed and samples and, from 2 spp on, by the variance of every pixel's estimate
+(Renderer.render_moments + trt.variance: the colour stop of trt_denoise_ex); and variance.png, the standard error per pixel (the square
+root of that variance, white = 0.25 and more)."""
 import os
 import sys
 import time
@@ -25,7 +27,11 @@ w, h, spp = (int(a) for a in argv[:3]) if len(argv) >= 3 else (300, 300, 300)
 world, camera = trt.world_from_description(trt.scenes.cornell(w, h))          # build_world + Camera::new, src/main.rs:7-16
 instance = trt.Renderer(spp, 8, 20, True, (0.001, 0.001, 0.001))             # Renderer::new(300, 8, 20, true, Some(0.001))
 t0 = time.perf_counter()
-image = instance.render(camera, world)
+if denoise:                                                                  # the same frame, bit for bit, with its second moments
+    accum, moment2, _ = instance.render_moments(camera, world)
+    image = trt.Image(accum)
+else:
+    image = instance.render(camera, world)
 dt = time.perf_counter() - t0
 image.save("output.png")
 st = instance.last_stats
@@ -46,8 +52,13 @@ if aov_dir:
 if denoise:
     guides = instance.render_aov(camera, world, channels=("albedo", "normal", "depth"))
     t0 = time.perf_counter()
-    clean = trt.denoise(image.data, guides["albedo"], guides["normal"], guides["depth"])
+    import numpy as np
+    var = trt.variance(accum, moment2, spp)                                  # +inf at 1 spp: unknown
+    clean = trt.denoise(image.data, guides["albedo"], guides["normal"], guides["depth"], variance=var if spp >= 2 else None)
     dt = time.perf_counter() - t0
     trt.Image(clean).save("denoised.png")
+    err = np.sqrt(np.where(np.isfinite(var), var, 0.0)).astype(np.float32)
+    trt.Image(np.ascontiguousarray(np.repeat((err / 0.25)[:, :, None], 3, axis=2), np.float32), gamma=1.0).save("variance.png")
     p = trt.denoise_params()
-    print(f"denoised ({p.iterations} passes, call {dt * 1e3:.1f} ms with its copies) -> denoised.png")
+    print(f"denoised ({p.iterations} passes, sigma_color {trt.denoise_color().sigma_color:g}, call {dt * 1e3:.1f} ms with its copies) -> denoised.png; "
+          f"standard error: median {float(np.median(err)):.4f}, 99th percentile {float(np.percentile(err, 99)):.4f} -> variance.png")

@@ -41,7 +41,8 @@ extern "C" {
  *              trt_intersect_device, trt_occluded_device; trt_query_plan, trt_query_launch_plan; trt_primary_rays,
  *              trt_primary_rays_device; trt_aov_buffers, trt_render_aov, trt_render_aov_device, trt_aov_launch_plan;
  *              trt_denoise_params, trt_denoise_params_default, trt_denoise_inputs, trt_denoise_scratch_bytes, trt_denoise,
- *              trt_denoise_device. */
+ *              trt_denoise_device; trt_render_moments, trt_render_moments_device, trt_variance, trt_variance_device;
+ *              trt_denoise_color, trt_denoise_color_default, trt_denoise_ex, trt_denoise_ex_device. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -279,6 +280,37 @@ int trt_band_copy_plan(uint32_t width, uint32_t height, uint32_t ndev, uint32_t 
 int trt_render_device(trt_scene *s, const trt_camera *cam, const trt_render_params *p, float *d_accum,
                       uint64_t *d_counters, void *stream);
 
+/* ---- The frame with its per-pixel second moments, and the variance of the pixel estimate ----
+ * trt_render / trt_render_device that also write `moment2` (rows*width*3 f32, the frame's layout): where the frame folds
+ *   accum.ch = accum.ch + c_s.ch * inv_spp                      (imager.rs:35,50; inv_spp = 1 / samples_per_pixel)
+ * over the samples s of a pixel in order, the same pass also folds
+ *   moment2.ch = moment2.ch + (c_s.ch * c_s.ch) * inv_spp
+ * per channel; each operator is one IEEE f32 operation, nothing is fused.  `accum` is bit-identical to what trt_render /
+ * trt_render_device write for the same arguments.  Bands, sample_begin / sample_end and accumulate behave for `moment2` exactly as
+ * for the frame: with samples_per_pixel equal, the result does not depend on how the sample range is split over calls.  Nothing to
+ * trace (no rows, an empty sample range, max_bounces == 0): both buffers are zeroed unless accumulate.  collect_stats and tuning as in
+ * trt_render.
+ * Only the streamed backend keeps per-sample records: p->backend must be TRT_BACKEND_STREAMED or TRT_BACKEND_AUTO.  Any other backend,
+ * or a NULL `moment2`, is TRT_ERR_INVALID_ARG before any device work.  Several GPUs: shard with the band fields; there is no multi form.
+ * trt_render_moments: HOST buffers, synchronous (the second device frame is allocated for the call and freed before it returns).
+ * trt_render_moments_device: buffers in HBM, asynchronous on `stream`, as trt_render_device. */
+int trt_render_moments(trt_scene *s, const trt_camera *cam, const trt_render_params *p, float *accum, float *moment2, trt_stats *stats);
+int trt_render_moments_device(trt_scene *s, const trt_camera *cam, const trt_render_params *p, float *d_accum, float *d_moment2,
+                              uint64_t *d_counters, void *stream);
+/* Variance of the pixel estimate, 1 f32 per pixel: the trace over the channels of the unbiased variance of the mean.  With S = accum
+ * (the mean of the N = samples_per_pixel samples) and M = moment2 (the mean of their squares), all f32, one IEEE operation per operator:
+ *   per channel  d = M - S*S;  d = d > 0 ? d : 0          (a NaN becomes 0)
+ *   variance = ((d.r + d.g) + d.b) * (1.0f / float(N - 1))
+ * N <= 1 writes +inf: unknown.  M - S*S cancels: its error is about 2^-23 * M relative to M (M is at most 225 for the light of 15 in
+ * the Cornell box, so about 3e-5 absolute), which matters only where the variance is that small anyway - and is the reason for the clamp:
+ * a constant pixel may give a tiny negative d.  The square root of a channel's share is the standard error of that pixel.
+ * trt_variance: HOST buffers, synchronous (uploads, runs the device kernel, downloads; there is no CPU path).  trt_variance_device:
+ * buffers in HBM on the calling thread's current device, asynchronous on `stream`.  A NULL buffer with npixels > 0 is
+ * TRT_ERR_INVALID_ARG before any device work; npixels == 0 succeeds and touches nothing, with or without a device. */
+int trt_variance(const float *accum, const float *moment2, uint32_t npixels, uint32_t samples_per_pixel, float *variance);
+int trt_variance_device(const float *d_accum, const float *d_moment2, uint32_t npixels, uint32_t samples_per_pixel, float *d_variance,
+                        void *stream);
+
 /* The literal Sampler plug-in form (sampler/mod.rs:10-17): n SamplePoints in, n SampledColors
  * out, HOST buffers.  Point i uses RNG stream (seed, pixel=i, sample=0).  With `stats` non-NULL the counting kernel runs
  * (reference-order walk of the reference tree: its counters equal the CPU path's); with NULL the production walk. */
@@ -398,7 +430,7 @@ int trt_aov_launch_plan(const trt_scene *s, uint32_t n_pixels, uint32_t compute_
  * depth, its sigma is > 0.
  * Consequences: a pixel whose normal is 0 (every sample missed) keeps its colour (to the rounding of (w*c) * (1/w)); a NaN guide removes its taps and never poisons the
  * frame; a NaN colour spreads only through taps with positive weight.  The weights do not depend on the colour (no colour edge-stop:
- * with unknown variance it made a 4-spp frame worse) and the albedo is not divided out (it is constant per material here).
+ * with unknown variance it made a 4-spp frame worse; trt_denoise_ex below has one, scaled by the variance) and the albedo is not divided out (it is constant per material here).
  * Whole frames only: a band of a sharded render has no neighbours across its seams, so bands and several GPUs are out of scope - gather
  * the frame and its buffers first.  width and height are at most 65536.
  *
@@ -428,6 +460,42 @@ uint64_t trt_denoise_scratch_bytes(uint32_t width, uint32_t height, const trt_de
 int trt_denoise(const trt_denoise_inputs *in, uint32_t width, uint32_t height, const trt_denoise_params *params, float *out);
 int trt_denoise_device(const trt_denoise_inputs *d_in, uint32_t width, uint32_t height, const trt_denoise_params *params,
                        float *d_out, void *d_scratch, uint64_t scratch_bytes, void *stream);
+
+/* ---- The same filter with a variance-guided colour stop ----
+ * trt_denoise's weights ignore the colour, so what the guides do not show - a shadow edge, the falloff of the light on a wall, a
+ * reflection - is blurred by the same amount at 4 and at 4096 samples per pixel.  trt_denoise_ex adds one more stop, scaled by the
+ * variance of each pixel's estimate (trt_variance): it backs off as the frame converges.  `color` == NULL, `variance` == NULL or
+ * sigma_color <= 0 switch the term off: the output is then trt_denoise's, byte for byte.  With the term on, all f32, one IEEE operation
+ * per operator, nothing fused:
+ *   prefilter (once): v_0(p) = sv * (1.0f / sw), with sv = sv + k*variance_q and sw = sw + k accumulated from 0 over the taps
+ *                    q = (x + dx, y + dy), dy = -1..1 outer, dx = -1..1 inner, that lie inside the image, k = b[dy+1] * b[dx+1],
+ *                    b = {0.25, 0.5, 0.25} (at 4 spp a single pixel's variance is itself an estimate from 4 numbers)
+ *   pass i, for every tap but the centre, after the depth term, on that pass's input image c_i:
+ *                    dc = c_p - c_q;  e = (dc.r*dc.r + dc.g*dc.g) + dc.b*dc.b;  m = 1 - e*inv_c(p);  m = m > 0 ? m : 0;  w = w*(m*m)
+ *                    with inv_c(p) = 1 / ((sigma_color*sigma_color) * v_i(p)): one division per pixel and pass
+ *   propagation:     beside acc and ws, va = va + (w*w) * v_i(q) over the taken taps (the centre among them), from 0;
+ *                    v_{i+1}(p) = va * (r*r) with r = 1 / ws: the variance of the weighted mean, were the taps independent.  Without it
+ *                    later passes would compare smoothed colours against the raw variance and the stop would go slack.
+ * Consequences: v_i(p) = +inf gives inv_c = 0, every m = 1 for a finite e, the term multiplies by 1 and the pass is trt_denoise's, bit
+ * for bit.  v_i(p) = 0 gives inv_c = inf, every neighbour's m is -inf or NaN, then 0: a converged pixel keeps its colour (to the
+ * rounding of (w*c) * (1/w)) and its v stays 0.  A NaN v_i(p) likewise keeps the pixel.  The prefilter spreads an inf or NaN of
+ * `variance` to the 3 x 3 around it, and the propagation carries a NaN v to every pixel that takes a tap on it: those are kept from the
+ * next pass on.  That also limits the first consequence over SEVERAL passes: a taken tap whose w*w underflows to 0 (w below about 2^-75:
+ * an edge pixel's normal stop) gives 0 * inf = NaN.  A 1-spp frame (trt_variance writes +inf everywhere) therefore comes out as from
+ * trt_denoise after one pass, but after four passes only where no such tap was in reach - on a 4-spp Cornell frame with v = +inf, 43 %
+ * of the pixels.  At 1 spp pass no variance.
+ * Scratch: trt_denoise_scratch_bytes, unchanged - v_i rides in the unused fourth word of the 16-byte colour records.
+ * Errors, besides trt_denoise's: a NaN sigma_color, a non-zero reserved word, an output that overlaps `variance`. */
+typedef struct {
+    const float *variance;        /* 1 f32 per pixel as trt_variance writes it, or NULL: term off */
+    float sigma_color;            /* <= 0: term off; NaN: TRT_ERR_INVALID_ARG */
+    uint32_t reserved[5];         /* zero */
+} trt_denoise_color;              /* 32 B */
+void trt_denoise_color_default(trt_denoise_color *out);
+int trt_denoise_ex(const trt_denoise_inputs *in, const trt_denoise_color *color, uint32_t width, uint32_t height,
+                   const trt_denoise_params *params, float *out);
+int trt_denoise_ex_device(const trt_denoise_inputs *d_in, const trt_denoise_color *color, uint32_t width, uint32_t height,
+                          const trt_denoise_params *params, float *d_out, void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /* Imager finalisation + Image -> RgbImage (imager.rs:52-53; utils/image.rs:92-111): c^(1/gamma),
  * clamp to [0, 0.999], *255, truncate; NaN -> 0.  HOST buffers, npixels*3 each. */

@@ -262,6 +262,20 @@ public:
         check(trt_render(world.get_bvh(), &camera.pod, &params_, img.linear(), stats));
         return img;
     }
+    // render() that also fills the per-pixel second moments (trt_render_moments; streamed backend): `moment2` gets width * height * 3
+    // floats.  The frame is render()'s, bit for bit.
+    Image render_moments(const Camera& camera, World& world, std::vector<float>& moment2, trt_stats* stats = nullptr) const {
+        Image img(camera.pod.width, camera.pod.height);
+        moment2.assign((size_t)camera.pod.width * camera.pod.height * 3, 0.0f);
+        check(trt_render_moments(world.get_bvh(), &camera.pod, &params_, img.linear(), moment2.data(), stats));
+        return img;
+    }
+    // Variance of every pixel's estimate (trt_variance: 1 float per pixel, +inf at 1 spp) from a frame and its second moments.
+    std::vector<float> variance(const Image& frame, const std::vector<float>& moment2) const {
+        std::vector<float> v((size_t)frame.width() * frame.height(), 0.0f);
+        check(trt_variance(frame.linear(), moment2.data(), frame.width() * frame.height(), params_.samples_per_pixel, v.data()));
+        return v;
+    }
     // All six feature buffers of the frame render() would trace: same seed, same samples, same primary rays.
     FeatureBuffers render_aov(const Camera& camera, World& world) const {
         FeatureBuffers out;
@@ -282,6 +296,20 @@ public:
         Image out(aov.width, aov.height);
         const trt_denoise_inputs in{frame.linear(), aov.albedo.data(), aov.normal.data(), aov.depth.data()};
         check(trt_denoise(&in, aov.width, aov.height, params, out.linear()));
+        return out;
+    }
+    // denoise() with the variance-guided colour stop (trt_denoise_ex): `variance` as variance() returned it; sigma_color <= 0 = the
+    // library's default (trt_denoise_color_default).
+    static Image denoise(const Image& frame, const FeatureBuffers& aov, const std::vector<float>& variance, float sigma_color = 0.0f,
+                         const trt_denoise_params* params = nullptr) {
+        if (variance.size() != (size_t)aov.width * aov.height) throw Error(TRT_ERR_INVALID_ARG, "one variance per pixel");
+        Image out(aov.width, aov.height);
+        const trt_denoise_inputs in{frame.linear(), aov.albedo.data(), aov.normal.data(), aov.depth.data()};
+        trt_denoise_color col;
+        trt_denoise_color_default(&col);
+        col.variance = variance.data();
+        if (sigma_color > 0.0f) col.sigma_color = sigma_color;
+        check(trt_denoise_ex(&in, &col, aov.width, aov.height, params, out.linear()));
         return out;
     }
     // The same call over several GPUs of the node (trt_render_multi): `devices` empty = every visible device.

@@ -110,6 +110,11 @@ class DenoiseInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FIELDS]
 
 
+class DenoiseColor(C.Structure):
+    """tinyrt.h trt_denoise_color: the variance image and sigma of trt_denoise_ex's colour stop (32 bytes)."""
+    _fields_ = [("variance", C.c_void_p), ("sigma_color", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -183,6 +188,11 @@ SIGNATURES = {
     "trt_kernel_timing_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "trt_render_device": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "trt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_render_moments_device": (C.c_int, [C.c_void_p, C.POINTER(CameraPOD), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "trt_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "trt_variance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
@@ -200,6 +210,10 @@ SIGNATURES = {
     "trt_denoise": (C.c_int, [C.POINTER(DenoiseInputs), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p]),
     "trt_denoise_device": (C.c_int, [C.POINTER(DenoiseInputs), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p,
                                      C.c_uint64, C.c_void_p]),
+    "trt_denoise_color_default": (None, [C.POINTER(DenoiseColor)]),
+    "trt_denoise_ex": (C.c_int, [C.POINTER(DenoiseInputs), C.POINTER(DenoiseColor), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p]),
+    "trt_denoise_ex_device": (C.c_int, [C.POINTER(DenoiseInputs), C.POINTER(DenoiseColor), C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams),
+                                        C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "trt_streamed_chunk_spp": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "trt_tonemap_u8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "trt_tonemap_u8_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),

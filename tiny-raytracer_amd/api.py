@@ -407,6 +407,32 @@ class Renderer:
                                     C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
 
 
+    def render_moments(self, camera, world, collect_stats=False, accum=None, moment2=None, **over):
+        """trt_render_moments: render() that also returns the per-pixel second moments - (accum, moment2, stats), both float32
+        [rows, width, 3]: accum is render()'s frame bit for bit, moment2 the sum of c_s * c_s / spp over the same samples in the same order.
+        Streamed backend only (BACKEND_AUTO or BACKEND_STREAMED).  `accum`, `moment2`: the buffers of earlier passes to continue
+        (over["accumulate"] = 1); `over`: sample range, bands.  variance(accum, moment2, spp) turns the pair into the variance per pixel."""
+        scene = world.get_bvh() if isinstance(world, World) else world
+        p = self.params(collect_stats=int(collect_stats), **over)
+        w, h = camera.get_image_size()
+        rows = p.rows_local if p.band_rows else h
+        bufs = []
+        for a in (accum, moment2):
+            if a is None:
+                a = np.zeros((rows, w, 3), np.float32)
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (rows, w, 3)
+            bufs.append(a)
+        st = Stats()
+        check(lib.trt_render_moments(scene._h, C.byref(camera.pod), C.byref(p), bufs[0].ctypes.data, bufs[1].ctypes.data, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return bufs[0], bufs[1], self.last_stats
+
+    def render_moments_device(self, camera, scene, d_accum_ptr, d_moment2_ptr, stream_ptr=0, d_counters_ptr=0, **over):
+        """Enqueue render_moments() on buffers already in HBM (device pointers as integers, each rows x width x 12 bytes); asynchronous."""
+        p = self.params(**over)
+        check(lib.trt_render_moments_device(scene._h, C.byref(camera.pod), C.byref(p), C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr),
+                                            C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
     def render_aov(self, camera, world, channels=tuple(AOV_CHANNELS), buffers=None, **over):
         """trt_render_aov: the first-hit feature buffers of this renderer's frame (same seed, samples and rays as render()), as a dict
         channel -> array [rows, width, 3] or [rows, width] for the `channels` asked (albedo, normal, depth, coverage: float32 sums over the
@@ -446,6 +472,25 @@ def tonemap_u8_device(d_accum_ptr, npixels, d_rgb_ptr, gamma=2.2, stream_ptr=0):
                                     C.c_void_p(stream_ptr)))
 
 
+def variance(accum, moment2, samples_per_pixel):
+    """trt_variance: the variance of every pixel's estimate from a frame and its second moments (Renderer.render_moments), float32 with
+    the frames' shape less the channel axis: the trace over r, g, b of the unbiased variance of the mean; +inf where samples_per_pixel <= 1."""
+    s = np.ascontiguousarray(accum, np.float32)
+    m = np.ascontiguousarray(moment2, np.float32)
+    if s.ndim < 1 or s.shape[-1] != 3 or m.shape != s.shape:
+        raise ValueError("accum and moment2 must have the same shape [..., 3]")
+    out = np.zeros(s.shape[:-1], np.float32)
+    check(lib.trt_variance(s.ctypes.data if s.size else None, m.ctypes.data if s.size else None, out.size, int(samples_per_pixel),
+                           out.ctypes.data if out.size else None))
+    return out
+
+
+def variance_device(d_accum_ptr, d_moment2_ptr, npixels, samples_per_pixel, d_variance_ptr, stream_ptr=0):
+    """Enqueue variance() on buffers already in HBM (device pointers as integers; npixels floats out); asynchronous on the stream."""
+    check(lib.trt_variance_device(C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), int(npixels), int(samples_per_pixel),
+                                  C.c_void_p(d_variance_ptr), C.c_void_p(stream_ptr)))
+
+
 def denoise_params(**over):
     """The library's default trt_denoise_params (iterations 4, normal_power_log2 7, sigma_albedo 0.1, sigma_depth 0.05) with `over`
     applied."""
@@ -463,10 +508,23 @@ def denoise_scratch_bytes(width, height, **params):
     return int(lib.trt_denoise_scratch_bytes(int(width), int(height), C.byref(denoise_params(**params))))
 
 
-def denoise(color, albedo=None, normal=None, depth=None, **params):
+def denoise_color(variance_ptr=None, sigma_color=None):
+    """trt_denoise_color for trt_denoise_ex: the library's default sigma_color unless one is given; `variance_ptr`: address of the
+    variance image (1 float per pixel, as variance() returns it) or None (term off)."""
+    c = _lib.DenoiseColor()
+    lib.trt_denoise_color_default(C.byref(c))
+    c.variance = variance_ptr or None
+    if sigma_color is not None:
+        c.sigma_color = float(sigma_color)
+    return c
+
+
+def denoise(color, albedo=None, normal=None, depth=None, variance=None, sigma_color=None, **params):
     """trt_denoise: the edge-avoiding a-trous filter of tinyrt.h over a frame (float32 [H, W, 3], as Renderer.render leaves it) guided by
     the feature buffers of Renderer.render_aov - albedo and normal [H, W, 3], depth [H, W]; None switches a term off.  `params`:
-    iterations, normal_power_log2, sigma_albedo, sigma_depth.  Returns float32 [H, W, 3]; the inputs are not changed."""
+    iterations, normal_power_log2, sigma_albedo, sigma_depth.  Returns float32 [H, W, 3]; the inputs are not changed.
+    `variance` (float32 [H, W], as variance() returns it) switches on trt_denoise_ex's variance-guided colour stop with `sigma_color`
+    (None: the library's default; <= 0: term off); without `variance` the call is trt_denoise as before."""
     c = np.ascontiguousarray(color, np.float32)
     if c.ndim != 3 or c.shape[2] != 3:
         raise ValueError("color must be [H, W, 3]")
@@ -483,16 +541,29 @@ def denoise(color, albedo=None, normal=None, depth=None, **params):
         keep.append(a)
         setattr(pod, name, a.ctypes.data if a.size else None)
     out = np.zeros((h, w, 3), np.float32)
-    check(lib.trt_denoise(C.byref(pod), w, h, C.byref(denoise_params(**params)), out.ctypes.data if out.size else None))
+    if variance is None:
+        check(lib.trt_denoise(C.byref(pod), w, h, C.byref(denoise_params(**params)), out.ctypes.data if out.size else None))
+        return out
+    v = np.ascontiguousarray(variance, np.float32)
+    if v.shape != (h, w):
+        raise ValueError(f"variance must be {[h, w]}")
+    col = denoise_color(v.ctypes.data if v.size else None, sigma_color)
+    check(lib.trt_denoise_ex(C.byref(pod), C.byref(col), w, h, C.byref(denoise_params(**params)), out.ctypes.data if out.size else None))
     return out
 
 
 def denoise_device(d_color_ptr, width, height, d_out_ptr, d_scratch_ptr, scratch_bytes, d_albedo_ptr=0, d_normal_ptr=0, d_depth_ptr=0,
-                   stream_ptr=0, **params):
+                   stream_ptr=0, d_variance_ptr=0, sigma_color=None, **params):
     """Enqueue denoise() on buffers already in HBM (device pointers as integers; a guide pointer of 0 switches its term off): nothing is
-    allocated, `d_scratch_ptr` holds at least denoise_scratch_bytes(width, height) bytes; asynchronous on the stream."""
+    allocated, `d_scratch_ptr` holds at least denoise_scratch_bytes(width, height) bytes; asynchronous on the stream.  `d_variance_ptr`
+    (width x height floats, as variance_device() writes them) and `sigma_color` as in denoise(): trt_denoise_ex_device, same scratch."""
     pod = _lib.DenoiseInputs()
     pod.color, pod.albedo, pod.normal, pod.depth = (d_color_ptr or None, d_albedo_ptr or None, d_normal_ptr or None, d_depth_ptr or None)
+    if d_variance_ptr:
+        col = denoise_color(d_variance_ptr, sigma_color)
+        check(lib.trt_denoise_ex_device(C.byref(pod), C.byref(col), int(width), int(height), C.byref(denoise_params(**params)),
+                                        C.c_void_p(d_out_ptr), C.c_void_p(d_scratch_ptr), int(scratch_bytes), C.c_void_p(stream_ptr)))
+        return
     check(lib.trt_denoise_device(C.byref(pod), int(width), int(height), C.byref(denoise_params(**params)), C.c_void_p(d_out_ptr),
                                  C.c_void_p(d_scratch_ptr), int(scratch_bytes), C.c_void_p(stream_ptr)))
 

@@ -505,8 +505,10 @@ int to_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs
     return TRT_OK;
 }
 
+// `d_moment2` with `launch_moments` (trt_render_moments*, streamed backend only - query_render_moments* refuse every other): a second
+// frame-shaped buffer for the second moments and the launcher that fills both (scene_query.h MomentsLaunch).
 int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* d_accum, uint64_t* d_counters,
-                   hipStream_t stream, uint32_t* rows_out) {
+                   hipStream_t stream, uint32_t* rows_out, float* d_moment2 = nullptr, MomentsLaunch launch_moments = nullptr) {
     RenderArgs ra;
     trt_tuning tn;
     uint32_t rows = 0;
@@ -523,6 +525,7 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
     if (rows == 0 || ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64)
         if (!ra.accumulate && bytes) TRT_HIP(hipMemsetAsync(d_accum, 0, bytes, stream));
+        if (!ra.accumulate && bytes && d_moment2) TRT_HIP(hipMemsetAsync(d_moment2, 0, bytes, stream));
         return TRT_OK;
     }
     const bool wavefront = p->backend == TRT_BACKEND_WAVEFRONT;
@@ -582,7 +585,11 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
         }
         if (rc != TRT_OK) return rc;
         hipError_t le;
-        if (streamed) {
+        if (streamed && d_moment2) {
+            le = launch_moments ? launch_moments(sc, cd, ra, tn, ws->ptr, ws->bytes, d_accum, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),
+                                                 p->collect_stats != 0, stream)
+                                : hipErrorInvalidDeviceFunction;                 // no launcher handed over: a bug, never a fallback
+        } else if (streamed) {
             le = launch_streamed(sc, cd, ra, tn, ws->ptr, ws->bytes, d_accum, reinterpret_cast<unsigned long long*>(d_counters), p->collect_stats != 0, stream);
         } else {
             le = launch_wavefront(sc, cd, ra, tn, ws->ptr, d_accum, reinterpret_cast<unsigned long long*>(d_counters), p->collect_stats != 0, stream);
@@ -929,8 +936,22 @@ int trt_render_device(trt_scene* s, const trt_camera* cam, const trt_render_para
     return enqueue_render(s, cam, p, d_accum, d_counters, reinterpret_cast<hipStream_t>(stream), nullptr);
 }
 
-int trt_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, trt_stats* stats) {
-    if (!s || !cam || !p || !accum) return fail(TRT_ERR_INVALID_ARG, "null argument");
+}  // extern "C"
+
+namespace {
+
+// What trt_render_moments* asks beyond trt_render: a second buffer, and a backend that keeps per-sample records.
+int check_moments(const trt_render_params* p, const float* moment2) {
+    if (!moment2) return fail(TRT_ERR_INVALID_ARG, "moment2 is null");
+    if (p->backend != TRT_BACKEND_STREAMED && p->backend != TRT_BACKEND_AUTO)
+        return fail(TRT_ERR_INVALID_ARG, "second moments come from the streamed backend's fold: backend must be TRT_BACKEND_STREAMED or TRT_BACKEND_AUTO");
+    return TRT_OK;
+}
+
+// trt_render, and with `moment2` trt_render_moments.  The second moments' device frame is the call's own: allocated here and freed before
+// the call returns, so what trt_render allocates and what a context keeps are as they were.
+int render_host(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, float* moment2, trt_stats* stats,
+                MomentsLaunch launch_moments) {
     int rc = require_device();
     if (rc != TRT_OK) return rc;
     RenderArgs probe;
@@ -946,9 +967,19 @@ int trt_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, 
     if (rc != TRT_OK) return rc;
     unsigned long long h_ctr[CTR_COUNT] = {0};
     float ms = 0.0f;
+    float* d_m2 = nullptr;
+    if (moment2) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_m2), bytes ? bytes : 16);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            context_release(s, dev, c);
+            return fail(TRT_ERR_OOM, std::string("second-moment frame: ") + hipGetErrorString(e));
+        }
+    }
     // from here on every exit drains the context's stream before the context goes back to the pool
     auto finish = [&](int code) {
         (void)hipStreamSynchronize(c->stream);
+        if (d_m2) (void)hipFree(d_m2);
         (void)hipGetLastError();
         context_release(s, dev, c);
         return code;
@@ -960,18 +991,49 @@ int trt_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, 
     } while (0)
     TRT_HIP_C(hipMemsetAsync(c->d_ctr, 0, sizeof(h_ctr), c->stream));
     if (p->accumulate && bytes) TRT_HIP_C(hipMemcpyAsync(c->d_accum, accum, bytes, hipMemcpyHostToDevice, c->stream));
+    if (p->accumulate && bytes && d_m2) TRT_HIP_C(hipMemcpyAsync(d_m2, moment2, bytes, hipMemcpyHostToDevice, c->stream));
     TRT_HIP_C(hipEventRecord(c->ev0, c->stream));
-    rc = enqueue_render(s, cam, p, c->d_accum, reinterpret_cast<uint64_t*>(c->d_ctr), c->stream, nullptr);
+    rc = enqueue_render(s, cam, p, c->d_accum, reinterpret_cast<uint64_t*>(c->d_ctr), c->stream, nullptr, d_m2, launch_moments);
     if (rc != TRT_OK) return finish(rc);
     TRT_HIP_C(hipEventRecord(c->ev1, c->stream));
     if (bytes) TRT_HIP_C(hipMemcpyAsync(accum, c->d_accum, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (bytes && d_m2) TRT_HIP_C(hipMemcpyAsync(moment2, d_m2, bytes, hipMemcpyDeviceToHost, c->stream));
     TRT_HIP_C(hipMemcpyAsync(h_ctr, c->d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
     TRT_HIP_C(hipStreamSynchronize(c->stream));
     TRT_HIP_C(hipEventElapsedTime(&ms, c->ev0, c->ev1));
 #undef TRT_HIP_C
+    if (d_m2) (void)hipFree(d_m2);
     context_release(s, dev, c);
     if (stats) { counters_to_stats(h_ctr, stats); stats->kernel_ms = ms; }
     return TRT_OK;
+}
+
+}  // namespace
+
+namespace trt {
+int query_render_moments(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, float* moment2, trt_stats* stats,
+                         MomentsLaunch launch) {
+    if (!s || !cam || !p || !accum) return fail(TRT_ERR_INVALID_ARG, "null argument");
+    const int rc = check_moments(p, moment2);
+    if (rc != TRT_OK) return rc;
+    return render_host(s, cam, p, accum, moment2, stats, launch);
+}
+int query_render_moments_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* d_accum, float* d_moment2,
+                                uint64_t* d_counters, hipStream_t stream, MomentsLaunch launch) {
+    if (!s || !cam || !p || !d_accum) return fail(TRT_ERR_INVALID_ARG, "null argument");
+    int rc = check_moments(p, d_moment2);
+    if (rc != TRT_OK) return rc;
+    rc = require_device();
+    if (rc != TRT_OK) return rc;
+    return enqueue_render(s, cam, p, d_accum, d_counters, stream, nullptr, d_moment2, launch);
+}
+}  // namespace trt
+
+extern "C" {
+
+int trt_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, trt_stats* stats) {
+    if (!s || !cam || !p || !accum) return fail(TRT_ERR_INVALID_ARG, "null argument");
+    return render_host(s, cam, p, accum, nullptr, stats, nullptr);
 }
 
 // ---- Renderer::render over several GPUs of one node ----

@@ -20,6 +20,11 @@
 // Out-of-image taps are read at clamped coordinates (global forms) or from unwritten halo records (LDS form) and discarded by a
 // select, as NaN and non-positive weights are: no tap branches, so the compiler hoists the loads of a row of taps together.
 //
+// The variance-guided colour stop (trt_denoise_ex) is a fourth term (kDnColour): the variance image v_i travels with the
+// colour - in the tuned forms in the fourth word of the 16-byte colour records, which the three forms load anyway, in the plain form in two
+// 4-byte ping-pong images behind the 12-byte ones - so the scratch is the same.  A prologue kernel (dn_var0_kernel) writes the 3 x 3
+// prefiltered v_0; every pass but the last writes v_{i+1} beside its colour.  With the term off nothing of this runs.
+//
 // Which form runs a pass: dn_choose below.  TRT_DENOISE_VARIANT = plain | packed | lds overrides it (the A/B switch of
 // tools/denoise_bench.py and the byte-equality test); it is not part of the ABI.
 #include <hip/hip_runtime.h>
@@ -36,24 +41,27 @@ namespace {
 
 static_assert(sizeof(trt_denoise_params) == 32, "trt_denoise_params layout (tinyrt.h)");
 static_assert(sizeof(trt_denoise_inputs) == 32, "trt_denoise_inputs layout (tinyrt.h)");
+static_assert(sizeof(trt_denoise_color) == 32, "trt_denoise_color layout (tinyrt.h)");
 
-constexpr uint32_t kDnNormal = 1u, kDnAlbedo = 2u, kDnDepth = 4u;          // which terms are on (template parameter F)
+constexpr uint32_t kDnNormal = 1u, kDnAlbedo = 2u, kDnDepth = 4u, kDnColour = 8u;      // which terms are on (template parameter F)
 constexpr uint32_t kDnMaxSide = 65536u;                                   // width, height: keeps every grid and every int coordinate in range
 constexpr int kDnTile = 32;                                               // LDS form: tile side; a wave = two rows of it
 constexpr int kDnLdsMaxStep = 4;                                          // (32 + 16)^2 x 48 B = 110 592 B; step 8 would need 196 KiB
 constexpr uint32_t kDnLdsPerCu = 160u * 1024u;
+constexpr float kDnSigmaColourDefault = 8.0f;                             // trt_denoise_color_default: chosen from the table of DESIGN.md 6.4
 
 struct DnPass {
     int width, height, step;
     uint32_t npow;               // normal_power_log2
     float inv_a;                 // 1 / (sigma_albedo * sigma_albedo), computed once on the host
     float sigma_depth;
+    float sigma_c2;              // sigma_color * sigma_color, computed once on the host
 };
 
 struct DnTap {
     float4 g0;                   // normal.xyz | depth
     float4 g1;                   // albedo.rgb | -
-    float4 c;                    // colour.rgb | -
+    float4 c;                    // colour.rgb | variance v_i (colour term on)
 };
 
 __device__ __forceinline__ int dn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
@@ -81,6 +89,7 @@ struct DnPlainFetch {
     const float* albedo;
     const float* depth;
     const float* c;              // 3 f32 per pixel
+    const float* v;              // 1 f32 per pixel: v_i (colour term on)
     int width, height;
     __device__ __forceinline__ size_t at(int x, int y) const { return (size_t)dn_clamp(y, height - 1) * (size_t)width + (size_t)dn_clamp(x, width - 1); }
     __device__ __forceinline__ void guides(int x, int y, DnTap& t) const {
@@ -92,6 +101,7 @@ struct DnPlainFetch {
     __device__ __forceinline__ void colour(int x, int y, DnTap& t) const {
         const size_t i = at(x, y);
         t.c.x = c[3 * i]; t.c.y = c[3 * i + 1]; t.c.z = c[3 * i + 2];
+        if (F & kDnColour) t.c.w = v[i];
     }
 };
 
@@ -114,7 +124,7 @@ struct DnLdsFetch {
 
 // One pixel of one pass: the definition, operation by operation.  (x, y) is inside the image.
 template <uint32_t F, class Fetch>
-__device__ __forceinline__ float3 dn_filter(const Fetch& f, const DnPass& a, int x, int y) {
+__device__ __forceinline__ float4 dn_filter(const Fetch& f, const DnPass& a, int x, int y) {
     const float kH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     DnTap p;
     p.g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -125,7 +135,13 @@ __device__ __forceinline__ float3 dn_filter(const Fetch& f, const DnPass& a, int
         const float s = (a.sigma_depth * p.g0.w) * (float)a.step;
         inv_z = 1.0f / (s * s);                                               // one division per pixel and pass
     }
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f, ws = 0.0f;
+    float inv_c = 0.0f;
+    if (F & kDnColour) {
+        p.c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        f.colour(x, y, p);
+        inv_c = 1.0f / (a.sigma_c2 * p.c.w);                                  // one division per pixel and pass
+    }
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, ws = 0.0f, va = 0.0f;
     // The rows of taps are a real loop, the five taps of a row are unrolled: fully unrolled, the scheduler hoists the loads of all 25 taps
     // (75 records, 226 VGPRs, spills under the 128 of a 1024-thread workgroup); a row in flight is 15 records.  What depends on dy comes
     // from selects over constants, so no operation of the definition is computed differently.
@@ -180,6 +196,13 @@ __device__ __forceinline__ float3 dn_filter(const Fetch& f, const DnPass& a, int
                 m = m > 0.0f ? m : 0.0f;
                 w = w * (m * m);
             }
+            if (F & kDnColour) {
+                const float er = p.c.x - q[k].c.x, eg = p.c.y - q[k].c.y, eb = p.c.z - q[k].c.z;
+                const float e = (er * er + eg * eg) + eb * eb;
+                float m = 1.0f - e * inv_c;
+                m = m > 0.0f ? m : 0.0f;
+                w = w * (m * m);
+            }
             if (dx == 0) w = dy == 0 ? w0 : w;                                // the centre tap keeps h * h whatever its guides hold
             // taken only if inside the image and w > 0: a zero or NaN weight adds nothing, not 0 * c
             const bool take = row_ok && qx >= 0 && qx < a.width && w > 0.0f;
@@ -188,10 +211,14 @@ __device__ __forceinline__ float3 dn_filter(const Fetch& f, const DnPass& a, int
             ag = take ? ng : ag;
             ab = take ? nb : ab;
             ws = take ? nw : ws;
+            if (F & kDnColour) {
+                const float nv = va + (w * w) * q[k].c.w;                      // the variance of the weighted mean, carried to the next pass
+                va = take ? nv : va;
+            }
         }
     }
     const float r = 1.0f / ws;                                                // the centre tap is always taken: ws > 0
-    return make_float3(ar * r, ag * r, ab * r);
+    return make_float4(ar * r, ag * r, ab * r, (F & kDnColour) ? va * (r * r) : 0.0f);
 }
 
 // The prologue of the tuned forms: caller's buffers -> 16-byte records.  A guide that is off leaves zeros nobody reads.
@@ -208,10 +235,30 @@ __global__ __launch_bounds__(256) void dn_pack_kernel(const float* color, const 
     g1[i] = b;
 }
 
-// out3 != nullptr: the last pass, 12-byte pixels for the caller; else the padded ping-pong image.
-__device__ __forceinline__ void dn_store(const float3& v, size_t i, float4* out4, float* out3) {
+// The prologue of the colour term: v_0 = the 3 x 3 average of the caller's variance, weights {0.25, 0.5, 0.25} per axis, dy outer, dx inner,
+// over the taps inside the image, divided by the sum of the weights used through one reciprocal.  out[i * stride]: the fourth word of the
+// packed colour records (stride 4) or the plain form's 4-byte image (stride 1).
+__global__ __launch_bounds__(256) void dn_var0_kernel(const float* variance, int width, int height, float* out, int stride) {
+    const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
+    if (x >= width || y >= height) return;
+    const float kB[3] = {0.25f, 0.5f, 0.25f};
+    float sv = 0.0f, sw = 0.0f;
+    for (int dy = -1; dy <= 1; dy++) {
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= width || qy < 0 || qy >= height) continue;
+            const float wt = kB[dy + 1] * kB[dx + 1];
+            sv = sv + wt * variance[(size_t)qy * (size_t)width + (size_t)qx];
+            sw = sw + wt;
+        }
+    }
+    out[((size_t)y * (size_t)width + (size_t)x) * (size_t)stride] = sv * (1.0f / sw);
+}
+
+// out3 != nullptr: the last pass, 12-byte pixels for the caller; else the padded ping-pong image (fourth word: v_{i+1}, or 0 with the colour term off).
+__device__ __forceinline__ void dn_store(const float4& v, size_t i, float4* out4, float* out3) {
     if (out3) { out3[3 * i] = v.x; out3[3 * i + 1] = v.y; out3[3 * i + 2] = v.z; }
-    else out4[i] = make_float4(v.x, v.y, v.z, 0.0f);
+    else out4[i] = v;
 }
 
 template <uint32_t F>
@@ -222,12 +269,17 @@ __global__ __launch_bounds__(256) void dn_packed_kernel(DnPass a, const float4* 
     dn_store(dn_filter<F>(f, a, x, y), (size_t)y * (size_t)a.width + (size_t)x, out4, out3);
 }
 
+// v_in / v_out (colour term on): the 4-byte images of v_i and v_{i+1}; v_out == nullptr in the last pass.
 template <uint32_t F>
-__global__ __launch_bounds__(256) void dn_plain_kernel(DnPass a, const float* normal, const float* albedo, const float* depth, const float* c, float* out3) {
+__global__ __launch_bounds__(256) void dn_plain_kernel(DnPass a, const float* normal, const float* albedo, const float* depth, const float* c, float* out3,
+                                                       const float* v_in, float* v_out) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     if (x >= a.width || y >= a.height) return;
-    const DnPlainFetch<F> f{normal, albedo, depth, c, a.width, a.height};
-    dn_store(dn_filter<F>(f, a, x, y), (size_t)y * (size_t)a.width + (size_t)x, nullptr, out3);
+    const DnPlainFetch<F> f{normal, albedo, depth, c, v_in, a.width, a.height};
+    const size_t i = (size_t)y * (size_t)a.width + (size_t)x;
+    const float4 r = dn_filter<F>(f, a, x, y);
+    dn_store(r, i, nullptr, out3);
+    if ((F & kDnColour) && v_out) v_out[i] = r.w;
 }
 
 // Dynamic LDS: colour tile | G0 tile (normal or depth on) | G1 tile (albedo on), each pitch * pitch records, pitch = 32 + 4 * step.
@@ -291,19 +343,29 @@ bool dn_choose_lds(DnVariant v, int step) {
         case 4u: CALL(4u); break;                                                                  \
         case 5u: CALL(5u); break;                                                                  \
         case 6u: CALL(6u); break;                                                                  \
-        default: CALL(7u); break;                                                                  \
+        case 7u: CALL(7u); break;                                                                  \
+        case 8u: CALL(8u); break;                                                                  \
+        case 9u: CALL(9u); break;                                                                  \
+        case 10u: CALL(10u); break;                                                                \
+        case 11u: CALL(11u); break;                                                                \
+        case 12u: CALL(12u); break;                                                                \
+        case 13u: CALL(13u); break;                                                                \
+        case 14u: CALL(14u); break;                                                                \
+        default: CALL(15u); break;                                                                 \
     }
 
 size_t dn_align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 
 // The caller's scratch: up to 15 bytes to reach a 16-byte boundary, then four images of 16 bytes per pixel - colour A, colour B, G0, G1.
-// (The plain form uses the first two as 12-byte images.)
+// (The plain form uses the first two as 12-byte images and, with the colour term on, the first 4 bytes per pixel of the other two for v_i.)
 uint64_t dn_scratch_bytes(uint32_t width, uint32_t height) { return 16u + 4u * (uint64_t)dn_align16((size_t)width * height * 16u); }
 
 struct DnPlan {
     trt_denoise_params p;
     uint32_t flags;
     float inv_a;
+    float sigma_c2 = 0.0f;               // colour term on: sigma_color * sigma_color
+    const float* variance = nullptr;     // colour term on: the caller's variance image
 };
 
 int dn_check_params(const trt_denoise_params* params, DnPlan& plan) {
@@ -340,6 +402,22 @@ int dn_check(const trt_denoise_inputs* in, uint32_t width, uint32_t height, cons
     return TRT_OK;
 }
 
+// trt_denoise_ex's extra argument, after dn_check: NULL, a NULL variance or sigma_color <= 0 leave the plan as trt_denoise's.
+int dn_check_colour(const trt_denoise_color* col, uint32_t width, uint32_t height, const float* out, DnPlan& plan) {
+    if (!col) return TRT_OK;
+    if (col->sigma_color != col->sigma_color) return query_fail(TRT_ERR_INVALID_ARG, "sigma_color is NaN");
+    for (int i = 0; i < 5; i++)
+        if (col->reserved[i] != 0u) return query_fail(TRT_ERR_INVALID_ARG, "trt_denoise_color.reserved must be zero");
+    const size_t n = (size_t)width * height;
+    if (col->variance && dn_overlap(out, n * 12u, col->variance, n * 4u)) return query_fail(TRT_ERR_INVALID_ARG, "the output must not overlap an input");
+    if (col->variance && col->sigma_color > 0.0f) {
+        plan.flags |= kDnColour;
+        plan.sigma_c2 = col->sigma_color * col->sigma_color;
+        plan.variance = col->variance;
+    }
+    return TRT_OK;
+}
+
 template <uint32_t F>
 hipError_t dn_launch_lds(const DnPass& a, dim3 grid, uint32_t lds, const float4* g0, const float4* g1, const float4* c, float4* out4, float* out3,
                          hipStream_t stream) {
@@ -368,15 +446,26 @@ hipError_t dn_launch(const trt_denoise_inputs& in, uint32_t width, uint32_t heig
     a.npow = plan.p.normal_power_log2;
     a.inv_a = plan.inv_a;
     a.sigma_depth = plan.p.sigma_depth;
+    a.sigma_c2 = plan.sigma_c2;
+    const bool colour = (flags & kDnColour) != 0u;
+    const float* const variance = plan.variance;           // (a device pointer: dn_launch's callers put it there)
     const dim3 rows_grid((width + 63u) / 64u, (height + 3u) / 4u), rows_block(64, 4);
     hipError_t e = hipSuccess;
     if (variant == DN_PLAIN) {
         float* const img[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + image)};
+        float* const vimg[2] = {reinterpret_cast<float*>(base + 2u * image), reinterpret_cast<float*>(base + 3u * image)};
+        if (colour) {
+            dn_var0_kernel<<<rows_grid, rows_block, 0, stream>>>(variance, a.width, a.height, vimg[0], 1);
+            e = hipGetLastError();
+        }
         const float* src = in.color;
         for (uint32_t i = 0; i < plan.p.iterations && e == hipSuccess; i++) {
             a.step = 1 << i;
-            float* const dst = i + 1u == plan.p.iterations ? d_out : img[i & 1u];
-#define DN_CALL(F) dn_plain_kernel<F><<<rows_grid, rows_block, 0, stream>>>(a, normal, albedo, depth, src, dst)
+            const bool last = i + 1u == plan.p.iterations;
+            float* const dst = last ? d_out : img[i & 1u];
+            const float* const v_in = colour ? vimg[i & 1u] : nullptr;
+            float* const v_out = colour && !last ? vimg[(i + 1u) & 1u] : nullptr;
+#define DN_CALL(F) dn_plain_kernel<F><<<rows_grid, rows_block, 0, stream>>>(a, normal, albedo, depth, src, dst, v_in, v_out)
             DN_FOR_FLAGS(flags, DN_CALL)
 #undef DN_CALL
             e = hipGetLastError();
@@ -389,6 +478,10 @@ hipError_t dn_launch(const trt_denoise_inputs& in, uint32_t width, uint32_t heig
     float4* const g1 = reinterpret_cast<float4*>(base + 3u * image);
     dn_pack_kernel<<<dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream>>>(in.color, albedo, normal, depth, n, col[0], g0, g1);
     e = hipGetLastError();
+    if (colour && e == hipSuccess) {
+        dn_var0_kernel<<<rows_grid, rows_block, 0, stream>>>(variance, a.width, a.height, &col[0]->w, 4);
+        e = hipGetLastError();
+    }
     const dim3 tile_grid((width + kDnTile - 1u) / kDnTile, (height + kDnTile - 1u) / kDnTile);
     for (uint32_t i = 0; i < plan.p.iterations && e == hipSuccess; i++) {
         a.step = 1 << i;
@@ -426,6 +519,13 @@ void trt_denoise_params_default(trt_denoise_params* out) {
     out->sigma_depth = 0.05f;
 }
 
+void trt_denoise_color_default(trt_denoise_color* out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->variance = nullptr;
+    out->sigma_color = trt::kDnSigmaColourDefault;                 // the table it was chosen from
+}
+
 // Host arithmetic only: works without a device.  0 = invalid arguments.
 uint64_t trt_denoise_scratch_bytes(uint32_t width, uint32_t height, const trt_denoise_params* params) {
     trt::DnPlan plan;
@@ -434,10 +534,12 @@ uint64_t trt_denoise_scratch_bytes(uint32_t width, uint32_t height, const trt_de
     return trt::dn_scratch_bytes(width, height);
 }
 
-int trt_denoise_device(const trt_denoise_inputs* d_in, uint32_t width, uint32_t height, const trt_denoise_params* params, float* d_out,
-                       void* d_scratch, uint64_t scratch_bytes, void* stream) {
+int trt_denoise_ex_device(const trt_denoise_inputs* d_in, const trt_denoise_color* color, uint32_t width, uint32_t height,
+                          const trt_denoise_params* params, float* d_out, void* d_scratch, uint64_t scratch_bytes, void* stream) {
     trt::DnPlan plan;
     int rc = trt::dn_check(d_in, width, height, params, d_out, plan);
+    if (rc != TRT_OK) return rc;
+    rc = trt::dn_check_colour(color, width, height, d_out, plan);
     if (rc != TRT_OK) return rc;
     if (!d_scratch) return trt::query_fail(TRT_ERR_INVALID_ARG, "null scratch");
     if (scratch_bytes < trt::dn_scratch_bytes(width, height))
@@ -449,19 +551,27 @@ int trt_denoise_device(const trt_denoise_inputs* d_in, uint32_t width, uint32_t 
     return TRT_OK;
 }
 
+int trt_denoise_device(const trt_denoise_inputs* d_in, uint32_t width, uint32_t height, const trt_denoise_params* params, float* d_out,
+                       void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return trt_denoise_ex_device(d_in, nullptr, width, height, params, d_out, d_scratch, scratch_bytes, stream);
+}
+
 // Host buffers: device copies of the call's own, one stream-ordered sequence on the default stream, complete when the call returns.
-int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, const trt_denoise_params* params, float* out) {
+int trt_denoise_ex(const trt_denoise_inputs* in, const trt_denoise_color* color, uint32_t width, uint32_t height, const trt_denoise_params* params,
+                   float* out) {
     trt::DnPlan plan;
     int rc = trt::dn_check(in, width, height, params, out, plan);
+    if (rc != TRT_OK) return rc;
+    rc = trt::dn_check_colour(color, width, height, out, plan);
     if (rc != TRT_OK) return rc;
     rc = trt::query_require_device();
     if (rc != TRT_OK) return rc;
     const size_t n = (size_t)width * height;
-    const void* const host[4] = {in->color, (plan.flags & trt::kDnAlbedo) ? in->albedo : nullptr, (plan.flags & trt::kDnNormal) ? in->normal : nullptr,
-                                 (plan.flags & trt::kDnDepth) ? in->depth : nullptr};
-    const size_t item[4] = {12u, 12u, 12u, 4u};
-    size_t off[4], total = 0;
-    for (int i = 0; i < 4; i++) { off[i] = total; if (host[i]) total += trt::dn_align16(n * item[i]); }
+    const void* const host[5] = {in->color, (plan.flags & trt::kDnAlbedo) ? in->albedo : nullptr, (plan.flags & trt::kDnNormal) ? in->normal : nullptr,
+                                 (plan.flags & trt::kDnDepth) ? in->depth : nullptr, (plan.flags & trt::kDnColour) ? plan.variance : nullptr};
+    const size_t item[5] = {12u, 12u, 12u, 4u, 4u};
+    size_t off[5], total = 0;
+    for (int i = 0; i < 5; i++) { off[i] = total; if (host[i]) total += trt::dn_align16(n * item[i]); }
     const size_t off_out = total;
     total += trt::dn_align16(n * 12u);
     const size_t off_scratch = total;
@@ -471,7 +581,7 @@ int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, c
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
     if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("denoise buffers: ") + hipGetErrorString(e)); }
     const char* what = "hipMemcpy of the inputs";
-    for (int i = 0; i < 4 && e == hipSuccess; i++)
+    for (int i = 0; i < 5 && e == hipSuccess; i++)
         if (host[i]) e = hipMemcpy(d + off[i], host[i], n * item[i], hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         trt_denoise_inputs din;
@@ -479,6 +589,7 @@ int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, c
         din.albedo = host[1] ? reinterpret_cast<const float*>(d + off[1]) : nullptr;
         din.normal = host[2] ? reinterpret_cast<const float*>(d + off[2]) : nullptr;
         din.depth = host[3] ? reinterpret_cast<const float*>(d + off[3]) : nullptr;
+        plan.variance = host[4] ? reinterpret_cast<const float*>(d + off[4]) : nullptr;
         what = "denoise launch";
         e = trt::dn_launch(din, width, height, plan, reinterpret_cast<float*>(d + off_out), d + off_scratch, nullptr);
     }
@@ -486,6 +597,10 @@ int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, c
     (void)hipFree(d);
     if (e != hipSuccess) return trt::query_fail_hip(e, what);
     return TRT_OK;
+}
+
+int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, const trt_denoise_params* params, float* out) {
+    return trt_denoise_ex(in, nullptr, width, height, params, out);
 }
 
 }  // extern "C"

@@ -137,6 +137,14 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
 // `workspace_bytes`: what the caller was granted (at least streamed_workspace_bytes for one sample): the launches are sized to it.
 hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
                            float* d_accum, unsigned long long* d_counters, bool stats, hipStream_t stream);
+// The same render with `d_moment2`, a second buffer with the frame's layout that receives the per-pixel second moments, folded in the same
+// pass over the radiance records (stream_fold_moments_kernel instead of stream_fold_kernel); launch_streamed is this with nullptr.  A
+// function of its own, and handed to capi.hip as a pointer (scene_query.h MomentsLaunch), so that capi.hip still calls nothing beyond the
+// launchers above and its host-only build links against their stand-ins as before.
+hipError_t launch_streamed_moments(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                                   float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats, hipStream_t stream);
+// Variance of the pixel estimate from a frame and its second moments (streamed.hip variance_kernel; tinyrt.h trt_variance): 1 f32 per pixel.
+hipError_t launch_variance(const float* d_accum, const float* d_moment2, uint32_t npixels, uint32_t samples_per_pixel, float* d_variance, hipStream_t stream);
 
 // Sampler plug-in form: n caller-supplied rays.
 // Imager finalisation on buffers in HBM (kernels.hip).

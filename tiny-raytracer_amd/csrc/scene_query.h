@@ -28,4 +28,15 @@ int query_scene_on_device(trt_scene* s, QueryScene& out);
 // range, accumulate, bands - validated as trt_render validates them (backend and tuning are not looked at).  rows = rows the call owns.
 int query_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs& ra, uint32_t& rows);
 void query_camera_dev(const trt_camera& cam, CameraDev& out);
+// trt_render / trt_render_device with a second frame-shaped buffer for the per-pixel second moments (streamed.hip trt_render_moments*): the
+// whole render path of capi.hip - validation (moment2 non-NULL, a backend that keeps per-sample records), contexts, workspaces - with the
+// streamed launch made through `launch` (kernels.h launch_streamed_moments), so that capi.hip itself names no launcher its host-only build
+// has no stand-in for.
+using MomentsLaunch = hipError_t (*)(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace,
+                                     size_t workspace_bytes, float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats,
+                                     hipStream_t stream);
+int query_render_moments(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, float* moment2, trt_stats* stats,
+                         MomentsLaunch launch);
+int query_render_moments_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* d_accum, float* d_moment2,
+                                uint64_t* d_counters, hipStream_t stream, MomentsLaunch launch);
 }  // namespace trt

@@ -20,8 +20,11 @@
 // two launches per chunk of samples (sized to a radiance buffer of at most 16 GB: streamed_chunk_spp) instead of one.  stream_sample_kernel keeps the
 // primary-ray stock of kernels.hip (items are taken ahead); stream_pool_kernel, used for small LDS scenes, generates the
 // primary rays of a whole wave at once into an LDS pool.
+#include <string>
+
 #include "kernels.h"
 #include "rt_path.h"
+#include "scene_query.h"
 
 namespace trt {
 
@@ -444,6 +447,58 @@ __global__ __launch_bounds__(256) void stream_fold_kernel(const float* __restric
     out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
 }
 
+// The same fold that also keeps the per-pixel second moment (tinyrt.h trt_render_moments): moment2[idx].ch += (c.ch * c.ch) * (1/spp), in the
+// same pass over the records, samples in order, one f32 operation per operator (nothing fused: -ffp-contract=off).  `moment2` has the frame's
+// layout; `accumulate` applies to both buffers.  The frame it writes is stream_fold_kernel's, bit for bit: the same operations in the same order.
+__global__ __launch_bounds__(256) void stream_fold_moments_kernel(const float* __restrict__ colors, float* __restrict__ accum, float* __restrict__ moment2,
+                                                                  uint32_t width, uint32_t rows, uint32_t tiles_x, uint32_t n_tiles, uint32_t n_spp,
+                                                                  float inv_spp, uint32_t accumulate) {
+    const uint32_t tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (tile >= n_tiles) return;
+    const uint32_t x = (tile % tiles_x) * 8u + (lane & 7u), row = (tile / tiles_x) * 8u + (lane >> 3);
+    if (x >= width || row >= rows) return;                                      // an edge tile's off-image lanes: records never written, never read
+    const unsigned long long px = 3ull * ((unsigned long long)row * width + x);
+    float* out = accum + px;
+    float* out2 = moment2 + px;
+    V3 acc = v3(0.0f, 0.0f, 0.0f), m2 = v3(0.0f, 0.0f, 0.0f);
+    if (accumulate) { acc = v3(out[0], out[1], out[2]); m2 = v3(out2[0], out2[1], out2[2]); }
+    const float* rec = colors + 3ull * ((unsigned long long)tile * n_spp * 64ull + lane);
+    for (uint32_t s = 0; s < n_spp; s++) {
+        const Radiance c = *reinterpret_cast<const Radiance*>(rec + 3ull * 64ull * s);      // one global_load_dwordx3
+        acc = acc + v3(c.r, c.g, c.b) * inv_spp;
+        m2.x = m2.x + (c.r * c.r) * inv_spp;
+        m2.y = m2.y + (c.g * c.g) * inv_spp;
+        m2.z = m2.z + (c.b * c.b) * inv_spp;
+    }
+    out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
+    out2[0] = m2.x; out2[1] = m2.y; out2[2] = m2.z;
+}
+
+// Variance of the pixel estimate from the two folded buffers (tinyrt.h trt_variance): S = accum (the mean), M = moment2 (the mean of the
+// squares); per channel d = M - S*S, clamped at 0 (NaN -> 0); variance = ((d.r + d.g) + d.b) * inv_nm1, inv_nm1 = 1.0f / float(N - 1) computed
+// once on the host; N <= 1: +inf (unknown).  M - S*S cancels in f32: its error is about 2^-23 * M, which is why d can come out below 0.
+__global__ __launch_bounds__(256) void variance_kernel(const float* __restrict__ accum, const float* __restrict__ moment2, uint32_t npixels, float inv_nm1,
+                                                       uint32_t known, float* __restrict__ variance) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npixels) return;
+    if (!known) { variance[i] = __builtin_inff(); return; }
+    const float* s = accum + 3ull * i;
+    const float* m = moment2 + 3ull * i;
+    float dr = m[0] - s[0] * s[0], dg = m[1] - s[1] * s[1], db = m[2] - s[2] * s[2];
+    dr = dr > 0.0f ? dr : 0.0f;
+    dg = dg > 0.0f ? dg : 0.0f;
+    db = db > 0.0f ? db : 0.0f;
+    variance[i] = ((dr + dg) + db) * inv_nm1;
+}
+
+hipError_t launch_variance(const float* d_accum, const float* d_moment2, uint32_t npixels, uint32_t samples_per_pixel, float* d_variance, hipStream_t stream) {
+    if (npixels == 0u) return hipSuccess;
+    const uint32_t known = samples_per_pixel > 1u ? 1u : 0u;
+    const float inv_nm1 = known ? 1.0f / (float)(samples_per_pixel - 1u) : 0.0f;
+    hipLaunchKernelGGL(variance_kernel, dim3((npixels + 255u) / 256u), dim3(256), 0, stream, d_accum, d_moment2, npixels, inv_nm1, known, d_variance);
+    return hipGetLastError();
+}
+
 // Samples per pixel per tracing / fold launch pair: as many as keep the radiance buffer within `radiance_gb` GiB (default 16; 16..256 spp).
 // Sized for 288 GB of HBM: a launch is a persistent grid that drains a batch queue, and its tail - the last waves finishing their longest
 // paths while the rest of the chip idles - is paid once per launch; the Cornell bench frame went from four 64-spp launches per 256-spp
@@ -671,8 +726,9 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
 // Name of the kernel that dominates a streamed render of this scene (for profiles and bench.py's roofline line).
 const char* streamed_kernel_name(const SceneLayout& L, const RenderArgs& ra, const trt_tuning& tn) { return streamed_launch_plan(L, ra, tn, false).kernel_name; }
 
-hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra_all, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
-                           float* d_accum, unsigned long long* d_counters, bool stats, hipStream_t stream) {
+// d_moment2 == nullptr: the frame only.
+static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra_all, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                                        float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats, hipStream_t stream) {
     if (ra_all.rows_local == 0 || cam.width == 0) return hipSuccess;
     uint32_t* batch_counter = static_cast<uint32_t*>(workspace);                                     // layout: streamed_workspace_bytes
     float* colors = reinterpret_cast<float*>(static_cast<char*>(workspace) + kWorkspaceHeader);
@@ -733,8 +789,13 @@ hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const Rende
         timing_mark(stream, false);
         if (e != hipSuccess) return e;
         const uint32_t fold_blocks = (n_tiles + 3u) / 4u;                           // four tiles (waves) per workgroup
-        hipLaunchKernelGGL(stream_fold_kernel, dim3(fold_blocks), dim3(256), 0, stream, colors, d_accum, cam.width, ra_all.rows_local, tiles_x, n_tiles,
-                           ra.sample_end - ra.sample_begin, ra_all.inv_spp, (first && !ra_all.accumulate) ? 0u : 1u);
+        if (d_moment2 == nullptr) {
+            hipLaunchKernelGGL(stream_fold_kernel, dim3(fold_blocks), dim3(256), 0, stream, colors, d_accum, cam.width, ra_all.rows_local, tiles_x, n_tiles,
+                               ra.sample_end - ra.sample_begin, ra_all.inv_spp, (first && !ra_all.accumulate) ? 0u : 1u);
+        } else {                                                                    // the frame and its second moments in the one pass over the records
+            hipLaunchKernelGGL(stream_fold_moments_kernel, dim3(fold_blocks), dim3(256), 0, stream, colors, d_accum, d_moment2, cam.width, ra_all.rows_local,
+                               tiles_x, n_tiles, ra.sample_end - ra.sample_begin, ra_all.inv_spp, (first && !ra_all.accumulate) ? 0u : 1u);
+        }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         first = false;
@@ -742,4 +803,64 @@ hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const Rende
     return hipSuccess;
 }
 
+hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                           float* d_accum, unsigned long long* d_counters, bool stats, hipStream_t stream) {
+    return launch_streamed_folds(sc, cam, ra, tn, workspace, workspace_bytes, d_accum, nullptr, d_counters, stats, stream);
+}
+
+hipError_t launch_streamed_moments(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                                   float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats, hipStream_t stream) {
+    if (d_moment2 == nullptr) return hipErrorInvalidValue;
+    return launch_streamed_folds(sc, cam, ra, tn, workspace, workspace_bytes, d_accum, d_moment2, d_counters, stats, stream);
+}
+
 }  // namespace trt
+
+// ---- C ABI of the second moments (tinyrt.h).  The render entry points are trt_render / trt_render_device with one more buffer: capi.hip
+// does the work (scene_query.h query_render_moments*) and is handed the launcher above. ----
+extern "C" {
+
+int trt_render_moments(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* accum, float* moment2, trt_stats* stats) {
+    return trt::query_render_moments(s, cam, p, accum, moment2, stats, &trt::launch_streamed_moments);
+}
+
+int trt_render_moments_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* d_accum, float* d_moment2,
+                              uint64_t* d_counters, void* stream) {
+    return trt::query_render_moments_device(s, cam, p, d_accum, d_moment2, d_counters, static_cast<hipStream_t>(stream), &trt::launch_streamed_moments);
+}
+
+// Variance of the pixel estimate.  Device form: asynchronous on `stream`.
+int trt_variance_device(const float* d_accum, const float* d_moment2, uint32_t npixels, uint32_t samples_per_pixel, float* d_variance, void* stream) {
+    if (npixels && (!d_accum || !d_moment2 || !d_variance)) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (npixels == 0u) return TRT_OK;
+    const int rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = trt::launch_variance(d_accum, d_moment2, npixels, samples_per_pixel, d_variance, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return trt::query_fail_hip(e, "variance launch");
+    return TRT_OK;
+}
+
+// Host form: device copies of the call's own, the same kernel, complete when the call returns.  There is no CPU path.
+int trt_variance(const float* accum, const float* moment2, uint32_t npixels, uint32_t samples_per_pixel, float* variance) {
+    if (npixels && (!accum || !moment2 || !variance)) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (npixels == 0u) return TRT_OK;
+    const int rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    const size_t frame = ((size_t)npixels * 12u + 15u) & ~(size_t)15u;
+    char* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), 2u * frame + (size_t)npixels * 4u);
+    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("variance buffers: ") + hipGetErrorString(e)); }
+    float* const d_s = reinterpret_cast<float*>(d);
+    float* const d_m = reinterpret_cast<float*>(d + frame);
+    float* const d_v = reinterpret_cast<float*>(d + 2u * frame);
+    const char* what = "hipMemcpy of the inputs";
+    e = hipMemcpy(d_s, accum, (size_t)npixels * 12u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_m, moment2, (size_t)npixels * 12u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { what = "variance launch"; e = trt::launch_variance(d_s, d_m, npixels, samples_per_pixel, d_v, nullptr); }
+    if (e == hipSuccess) { what = "hipMemcpy of the result"; e = hipMemcpy(variance, d_v, (size_t)npixels * 4u, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
+    (void)hipFree(d);
+    if (e != hipSuccess) return trt::query_fail_hip(e, what);
+    return TRT_OK;
+}
+
+}  // extern "C"
