@@ -361,6 +361,19 @@ extern "C" {
     pub fn trt_variance(accum: *const f32, moment2: *const f32, npixels: u32, samples_per_pixel: u32, variance: *mut f32) -> c_int;
     pub fn trt_variance_device(d_accum: *const f32, d_moment2: *const f32, npixels: u32, samples_per_pixel: u32,
                                d_variance: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn trt_render_pixels(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, pixels: *const u32, n: u32,
+                             accum: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_render_pixels_device(s: *mut trt_scene, cam: *const trt_camera, p: *const trt_render_params, d_pixels: *const u32, n: u32,
+                                    d_count: *const u32, d_accum: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
+                                    stream: *mut c_void) -> c_int;
+    pub fn trt_pixels_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_select_pixels(accum: *const f32, moment2: *const f32, npixels: u32, samples_per_pixel: u32, samples_done: u32,
+                             candidates: *const u32, n_candidates: u32, rel_tol: f32, abs_tol: f32, selected: *mut u32,
+                             count: *mut u32) -> c_int;
+    pub fn trt_select_pixels_device(d_accum: *const f32, d_moment2: *const f32, npixels: u32, samples_per_pixel: u32, samples_done: u32,
+                                    d_candidates: *const u32, n_candidates: u32, rel_tol: f32, abs_tol: f32, d_selected: *mut u32,
+                                    d_count: *mut u32, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> c_int;
+    pub fn trt_select_scratch_bytes(n_candidates: u32) -> u64;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

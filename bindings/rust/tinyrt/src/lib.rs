@@ -366,6 +366,47 @@ impl Renderer {
         Ok((Image { width, height, gamma: 2.2, data }, moment2, variance))
     }
 
+    /// Samples `[sample_begin, sample_end)` of the listed pixels only (`trt_render_pixels`), added to the running sums in `frame` and
+    /// `moment2`: every listed pixel gets the bytes `render_moments` would leave there for that range, every other pixel is untouched.
+    /// `pixels`: indices `y * width + x`, each at most once.
+    pub fn render_pixels(&self, camera: &Camera, world: &mut World, pixels: &[u32], sample_begin: u32, sample_end: u32,
+                         frame: &mut Image, moment2: &mut [Float]) -> Result<(), Error> {
+        let (width, height) = camera.get_image_size();
+        if frame.data.len() != width * height * 3 || moment2.len() != width * height * 3 {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "frame and moment2 have the camera's size".to_string() });
+        }
+        let scene = world.get_bvh()?;
+        let params = sys::trt_render_params {
+            samples_per_pixel: self.samples_per_pixel as u32,
+            max_bounces: self.max_bounces as u32,
+            background: self.background_color.raw(),
+            seed: self.seed,
+            sample_begin,
+            sample_end,
+            accumulate: 1,
+            ..Default::default()
+        };
+        check(unsafe {
+            sys::trt_render_pixels(scene, &camera.pod, &params, pixels.as_ptr(), pixels.len() as u32, frame.data.as_mut_ptr(),
+                                   moment2.as_mut_ptr(), ptr::null_mut())
+        })
+    }
+
+    /// The candidates (`None` = every pixel) whose estimate after `samples_done` samples is still too noisy (`trt_select_pixels`), in order.
+    pub fn select_pixels(&self, frame: &Image, moment2: &[Float], samples_done: u32, rel_tol: Float, abs_tol: Float,
+                         candidates: Option<&[u32]>) -> Result<Vec<u32>, Error> {
+        let npixels = (frame.width * frame.height) as u32;
+        let n = candidates.map_or(npixels, |c| c.len() as u32);
+        let mut out = vec![0u32; n as usize];
+        let mut count = 0u32;
+        check(unsafe {
+            sys::trt_select_pixels(frame.data.as_ptr(), moment2.as_ptr(), npixels, self.samples_per_pixel as u32, samples_done,
+                                   candidates.map_or(ptr::null(), |c| c.as_ptr()), n, rel_tol, abs_tol, out.as_mut_ptr(), &mut count)
+        })?;
+        out.truncate(count as usize);
+        Ok(out)
+    }
+
     /// All six feature buffers of the frame `render` would trace: same seed, same samples, same primary rays.
     pub fn render_aov(&self, camera: &Camera, world: &mut World) -> Result<FeatureBuffers, Error> {
         let (width, height) = camera.get_image_size();

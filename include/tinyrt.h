@@ -42,7 +42,9 @@ extern "C" {
  *              trt_primary_rays_device; trt_aov_buffers, trt_render_aov, trt_render_aov_device, trt_aov_launch_plan;
  *              trt_denoise_params, trt_denoise_params_default, trt_denoise_inputs, trt_denoise_scratch_bytes, trt_denoise,
  *              trt_denoise_device; trt_render_moments, trt_render_moments_device, trt_variance, trt_variance_device;
- *              trt_denoise_color, trt_denoise_color_default, trt_denoise_ex, trt_denoise_ex_device. */
+ *              trt_denoise_color, trt_denoise_color_default, trt_denoise_ex, trt_denoise_ex_device; trt_render_pixels,
+ *              trt_render_pixels_device, trt_pixels_launch_plan, trt_select_pixels, trt_select_pixels_device,
+ *              trt_select_scratch_bytes. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -409,6 +411,60 @@ int trt_render_aov_device(trt_scene *s, const trt_camera *cam, const trt_render_
 /* How trt_render_aov[_device] launches a local image of n_pixels on this scene: trt_query_launch_plan's rule and fields with pixels in
  * place of rays (rays_per_wave = pixels a wave owns, each for all of its samples), over the feature-buffer kernels' own table. */
 int trt_aov_launch_plan(const trt_scene *s, uint32_t n_pixels, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Sparse rendering of chosen pixels, and the selection of the pixels that are still too noisy ----
+ * Every render entry point above traces all pixels of its rows; the band fields cut rows, never columns.  trt_render_pixels traces a
+ * LIST: `pixels` holds n local pixel indices r * width + x over the rows the call owns (rows = p->rows_local, or height when
+ * p->band_rows == 0).  Re-render a screen region, refine what a user looks at, finish the neighbourhood of a firefly - or sample
+ * adaptively: render a few samples everywhere, then loop over trt_select_pixels and trt_render_pixels.
+ * Contract: after the call the bytes of every listed pixel in `accum` (and in `moment2`, which may be NULL: not wanted) are what
+ * trt_render_moments_device leaves there for the same `p` - sample range, accumulate, band fields, seed, background, max_bounces - and
+ * the same prior contents.  That includes "nothing to trace" (an empty sample range, max_bounces == 0): the listed pixels are zeroed
+ * unless accumulate.  Every other byte of both buffers is untouched, also with accumulate == 0.  The fold is the imager's own sequence
+ * of f32 additions in sample order, so with samples_per_pixel equal a pixel refined later is bit-identical to the same pixel of a
+ * full render of the same samples.  `backend` and `tuning` are ignored, as in trt_render_aov; collect_stats must be 0
+ * (TRT_ERR_INVALID_ARG otherwise: there are no counting kernels); stats / d_counters receive samples and rays ([0] and [1]) only.
+ * One kernel of its own (a lane owns a pixel for all samples of the call and folds in registers); none of the render kernels takes part.
+ * A wave works through a contiguous run of the list, so neighbouring entries that are neighbouring pixels travel together.
+ * trt_render_pixels: HOST buffers (`accum`, `moment2`: whole local frames, rows * width * 3 f32), synchronous.  The list is validated
+ *   before any device work: an index >= rows * width, or one listed twice, is TRT_ERR_INVALID_ARG.  A NULL scene, camera or params, or
+ *   a NULL list or `accum` with n > 0, is TRT_ERR_INVALID_ARG; then TRT_ERR_NO_DEVICE.  n == 0 succeeds and touches nothing.
+ * trt_render_pixels_device: buffers in HBM on the calling thread's current device, asynchronous on `stream`.  The list is NOT validated:
+ *   an entry >= rows * width is skipped (neither read nor written); duplicate indices are the caller's error - that pixel's value is
+ *   unspecified, nothing else is affected.  With `d_count` non-NULL the kernel uses the first min(*d_count, n) entries - the count
+ *   trt_select_pixels_device wrote earlier on the same stream - and n only sizes the launch.  `d_counters`: 16 uint64 as in
+ *   trt_render_device, or NULL. */
+int trt_render_pixels(trt_scene *s, const trt_camera *cam, const trt_render_params *p, const uint32_t *pixels, uint32_t n,
+                      float *accum, float *moment2, trt_stats *stats);
+int trt_render_pixels_device(trt_scene *s, const trt_camera *cam, const trt_render_params *p, const uint32_t *d_pixels, uint32_t n,
+                             const uint32_t *d_count, float *d_accum, float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_render_pixels[_device] launches a list of n pixels on this scene: trt_query_launch_plan's rule and fields with list entries in
+ * place of rays (rays_per_wave = entries a wave owns, each for all samples of the call), over the sparse render kernels' own table. */
+int trt_pixels_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* Selection: from a candidate list, the pixels whose estimate is still too noisy, in candidate order (stable; a deterministic scan, the
+ * same output on every run).  `accum` = S and `moment2` = M are the running sums as trt_render_moments leaves them after samples_done = n
+ * of N = samples_per_pixel samples (both carry the frame's fixed 1 / N scale); n is the same for every candidate.  `candidates` holds
+ * n_candidates pixel indices, or is NULL: candidate i is pixel i.  On the host, once: k = float(N) / float(n), inv = 1.0f / float(n - 1),
+ * rel2 = rel_tol * rel_tol, abs2 = abs_tol * abs_tol.  Per candidate, all f32, one IEEE operation per operator, nothing fused:
+ *   per channel: s = S.ch * k;  q = M.ch * k;  d = q - s*s;  d = d > 0 ? d : 0
+ *   v = ((d.r + d.g) + d.b) * inv                    (the variance of the mean after n samples, as trt_variance defines it)
+ *   l = (s.r + s.g) + s.b;  b = rel2 * (l*l);  b = b + abs2
+ *   keep = v > b                                     (a NaN on either side: not kept)
+ * n <= 1 keeps every candidate: the variance is unknown.  A candidate index >= npixels is not kept and is not read.  `selected` has
+ * room for n_candidates indices; the first *count are written.
+ * trt_select_pixels: HOST buffers, synchronous.  trt_select_pixels_device: buffers in HBM, asynchronous on `stream`; allocates nothing:
+ * `d_scratch` holds at least trt_select_scratch_bytes(n_candidates) bytes (host arithmetic only; 4-byte aligned).
+ * Errors: TRT_ERR_INVALID_ARG before any device work - a NULL count, samples_per_pixel == 0, samples_done > samples_per_pixel, with
+ * n_candidates > 0 a NULL `accum`, `moment2` or `selected`, for the device form a NULL or too small scratch - then TRT_ERR_NO_DEVICE.
+ * n_candidates == 0 succeeds, writes count 0 and touches nothing else, with or without a device (without one the device form has no
+ * buffer to write and writes nothing). */
+int trt_select_pixels(const float *accum, const float *moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,
+                      const uint32_t *candidates, uint32_t n_candidates, float rel_tol, float abs_tol, uint32_t *selected, uint32_t *count);
+int trt_select_pixels_device(const float *d_accum, const float *d_moment2, uint32_t npixels, uint32_t samples_per_pixel,
+                             uint32_t samples_done, const uint32_t *d_candidates, uint32_t n_candidates, float rel_tol, float abs_tol,
+                             uint32_t *d_selected, uint32_t *d_count, void *d_scratch, uint64_t scratch_bytes, void *stream);
+uint64_t trt_select_scratch_bytes(uint32_t n_candidates);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

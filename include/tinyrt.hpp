@@ -276,6 +276,31 @@ public:
         check(trt_variance(frame.linear(), moment2.data(), frame.width() * frame.height(), params_.samples_per_pixel, v.data()));
         return v;
     }
+    // Samples [sample_begin, sample_end) of the listed pixels only (trt_render_pixels), added to the running sums in `frame` and `moment2`
+    // (accumulate): every listed pixel gets the bytes render_moments would leave there for that range, every other pixel is untouched.
+    // `pixels`: indices y * width + x, each at most once.
+    void render_pixels(const Camera& camera, World& world, const std::vector<uint32_t>& pixels, uint32_t sample_begin, uint32_t sample_end,
+                       Image& frame, std::vector<float>& moment2, trt_stats* stats = nullptr) const {
+        if (moment2.size() != (size_t)camera.pod.width * camera.pod.height * 3) throw Error(TRT_ERR_INVALID_ARG, "moment2 has the frame's size");
+        trt_render_params p = params_;
+        p.sample_begin = sample_begin;
+        p.sample_end = sample_end;
+        p.accumulate = 1;
+        p.collect_stats = 0;
+        check(trt_render_pixels(world.get_bvh(), &camera.pod, &p, pixels.data(), (uint32_t)pixels.size(), frame.linear(), moment2.data(), stats));
+    }
+    // The candidates (empty = every pixel) whose estimate after `samples_done` samples is still too noisy (trt_select_pixels), in order.
+    std::vector<uint32_t> select_pixels(const Image& frame, const std::vector<float>& moment2, uint32_t samples_done, float rel_tol,
+                                        float abs_tol, const std::vector<uint32_t>& candidates = {}) const {
+        const uint32_t npixels = frame.width() * frame.height();
+        const uint32_t n = candidates.empty() ? npixels : (uint32_t)candidates.size();
+        std::vector<uint32_t> out(n);
+        uint32_t count = 0;
+        check(trt_select_pixels(frame.linear(), moment2.data(), npixels, params_.samples_per_pixel, samples_done,
+                                candidates.empty() ? nullptr : candidates.data(), n, rel_tol, abs_tol, out.data(), &count));
+        out.resize(count);
+        return out;
+    }
     // All six feature buffers of the frame render() would trace: same seed, same samples, same primary rays.
     FeatureBuffers render_aov(const Camera& camera, World& world) const {
         FeatureBuffers out;

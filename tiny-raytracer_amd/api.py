@@ -188,6 +188,13 @@ class Scene:
         check(lib.trt_aov_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    def pixels_plan(self, n, compute_units=0):
+        """trt_pixels_launch_plan: how Renderer.render_pixels launches a list of n pixels on this scene, as a dict with query_plan()'s
+        fields (rays_per_wave = list entries a wave owns)."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_pixels_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""
@@ -433,6 +440,59 @@ class Renderer:
         check(lib.trt_render_moments_device(scene._h, C.byref(camera.pod), C.byref(p), C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr),
                                             C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
 
+    def render_pixels(self, camera, world, pixels, accum, moment2=None, **over):
+        """trt_render_pixels: trace only the listed pixels - `pixels`: uint32 local indices r * width + x, each at most once - and leave in
+        `accum` (and `moment2`, or None: not wanted; float32 [rows, width, 3], changed in place) the bytes render_moments() would leave
+        there for the same sample range, accumulate flag, bands and prior contents; every other pixel is untouched.  `over`: sample
+        range, accumulate, bands.  Returns the stats (samples and rays)."""
+        scene = world.get_bvh() if isinstance(world, World) else world
+        p = self.params(**over)
+        w, h = camera.get_image_size()
+        rows = p.rows_local if p.band_rows else h
+        px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        for a in (accum, moment2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (rows, w, 3))
+        st = Stats()
+        check(lib.trt_render_pixels(scene._h, C.byref(camera.pod), C.byref(p), px.ctypes.data if len(px) else None, len(px),
+                                    accum.ctypes.data if accum is not None and accum.size else None,
+                                    moment2.ctypes.data if moment2 is not None and moment2.size else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
+    def render_pixels_device(self, camera, scene, d_pixels_ptr, n, d_accum_ptr, d_moment2_ptr=0, d_count_ptr=0, stream_ptr=0,
+                             d_counters_ptr=0, **over):
+        """Enqueue render_pixels() on buffers already in HBM (device pointers as integers: n uint32 indices, frames of rows x width x 12
+        bytes); asynchronous on the stream.  The list is not validated: an index past the local image is skipped, duplicates are the
+        caller's error.  `d_count_ptr`: a uint32 in HBM (as select_pixels_device writes it); the first min(count, n) entries are used."""
+        p = self.params(**over)
+        check(lib.trt_render_pixels_device(scene._h, C.byref(camera.pod), C.byref(p), C.c_void_p(d_pixels_ptr), int(n), C.c_void_p(d_count_ptr),
+                                           C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def render_adaptive(self, camera, world, min_spp, step_spp, rel_tol, abs_tol=0.0):
+        """Adaptive sampling with this renderer's samples_per_pixel N as the cap: every pixel gets samples [0, min_spp); then, while some
+        are still too noisy (select_pixels) and fewer than N samples are done, those pixels alone get the next step_spp samples
+        (render_pixels).  The active set only shrinks: a pixel once dropped is never sampled again.  Returns (frame, accum, moment2, count):
+        the raw sums with their fixed 1 / N scale, count uint32 [H, W] = samples each pixel received (min_spp plus a multiple of
+        step_spp, capped at N), and frame = accum * (float32(N) / float32(count)), the estimate of every pixel at its own count.  A
+        pixel with count c holds exactly the bytes a full render of samples [0, c) would."""
+        n_cap, min_spp, step_spp = self.samples_per_pixel, int(min_spp), int(step_spp)
+        if not 2 <= min_spp <= n_cap or step_spp < 1:
+            raise ValueError("render_adaptive needs 2 <= min_spp <= samples_per_pixel and step_spp >= 1")
+        w, h = camera.get_image_size()
+        accum, moment2, _ = self.render_moments(camera, world, sample_begin=0, sample_end=min_spp)
+        count = np.full(h * w, min_spp, np.uint32)
+        done = min_spp
+        active = select_pixels(accum, moment2, n_cap, done, rel_tol, abs_tol)
+        while len(active) and done < n_cap:
+            nxt = min(done + step_spp, n_cap)
+            self.render_pixels(camera, world, active, accum, moment2, sample_begin=done, sample_end=nxt, accumulate=1)
+            count[active] = nxt
+            done = nxt
+            active = select_pixels(accum, moment2, n_cap, done, rel_tol, abs_tol, candidates=active)
+        count = count.reshape(h, w)
+        scale = np.float32(n_cap) / count.astype(np.float32)
+        return accum * scale[..., None], accum, moment2, count
+
     def render_aov(self, camera, world, channels=tuple(AOV_CHANNELS), buffers=None, **over):
         """trt_render_aov: the first-hit feature buffers of this renderer's frame (same seed, samples and rays as render()), as a dict
         channel -> array [rows, width, 3] or [rows, width] for the `channels` asked (albedo, normal, depth, coverage: float32 sums over the
@@ -489,6 +549,41 @@ def variance_device(d_accum_ptr, d_moment2_ptr, npixels, samples_per_pixel, d_va
     """Enqueue variance() on buffers already in HBM (device pointers as integers; npixels floats out); asynchronous on the stream."""
     check(lib.trt_variance_device(C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), int(npixels), int(samples_per_pixel),
                                   C.c_void_p(d_variance_ptr), C.c_void_p(stream_ptr)))
+
+
+def select_pixels(accum, moment2, samples_per_pixel, samples_done, rel_tol, abs_tol=0.0, candidates=None):
+    """trt_select_pixels: the candidates (uint32 pixel indices; None = every pixel) whose estimate after samples_done of samples_per_pixel
+    samples is still too noisy - variance of the mean > rel_tol^2 * (r + g + b)^2 + abs_tol^2, as tinyrt.h spells it out - in candidate
+    order, as a uint32 array.  `accum`, `moment2`: the running sums as Renderer.render_moments leaves them, float32 [..., 3].
+    samples_done <= 1 keeps every candidate."""
+    s = np.ascontiguousarray(accum, np.float32)
+    m = np.ascontiguousarray(moment2, np.float32)
+    if s.ndim < 1 or s.shape[-1] != 3 or m.shape != s.shape:
+        raise ValueError("accum and moment2 must have the same shape [..., 3]")
+    npixels = s.size // 3
+    cand = None if candidates is None else np.ascontiguousarray(candidates, np.uint32).reshape(-1)
+    n = npixels if cand is None else len(cand)
+    out = np.zeros(n, np.uint32)
+    count = C.c_uint32(0)
+    check(lib.trt_select_pixels(s.ctypes.data if s.size else None, m.ctypes.data if s.size else None, npixels, int(samples_per_pixel),
+                                int(samples_done), cand.ctypes.data if cand is not None and n else None, n, float(rel_tol), float(abs_tol),
+                                out.ctypes.data if n else None, C.byref(count)))
+    return out[:count.value].copy()
+
+
+def select_scratch_bytes(n):
+    """trt_select_scratch_bytes: what select_pixels_device needs as scratch for n candidates (host arithmetic)."""
+    return int(lib.trt_select_scratch_bytes(int(n)))
+
+
+def select_pixels_device(d_accum_ptr, d_moment2_ptr, npixels, samples_per_pixel, samples_done, n, rel_tol, abs_tol, d_selected_ptr, d_count_ptr,
+                         d_scratch_ptr, scratch_bytes, d_candidates_ptr=0, stream_ptr=0):
+    """Enqueue select_pixels() on buffers already in HBM (device pointers as integers): n candidates (d_candidates_ptr 0: pixel i), up to n
+    indices and a uint32 count out; nothing is allocated, `d_scratch_ptr` holds at least select_scratch_bytes(n) bytes; asynchronous."""
+    check(lib.trt_select_pixels_device(C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), int(npixels), int(samples_per_pixel), int(samples_done),
+                                       C.c_void_p(d_candidates_ptr), int(n), float(rel_tol), float(abs_tol), C.c_void_p(d_selected_ptr),
+                                       C.c_void_p(d_count_ptr), C.c_void_p(d_scratch_ptr), int(scratch_bytes),
+                                       C.c_void_p(stream_ptr)))
 
 
 def denoise_params(**over):

@@ -1,0 +1,563 @@
+// pixels.hip — sparse rendering of caller-chosen pixels (tinyrt.h trt_render_pixels / trt_render_pixels_device) and the selection of the
+// pixels whose estimate is still too noisy (trt_select_pixels / trt_select_pixels_device), written for gfx950 (CDNA4) only.
+//
+// The render entry points trace every pixel of their rows for a whole sample range; the band fields cut rows, never columns.  This unit
+// traces a LIST of pixels and leaves, for each of them, the bytes trt_render_moments_device would have left: the same RNG stream
+// (seed, image pixel, sample), the same bounce loop (closest hit, shade_hit of rt_path.h), and the imager's fold
+//   acc.ch = acc.ch + c.ch * inv_spp;   m2.ch = m2.ch + (c.ch * c.ch) * inv_spp
+// in sample order, one IEEE f32 operation per operator (streamed.hip stream_fold_moments_kernel), here in registers: a lane owns a pixel
+// for all samples of the call, so no radiance record goes through memory and there is no second kernel.  Every other byte of the two
+// buffers is left alone.  Adaptive sampling is then a host loop over two primitives: render a list, select the next one (api.py).
+//
+// There is no walk code in this file and none of the render kernels is touched: the kernel calls the entry points of rt_path.h the way
+// aov.hip does, with the dynamic LDS laid out the same way (scene copy | leaf stack: threads x slots x 8 bytes), and is launched by the
+// rule of the queries (query_plan.h) with list entries in place of rays: a wave owns a contiguous run of the list.
+//
+// Work: the wave runs in rounds.  At the top of a round every lane without a pixel takes the next entry of the run, every lane without a
+// path starts its pixel's next sample; then all lanes that own a pixel trace one bounce.  A lane whose path ended in a round therefore has
+// a new one in the next, whatever the walk: no lane idles while its neighbours finish longer paths.  With the two resumable walks (LDS
+// tree, 16-byte nodes) a walk still under way when at most `stragglers` lanes walk is parked in the lane's leaf stack and resumed beside
+// the fresh rays, exactly as in aov_kernel.
+#include <vector>
+
+#include "kernels.h"
+#include "query_plan.h"
+#include "rt_path.h"
+#include "scene_query.h"
+
+namespace trt {
+
+TRT_DEV uint32_t px_rank(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+struct PixelsArgs {
+    const uint32_t* pixels;          // n local pixel indices r * width + x
+    const uint32_t* d_count;         // nullptr, or the number of entries to use (at most n)
+    float* accum;                    // npixels x 3
+    float* moment2;                  // npixels x 3, or nullptr: not wanted
+    unsigned long long* counters;    // nullptr, or [CTR_SAMPLES], [CTR_RAYS] are added to
+    uint32_t n, npixels;             // list length; pixels of the local image (rows x width): an entry >= npixels is skipped
+    uint32_t pixels_per_wave;        // wave w owns entries [w * pixels_per_wave, ...)
+    uint32_t slots, stragglers;      // as in query.hip QueryArgs
+};
+
+// Entries the launch uses: min(*d_count, n).  The count may have been written by the kernel before this one on the stream
+// (select_write_kernel), so it is read with a vector load from memory (volatile: never through the scalar cache) and made wave-uniform.
+TRT_DEV uint32_t px_entries(const uint32_t* d_count, uint32_t n) {
+    if (d_count == nullptr) return n;
+    const uint32_t c = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile uint32_t*>(d_count));
+    return c < n ? c : n;
+}
+
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_pixels: nothing to trace launches pixels_zero_kernel or nothing)
+template <int MODE, int WALK, int THREADS, int MINW>
+__global__ __launch_bounds__(THREADS, MINW) void pixels_kernel(SceneDev scd, CameraDev cam, RenderArgs ra, PixelsArgs pa, const float4* __restrict__ leaf_list,
+                                                                    const uint4* __restrict__ nodes16) {
+    stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    const uint32_t n = px_entries(pa.d_count, pa.n);
+    const unsigned long long begin64 = (unsigned long long)wave * pa.pixels_per_wave;
+    if (begin64 >= n) return;                                               // (after the barriers above)
+    const uint32_t begin = (uint32_t)begin64;
+    const uint32_t count = n - begin < pa.pixels_per_wave ? n - begin : pa.pixels_per_wave;
+    // postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave (query.hip)
+    float2* const stack = WALK != WALK_REGS
+        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * pa.slots) + lane
+        : nullptr;
+    const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
+    Counters<false> ctr;
+    constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
+
+    uint32_t cursor = 0;                                                    // wave-uniform
+    bool own = false, has_path = false, walking = false;                    // the lane owns a pixel; a path of it is under way; its walk is parked
+    uint32_t pix = 0, s = 0;
+    uint32_t n_samples = 0, n_rays = 0;
+    V3 acc = v3(0.0f, 0.0f, 0.0f), m2 = v3(0.0f, 0.0f, 0.0f);
+    Path p;
+    p.ray.o = v3(0.0f, 0.0f, 0.0f); p.ray.d = v3(0.0f, 0.0f, 0.0f);
+    p.color = v3(0.0f, 0.0f, 0.0f); p.atten = v3(0.0f, 0.0f, 0.0f);
+    p.remain = 0u;
+    p.rng.s0 = 0u; p.rng.s1 = 0u;
+    for (;;) {
+        // ---- refill: every lane without a pixel takes the next entry of the run ----
+        const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
+        if (need != 0ull && cursor < count) {
+            const uint32_t item = cursor + px_rank(need);
+            if (!own && item < count) {
+                pix = pa.pixels[begin + item];
+                if (pix < pa.npixels) {                                     // an entry past the local image is skipped: neither read nor written
+                    s = ra.sample_begin;
+                    if (ra.accumulate) {
+                        const float* const a = pa.accum + 3ull * pix;
+                        acc = v3(a[0], a[1], a[2]);
+                        if (pa.moment2) { const float* const m = pa.moment2 + 3ull * pix; m2 = v3(m[0], m[1], m[2]); }
+                    } else {
+                        acc = v3(0.0f, 0.0f, 0.0f);
+                        m2 = v3(0.0f, 0.0f, 0.0f);
+                    }
+                    own = true;
+                }
+            }
+            cursor += (uint32_t)__builtin_popcountll(need);
+            if (cursor > count) cursor = count;
+        }
+        if (__builtin_amdgcn_ballot_w64(own) == 0ull) {
+            if (cursor >= count) break;                                     // the run is done
+            continue;                                                       // 64 skipped entries: take the next ones
+        }
+        if (own) {
+            if (!has_path) {                                                // cpu.rs:42-45
+                const uint32_t row = pix / cam.width, x = pix - row * cam.width;
+                path_begin(p, cam, ra, x, image_row(ra, row), s);
+                has_path = true;
+                n_samples++;
+            }
+            bool ended = false;
+            if constexpr (kResumable) {
+                Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, p.ray, false);      // a new walk, or the frame of a parked one
+                if (walking) trav_unpark(stack, tr); else { tr.t_best = __builtin_inff(); n_rays++; }
+                const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+                walking = !closest_hit_resume<MODE, false, WALK, false>(sc, p.ray, tr, ctr, pa.slots, stack, leaf_list, nodes16, pa.stragglers, entered);
+                if (!walking) ended = shade_hit<MODE, false>(sc, p, tr.prim_best, tr.t_best, background, ctr);
+            } else {
+                n_rays++;
+                float t = 0.0f;
+                const uint32_t prim = closest_hit<MODE, false, WALK, false>(sc, p.ray, false, t, ctr, pa.slots, stack, leaf_list, nodes16, flat_reuse);
+                ended = shade_hit<MODE, false>(sc, p, prim, t, background, ctr);
+            }
+            if (ended) {
+                // imager.rs:35,50 and the second moment beside it, in the operation order of stream_fold_moments_kernel
+                acc = acc + p.color * ra.inv_spp;
+                m2.x = m2.x + (p.color.x * p.color.x) * ra.inv_spp;
+                m2.y = m2.y + (p.color.y * p.color.y) * ra.inv_spp;
+                m2.z = m2.z + (p.color.z * p.color.z) * ra.inv_spp;
+                has_path = false;
+                s += 1u;
+                if (s == ra.sample_end) {
+                    float* const a = pa.accum + 3ull * pix;
+                    a[0] = acc.x; a[1] = acc.y; a[2] = acc.z;
+                    if (pa.moment2) { float* const m = pa.moment2 + 3ull * pix; m[0] = m2.x; m[1] = m2.y; m[2] = m2.z; }
+                    own = false;
+                }
+            }
+        }
+    }
+    flush_counters<false>(pa.counters, n_samples, n_rays, ctr);
+}
+
+// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the listed pixels become 0, as the frame of trt_render_moments does.
+__global__ __launch_bounds__(256) void pixels_zero_kernel(const uint32_t* __restrict__ pixels, const uint32_t* d_count, uint32_t n, uint32_t npixels,
+                                                          float* __restrict__ accum, float* __restrict__ moment2) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= px_entries(d_count, n)) return;
+    const uint32_t pix = pixels[i];
+    if (pix >= npixels) return;
+    float* const a = accum + 3ull * pix;
+    a[0] = 0.0f; a[1] = 0.0f; a[2] = 0.0f;
+    if (moment2) { float* const m = moment2 + 3ull * pix; m[0] = 0.0f; m[1] = 0.0f; m[2] = 0.0f; }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Selection (tinyrt.h trt_select_pixels): from a candidate list, the pixels whose estimate after `samples_done` samples is still too
+// noisy, in candidate order.  Three launches, no atomic anywhere, so the output is the same list on every run:
+//   select_count_kernel   a workgroup counts the kept candidates of its tile of kSelectTile
+//   select_scan_kernel    ONE workgroup turns the tile counts into exclusive offsets (chunks of kSelectTile, carried in order) and writes the total
+//   select_write_kernel   a workgroup evaluates its tile again and writes the kept indices from its offset on, ranked by ballot within a wave
+// The test is evaluated twice rather than kept: 24 bytes read per candidate against a flag written and read back, and no scratch per candidate.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kSelectTile = 256u;
+
+struct SelectArgs {
+    const float* accum;
+    const float* moment2;
+    const uint32_t* candidates;      // nullptr: candidate i is pixel i
+    uint32_t n, npixels;
+    float k, inv, rel2, abs2;        // N / n, 1 / (n - 1), rel_tol^2, abs_tol^2: computed once on the host
+    uint32_t known;                  // 0: samples_done <= 1, the variance is unknown and every candidate is kept
+};
+
+// all f32, one IEEE operation per operator, nothing fused (-ffp-contract=off); the sums of tinyrt.h trt_select_pixels
+TRT_DEV bool select_keep(const SelectArgs& sa, uint32_t i) {
+    const uint32_t pix = sa.candidates ? sa.candidates[i] : i;
+    if (pix >= sa.npixels) return false;                                    // not kept and not read
+    if (!sa.known) return true;
+    const float* const S = sa.accum + 3ull * pix;
+    const float* const M = sa.moment2 + 3ull * pix;
+    const float sr = S[0] * sa.k, sg = S[1] * sa.k, sb = S[2] * sa.k;
+    const float qr = M[0] * sa.k, qg = M[1] * sa.k, qb = M[2] * sa.k;
+    float dr = qr - sr * sr, dg = qg - sg * sg, db = qb - sb * sb;
+    dr = dr > 0.0f ? dr : 0.0f;
+    dg = dg > 0.0f ? dg : 0.0f;
+    db = db > 0.0f ? db : 0.0f;
+    const float v = ((dr + dg) + db) * sa.inv;
+    const float l = (sr + sg) + sb;
+    float b = sa.rel2 * (l * l);
+    b = b + sa.abs2;
+    return v > b;                                                           // a NaN on either side: not kept
+}
+
+// Kept candidates of the workgroup's tile before this lane (exclusive), and the tile's total; `waves`: LDS, 4 words.
+TRT_DEV uint32_t select_tile_rank(bool keep, uint32_t* waves, uint32_t& total) {
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(keep);
+    const uint32_t w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) waves[w] = (uint32_t)__builtin_popcountll(mask);
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+    for (uint32_t k = 0; k < kSelectTile / 64u; k++) { if (k < w) before += waves[k]; total += waves[k]; }
+    return before + px_rank(mask);
+}
+
+__global__ __launch_bounds__(kSelectTile) void select_count_kernel(SelectArgs sa, uint32_t* __restrict__ tile_counts) {
+    __shared__ uint32_t waves[kSelectTile / 64u];
+    const uint32_t i = blockIdx.x * kSelectTile + threadIdx.x;
+    const bool keep = i < sa.n && select_keep(sa, i);
+    uint32_t total = 0;
+    (void)select_tile_rank(keep, waves, total);
+    if (threadIdx.x == 0u) tile_counts[blockIdx.x] = total;
+}
+
+// one workgroup: tile_counts[t] becomes the number of kept candidates in the tiles before t; *count the number kept in all
+__global__ __launch_bounds__(kSelectTile) void select_scan_kernel(uint32_t* __restrict__ tile_counts, uint32_t n_tiles, uint32_t* __restrict__ count) {
+    __shared__ uint32_t part[kSelectTile];
+    uint32_t carry = 0;                                                     // the same in every lane
+    for (uint32_t base = 0; base < n_tiles; base += kSelectTile) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t c = t < n_tiles ? tile_counts[t] : 0u;
+        part[threadIdx.x] = c;
+        __syncthreads();
+        // inclusive scan of the chunk (Hillis-Steele: 8 steps of 256 lanes)
+        for (uint32_t off = 1; off < kSelectTile; off <<= 1) {
+            const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (t < n_tiles) tile_counts[t] = carry + part[threadIdx.x] - c;
+        carry += part[kSelectTile - 1u];
+        __syncthreads();                                                    // (before the next chunk overwrites part[])
+    }
+    if (threadIdx.x == 0u) *count = carry;
+}
+
+__global__ __launch_bounds__(kSelectTile) void select_write_kernel(SelectArgs sa, const uint32_t* __restrict__ tile_offsets, uint32_t* __restrict__ selected) {
+    __shared__ uint32_t waves[kSelectTile / 64u];
+    const uint32_t i = blockIdx.x * kSelectTile + threadIdx.x;
+    const bool keep = i < sa.n && select_keep(sa, i);
+    uint32_t total = 0;
+    const uint32_t rank = select_tile_rank(keep, waves, total);
+    // offset + rank < number kept <= n: within the caller's n entries
+    if (keep) selected[tile_offsets[blockIdx.x] + rank] = sa.candidates ? sa.candidates[i] : i;
+}
+
+namespace {
+
+struct PixelsKernel {
+    const void* fn;
+    int mode, walk, threads, minw;
+};
+#define TRT_PIXELS(MODE, WALK, THREADS, MINW) \
+    PixelsKernel{reinterpret_cast<const void*>(&pixels_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// the (scene mode, walk, workgroup shape) set of aov.hip kAovKernels, with the register-slot fallback (query_plan.h), so that every scene
+// has a kernel.  A lane carries a whole path (ray, colour, attenuation, RNG) and two running sums across the walk, where the feature
+// buffers carry a ray and eight sums: the launch bounds are the highest at which the instantiation uses no scratch memory
+// (profiles/pixels_resource_usage.txt).  The plan reports the bound (kernel_waves_per_simd).
+const PixelsKernel kPixelsKernels[] = {
+    TRT_PIXELS(MODE_LDS, WALK_FLAT, 256, 5),
+    TRT_PIXELS(MODE_LDS, WALK_LDS_STACK, 256, 5),
+    TRT_PIXELS(MODE_LDS, WALK_LDS_STACK, 768, 5),
+    TRT_PIXELS(MODE_LDS, WALK_REGS, 512, 5),
+    TRT_PIXELS(MODE_GLOBAL, WALK_COMPACT, 256, 5),
+    TRT_PIXELS(MODE_GLOBAL, WALK_REGS, 256, 5),
+};
+#undef TRT_PIXELS
+
+const PixelsKernel* plan_pixels(const SceneLayout& L, uint32_t n, uint32_t cus, trt_query_plan& q) {
+    return plan_batch(L, n, cus, kPixelsKernels, sizeof(kPixelsKernels) / sizeof(kPixelsKernels[0]), q);
+}
+
+// the launch pattern of kernels.hip: a big dynamic LDS is asked for, and trt_kernel_timing_* brackets the launch
+hipError_t launch(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t stream) {
+    if (lds > 48u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    timing_mark(stream, true);
+    const hipError_t le = hipLaunchKernel(fn, grid, block, args, lds, stream);
+    timing_mark(stream, false);
+    return le;
+}
+
+// npixels = rows x width of the local image
+hipError_t launch_pixels(const QueryScene& qs, const CameraDev& cd, RenderArgs ra, uint32_t npixels, const uint32_t* d_pixels, uint32_t n,
+                         const uint32_t* d_count, float* d_accum, float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+    if (n == 0 || npixels == 0) return hipSuccess;
+    if (ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
+        // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
+        if (ra.accumulate) return hipSuccess;
+        hipLaunchKernelGGL(pixels_zero_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_pixels, d_count, n, npixels, d_accum, d_moment2);
+        return hipGetLastError();
+    }
+    const SceneLayout& L = qs.scene.L;
+    int dev = 0, cus = 256;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    trt_query_plan q;
+    const PixelsKernel* const k = plan_pixels(L, n, (uint32_t)cus, q);
+    if (k == nullptr) return hipErrorInvalidDeviceFunction;                         // no instantiation for this plan: a bug, never a fallback
+    const bool flat = k->walk == WALK_FLAT, compact = k->walk == WALK_COMPACT;
+    // what the walks assume, checked where the launch is made (query.hip launch_query)
+    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.leaf_slots < 2u) || (compact && L.off_compact == 0u) ||
+        (k->walk != WALK_REGS && (q.leaf_slots < 1u || q.leaf_slots > kLdsLeafSlotsMax)))
+        return hipErrorInvalidConfiguration;
+    SceneDev scd = qs.scene;
+    CameraDev cam = cd;
+    ra.flat_reuse = qs.flat_reuse;
+    PixelsArgs pa{d_pixels, d_count, d_accum, d_moment2, d_counters, n, npixels, q.rays_per_wave, q.leaf_slots, q.stragglers};
+    const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
+    const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
+    void* args[] = {&scd, &cam, &ra, &pa, &leaf_list, &nodes16};
+    return launch(k->fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+}
+
+// What both forms check before any device work.  npixels = pixels of the local image.
+int pixels_check(const trt_scene* s, const trt_camera* cam, const trt_render_params* p, const uint32_t* pixels, uint32_t n, const float* accum,
+                 RenderArgs& ra, uint32_t& npixels, CameraDev& cd) {
+    if (!s || !cam || !p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (p->collect_stats != 0u) return query_fail(TRT_ERR_INVALID_ARG, "the sparse render has no counting kernels: collect_stats must be 0");
+    uint32_t rows = 0;
+    const int rc = query_render_args(cam, p, ra, rows);
+    if (rc != TRT_OK) return rc;
+    if ((unsigned long long)rows * cam->width > 0xFFFFFFFFull) return query_fail(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 pixels");
+    npixels = rows * cam->width;
+    query_camera_dev(*cam, cd);
+    if (n > 0u && (!pixels || !accum)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
+    return TRT_OK;
+}
+
+size_t select_tiles(uint32_t n) { return ((size_t)n + kSelectTile - 1u) / kSelectTile; }
+
+int select_check(const float* accum, const float* moment2, uint32_t samples_per_pixel, uint32_t samples_done, uint32_t n, const uint32_t* selected,
+                 const uint32_t* count) {
+    if (!count) return query_fail(TRT_ERR_INVALID_ARG, "count is null");
+    if (samples_per_pixel == 0u) return query_fail(TRT_ERR_INVALID_ARG, "samples_per_pixel must be positive");
+    if (samples_done > samples_per_pixel) return query_fail(TRT_ERR_INVALID_ARG, "samples_done must not exceed samples_per_pixel");
+    if (n > 0u && (!accum || !moment2 || !selected)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
+    return TRT_OK;
+}
+
+SelectArgs select_args(const float* d_accum, const float* d_moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,
+                       const uint32_t* d_candidates, uint32_t n, float rel_tol, float abs_tol) {
+    SelectArgs sa{};
+    sa.accum = d_accum; sa.moment2 = d_moment2; sa.candidates = d_candidates;
+    sa.n = n; sa.npixels = npixels;
+    sa.known = samples_done > 1u ? 1u : 0u;
+    sa.k = sa.known ? (float)samples_per_pixel / (float)samples_done : 0.0f;
+    sa.inv = sa.known ? 1.0f / (float)(samples_done - 1u) : 0.0f;
+    sa.rel2 = rel_tol * rel_tol;
+    sa.abs2 = abs_tol * abs_tol;
+    return sa;
+}
+
+// n > 0; d_scratch holds select_tiles(n) words
+hipError_t launch_select(const SelectArgs& sa, uint32_t* d_selected, uint32_t* d_count, uint32_t* d_scratch, hipStream_t stream) {
+    const uint32_t tiles = (uint32_t)select_tiles(sa.n);
+    hipLaunchKernelGGL(select_count_kernel, dim3(tiles), dim3(kSelectTile), 0, stream, sa, d_scratch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelectTile), 0, stream, d_scratch, tiles, d_count);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(select_write_kernel, dim3(tiles), dim3(kSelectTile), 0, stream, sa, static_cast<const uint32_t*>(d_scratch), d_selected);
+    return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace trt
+
+extern "C" {
+
+int trt_render_pixels_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const uint32_t* d_pixels, uint32_t n,
+                             const uint32_t* d_count, float* d_accum, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::RenderArgs ra;
+    trt::CameraDev cd;
+    uint32_t npixels = 0;
+    int rc = trt::pixels_check(s, cam, p, d_pixels, n, d_accum, ra, npixels, cd);
+    if (rc != TRT_OK) return rc;
+    if (n == 0u) return TRT_OK;
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    trt::QueryScene qs;
+    rc = trt::query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = trt::launch_pixels(qs, cd, ra, npixels, d_pixels, n, d_count, d_accum, d_moment2,
+                                            reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return trt::query_fail_hip(e, "sparse render launch");
+    return TRT_OK;
+}
+
+// Host buffers: the list is validated, then device copies of the list and of the two frames are the call's own, one stream-ordered sequence
+// on the default stream, complete when the call returns.  Only the listed pixels are copied back into the caller's buffers.
+int trt_render_pixels(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const uint32_t* pixels, uint32_t n, float* accum,
+                      float* moment2, trt_stats* stats) {
+    trt::RenderArgs ra;
+    trt::CameraDev cd;
+    uint32_t npixels = 0;
+    int rc = trt::pixels_check(s, cam, p, pixels, n, accum, ra, npixels, cd);
+    if (rc != TRT_OK) return rc;
+    {
+        std::vector<uint64_t> seen(((size_t)npixels + 63u) / 64u, 0ull);
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t pix = pixels[i];
+            if (pix >= npixels) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " at entry " + std::to_string(i) + " is outside the local image");
+            if (seen[pix >> 6] >> (pix & 63u) & 1ull) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " is listed twice");
+            seen[pix >> 6] |= 1ull << (pix & 63u);
+        }
+    }
+    if (n == 0u) {
+        if (stats) *stats = trt_stats{};
+        return TRT_OK;
+    }
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    trt::QueryScene qs;
+    rc = trt::query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u;
+    const size_t off_list = 0, off_acc = trt::q_align16(list), off_m2 = off_acc + trt::q_align16(frame);
+    const size_t off_ctr = off_m2 + (moment2 ? trt::q_align16(frame) : 0u), total = off_ctr + trt::CTR_COUNT * sizeof(unsigned long long);
+    char* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
+    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("sparse render buffers: ") + hipGetErrorString(e)); }
+    float* const d_acc = reinterpret_cast<float*>(d + off_acc);
+    float* const d_m2 = moment2 ? reinterpret_cast<float*>(d + off_m2) : nullptr;
+    unsigned long long* const d_ctr = reinterpret_cast<unsigned long long*>(d + off_ctr);
+    unsigned long long h_ctr[trt::CTR_COUNT] = {0};
+    std::vector<float> back(3u * (size_t)npixels);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.0f;
+    const char* what = "hipMemcpy of the list";
+    e = hipMemcpy(d + off_list, pixels, list, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { what = "hipMemset of the counters"; e = hipMemset(d_ctr, 0, sizeof(h_ctr)); }
+    // the running sums a pass continues go up; a pass that starts them reads nothing
+    if (e == hipSuccess && ra.accumulate) { what = "hipMemcpy of the frame"; e = hipMemcpy(d_acc, accum, frame, hipMemcpyHostToDevice); }
+    if (e == hipSuccess && ra.accumulate && d_m2) { what = "hipMemcpy of the second moments"; e = hipMemcpy(d_m2, moment2, frame, hipMemcpyHostToDevice); }
+    if (e == hipSuccess) { what = "hipEventCreate"; e = hipEventCreate(&ev0); }
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev0, nullptr); }
+    if (e == hipSuccess) {
+        what = "sparse render launch";
+        e = trt::launch_pixels(qs, cd, ra, npixels, reinterpret_cast<const uint32_t*>(d + off_list), n, nullptr, d_acc, d_m2, d_ctr, nullptr);
+    }
+    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev1, nullptr); }
+    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
+    for (int b = 0; b < 2 && e == hipSuccess && wrote; b++) {
+        float* const host = b == 0 ? accum : moment2;
+        if (!host) continue;
+        what = "hipMemcpy of the results";
+        e = hipMemcpy(back.data(), b == 0 ? d_acc : d_m2, frame, hipMemcpyDeviceToHost);       // (waits for the kernel: same stream)
+        if (e != hipSuccess) break;
+        for (uint32_t i = 0; i < n; i++) {
+            const size_t o = 3u * (size_t)pixels[i];
+            host[o] = back[o]; host[o + 1u] = back[o + 1u]; host[o + 2u] = back[o + 2u];
+        }
+    }
+    if (e == hipSuccess) { what = "hipMemcpy of the counters"; e = hipMemcpy(h_ctr, d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost); }
+    if (e == hipSuccess) { what = "hipEventElapsedTime"; e = hipEventSynchronize(ev1); if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1); }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(d);
+    if (e != hipSuccess) return trt::query_fail_hip(e, what);
+    if (stats) {
+        *stats = trt_stats{};
+        stats->samples = h_ctr[trt::CTR_SAMPLES];
+        stats->rays = h_ctr[trt::CTR_RAYS];
+        stats->kernel_ms = ms;
+    }
+    return TRT_OK;
+}
+
+// How launch_pixels would launch a list of n pixels on this scene (host arithmetic only: works without a GPU when the CU count is given).
+int trt_pixels_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    if (!s || !out) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (compute_units == 0u) {
+        const int rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        int dev = 0, cus = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess || cus <= 0) return trt::query_fail_hip(e, "compute unit count of the current device");
+        compute_units = (uint32_t)cus;
+    }
+    (void)trt::plan_pixels(trt::query_scene_layout(s), n, compute_units, *out);      // no instantiation: has_kernel = 0 says so
+    return TRT_OK;
+}
+
+uint64_t trt_select_scratch_bytes(uint32_t n) { return (uint64_t)trt::q_align16(trt::select_tiles(n) * sizeof(uint32_t)); }
+
+int trt_select_pixels_device(const float* d_accum, const float* d_moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,
+                             const uint32_t* d_candidates, uint32_t n, float rel_tol, float abs_tol, uint32_t* d_selected, uint32_t* d_count,
+                             void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    int rc = trt::select_check(d_accum, d_moment2, samples_per_pixel, samples_done, n, d_selected, d_count);
+    if (rc != TRT_OK) return rc;
+    if (n > 0u && (!d_scratch || scratch_bytes < trt_select_scratch_bytes(n)))
+        return trt::query_fail(TRT_ERR_INVALID_ARG, "scratch is null or smaller than trt_select_scratch_bytes(n)");
+    if (n == 0u) {
+        // count 0 and nothing else; without a device there is no buffer to write it to
+        if (trt_device_count() > 0) {
+            const hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return trt::query_fail_hip(e, "hipMemsetAsync of the count");
+        }
+        return TRT_OK;
+    }
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    const trt::SelectArgs sa = trt::select_args(d_accum, d_moment2, npixels, samples_per_pixel, samples_done, d_candidates, n, rel_tol, abs_tol);
+    const hipError_t e = trt::launch_select(sa, d_selected, d_count, static_cast<uint32_t*>(d_scratch), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return trt::query_fail_hip(e, "selection launch");
+    return TRT_OK;
+}
+
+// Host buffers: device copies of the call's own on the default stream, complete when the call returns.
+int trt_select_pixels(const float* accum, const float* moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,
+                      const uint32_t* candidates, uint32_t n, float rel_tol, float abs_tol, uint32_t* selected, uint32_t* count) {
+    int rc = trt::select_check(accum, moment2, samples_per_pixel, samples_done, n, selected, count);
+    if (rc != TRT_OK) return rc;
+    if (n == 0u) { *count = 0u; return TRT_OK; }
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u, scratch = (size_t)trt_select_scratch_bytes(n);
+    const size_t off_acc = 0, off_m2 = trt::q_align16(frame), off_cand = off_m2 + trt::q_align16(frame);
+    const size_t off_sel = off_cand + (candidates ? trt::q_align16(list) : 0u), off_scratch = off_sel + trt::q_align16(list);
+    const size_t off_count = off_scratch + scratch, total = off_count + 16u;
+    char* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
+    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("selection buffers: ") + hipGetErrorString(e)); }
+    const char* what = "hipMemcpy of the sums";
+    if (frame) e = hipMemcpy(d + off_acc, accum, frame, hipMemcpyHostToDevice);
+    if (e == hipSuccess && frame) e = hipMemcpy(d + off_m2, moment2, frame, hipMemcpyHostToDevice);
+    if (e == hipSuccess && candidates) { what = "hipMemcpy of the candidates"; e = hipMemcpy(d + off_cand, candidates, list, hipMemcpyHostToDevice); }
+    uint32_t kept = 0;
+    if (e == hipSuccess) {
+        const trt::SelectArgs sa = trt::select_args(reinterpret_cast<const float*>(d + off_acc), reinterpret_cast<const float*>(d + off_m2), npixels,
+                                                    samples_per_pixel, samples_done,
+                                                    candidates ? reinterpret_cast<const uint32_t*>(d + off_cand) : nullptr, n, rel_tol, abs_tol);
+        what = "selection launch";
+        e = trt::launch_select(sa, reinterpret_cast<uint32_t*>(d + off_sel), reinterpret_cast<uint32_t*>(d + off_count),
+                               reinterpret_cast<uint32_t*>(d + off_scratch), nullptr);
+    }
+    if (e == hipSuccess) { what = "hipMemcpy of the count"; e = hipMemcpy(&kept, d + off_count, sizeof(kept), hipMemcpyDeviceToHost); }      // (waits for the kernels: same stream)
+    if (e == hipSuccess && kept > n) { (void)hipFree(d); return trt::query_fail(TRT_ERR_HIP, "selection kept more candidates than it was given"); }
+    if (e == hipSuccess && kept) { what = "hipMemcpy of the selection"; e = hipMemcpy(selected, d + off_sel, (size_t)kept * 4u, hipMemcpyDeviceToHost); }
+    (void)hipFree(d);
+    if (e != hipSuccess) return trt::query_fail_hip(e, what);
+    *count = kept;
+    return TRT_OK;
+}
+
+}  // extern "C"
