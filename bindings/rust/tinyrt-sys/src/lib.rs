@@ -370,6 +370,8 @@ extern "C" {
     pub fn trt_select_pixels(accum: *const f32, moment2: *const f32, npixels: u32, samples_per_pixel: u32, samples_done: u32,
                              candidates: *const u32, n_candidates: u32, rel_tol: f32, abs_tol: f32, selected: *mut u32,
                              count: *mut u32) -> c_int;
+    // (host form above: `selected` may alias `candidates`; device form below: the n_candidates words at `d_selected` must not overlap the
+    // n_candidates words at `d_candidates` - TRT_ERR_INVALID_ARG - because the kernels cannot compact in place)
     pub fn trt_select_pixels_device(d_accum: *const f32, d_moment2: *const f32, npixels: u32, samples_per_pixel: u32, samples_done: u32,
                                     d_candidates: *const u32, n_candidates: u32, rel_tol: f32, abs_tol: f32, d_selected: *mut u32,
                                     d_count: *mut u32, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> c_int;

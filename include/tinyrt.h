@@ -455,8 +455,13 @@ int trt_pixels_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_unit
  * room for n_candidates indices; the first *count are written.
  * trt_select_pixels: HOST buffers, synchronous.  trt_select_pixels_device: buffers in HBM, asynchronous on `stream`; allocates nothing:
  * `d_scratch` holds at least trt_select_scratch_bytes(n_candidates) bytes (host arithmetic only; 4-byte aligned).
+ * Aliasing: the HOST form works on device copies of its own, so `selected` may be `candidates` (a list shrunk in place).  The DEVICE form
+ * must not select in place: a workgroup writes d_selected[k] while others still read d_candidates[i], and although k <= i the slot k may
+ * be a candidate of an earlier tile that has not been read yet.  [d_candidates, d_candidates + 4 n_candidates) and [d_selected,
+ * d_selected + 4 n_candidates) must not overlap (TRT_ERR_INVALID_ARG; adjacent ranges are fine): keep two lists and swap them.
  * Errors: TRT_ERR_INVALID_ARG before any device work - a NULL count, samples_per_pixel == 0, samples_done > samples_per_pixel, with
- * n_candidates > 0 a NULL `accum`, `moment2` or `selected`, for the device form a NULL or too small scratch - then TRT_ERR_NO_DEVICE.
+ * n_candidates > 0 a NULL `accum`, `moment2` or `selected`, for the device form a NULL or too small scratch or a `d_selected` that
+ * overlaps `d_candidates` - then TRT_ERR_NO_DEVICE.
  * n_candidates == 0 succeeds, writes count 0 and touches nothing else, with or without a device (without one the device form has no
  * buffer to write and writes nothing). */
 int trt_select_pixels(const float *accum, const float *moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,

@@ -195,3 +195,31 @@ def test_aov_launch_plan_invariants_on_every_scene_and_option_of_the_gpu_tests(t
     assert shapes == AOV_KERNEL_SHAPES, sorted(shapes)
     assert {(1, WALK_LDS_TREE), (1, WALK_LOCK_STEP), (0, WALK_LOCK_STEP)} <= routes, sorted(routes)
     assert lengthened > 0                                                    # 2^24 pixels lengthen the runs of some shape
+
+
+def test_the_gpu_tests_case_lists_reach_every_kernel_and_every_route_to_the_fallback(trt):
+    """tests/test_gpu_aov.py renders its SCENES with default options and its WALK_CASES with theirs; passed through the plan at the image
+    size that module uses for them, the union must launch all six instantiations of kAovKernels and reach the register-slot fallback from
+    an LDS tree plan, from a lock-step plan in LDS and from a lock-step plan in global memory - so that dropping a case there, or a later
+    change to the plan, cannot leave a kernel or a route unrun without this test failing."""
+    import test_gpu_aov as A
+    import test_gpu_queries as G
+    import walk_ray_cases as W
+    cases = [(name, {}, G.DEFAULT_SHAPES[name]) for name in A.SCENES] + list(A.WALK_CASES)
+    assert len(cases) == len(A.SCENES) + len(G.OTHER_WALKS)
+    n = A.SIZES[0][0] * A.SIZES[0][1]
+    shapes, routes, worlds = set(), set(), {}
+    for name, options, shape in cases:
+        if name not in worlds:
+            worlds[name] = trt.world_from_description(W.scene(trt, name))[0]
+        host_options = {k: v for k, v in options.items() if k != "on_device"}           # (both compilers give the same bytes: tests/test_gpu_scene_build.py)
+        sc = worlds[name].get_bvh(**host_options) if host_options else worlds[name].get_bvh()
+        q = sc.aov_plan(n, 256)
+        assert G.plan_shape(q) == shape, (name, options, G.plan_shape(q), shape)
+        shapes.add(shape[:3])
+        if q["fallback"]:
+            routes.add((q["scene_mode"], q["streamed_walk"]))
+    # the default compilations alone miss the register-slot walk from global memory
+    assert {G.DEFAULT_SHAPES[name][:3] for name in A.SCENES} == AOV_KERNEL_SHAPES - {(0, 5, 256)}
+    assert shapes == AOV_KERNEL_SHAPES, sorted(shapes)
+    assert {(1, WALK_LDS_TREE), (1, WALK_LOCK_STEP), (0, WALK_LOCK_STEP)} <= routes, sorted(routes)

@@ -19,6 +19,11 @@ What is compared with what:
  4. every buffer with the numpy fold of trt_intersect on the exported rays, and the device forms with the host forms;
  5. split sample ranges, two shards, every subset of buffers with guard bytes behind each, and the device scene compiler with one pass.
 
+ 6. the scenes compiled with another placement option or by the device compiler (test_gpu_queries.OTHER_WALKS: the LDS tree on Cornell, the
+    lock-step list with more than 32 leaves, register slots from global memory and as the streamed plan's own walk, each route to the
+    fallback) at 67 x 35: normal, depth and the indices with the oracle fold of 3, albedo and coverage with the default compilation's
+    bytes, which 2 pins to the oracle's renderer.
+
 Bits are compared, except that a component the reference fold makes NaN is compared by NaN-ness (tests/test_gpu_queries.py
 assert_records_equal).  Every GPU step is one in-process call; nothing is built here and no child process is started."""
 import ctypes as C
@@ -36,6 +41,9 @@ SCENES = ["cornell", "prims33", "random_spheres", "mixed400", "prims600", "grid3
 SIZES = [(67, 35), (131, 70)]
 SPP, SEED = 3, 5
 MISS = 0xFFFFFFFF
+# (scene, scene options, kernel shape): the compilations whose walks the default ones above do not launch - aov_kernel<MODE_GLOBAL,
+# WALK_REGS, 256> among them - at SIZES[0]; tests/test_aov_abi.py checks without a GPU that SCENES and these reach all of kAovKernels
+WALK_CASES = G.OTHER_WALKS
 INV = np.float32(1.0) / np.float32(SPP)                                     # imager.rs:35
 
 
@@ -331,3 +339,24 @@ def test_the_device_compiled_scene_gives_the_same_bytes(trt, case, name):
     got = c["renderer"].render_aov(c["cam"], other)
     for ch in trt.AOV_CHANNELS:
         assert got[ch].tobytes() == c["aov"][ch].tobytes(), (name, ch)
+
+
+@pytest.mark.parametrize("name,options,shape", WALK_CASES,
+                         ids=["%s-%s" % (name, ",".join("%s=%s" % kv for kv in sorted(options.items()))) for name, options, _ in WALK_CASES])
+def test_every_other_walk_gives_the_oracles_first_hits_and_the_default_compilations_bytes(trt, case, name, options, shape):
+    c = case(name, SIZES[0])
+    other = c["world"].get_bvh(**options)
+    assert other is not c["scene"]
+    plan = other.aov_plan(c["n"])
+    assert G.plan_shape(plan) == shape, (name, options, plan)
+    assert plan["rays_per_wave"] == 256 and plan["workgroups"] == expected_workgroups(plan, c["n"]), plan
+    aov = c["renderer"].render_aov(c["cam"], other)
+    rec = c["rec"]
+    hits = [r["hit"] for r in rec]
+    assert_same(aov["normal"].reshape(-1, 3), fold([r["normal"] for r in rec]), (name, options, "normal"))
+    assert_same(aov["depth"].reshape(-1), fold([r["t"] for r in rec], hits), (name, options, "depth"))
+    assert_same(aov["coverage"].reshape(-1), fold([h.astype(np.float32) for h in hits]), (name, options, "coverage"))
+    assert_same(aov["geometry"].reshape(-1), rec[0]["geo"], (name, options, "geometry"))
+    assert_same(aov["material"].reshape(-1), rec[0]["mat"], (name, options, "material"))
+    for ch in ("albedo", "coverage"):
+        assert aov[ch].tobytes() == c["aov"][ch].tobytes(), (name, options, ch)

@@ -7,7 +7,7 @@ moments after 4 of 8 samples.  List lengths: 0, 1, 63, 64, 65 (both sides of a w
 scans), 65 537 (one beyond the 256 x 256 candidates one chunk of the second scan level covers) and 196 613 (three chunks: the carry).
 Candidate lists: NULL (the pixels 0 .. n-1), a fixed shuffle, and lists with entries past npixels, which are not kept and not read.
 The order of the output is the candidates'; the restatement must keep some and drop some wherever that is possible, so no comparison
-is between two empty or two full lists.  Every GPU step is one in-process call."""
+is between two empty or two full lists.  The host form may select in place (selected == candidates).  Every GPU step is one in-process call."""
 import numpy as np
 import pytest
 
@@ -170,3 +170,19 @@ def test_the_oracles_cornell_moments(trt, orc):
         assert 0 < len(want) < 19 * 13
         cand = np.random.default_rng(3).permutation(19 * 13).astype(np.uint32)
         host_and_device(trt, s, m, 8, 4, rel_tol, abs_tol, cand, len(cand), ("cornell, shuffled", rel_tol, abs_tol))
+
+
+def test_the_host_form_may_select_in_place(trt, sums):
+    """selected == candidates: the host form works on device copies of its own, so a list may be shrunk in place (the device form refuses
+    overlapping lists: tests/test_pixels_abi.py).  Three chunks of the second scan level long, so that many tiles write slots other tiles own."""
+    import ctypes as C
+    s, m = sums
+    cand = np.random.default_rng(5).permutation(len(s)).astype(np.uint32)[:LENGTHS[-1]]
+    want = restated_select(s, m, 16, 4, 0.02, 0.0, cand)
+    assert 0 < len(want) < len(cand)
+    buf = cand.copy()
+    count = C.c_uint32(0xCDCDCDCD)
+    trt._lib.check(trt.lib.trt_select_pixels(s.ctypes.data, m.ctypes.data, len(s), 16, 4, buf.ctypes.data, len(buf), 0.02, 0.0, buf.ctypes.data,
+                                             C.byref(count)))
+    assert count.value == len(want) and np.array_equal(buf[:len(want)], want), "selecting in place on the host"
+    assert np.array_equal(buf[len(want):], cand[len(want):]), "written behind the selection"

@@ -260,3 +260,71 @@ def test_pixels_launch_plan_invariants_on_every_scene_and_option_of_the_gpu_test
     assert shapes == PIXELS_KERNEL_SHAPES, sorted(shapes)
     assert {(1, WALK_LDS_TREE), (1, WALK_LOCK_STEP), (0, WALK_LOCK_STEP)} <= routes, sorted(routes)
     assert lengthened > 0                                                    # 2^24 entries lengthen the runs of some shape
+
+
+def test_the_gpu_tests_case_lists_reach_every_kernel_and_every_route_to_the_fallback(trt):
+    """tests/test_gpu_pixels.py renders its SCENES with default options and tests/test_gpu_pixels_walks.py its CASES; passed through the
+    plan at the image sizes those modules use, the union must launch all six instantiations of kPixelsKernels and reach the register-slot
+    fallback from an LDS tree plan, from a lock-step plan in LDS and from a lock-step plan in global memory - so that dropping a case
+    there, or a later change to the plan, cannot leave a kernel or a route unrun without this test failing."""
+    import test_gpu_pixels as P
+    import test_gpu_pixels_walks as PW
+    import test_gpu_queries as G
+    import walk_ray_cases as W
+    cases = [(name, {}, G.DEFAULT_SHAPES[name]) for name in P.SCENES] + list(PW.CASES)
+    assert len(cases) == len(P.SCENES) + len(G.OTHER_WALKS) + 2 and [c[0] for c in cases[-2:]] == ["degenerate", "nonfinite"]
+    shapes, routes, worlds = set(), set(), {}
+    for name, options, shape in cases:
+        if name not in worlds:
+            worlds[name] = trt.world_from_description(W.scene(trt, name))[0]
+        host_options = {k: v for k, v in options.items() if k != "on_device"}           # (both compilers give the same bytes: tests/test_gpu_scene_build.py)
+        sc = worlds[name].get_bvh(**host_options) if host_options else worlds[name].get_bvh()
+        for w, h in PW.SIZES:
+            q = sc.pixels_plan(w * h, 256)
+            assert G.plan_shape(q) == shape, (name, options, G.plan_shape(q), shape)
+            shapes.add(shape[:3])
+            if q["fallback"]:
+                routes.add((q["scene_mode"], q["streamed_walk"]))
+    # the default compilations alone miss the register-slot walk from global memory: the reason tests/test_gpu_pixels_walks.py exists
+    assert {G.DEFAULT_SHAPES[name][:3] for name in P.SCENES} == PIXELS_KERNEL_SHAPES - {(0, 5, 256)}
+    assert shapes == PIXELS_KERNEL_SHAPES, sorted(shapes)
+    assert {(1, WALK_LDS_TREE), (1, WALK_LOCK_STEP), (0, WALK_LOCK_STEP)} <= routes, sorted(routes)
+
+
+def test_the_device_selection_refuses_overlapping_lists_before_any_device_work(trt):
+    """select_write_kernel cannot compact in place, so trt_select_pixels_device returns TRT_ERR_INVALID_ARG when the n words at d_selected
+    overlap the n words at d_candidates: equal pointers, a partial overlap on either side.  Adjacent ranges pass this check and reach the
+    next one (here made to fail: a scratch that is too small - host pointers are handed in, so no call may get as far as a launch)."""
+    n = 300
+    s = np.full((n, 3), 0.5, np.float32)
+    buf = np.full(3 * n, 9, np.uint32)
+    count = C.c_uint32(77)
+    scratch = np.zeros(64, np.uint32)
+    assert trt.select_scratch_bytes(n) <= 4 * len(scratch)
+
+    def call(cand_word, sel_word, scr_bytes=4 * len(scratch)):
+        return trt.lib.trt_select_pixels_device(s.ctypes.data, s.ctypes.data, n, 8, 4, buf.ctypes.data + 4 * cand_word, n, 0.1, 0.0,
+                                                buf.ctypes.data + 4 * sel_word, C.byref(count), scratch.ctypes.data, scr_bytes, None)
+
+    for cand_word, sel_word in ((n, n), (n, n + 1), (n, n - 1), (n, 2 * n - 1), (n, 1), (0, n - 1), (n - 1, 0)):
+        _invalid(trt, call(cand_word, sel_word))
+        assert "overlap" in trt.lib.trt_last_error().decode(), (cand_word, sel_word)
+        _invalid(trt, call(cand_word, sel_word, scr_bytes=0))              # ... and before the scratch is looked at
+        assert "overlap" in trt.lib.trt_last_error().decode(), (cand_word, sel_word)
+    for cand_word, sel_word in ((n, 2 * n), (n, 0), (0, n), (0, 2 * n)):
+        _invalid(trt, call(cand_word, sel_word, scr_bytes=0))
+        assert "scratch" in trt.lib.trt_last_error().decode(), (cand_word, sel_word)
+    # candidates NULL (the pixels 0 .. n-1) has nothing to overlap; n == 0 reads and writes no list
+    _invalid(trt, trt.lib.trt_select_pixels_device(s.ctypes.data, s.ctypes.data, n, 8, 4, None, n, 0.1, 0.0, buf.ctypes.data, C.byref(count),
+                                                   scratch.ctypes.data, 0, None))
+    assert "scratch" in trt.lib.trt_last_error().decode()
+    if trt.lib.trt_device_count() == 0:
+        assert trt.lib.trt_select_pixels_device(None, None, 0, 8, 4, buf.ctypes.data, 0, 0.1, 0.0, buf.ctypes.data, C.byref(count), None, 0,
+                                                None) == trt._lib.TRT_OK
+        # without a device the well-formed adjacent call gets as far as the device check
+        assert call(n, 2 * n) == trt._lib.ERR_NO_DEVICE
+    assert count.value == 77 and (buf == 9).all()
+    with pytest.raises(trt.TinyRTError) as e:
+        trt.select_pixels_device(s.ctypes.data, s.ctypes.data, n, 8, 4, n, 0.1, 0.0, buf.ctypes.data, C.addressof(count), scratch.ctypes.data,
+                                 4 * len(scratch), d_candidates_ptr=buf.ctypes.data)
+    assert e.value.code == trt._lib.ERR_INVALID_ARG

@@ -579,7 +579,9 @@ def select_scratch_bytes(n):
 def select_pixels_device(d_accum_ptr, d_moment2_ptr, npixels, samples_per_pixel, samples_done, n, rel_tol, abs_tol, d_selected_ptr, d_count_ptr,
                          d_scratch_ptr, scratch_bytes, d_candidates_ptr=0, stream_ptr=0):
     """Enqueue select_pixels() on buffers already in HBM (device pointers as integers): n candidates (d_candidates_ptr 0: pixel i), up to n
-    indices and a uint32 count out; nothing is allocated, `d_scratch_ptr` holds at least select_scratch_bytes(n) bytes; asynchronous."""
+    indices and a uint32 count out; nothing is allocated, `d_scratch_ptr` holds at least select_scratch_bytes(n) bytes; asynchronous.
+    The n words at d_selected_ptr must not overlap the n words at d_candidates_ptr (TinyRTError, ERR_INVALID_ARG): the kernels cannot
+    compact in place - keep two lists and swap them.  (select_pixels, the host form, may be given its candidates' own array.)"""
     check(lib.trt_select_pixels_device(C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), int(npixels), int(samples_per_pixel), int(samples_done),
                                        C.c_void_p(d_candidates_ptr), int(n), float(rel_tol), float(abs_tol), C.c_void_p(d_selected_ptr),
                                        C.c_void_p(d_count_ptr), C.c_void_p(d_scratch_ptr), int(scratch_bytes),

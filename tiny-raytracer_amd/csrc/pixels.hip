@@ -505,6 +505,13 @@ int trt_select_pixels_device(const float* d_accum, const float* d_moment2, uint3
                              void* d_scratch, uint64_t scratch_bytes, void* stream) {
     int rc = trt::select_check(d_accum, d_moment2, samples_per_pixel, samples_done, n, d_selected, d_count);
     if (rc != TRT_OK) return rc;
+    if (n > 0u && d_candidates) {
+        // select_write_kernel writes selected[offset + rank] while other workgroups still read candidates[i]: offset + rank <= i, but that
+        // slot may be a candidate of an earlier tile that has not been read yet - compacting in place is a race, so overlap is refused
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(d_candidates), s0 = reinterpret_cast<uintptr_t>(d_selected), bytes = (uintptr_t)n * 4u;
+        if (c0 < s0 ? s0 - c0 < bytes : c0 - s0 < bytes)
+            return trt::query_fail(TRT_ERR_INVALID_ARG, "d_selected overlaps d_candidates: the device form does not select in place");
+    }
     if (n > 0u && (!d_scratch || scratch_bytes < trt_select_scratch_bytes(n)))
         return trt::query_fail(TRT_ERR_INVALID_ARG, "scratch is null or smaller than trt_select_scratch_bytes(n)");
     if (n == 0u) {
