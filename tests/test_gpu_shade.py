@@ -1,0 +1,208 @@
+"""shade_hit and the vector helpers it rests on, case by case against the oracle - every word, no tolerance.
+
+tests/native/shade_cases.hip (built here for gfx950 with the library's own CXXFLAGS; one build - shading does not depend on the
+box-loop switch) loads each case of tests/shade_cases.py into a Path, calls the product's shade_hit<MODE, STATS, LAZY> and writes
+back the 15 words of the Path, `ended` and, with STATS, the five shade counters; a second kernel runs normalized, ray_new, reflect,
+refract, near_zero and ray_at on a list of vectors.  Instantiations: <LDS, false, false>, <LDS, false, true>, <LDS, true, false>,
+<GLOBAL, false, false>, <GLOBAL, false, true>; the GLOBAL forms read the same 32-primitive scene through SceneAcc<MODE_GLOBAL> (the
+accessor allows it: same element offsets), so "the zoo from global memory" needs no padding spheres.  The LAZY forms run only the
+cases whose incoming colour is +0 on the scene with lazy_color set (the harness refuses anything else).  Each scene's list goes in
+twice: one wave takes the whole shuffled list 64 cases at a time (its lanes hold different material kinds), then waves with lists
+of 1, 63, 64 and 65 cases from a second shuffle; every copy must equal the expectation.
+
+NaN words: a shade record is compared by its bits throughout - the 0/0 of a u3 = 0 draw and the inf * 0 of an infinite attenuation
+give the oracle's bit patterns on gfx950.  The vector rows also feed NaN and inf INPUTS to the helpers, where x86-64 and gfx950
+propagate payloads and signs differently (which operand's NaN survives an addition; inf - inf): there, float words that are NaN on
+BOTH sides compare by class, every other word by its bits, and the count of such words is printed per helper.
+
+Negative control: the zoo with every dielectric index moved one float up, against the expectation of the unmoved scene - no case
+on another material may differ, and of the total-reflection straddle cases of the back-face indices (ri = index: 1.5, 2.4) every
+one that can differ must: those with ri * sinv == 1.0 (now total reflection: no draw) and those below 1.0 that refract (eta moved).
+The others cannot: above 1.0 both scenes reflect without a draw, below 1.0 with a draw of 0 both reflect after one draw, and
+reflect() does not read the index; a front-face ri = 1 / index need not move at all.  The answers also equal the oracle's for the
+moved scene word for word.
+
+Measured on an MI355X (seed 1):
+  * 1436 cases per scene (1024 generic; dielectric_scaled_dir 140, dielectric_tir_straddle 34, dielectric_draw_edge 32, front_face_sphere 26,
+    extreme_quad 24 (12 on the tiny, 12 on the huge quad), extreme_quad_grazing 12,
+    metal_incidence 20, metal_below_surface 18, dielectric_cos_above_one 16, front_face_quad 16, miss 16, dielectric_grazing 10, metal_tiny_dir 9,
+    front_face_far 8, light 8, lam_not_near_zero 5, lam_u3_zero 4, lam_domain_edge 4, generic_big_inside 4, lam_zero_sum 3, lam_tiny_sum 3), each
+    twice in the lists: 2872 answers per carried instantiation, 2344 per LAZY one on `zoo` (none on `hot`), 43 080 answers over three scene
+    runs x five instantiations, and 8349 vectors.
+  * 0 differing words in every instantiation on both scenes and in the vector helpers; there 2616 NaN words were compared by class
+    (normalized 270, ray_new 270, reflect 1258, refract 818; 25 of them in rows with finite inputs, where 2^39-sized operands overflow to
+    inf - inf); LAZY == carried, LDS == global; counters (shade, lambertian, metal, dielectric, light) 2840, 618, 670, 1018, 534.
+  * control: 542 of 2872 answers differ, all on dielectrics, 32 of the 68 straddle answers among them; == the oracle on the moved scene.
+  * this file 3.6 s (the harness builds in 2.3 s and runs in 0.3 s) of the 170 s that the whole `-m gpu` suite (868 tests) takes with it: 2 %.
+"""
+import os
+import re
+import subprocess
+import time
+
+import numpy as np
+import pytest
+
+import shade_cases as S
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tiny-raytracer_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+VARIANTS = ["lds_carried", "lds_lazy", "lds_stats", "global_carried", "global_lazy"]
+RUNS = ["zoo", "hot", "control"]
+
+
+def library_cxxflags():
+    """CXXFLAGS of the library's Makefile: the harness is built with the flags shade_hit is built with."""
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        m = re.search(r"^CXXFLAGS\s*\?=\s*(.+)$", f.read(), re.M)
+    assert m, "CXXFLAGS not found in the library's Makefile"
+    flags = m.group(1).split()
+    assert "-ffp-contract=off" in flags and "-O3" in flags, flags
+    return flags
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("shade_cases") / "shade_cases")
+    t0 = time.time()
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", *library_cxxflags(), "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "native", "shade_cases.hip"),
+                        os.path.join(CSRC, "scene_host.cpp")], timeout=900)
+    assert r.returncode == 0, "the harness does not compile"
+    print(f"\nharness built in {time.time() - t0:.1f} s")
+    return exe
+
+
+@pytest.fixture(scope="module")
+def results(orc, harness, tmp_path_factory):
+    """One child process for everything, under its own time limit; a non-zero exit fails everything and nothing is run again.
+    run name -> dict(sc, cases, order, exp [file position, 16], out {variant: [file position, 21]}); 'vec' -> (cases, expectation, out)."""
+    d = tmp_path_factory.mktemp("shade")
+    res, cmd = {}, [harness]
+    for run in RUNS:
+        scene = "zoo" if run == "control" else run
+        if run == "control":
+            sc, cases, order, tasks, exp = (res["zoo"][k] for k in ("sc", "cases", "order", "tasks", "exp"))
+            S.write_scene_file(str(d / "control.scene"), S.moved_indices(sc.desc))
+        else:
+            sc = S.Scene(scene)
+            cases = S.case_list(orc, sc)
+            order, tasks = S.wave_lists(len(cases))
+            exp = S.expectations(orc, sc, cases)[order]
+            S.write_scene_file(str(d / f"{run}.scene"), sc.desc)
+        S.write_case_file(str(d / f"{run}.cases"), sc, cases, order, tasks)
+        res[run] = dict(sc=sc, cases=cases, order=order, tasks=tasks, exp=exp)
+        cmd += ["run", str(d / f"{run}.scene"), str(d / f"{run}.cases"), str(d / f"{run}.bin"), str(d / f"{run}.txt")]
+    vc = S.vector_cases()
+    S.write_vector_file(str(d / "vec.in"), vc)
+    cmd += ["vec", str(d / "vec.in"), str(d / "vec.bin")]
+    t0 = time.time()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    print(f"\nharness ran in {time.time() - t0:.2f} s: {r.stdout.strip()}")
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    for run in RUNS:
+        with open(d / f"{run}.txt") as f:
+            lines = f.read().split("\n")
+        layout = dict(kv.split("=") for kv in lines[0].split()[1:])
+        assert [l.split()[1] for l in lines[1:] if l.startswith("variant ")] == VARIANTS
+        assert int(layout["lazy_color"]) == (0 if run == "hot" else 1) and int(layout["n_spheres"]) + int(layout["n_quads"]) == 32
+        words = np.fromfile(d / f"{run}.bin", np.uint32).reshape(len(VARIANTS), len(res[run]["order"]), S.OUT_WORDS)
+        res[run]["out"] = dict(zip(VARIANTS, words))
+        res[run]["lazy_ok"] = np.array([c["lazy_ok"] for c in res[run]["cases"]])[res[run]["order"]]
+    res["vec"] = (vc, S.vector_expectation(orc, vc), np.fromfile(d / "vec.bin", np.uint32).reshape(len(vc), S.VEC_OUT_WORDS))
+    return res
+
+
+def describe(res, pos):
+    c = res["cases"][res["order"][pos]]
+    return (int(res["order"][pos]), c["cls"], c["geo"])
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("run", ["zoo", "hot"])
+def test_every_word_equals_the_oracle(results, run, variant):
+    res = results[run]
+    got, exp = res["out"][variant][:, :16], res["exp"]
+    rows = res["lazy_ok"] if variant.endswith("_lazy") else np.ones(len(exp), bool)
+    if variant.endswith("_lazy"):
+        assert (res["out"][variant][~rows] == 0xCDCDCDCD).all()              # the LAZY forms leave the other cases alone
+        assert rows.any() == (run == "zoo")
+    bad, nan_bits = S.differing_words(got[rows], exp[rows], np.zeros(16, bool))       # by the bits, NaN words included
+    per_class = {}
+    for p in np.flatnonzero(rows):
+        per_class[res["cases"][res["order"][p]]["cls"]] = per_class.get(res["cases"][res["order"][p]]["cls"], 0) + 1
+    print(f"\n{run} {variant}: {int(rows.sum())} answers ({len(res['cases'])} cases, each at least twice), {int(bad.sum())} differing words; "
+          f"per class: {per_class}")
+    where = np.flatnonzero(rows)[np.flatnonzero(bad.any(axis=1))]
+    assert len(where) == 0, (run, variant, f"{len(where)} answers differ", [describe(res, p) for p in where[:8]], got[where[:3]], exp[where[:3]])
+    # every copy of a case gets the same bits
+    n = len(res["cases"])
+    first, second = np.argsort(res["order"][:n]), n + np.argsort(res["order"][n:])
+    both = rows[first] & rows[second]
+    assert np.array_equal(res["out"][variant][first][both], res["out"][variant][second][both])
+
+
+@pytest.mark.parametrize("run", ["zoo", "hot"])
+def test_lazy_equals_carried_and_lds_equals_global(results, run):
+    out, rows = results[run]["out"], results[run]["lazy_ok"]
+    assert np.array_equal(out["lds_carried"], out["global_carried"])
+    assert np.array_equal(out["lds_lazy"], out["global_lazy"])
+    assert np.array_equal(out["lds_lazy"][rows], out["lds_carried"][rows])
+    assert np.array_equal(out["lds_stats"][:, :16], out["lds_carried"][:, :16])
+
+
+@pytest.mark.parametrize("run", ["zoo", "hot"])
+def test_shade_counters_equal_the_case_counts(results, run):
+    res = results[run]
+    kinds = np.array([S.kind_of_case(res["sc"], c) for c in res["cases"]])[res["order"]]
+    ctr = res["out"]["lds_stats"][:, 16:21].astype(np.int64)
+    want = np.stack([kinds >= 0] + [kinds == k for k in range(4)], axis=1).astype(np.int64)
+    print(f"\n{run}: shade counters {ctr.sum(axis=0).tolist()} (shade, lambertian, metal, dielectric, light)")
+    assert np.array_equal(ctr, want)
+    assert (res["out"]["lds_carried"][:, 16:21] == 0).all()
+
+
+def test_vector_helpers_equal_the_oracle(results):
+    vc, exp, got = results["vec"]
+    bad, nan_bits = S.differing_words(got, exp, S.VEC_FLOAT_WORDS)
+    names = ["normalized"] * 3 + ["ray_new.o"] * 3 + ["ray_new.d"] * 3 + ["reflect"] * 3 + ["refract"] * 3 + ["near_zero"] + ["ray_at"] * 3 + ["pad"]
+    by_helper = {k: int(nan_bits[:, [i for i, n in enumerate(names) if n == k]].sum()) for k in dict.fromkeys(names)}
+    finite = np.isfinite(vc).all(axis=1)
+    print(f"\nvector helpers: {len(vc)} vectors, {int(bad.sum())} differing words, {int(nan_bits.sum())} NaN words compared by class: {by_helper}; "
+          f"{int(nan_bits[finite].sum())} of them in rows whose inputs are all finite")
+    rows = np.flatnonzero(bad.any(axis=1))
+    assert len(rows) == 0, (f"{len(rows)} vectors differ", [(int(r), [names[k] for k in np.flatnonzero(bad[r])], vc[r].tolist()) for r in rows[:6]])
+
+
+def test_control_moved_indices_are_seen_by_the_straddles_alone(results, orc):
+    res = results["control"]
+    got, exp = res["out"]["lds_carried"][:, :16], res["exp"]
+    bad = (got != exp).any(axis=1)
+    sc = res["sc"]
+    cases = [res["cases"][i] for i in res["order"]]
+    kinds = np.array([S.kind_of_case(sc, c) for c in cases])
+    names = np.array([sc.desc["materials"][sc.geo_mat[c["geo"]]][0] if c["geo"] >= 0 else "" for c in cases])
+    straddle = np.array([c["cls"] == "dielectric_tir_straddle" for c in cases])
+    print(f"\ncontrol: {int(bad.sum())} answers differ, {int((bad & straddle).sum())} of {int(straddle.sum())} straddle answers; by material:",
+          {str(m): int((bad & (names == m)).sum()) for m in sorted(set(names[bad]))})
+    assert not bad[kinds != S.DIELECTRIC].any()
+    # the back-face indices (ri = index): every straddle copy that CAN differ does - the product 1.0 becomes total reflection (no draw:
+    # the rng words change even where both reflect), and below 1.0 a refracted ray bends by the moved index.  The others cannot: above
+    # 1.0 both scenes reflect totally without a draw, and below 1.0 with a draw of 0 both reflect after one draw - reflect() does not
+    # read the index.  (Front face: ri = 1 / index, which one float in the index need not move.)
+    must = 0
+    for p in np.flatnonzero(straddle & ((names == "die15") | (names == "die24"))):
+        tr = {}
+        S.restate(orc, sc, cases[p], 0, tr)
+        if tr["prod"] == np.float32(1.0) or (tr["prod"] < np.float32(1.0) and not tr["do_reflect"]):
+            must += 1
+            assert bad[p], (describe(res, p), tr["prod"], tr["do_reflect"])
+        elif tr["prod"] > np.float32(1.0) or tr["do_reflect"]:
+            assert not bad[p], (describe(res, p), tr["prod"])
+    assert must >= 12                                                             # (3 per index in the list, each copied at least twice)
+    # and the device follows the moved scene to the bit: exactly the oracle's answers for it
+    moved = S.Scene("zoo", desc=S.moved_indices(sc.desc))
+    exp_moved = S.expectations(orc, moved, res["cases"])[res["order"]]
+    assert np.array_equal(got, exp_moved)
+    assert np.array_equal(bad, (exp_moved != exp).any(axis=1))
