@@ -59,6 +59,30 @@ TRT_DEV float div_by_refined_rcp(float a, float b, float r1) {
     const float e2 = __builtin_fmaf(-b, q1, a);
     return __builtin_fmaf(e2, r1, q1);
 }
+// The reciprocal that the sequence above takes: the hardware's estimate and one Newton step, as hipcc's own expansion of a / b forms it.
+TRT_DEV float refined_rcp(float b) {
+    const float r0 = __builtin_amdgcn_rcpf(b);
+    const float e = __builtin_fmaf(-b, r0, 1.0f);
+    return __builtin_fmaf(e, r0, r0);
+}
+// The primary ray's image coordinates (pointgen.rs:41-43): u = nu / (width - 1), v = nv / (height - 1) with nu = x + random, nv = y + random.
+// The two denominators are the same for every ray of a launch.  For a width and a height of 2 or more they are floats in [1, 2^32] and
+// a numerator is +0 (column or row 0 with a draw of 0) or lies in [2^-23, 2^32]: inside div_by_refined_rcp's range, so each quotient is
+// the five operations on a reciprocal refined once per denominator (loop-invariant where the camera is).  A numerator of +0 needs no
+// case of its own: q0 = 0 * r1 = +0, both residuals are fma(-b, +0, +0) = +0 and both corrections fma(+0, r1, +0) = +0, which is 0 / b.
+// A 1-wide or 1-high image divides by zero (inf, or NaN for 0 / 0, as the reference does): both quotients are then the plain divisions.
+// The choice reads the image size only, so it is the same for every lane.  tests/native/unit_math_check.cpp compares every numerator that
+// exists at five widths with `/`.
+TRT_COLD void pixel_uv_plain(float dw, float dh, float nu, float nv, float& u, float& v) { u = nu / dw; v = nv / dh; }
+TRT_DEV void pixel_uv(uint32_t width, uint32_t height, float nu, float nv, float& u, float& v) {
+    const float dw = (float)(width - 1u), dh = (float)(height - 1u);
+    if (__builtin_expect(width >= 2u && height >= 2u, 1)) {
+        u = div_by_refined_rcp(nu, dw, refined_rcp(dw));
+        v = div_by_refined_rcp(nv, dh, refined_rcp(dh));
+    } else {
+        pixel_uv_plain(dw, dh, nu, nv, u, v);
+    }
+}
 // sqrtf likewise: hipcc scales a tiny argument by 2^32, takes v_sqrt_f32, steps the estimate one ulp down / up with an FMA residual
 // each, scales back and passes 0 / inf through by a class test (16 instructions).  For x in [2^-80, 2^81) the scaling and the
 // class test are identities; the 9 instructions that remain give sqrtf's bits for EVERY float in that range
@@ -135,6 +159,28 @@ TRT_DEV void dm_sincos(float x, float& sn, float& cs) {
     cs = c;
 }
 
+// dm_sincos for 0 <= x < 8192 (+0 included, -0 not): the sampler's theta = 2 pi u lies in [0, 6.29) and its phi = acos(1 - 2u) in
+// [0, pi].  On that domain fabs(x) is x, the |x| < 8192 exit is never taken and the closing `x < 0 ? -s : s` selects s: the three
+// steps are identities and are left out; everything else is dm_sincos's sequence, operation for operation.
+// tests/native/unit_math_check.cpp (host) and unit_math_exhaustive.hip (device) compare the two on every theta and phi there is.
+TRT_DEV void dm_sincos_nonneg(float x, float& sn, float& cs) {
+    const float FOPI = 1.27323954473516f;
+    const float DP1 = 0.78515625f, DP2 = 2.4187564849853515625e-4f, DP3 = 3.77489497744594108e-8f;
+    uint32_t j = (uint32_t)(x * FOPI);
+    j = (j + 1u) & ~1u;
+    float y = (float)j;
+    float r = __builtin_fmaf(-y, DP3, __builtin_fmaf(-y, DP2, __builtin_fmaf(-y, DP1, x)));
+    float z = r * r;
+    float ps = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f) * z, r, r);
+    float pc = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f) * z, z,
+                              __builtin_fmaf(-0.5f, z, 1.0f));
+    uint32_t q = (j >> 1) & 3u;
+    float s = (q & 1u) ? pc : ps;
+    float c = (q & 1u) ? ps : pc;
+    sn = (q & 2u) ? -s : s;
+    cs = ((q + 1u) & 2u) ? -c : c;
+}
+
 TRT_DEV float dm_asin_poly(float z) {
     return __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(__builtin_fmaf(4.2163199048e-2f, z, 2.4181311049e-2f), z, 4.5470025998e-2f), z,
                                          7.4953002686e-2f), z, 1.6666752422e-1f);
@@ -152,6 +198,21 @@ TRT_DEV float dm_acos(float x) {
     const float z = big ? 0.5f * (1.0f - ax) : x * x;
     // z <= 0.25; it is 0 for x = +-1 and tiny next to it: the short sqrt applies from 2^-80 up
     const float w = big ? (__builtin_expect(z >= 8.271806125530277e-25f, 1) ? sqrt_in_range(z) : sqrt_plain(z)) : x;
+    const float r = __builtin_fmaf(dm_asin_poly(z) * z, w, w);
+    const float two_r = r + r;
+    return big ? (x > 0.0f ? two_r : PI_F - two_r) : PIO2_F - r;
+}
+
+// dm_acos for x = 1 - 2u, u = k 2^-23 (k < 2^23): x is the exact 1 - k 2^-22, in (-1, 1].  In the outer ranges z = (1 - |x|) / 2 is
+// then 0 (x = 1 only) or a multiple of 2^-23, never a value in (0, 2^-80) - and for z = 0 sqrt_in_range returns +0 like sqrtf does
+// (the estimate is +0, the step down is a NaN whose comparison fails, the step up has the residual +0, which is not > 0).  So the
+// `z >= 2^-80` choice between the two square roots always gives what sqrt_in_range gives, and it is left out with sqrt_plain.
+TRT_DEV float dm_acos_unit(float x) {
+    const float PI_F = 3.14159265358979323846f, PIO2_F = 1.57079632679489661923f;
+    const float ax = __builtin_fabsf(x);
+    const bool big = ax > 0.5f;
+    const float z = big ? 0.5f * (1.0f - ax) : x * x;
+    const float w = big ? sqrt_in_range(z) : x;
     const float r = __builtin_fmaf(dm_asin_poly(z) * z, w, w);
     const float two_r = r + r;
     return big ? (x > 0.0f ? two_r : PI_F - two_r) : PIO2_F - r;
@@ -179,6 +240,24 @@ TRT_DEV float dm_cbrt(float x) {
     y = __builtin_fmaf(-THIRD * e, r2, y);
     y = y * scale;
     return __uint_as_float(__float_as_uint(y) | sign);
+}
+
+// dm_cbrt for x == +0 or 2^-23 <= x < 1 (every u = k 2^-23).  x is not negative, infinite, NaN or subnormal: the sign is 0 and
+// OR-ing it back changes nothing, the inf / NaN half of the early return and the subnormal rescale are never taken, and `y * scale`
+// multiplies by 1.  They are left out.  The zero test stays (the Newton steps overflow to 0 * inf for a = 0).
+TRT_DEV float dm_cbrt_unit(float x) {
+    const float THIRD = 0.333333343267440796f, FOUR_THIRDS = 1.33333337306976318f;
+    const uint32_t ua = __float_as_uint(x);
+    if (ua == 0u) return x;
+    float r = __uint_as_float(0x54a21d2au - ua / 3u);
+    const float a3 = x * THIRD;
+    r = r * __builtin_fmaf(-a3, r * r * r, FOUR_THIRDS);
+    r = r * __builtin_fmaf(-a3, r * r * r, FOUR_THIRDS);
+    const float r2 = r * r;
+    float y = x * r2;
+    const float hi = y * y, lo = __builtin_fmaf(y, y, -hi);
+    const float e = __builtin_fmaf(hi, y, -x) + lo * y;
+    return __builtin_fmaf(-THIRD * e, r2, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -225,6 +304,24 @@ TRT_DEV V3 random_in_unit_sphere(Rng& g) {
     float sin_phi, cos_phi, sin_theta, cos_theta;
     dm_sincos(phi, sin_phi, cos_phi);
     dm_sincos(theta, sin_theta, cos_theta);
+    float x = r * sin_phi * cos_theta;
+    float y = r * sin_phi * sin_theta;
+    float z = r * cos_phi;
+    return v3(x, y, z);
+}
+// random_in_unit_sphere with the unit-domain forms above: u1, u2, u3 are rng_random's k 2^-23, so theta = 2 pi u1 is in [0, 6.29),
+// 1 - 2 u2 is dm_acos_unit's argument, phi is in [0, pi] and u3 is dm_cbrt_unit's.  Same draws, same bits (compared on 2^22 generator
+// states besides the per-function checks); this is the one the path kernels call (rt_path.h shade_hit).
+TRT_DEV V3 random_in_unit_sphere_unit(Rng& g) {
+    float u1 = rng_random(g);
+    float u2 = rng_random(g);
+    float u3 = rng_random(g);
+    float theta = (2.0f * 3.14159265358979323846f) * u1;
+    float phi = dm_acos_unit(1.0f - 2.0f * u2);
+    float r = dm_cbrt_unit(u3);
+    float sin_phi, cos_phi, sin_theta, cos_theta;
+    dm_sincos_nonneg(phi, sin_phi, cos_phi);
+    dm_sincos_nonneg(theta, sin_theta, cos_theta);
     float x = r * sin_phi * cos_theta;
     float y = r * sin_phi * sin_theta;
     float z = r * cos_phi;

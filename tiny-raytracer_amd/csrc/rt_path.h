@@ -1155,7 +1155,7 @@ TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t
         // Both draw ONE point in the unit sphere (three random numbers, acos, cbrt, two sincos: the expensive part of a shade) and use
         // it differently: evaluated once for the lanes of either kind - as two branches a wave that holds both kinds (nearly every wave
         // of the random-spheres scene) ran that code twice, the second time for a handful of metal lanes.  Same draws, same operations.
-        const V3 in_sphere = random_in_unit_sphere(p.rng);
+        const V3 in_sphere = random_in_unit_sphere_unit(p.rng);               // rt_device.h: the general one, less its identities
         if (kind == TRT_LAMBERTIAN) {                                  // lambertian.rs:16-22: normal + random_unit_vector (vec3extend.rs:32-34)
             dir = normal + normalized(in_sphere);
             if (near_zero(dir)) dir = normal;
@@ -1187,8 +1187,10 @@ TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t
 
 // SamplePointGenerator::generate body (pointgen.rs:41-43) + Camera::get_ray (camera.rs:58-66)
 TRT_DEV Ray primary_ray(const CameraDev& cam, uint32_t x, uint32_t y, Rng& rng) {
-    float u = ((float)x + rng_random(rng)) / (float)(cam.width - 1u);
-    float v = ((float)y + rng_random(rng)) / (float)(cam.height - 1u);
+    const float nu = (float)x + rng_random(rng);
+    const float nv = (float)y + rng_random(rng);
+    float u, v;
+    pixel_uv(cam.width, cam.height, nu, nv, u, v);                    // nu / (width - 1), nv / (height - 1): rt_device.h
     float px, py;
     random_in_unit_disk(rng, px, py);
     V3 pos = v3(cam.pos[0], cam.pos[1], cam.pos[2]);

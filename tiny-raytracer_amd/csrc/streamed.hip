@@ -167,12 +167,39 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
 // ------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kPoolDwords = 9u;         // origin, direction, rng state, radiance slot
 
+// The streamed kernels' argument list as the kernel-argument segment lays it out (every argument at its natural alignment, in order).
+// stream_pool_kernel reads the arguments that only its refill branch needs - the camera, the band layout, the tile arithmetic: ~40 words,
+// used once per ~7 rounds - from that segment INSIDE the branch instead of taking them from the by-value parameters: those are loaded at
+// kernel entry and stay live in SGPRs over the whole round loop, where the walk pins s[36:51] besides, and the compiler moved the overflow
+// through a VGPR's lanes (v_writelane / v_readlane, a vector instruction each) on the path every round takes.  The empty asm makes the
+// pointer opaque, so the loads (scalar loads, wave-uniform) can neither be merged with the entry loads nor hoisted out of the branch.
+struct StreamKernargs {
+    SceneDev scd; CameraDev cam; RenderArgs ra;
+    float* colors; uint32_t* batch_counter; unsigned long long* counters;
+    uint32_t tiles_x, n_tiles, n_batches, batch_spp;
+    const float4* leaf_list; const uint4* nodes16;
+};
+struct StreamTileArgs { uint32_t tiles_x, n_tiles, n_batches, batch_spp; };
+template <class T>
+TRT_DEV T kernarg_reload(size_t offset) {
+    static_assert(sizeof(T) % 4 == 0, "whole words");
+    typedef const __attribute__((address_space(4))) uint32_t* WordPtr;
+    WordPtr w = (WordPtr)__builtin_amdgcn_kernarg_segment_ptr() + offset / 4;
+    asm volatile("" : "+s"(w));
+    uint32_t words[sizeof(T) / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(T) / 4; i++) words[i] = w[i];
+    T v;
+    __builtin_memcpy(&v, words, sizeof(T));
+    return v;
+}
+
 template <int MODE, bool STATS, int MINW = 1, int THREADS = 256, int WALK = WALK_RUNTIME, bool LAZY = false>
-__global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd, CameraDev cam, RenderArgs ra,
-                                                                           float* __restrict__ colors,
-                                                                           uint32_t* __restrict__ batch_counter,
+__global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd, CameraDev cam_entry, RenderArgs ra,
+                                                                           float* __restrict__ colors_entry,
+                                                                           uint32_t* __restrict__ batch_counter_entry,
                                                                            unsigned long long* __restrict__ counters,
-                                                                           uint32_t tiles_x, uint32_t n_tiles, uint32_t n_batches, uint32_t batch_spp,
+                                                                           uint32_t tiles_x_entry, uint32_t n_tiles_entry, uint32_t n_batches_entry, uint32_t batch_spp_entry,
                                                                            const float4* __restrict__ leaf_list,
                                                                            const uint4* __restrict__ nodes16) {
     stage_scene_to_lds<MODE>(scd);
@@ -180,7 +207,6 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
-    const uint32_t n_spp = ra.sample_end - ra.sample_begin;
     char* const lds_tail = reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u);
     float2* const leaf_stack = reinterpret_cast<float2*>(lds_tail) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane;
     // the pool: field f of entry e at pool[f * 64 + e]
@@ -209,7 +235,14 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
             if (need == 0ull) break;
             if (pool_count == 0u) {
                 if (exhausted) break;
+                // refill-only arguments, read here and not carried through the rounds (kernarg_reload above)
+                const CameraDev cam = kernarg_reload<CameraDev>(offsetof(StreamKernargs, cam));
+                const RenderArgs rr = kernarg_reload<RenderArgs>(offsetof(StreamKernargs, ra));
+                const StreamTileArgs ta = kernarg_reload<StreamTileArgs>(offsetof(StreamKernargs, tiles_x));
+                const uint32_t n_spp = rr.sample_end - rr.sample_begin;
                 if (cursor >= items_per_batch) {
+                    uint32_t* const batch_counter = kernarg_reload<uint32_t*>(offsetof(StreamKernargs, batch_counter));
+                    const uint32_t tiles_x = ta.tiles_x, n_tiles = ta.n_tiles, n_batches = ta.n_batches, batch_spp = ta.batch_spp;
                     uint32_t b = 0;
                     if (lane == 0u) b = atomicAdd(batch_counter, 1u);
                     b = __builtin_amdgcn_readfirstlane(b);
@@ -227,12 +260,12 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                 cursor += 64u;
                 const uint32_t ds = ds0 + (item >> 6);
                 const uint32_t x = tile_x0 + (lane & 7u), row = tile_row0 + (lane >> 3);
-                const bool valid = x < cam.width && row < ra.rows_local;                  // off-image items of an edge tile are dropped
+                const bool valid = x < cam.width && row < rr.rows_local;                  // off-image items of an edge tile are dropped
                 const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
                 if (valid) {
                     if constexpr (STATS) { if (first_active_lane()) ctr.w_gen++; }
-                    const uint32_t y = image_row(ra, row);
-                    Rng rng = rng_seed(ra.seed_key, y * cam.width + x, ra.sample_begin + ds);        // cpu.rs:42-45
+                    const uint32_t y = image_row(rr, row);
+                    Rng rng = rng_seed(rr.seed_key, y * cam.width + x, rr.sample_begin + ds);        // cpu.rs:42-45
                     const Ray ray = primary_ray(cam, x, y, rng);
                     const uint32_t e = st_rank(vmask);
                     pool[0u * 64u + e] = __float_as_uint(ray.o.x); pool[1u * 64u + e] = __float_as_uint(ray.o.y); pool[2u * 64u + e] = __float_as_uint(ray.o.z);
@@ -273,7 +306,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                 walking = !closest_hit_resume<MODE, STATS, WALK>(sc, p.ray, tr, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.stragglers, entered);
                 if (!walking) {
                     if (shade_hit<MODE, STATS, LAZY>(sc, p, tr.prim_best, tr.t_best, background, ctr)) {
-                        radiance_store(colors, out_idx, p.color);
+                        radiance_store(kernarg_reload<float*>(offsetof(StreamKernargs, colors)), out_idx, p.color);       // the pointer: as the refill arguments
                         has_path = false;
                     }
                 }
@@ -282,7 +315,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                 float t;
                 const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, flat_reuse);
                 if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
-                    radiance_store(colors, out_idx, p.color);
+                    radiance_store(kernarg_reload<float*>(offsetof(StreamKernargs, colors)), out_idx, p.color);       // the pointer: as the refill arguments
                     has_path = false;
                 }
             }
