@@ -4,11 +4,12 @@
 // What a denoiser, a matte or a picking buffer needs of a frame: per pixel the albedo, normal, depth and coverage of the camera rays'
 // first hits, folded over the samples as the imager folds radiance (acc = acc + value * (1/spp), in sample order, imager.rs:35,50), and
 // the geometry / material index of sample 0.  The rays are the render's own: rng_seed(seed, y * W + x, s) followed by primary_ray
-// (rt_path.h), the first hit is BVH::hit over [0.001, +inf) - the record trt_intersect gives for that ray (query.hip q_store).
+// (rt_path.h), the first hit is BVH::hit over [0.001, +inf) - the record trt_intersect gives for that ray (wave_run.h hit_surface).
 //
 // One kernel generates the ray, walks and folds: no ray and no record goes through memory.  There is no walk code in this file: the
-// kernel calls the entry points of rt_path.h the way query.hip does, with the dynamic LDS laid out the same way (scene copy | leaf
-// stack: threads x slots x 8 bytes), and is launched by the rule of the queries (query_plan.h) with pixels in place of rays.
+// kernel calls the entry points of rt_path.h with the dynamic LDS laid out as the queries lay it out (scene copy | leaf stack: threads x
+// slots x 8 bytes; the run, the place of the stack and the refill's cursor step are wave_run.h's), and is launched by the rule of the queries (query_plan.h)
+// with pixels in place of rays.
 //
 // Work: a wave owns a contiguous run of the local image's pixels, and a lane owns a pixel for all of its samples, so the sums run in
 // sample order without atomics and without a second kernel.  With the two resumable walks (LDS tree, 16-byte nodes) the wave works in the
@@ -20,15 +21,12 @@
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
+#include "wave_run.h"
 
 namespace trt {
 
 static_assert(sizeof(trt_aov_buffers) == 48, "trt_aov_buffers layout (tinyrt.h)");
 static_assert(sizeof(trt_ray) == 24, "trt_ray layout (tinyrt.h)");
-
-TRT_DEV uint32_t aov_rank(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 // The ray the render traces for sample s of local pixel `pix` (row-major over the rows this call owns): path_begin's first two lines.
 TRT_DEV Ray aov_primary_ray(const CameraDev& cam, const RenderArgs& ra, uint32_t pix, uint32_t s) {
@@ -65,8 +63,8 @@ TRT_DEV AovSums aov_begin(const AovArgs& aa, bool load, uint32_t pix) {
     return a;
 }
 
-// One sample's first hit folded into the pixel's sums.  The record is that of query.hip q_store (HitRecord::new, hittable/mod.rs:28-48,
-// in the operation order of rt_path.h shade_hit); the indices of sample 0 go straight to their buffers.
+// One sample's first hit folded into the pixel's sums.  The record is the one the queries store (wave_run.h hit_surface); the indices of
+// sample 0 go straight to their buffers.
 template <int MODE>
 TRT_DEV void aov_fold(const SceneAcc<MODE>& sc, const AovArgs& aa, const RenderArgs& ra, uint32_t pix, uint32_t s, const Ray& ray, uint32_t prim,
                       float t, AovSums& a) {
@@ -74,22 +72,10 @@ TRT_DEV void aov_fold(const SceneAcc<MODE>& sc, const AovArgs& aa, const RenderA
     V3 normal = v3(0.0f, 0.0f, 0.0f);
     uint32_t geo = 0xFFFFFFFFu, mat = 0xFFFFFFFFu;
     if (prim != PRIM_NONE) {
-        const uint32_t k = prim & PRIM_INDEX_MASK;
-        if (prim & PRIM_QUAD_BIT) {
-            const float4 q0 = sc.quad(0, k), q1 = sc.quad(1, k), q4 = sc.quad(4, k);
-            const bool front_face = dot(ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;      // outward normal = n, un-normalised (quad.rs:45)
-            const V3 nu = v3(q4.y, q4.z, q4.w);                                    // n.normalized(), precomputed on the host
-            normal = front_face ? nu : -nu;
-            mat = __float_as_uint(q1.w);
-        } else {
-            const float4 sp = sc.sphere(k);
-            const V3 outward = ray_at(ray, t) - v3(sp.x, sp.y, sp.z);              // sphere.rs:47-51 (p = ray.at(t))
-            const bool front_face = dot(ray.d, outward) < 0.0f;
-            const V3 nu = normalized(outward);
-            normal = front_face ? nu : -nu;
-            mat = sc.sphere_material(k);
-        }
-        geo = aa.geo_index[k + ((prim & PRIM_QUAD_BIT) ? sc.L.n_spheres : 0u)];
+        const HitSurface h = hit_surface<MODE>(sc, aa.geo_index, ray, prim, t);
+        normal = h.normal;
+        geo = h.geometry;
+        mat = h.material;
         const float4 m = sc.material(mat);
         albedo = v3(m.x, m.y, m.z);                                                // the emitted colour of a light
         a.depth = a.depth + t * ra.inv_spp;                                        // a miss adds nothing
@@ -118,15 +104,12 @@ __global__ __launch_bounds__(THREADS, MINW) void aov_kernel(SceneDev scd, Camera
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    const unsigned long long begin64 = (unsigned long long)wave * aa.pixels_per_wave;
+    const unsigned long long begin64 = wave_begin<THREADS>(aa.pixels_per_wave);
     if (begin64 >= aa.n) return;                                            // (after the barriers above)
     const uint32_t begin = (uint32_t)begin64;
-    const uint32_t count = aa.n - begin < aa.pixels_per_wave ? aa.n - begin : aa.pixels_per_wave;
-    // postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave (query.hip)
-    float2* const stack = WALK != WALK_REGS
-        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * aa.slots) + lane
-        : nullptr;
+    const uint32_t count = wave_count(aa.n, aa.pixels_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * aa.slots) + lane : nullptr;
     Counters<false> ctr;
     constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
 
@@ -141,15 +124,14 @@ __global__ __launch_bounds__(THREADS, MINW) void aov_kernel(SceneDev scd, Camera
         for (;;) {
             const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
             if (need != 0ull && cursor < count) {
-                const uint32_t item = cursor + aov_rank(need);
+                const uint32_t item = cursor + wave_rank(need);
                 if (!own && item < count) {
                     pix = begin + item;
                     s = ra.sample_begin;
                     sums = aov_begin(aa, ra.accumulate != 0u, pix);
                     own = true;
                 }
-                cursor += (uint32_t)__builtin_popcountll(need);
-                if (cursor > count) cursor = count;
+                cursor = wave_advance(cursor, need, count);
             }
             if (__builtin_amdgcn_ballot_w64(own) == 0ull) break;            // (a lane without a pixel found none left: the run is done)
             if (own) {
@@ -197,18 +179,16 @@ __global__ __launch_bounds__(256) void primary_rays_kernel(CameraDev cam, Render
 
 namespace {
 
-struct AovKernel {
-    const void* fn;
-    int mode, walk, threads, minw;
-};
 #define TRT_AOV(MODE, WALK, THREADS, MINW) \
-    AovKernel{reinterpret_cast<const void*>(&aov_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
-// the (scene mode, walk, workgroup shape) set of query.hip kQueryKernels, with its register-slot fallback (query_plan.h), so that every
+    BatchKernel{reinterpret_cast<const void*>(&aov_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// the (scene mode, walk, workgroup shape) set of the queries' table, with its register-slot fallback (query_plan.h), so that every
 // scene has a kernel.  Launch bounds: the queries', except for the two walks that run to their end sample after sample with the eight
 // sums live across the walk - under the 64 VGPRs of 8 waves per SIMD the lock-step kernel spills 11 VGPRs (40 B of scratch per lane) and
 // the register-slot kernel for scenes in global memory 3 (16 B); folding into the output buffers in place instead still spills 7 and 1;
-// at 7 waves (72 VGPRs) neither spills (profiles/aov_resource_usage.txt).  The plan reports the bound (kernel_waves_per_simd).
-const AovKernel kAovKernels[] = {
+// at 7 waves (72 VGPRs) neither spilled when the bound was chosen.  Since the shade and ray set-up trims of rt_path.h the lock-step
+// kernel spills 2 VGPRs (12 B of scratch per lane) at 7 waves again; the bound was not revisited (profiles/aov_resource_usage.txt has
+// the current table).  The plan reports the bound (kernel_waves_per_simd).
+const BatchKernel kAovKernels[] = {
     TRT_AOV(MODE_LDS, WALK_FLAT, 256, 7),
     TRT_AOV(MODE_LDS, WALK_LDS_STACK, 256, 8),
     TRT_AOV(MODE_LDS, WALK_LDS_STACK, 768, 6),
@@ -217,19 +197,7 @@ const AovKernel kAovKernels[] = {
     TRT_AOV(MODE_GLOBAL, WALK_REGS, 256, 7),
 };
 #undef TRT_AOV
-
-const AovKernel* plan_aov(const SceneLayout& L, uint32_t n_pixels, uint32_t cus, trt_query_plan& q) {
-    return plan_batch(L, n_pixels, cus, kAovKernels, sizeof(kAovKernels) / sizeof(kAovKernels[0]), q);
-}
-
-// The parameters both units read, validated as trt_render validates them.  rows = rows the call owns.
-int aov_args(const trt_camera* cam, const trt_render_params* p, RenderArgs& ra, uint32_t& rows, CameraDev& cd) {
-    const int rc = query_render_args(cam, p, ra, rows);
-    if (rc != TRT_OK) return rc;
-    if ((unsigned long long)rows * cam->width > 0xFFFFFFFFull) return query_fail(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 pixels");
-    query_camera_dev(*cam, cd);
-    return TRT_OK;
-}
+constexpr size_t kAovShapes = sizeof(kAovKernels) / sizeof(kAovKernels[0]);
 
 bool any_buffer(const trt_aov_buffers* b) { return b->albedo || b->normal || b->depth || b->coverage || b->geometry || b->material; }
 
@@ -247,31 +215,16 @@ hipError_t launch_aov(const QueryScene& qs, const CameraDev& cd, RenderArgs ra, 
         }
         return hipSuccess;
     }
-    const SceneLayout& L = qs.scene.L;
-    int dev = 0, cus = 256;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    trt_query_plan q;
-    const AovKernel* const k = plan_aov(L, n, (uint32_t)cus, q);
-    if (k == nullptr) return hipErrorInvalidDeviceFunction;                         // no instantiation for this plan: a bug, never a fallback
-    const bool flat = k->walk == WALK_FLAT, compact = k->walk == WALK_COMPACT;
-    // what the walks assume, checked where the launch is made (query.hip launch_query)
-    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.leaf_slots < 2u) || (compact && L.off_compact == 0u) ||
-        (k->walk != WALK_REGS && (q.leaf_slots < 1u || q.leaf_slots > kLdsLeafSlotsMax)))
-        return hipErrorInvalidConfiguration;
-    if (q.lds_bytes > 48u * 1024u) {
-        e = hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
     SceneDev scd = qs.scene;
+    BatchLaunch bl;
+    const hipError_t e = batch_prepare(scd, n, kAovKernels, kAovShapes, bl);
+    if (e != hipSuccess) return e;
+    const trt_query_plan& q = bl.q;
     CameraDev cam = cd;
     ra.flat_reuse = qs.flat_reuse;
     AovArgs aa{b.albedo, b.normal, b.depth, b.coverage, b.geometry, b.material, qs.geo_index, n, q.rays_per_wave, q.leaf_slots, q.stragglers};
-    const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
-    const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
-    void* args[] = {&scd, &cam, &ra, &aa, &leaf_list, &nodes16};
-    return hipLaunchKernel(k->fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    void* args[] = {&scd, &cam, &ra, &aa, &bl.leaf_list, &bl.nodes16};
+    return hipLaunchKernel(bl.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
 }
 
 // TRT_ERR_INVALID_ARG before any device work, then TRT_ERR_NO_DEVICE (the queries' order).
@@ -279,7 +232,7 @@ int aov_check(const trt_scene* s, const trt_camera* cam, const trt_render_params
               CameraDev& cd) {
     if (!s || !cam || !p || !b) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     if (!any_buffer(b)) return query_fail(TRT_ERR_INVALID_ARG, "no buffer is wanted: all six pointers are null");
-    const int rc = aov_args(cam, p, ra, rows, cd);
+    const int rc = batch_render_args(cam, p, ra, rows, cd);
     if (rc != TRT_OK) return rc;
     return query_require_device();
 }
@@ -290,7 +243,7 @@ int rays_check(const trt_camera* cam, const trt_render_params* p, uint32_t s, co
     trt_render_params q = *p;                                       // seed and bands only: the sample range is not read
     q.sample_begin = 0u;
     q.sample_end = 0u;
-    const int rc = aov_args(cam, &q, ra, rows, cd);
+    const int rc = batch_render_args(cam, &q, ra, rows, cd);
     if (rc != TRT_OK) return rc;
     if (rows && !rays) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
     return query_require_device();
@@ -396,20 +349,9 @@ int trt_render_aov(trt_scene* s, const trt_camera* cam, const trt_render_params*
     return TRT_OK;
 }
 
-// How launch_aov would launch a local image of n_pixels on this scene (host arithmetic only: works without a GPU when the CU count is given).
+// How launch_aov would launch a local image of n_pixels on this scene.
 int trt_aov_launch_plan(const trt_scene* s, uint32_t n_pixels, uint32_t compute_units, trt_query_plan* out) {
-    if (!s || !out) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    if (compute_units == 0u) {
-        const int rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        int dev = 0, cus = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess || cus <= 0) return trt::query_fail_hip(e, "compute unit count of the current device");
-        compute_units = (uint32_t)cus;
-    }
-    (void)trt::plan_aov(trt::query_scene_layout(s), n_pixels, compute_units, *out);     // no instantiation: has_kernel = 0 says so
-    return TRT_OK;
+    return trt::batch_launch_plan(s, n_pixels, compute_units, trt::kAovKernels, trt::kAovShapes, out);
 }
 
 }  // extern "C"

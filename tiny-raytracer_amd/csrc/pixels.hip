@@ -9,27 +9,25 @@
 // for all samples of the call, so no radiance record goes through memory and there is no second kernel.  Every other byte of the two
 // buffers is left alone.  Adaptive sampling is then a host loop over two primitives: render a list, select the next one (api.py).
 //
-// There is no walk code in this file and none of the render kernels is touched: the kernel calls the entry points of rt_path.h the way
-// aov.hip does, with the dynamic LDS laid out the same way (scene copy | leaf stack: threads x slots x 8 bytes), and is launched by the
-// rule of the queries (query_plan.h) with list entries in place of rays: a wave owns a contiguous run of the list.
+// There is no walk code in this file and none of the render kernels is touched: the kernel calls the entry points of rt_path.h with the
+// dynamic LDS laid out as the queries lay it out (scene copy | leaf stack: threads x slots x 8 bytes; the run, the place of the stack and the refill's
+// cursor step are wave_run.h's), and is launched by the rule of the queries (query_plan.h) with list entries in place of rays: a wave owns a
+// contiguous run of the list.
 //
 // Work: the wave runs in rounds.  At the top of a round every lane without a pixel takes the next entry of the run, every lane without a
 // path starts its pixel's next sample; then all lanes that own a pixel trace one bounce.  A lane whose path ended in a round therefore has
 // a new one in the next, whatever the walk: no lane idles while its neighbours finish longer paths.  With the two resumable walks (LDS
 // tree, 16-byte nodes) a walk still under way when at most `stragglers` lanes walk is parked in the lane's leaf stack and resumed beside
-// the fresh rays, exactly as in aov_kernel.
+// the fresh rays, as the feature buffers' and the queries' kernels do.
 #include <vector>
 
 #include "kernels.h"
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
+#include "wave_run.h"
 
 namespace trt {
-
-TRT_DEV uint32_t px_rank(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 struct PixelsArgs {
     const uint32_t* pixels;          // n local pixel indices r * width + x
@@ -58,16 +56,13 @@ __global__ __launch_bounds__(THREADS, MINW) void pixels_kernel(SceneDev scd, Cam
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     const uint32_t n = px_entries(pa.d_count, pa.n);
-    const unsigned long long begin64 = (unsigned long long)wave * pa.pixels_per_wave;
+    const unsigned long long begin64 = wave_begin<THREADS>(pa.pixels_per_wave);
     if (begin64 >= n) return;                                               // (after the barriers above)
     const uint32_t begin = (uint32_t)begin64;
-    const uint32_t count = n - begin < pa.pixels_per_wave ? n - begin : pa.pixels_per_wave;
-    // postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave (query.hip)
-    float2* const stack = WALK != WALK_REGS
-        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * pa.slots) + lane
-        : nullptr;
+    const uint32_t count = wave_count(n, pa.pixels_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * pa.slots) + lane : nullptr;
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
     Counters<false> ctr;
     constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(THREADS, MINW) void pixels_kernel(SceneDev scd, Cam
         // ---- refill: every lane without a pixel takes the next entry of the run ----
         const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
         if (need != 0ull && cursor < count) {
-            const uint32_t item = cursor + px_rank(need);
+            const uint32_t item = cursor + wave_rank(need);
             if (!own && item < count) {
                 pix = pa.pixels[begin + item];
                 if (pix < pa.npixels) {                                     // an entry past the local image is skipped: neither read nor written
@@ -102,8 +97,7 @@ __global__ __launch_bounds__(THREADS, MINW) void pixels_kernel(SceneDev scd, Cam
                     own = true;
                 }
             }
-            cursor += (uint32_t)__builtin_popcountll(need);
-            if (cursor > count) cursor = count;
+            cursor = wave_advance(cursor, need, count);
         }
         if (__builtin_amdgcn_ballot_w64(own) == 0ull) {
             if (cursor >= count) break;                                     // the run is done
@@ -209,7 +203,7 @@ TRT_DEV uint32_t select_tile_rank(bool keep, uint32_t* waves, uint32_t& total) {
     uint32_t before = 0;
     total = 0;
     for (uint32_t k = 0; k < kSelectTile / 64u; k++) { if (k < w) before += waves[k]; total += waves[k]; }
-    return before + px_rank(mask);
+    return before + wave_rank(mask);
 }
 
 __global__ __launch_bounds__(kSelectTile) void select_count_kernel(SelectArgs sa, uint32_t* __restrict__ tile_counts) {
@@ -256,17 +250,13 @@ __global__ __launch_bounds__(kSelectTile) void select_write_kernel(SelectArgs sa
 
 namespace {
 
-struct PixelsKernel {
-    const void* fn;
-    int mode, walk, threads, minw;
-};
 #define TRT_PIXELS(MODE, WALK, THREADS, MINW) \
-    PixelsKernel{reinterpret_cast<const void*>(&pixels_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
-// the (scene mode, walk, workgroup shape) set of aov.hip kAovKernels, with the register-slot fallback (query_plan.h), so that every scene
+    BatchKernel{reinterpret_cast<const void*>(&pixels_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// the (scene mode, walk, workgroup shape) set of the queries' table, with the register-slot fallback (query_plan.h), so that every scene
 // has a kernel.  A lane carries a whole path (ray, colour, attenuation, RNG) and two running sums across the walk, where the feature
 // buffers carry a ray and eight sums: the launch bounds are the highest at which the instantiation uses no scratch memory
 // (profiles/pixels_resource_usage.txt).  The plan reports the bound (kernel_waves_per_simd).
-const PixelsKernel kPixelsKernels[] = {
+const BatchKernel kPixelsKernels[] = {
     TRT_PIXELS(MODE_LDS, WALK_FLAT, 256, 5),
     TRT_PIXELS(MODE_LDS, WALK_LDS_STACK, 256, 5),
     TRT_PIXELS(MODE_LDS, WALK_LDS_STACK, 768, 5),
@@ -275,22 +265,7 @@ const PixelsKernel kPixelsKernels[] = {
     TRT_PIXELS(MODE_GLOBAL, WALK_REGS, 256, 5),
 };
 #undef TRT_PIXELS
-
-const PixelsKernel* plan_pixels(const SceneLayout& L, uint32_t n, uint32_t cus, trt_query_plan& q) {
-    return plan_batch(L, n, cus, kPixelsKernels, sizeof(kPixelsKernels) / sizeof(kPixelsKernels[0]), q);
-}
-
-// the launch pattern of kernels.hip: a big dynamic LDS is asked for, and trt_kernel_timing_* brackets the launch
-hipError_t launch(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t stream) {
-    if (lds > 48u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(fn, grid, block, args, lds, stream);
-    timing_mark(stream, false);
-    return le;
-}
+constexpr size_t kPixelsShapes = sizeof(kPixelsKernels) / sizeof(kPixelsKernels[0]);
 
 // npixels = rows x width of the local image
 hipError_t launch_pixels(const QueryScene& qs, const CameraDev& cd, RenderArgs ra, uint32_t npixels, const uint32_t* d_pixels, uint32_t n,
@@ -302,27 +277,20 @@ hipError_t launch_pixels(const QueryScene& qs, const CameraDev& cd, RenderArgs r
         hipLaunchKernelGGL(pixels_zero_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_pixels, d_count, n, npixels, d_accum, d_moment2);
         return hipGetLastError();
     }
-    const SceneLayout& L = qs.scene.L;
-    int dev = 0, cus = 256;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    trt_query_plan q;
-    const PixelsKernel* const k = plan_pixels(L, n, (uint32_t)cus, q);
-    if (k == nullptr) return hipErrorInvalidDeviceFunction;                         // no instantiation for this plan: a bug, never a fallback
-    const bool flat = k->walk == WALK_FLAT, compact = k->walk == WALK_COMPACT;
-    // what the walks assume, checked where the launch is made (query.hip launch_query)
-    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.leaf_slots < 2u) || (compact && L.off_compact == 0u) ||
-        (k->walk != WALK_REGS && (q.leaf_slots < 1u || q.leaf_slots > kLdsLeafSlotsMax)))
-        return hipErrorInvalidConfiguration;
     SceneDev scd = qs.scene;
+    BatchLaunch b;
+    const hipError_t e = batch_prepare(scd, n, kPixelsKernels, kPixelsShapes, b);
+    if (e != hipSuccess) return e;
+    const trt_query_plan& q = b.q;
     CameraDev cam = cd;
     ra.flat_reuse = qs.flat_reuse;
     PixelsArgs pa{d_pixels, d_count, d_accum, d_moment2, d_counters, n, npixels, q.rays_per_wave, q.leaf_slots, q.stragglers};
-    const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
-    const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
-    void* args[] = {&scd, &cam, &ra, &pa, &leaf_list, &nodes16};
-    return launch(k->fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    void* args[] = {&scd, &cam, &ra, &pa, &b.leaf_list, &b.nodes16};
+    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
+    timing_mark(stream, true);
+    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    timing_mark(stream, false);
+    return le;
 }
 
 // What both forms check before any device work.  npixels = pixels of the local image.
@@ -331,11 +299,9 @@ int pixels_check(const trt_scene* s, const trt_camera* cam, const trt_render_par
     if (!s || !cam || !p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     if (p->collect_stats != 0u) return query_fail(TRT_ERR_INVALID_ARG, "the sparse render has no counting kernels: collect_stats must be 0");
     uint32_t rows = 0;
-    const int rc = query_render_args(cam, p, ra, rows);
+    const int rc = batch_render_args(cam, p, ra, rows, cd);
     if (rc != TRT_OK) return rc;
-    if ((unsigned long long)rows * cam->width > 0xFFFFFFFFull) return query_fail(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 pixels");
     npixels = rows * cam->width;
-    query_camera_dev(*cam, cd);
     if (n > 0u && (!pixels || !accum)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
     return TRT_OK;
 }
@@ -482,20 +448,9 @@ int trt_render_pixels(trt_scene* s, const trt_camera* cam, const trt_render_para
     return TRT_OK;
 }
 
-// How launch_pixels would launch a list of n pixels on this scene (host arithmetic only: works without a GPU when the CU count is given).
+// How launch_pixels would launch a list of n pixels on this scene.
 int trt_pixels_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    if (!s || !out) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    if (compute_units == 0u) {
-        const int rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        int dev = 0, cus = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess || cus <= 0) return trt::query_fail_hip(e, "compute unit count of the current device");
-        compute_units = (uint32_t)cus;
-    }
-    (void)trt::plan_pixels(trt::query_scene_layout(s), n, compute_units, *out);      // no instantiation: has_kernel = 0 says so
-    return TRT_OK;
+    return trt::batch_launch_plan(s, n, compute_units, trt::kPixelsKernels, trt::kPixelsShapes, out);
 }
 
 uint64_t trt_select_scratch_bytes(uint32_t n) { return (uint64_t)trt::q_align16(trt::select_tiles(n) * sizeof(uint32_t)); }

@@ -7,7 +7,8 @@
 // stack: threads x slots x 8 bytes), and run the walk the streamed launch plan picks for the scene (query_plan below).
 //
 // Work: a wave owns a contiguous run of the caller's rays, in the caller's order - nothing is sorted or compacted, coherence is the
-// caller's business.  With the two resumable walks (LDS tree, 16-byte nodes) the wave works in the rounds of stream_sample_kernel: a lane
+// caller's business (the run, the place of the leaf stack and the refill's cursor step are wave_run.h's, shared with aov.hip and pixels.hip; the launch is
+// query_plan.h's).  With the two resumable walks (LDS tree, 16-byte nodes) the wave works in the rounds of stream_sample_kernel: a lane
 // whose walk completed writes its answer and takes the next ray of the run, a lane whose walk is still under way when at most
 // `stragglers` lanes walk parks it in its leaf stack and resumes beside the fresh rays, so one long walk does not hold 63 lanes.  The
 // other walks (lock-step list, register slots) run to their end, 64 rays of the run at a time.
@@ -18,14 +19,12 @@
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
+#include "wave_run.h"
 
 namespace trt {
 
 static_assert(sizeof(trt_hit) == 28 && offsetof(trt_hit, normal) == 16, "trt_hit layout (tinyrt.h)");
 
-TRT_DEV uint32_t q_rank(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 TRT_DEV Ray q_load_ray(const float* __restrict__ rays, uint32_t idx) {
     const float* r = rays + 6ull * idx;
     Ray ray;
@@ -34,9 +33,8 @@ TRT_DEV Ray q_load_ray(const float* __restrict__ rays, uint32_t idx) {
     return ray;
 }
 
-// The answer of one ray.  ANY: one byte.  Else the record of HitRecord::new (hittable/mod.rs:28-48) for the winning primitive, restated
-// from the lines of rt_path.h shade_hit that compute front_face, normal and the material index, in their operation order; `geometry` is
-// the primitive's insertion index (scene_query.h geo_index).  A miss: t = +inf, geometry = material = 0xFFFFFFFF, everything else 0.
+// The answer of one ray.  ANY: one byte.  Else the record of HitRecord::new (hittable/mod.rs:28-48) for the winning primitive
+// (wave_run.h hit_surface).  A miss: t = +inf, geometry = material = 0xFFFFFFFF, everything else 0.
 template <int MODE, bool ANY>
 TRT_DEV void q_store(const SceneAcc<MODE>& sc, const uint32_t* __restrict__ geo_index, void* __restrict__ out, uint32_t idx, const Ray& ray,
                      uint32_t prim, float t) {
@@ -49,29 +47,12 @@ TRT_DEV void q_store(const SceneAcc<MODE>& sc, const uint32_t* __restrict__ geo_
             rec[4] = 0u; rec[5] = 0u; rec[6] = 0u;
             return;
         }
-        const uint32_t k = prim & PRIM_INDEX_MASK;
-        V3 normal;
-        bool front_face;
-        uint32_t mat;
-        if (prim & PRIM_QUAD_BIT) {
-            const float4 q0 = sc.quad(0, k), q1 = sc.quad(1, k), q4 = sc.quad(4, k);
-            front_face = dot(ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;          // outward normal = n, un-normalised (quad.rs:45)
-            const V3 nu = v3(q4.y, q4.z, q4.w);                            // n.normalized(), precomputed on the host
-            normal = front_face ? nu : -nu;
-            mat = __float_as_uint(q1.w);
-        } else {
-            const float4 sp = sc.sphere(k);
-            const V3 outward = ray_at(ray, t) - v3(sp.x, sp.y, sp.z);      // sphere.rs:47-51 (p = ray.at(t))
-            front_face = dot(ray.d, outward) < 0.0f;
-            const V3 nu = normalized(outward);
-            normal = front_face ? nu : -nu;
-            mat = sc.sphere_material(k);
-        }
+        const HitSurface h = hit_surface<MODE>(sc, geo_index, ray, prim, t);
         rec[0] = __float_as_uint(t);
-        rec[1] = geo_index[k + ((prim & PRIM_QUAD_BIT) ? sc.L.n_spheres : 0u)];
-        rec[2] = mat;
-        rec[3] = front_face ? 1u : 0u;
-        rec[4] = __float_as_uint(normal.x); rec[5] = __float_as_uint(normal.y); rec[6] = __float_as_uint(normal.z);
+        rec[1] = h.geometry;
+        rec[2] = h.material;
+        rec[3] = h.front_face ? 1u : 0u;
+        rec[4] = __float_as_uint(h.normal.x); rec[5] = __float_as_uint(h.normal.y); rec[6] = __float_as_uint(h.normal.z);
     }
 }
 
@@ -94,15 +75,12 @@ __global__ __launch_bounds__(THREADS, MINW) void query_kernel(SceneDev scd, Quer
     const float* __restrict__ const rays = qa.rays;
     const float* __restrict__ const t_max = qa.t_max;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    const unsigned long long begin64 = (unsigned long long)wave * qa.rays_per_wave;
+    const unsigned long long begin64 = wave_begin<THREADS>(qa.rays_per_wave);
     if (begin64 >= qa.n) return;                                            // (after the barriers above)
     const uint32_t begin = (uint32_t)begin64;
-    const uint32_t count = qa.n - begin < qa.rays_per_wave ? qa.n - begin : qa.rays_per_wave;
-    // postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave (streamed.hip)
-    float2* const stack = WALK != WALK_REGS
-        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * qa.slots) + lane
-        : nullptr;
+    const uint32_t count = wave_count(qa.n, qa.rays_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * qa.slots) + lane : nullptr;
     Counters<false> ctr;
     constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
 
@@ -116,7 +94,7 @@ __global__ __launch_bounds__(THREADS, MINW) void query_kernel(SceneDev scd, Quer
         for (;;) {
             const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
             if (need != 0ull && cursor < count) {
-                const uint32_t item = cursor + q_rank(need);
+                const uint32_t item = cursor + wave_rank(need);
                 if (!has && item < count) {
                     idx = begin + item;
                     ray = q_load_ray(rays, idx);
@@ -124,8 +102,7 @@ __global__ __launch_bounds__(THREADS, MINW) void query_kernel(SceneDev scd, Quer
                     if (tm > kTMin) has = true;
                     else q_store<MODE, ANY>(sc, qa.geo_index, qa.out, idx, ray, PRIM_NONE, 0.0f);      // an empty or NaN range: a miss, not walked
                 }
-                cursor += (uint32_t)__builtin_popcountll(need);
-                if (cursor > count) cursor = count;
+                cursor = wave_advance(cursor, need, count);
             }
             if (__builtin_amdgcn_ballot_w64(has) == 0ull) {
                 if (cursor >= count) break;
@@ -159,14 +136,8 @@ __global__ __launch_bounds__(THREADS, MINW) void query_kernel(SceneDev scd, Quer
 
 namespace {
 
-struct QueryKernel {
-    const void* closest;
-    const void* any;
-    int mode, walk, threads, minw;
-};
-#define TRT_QUERY(MODE, WALK, THREADS, MINW)                                                                      \
-    QueryKernel{reinterpret_cast<const void*>(&query_kernel<MODE, WALK, false, THREADS, MINW>),                 \
-                reinterpret_cast<const void*>(&query_kernel<MODE, WALK, true, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+#define TRT_QUERY(ANY, MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&query_kernel<MODE, WALK, ANY, THREADS, MINW>), MODE, WALK, THREADS, MINW}
 // one instantiation per (scene mode, walk, workgroup shape) the streamed launch plan produces for the scenes the tuning was measured on:
 // lock-step list in LDS / 256 lanes (up to 32 primitives), LDS tree with the leaf stack in LDS at 256 and at 768 lanes, 16-byte nodes from
 // global memory; and the register-slot walk for LDS scenes (512 lanes) and for scenes in global memory (256 lanes).  The table does NOT
@@ -174,50 +145,33 @@ struct QueryKernel {
 // no resident 512-lane workgroup (scene copies of roughly 56 to 64 KB) is planned as LDS tree / 512 lanes, which is not here, and
 // neither are the plans only scene options reach (a tree walk from global memory with the 16-byte nodes switched off; the lock-step
 // list forced on a scene of more than 32 primitives that is in LDS at 768 lanes or in global memory).  Those run the register-slot
-// instantiation of their scene mode (plan_query: fallback), which walks the culling tree every compiled scene carries and needs neither
-// the leaf list nor the 16-byte nodes.
-const QueryKernel kQueryKernels[] = {
-    TRT_QUERY(MODE_LDS, WALK_FLAT, 256, 8),
-    TRT_QUERY(MODE_LDS, WALK_LDS_STACK, 256, 8),
-    TRT_QUERY(MODE_LDS, WALK_LDS_STACK, 768, 6),
-    TRT_QUERY(MODE_LDS, WALK_REGS, 512, 6),
-    TRT_QUERY(MODE_GLOBAL, WALK_COMPACT, 256, 8),
-    TRT_QUERY(MODE_GLOBAL, WALK_REGS, 256, 8),
-};
+// instantiation of their scene mode (query_plan.h plan_batch: fallback), which walks the culling tree every compiled scene carries and
+// needs neither the leaf list nor the 16-byte nodes.  Row 0: the closest-hit form, row 1: the occlusion form of the same shapes.
+#define TRT_QUERY_TABLE(ANY)                                \
+    {                                                       \
+        TRT_QUERY(ANY, MODE_LDS, WALK_FLAT, 256, 8),        \
+        TRT_QUERY(ANY, MODE_LDS, WALK_LDS_STACK, 256, 8),   \
+        TRT_QUERY(ANY, MODE_LDS, WALK_LDS_STACK, 768, 6),   \
+        TRT_QUERY(ANY, MODE_LDS, WALK_REGS, 512, 6),        \
+        TRT_QUERY(ANY, MODE_GLOBAL, WALK_COMPACT, 256, 8),  \
+        TRT_QUERY(ANY, MODE_GLOBAL, WALK_REGS, 256, 8),     \
+    }
+constexpr size_t kQueryShapes = 6;
+const BatchKernel kQueryKernels[2][kQueryShapes] = {TRT_QUERY_TABLE(false), TRT_QUERY_TABLE(true)};
+#undef TRT_QUERY_TABLE
 #undef TRT_QUERY
 
-// How a batch of n rays is launched on this scene with `cus` compute units (what trt_query_launch_plan reports and launch_query launches):
-// the rule of query_plan.h over kQueryKernels.  Returns the instantiation, nullptr if there is none.
-const QueryKernel* plan_query(const SceneLayout& L, uint32_t n, uint32_t cus, trt_query_plan& q) {
-    return plan_batch(L, n, cus, kQueryKernels, sizeof(kQueryKernels) / sizeof(kQueryKernels[0]), q);
-}
-
+// launches exactly what trt_query_launch_plan reports (query_plan.h: one rule)
 hipError_t launch_query(const QueryScene& qs, const float* d_rays, const float* d_t_max, uint32_t n, void* d_out, bool any, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const SceneLayout& L = qs.scene.L;
-    int dev = 0, cus = 256;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    trt_query_plan q;
-    const QueryKernel* const k = plan_query(L, n, (uint32_t)cus, q);
-    if (k == nullptr) return hipErrorInvalidDeviceFunction;                         // no instantiation for this plan: a bug, never a fallback
-    const bool flat = k->walk == WALK_FLAT, compact = k->walk == WALK_COMPACT;
-    // what the walks assume, checked where the launch is made
-    if (q.lds_bytes > kQueryLdsPerCu || (flat && q.leaf_slots < 2u) || (compact && L.off_compact == 0u) ||
-        (k->walk != WALK_REGS && (q.leaf_slots < 1u || q.leaf_slots > kLdsLeafSlotsMax)))
-        return hipErrorInvalidConfiguration;
-    const void* fn = any ? k->any : k->closest;
-    if (q.lds_bytes > 48u * 1024u) {
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
     SceneDev scd = qs.scene;
+    BatchLaunch b;
+    const hipError_t e = batch_prepare(scd, n, kQueryKernels[any ? 1 : 0], kQueryShapes, b);
+    if (e != hipSuccess) return e;
+    const trt_query_plan& q = b.q;
     QueryArgs qa{d_rays, d_t_max, d_out, qs.geo_index, n, q.rays_per_wave, q.leaf_slots, q.stragglers, qs.flat_reuse};
-    const float4* leaf_list = (flat || compact) ? scd.blob + L.off_leaf_list : nullptr;
-    const uint4* nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
-    void* args[] = {&scd, &qa, &leaf_list, &nodes16};
-    return hipLaunchKernel(fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    void* args[] = {&scd, &qa, &b.leaf_list, &b.nodes16};
+    return hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
 }
 
 // Argument checks shared by the four entry points: TRT_ERR_INVALID_ARG before any device work, then TRT_ERR_NO_DEVICE (trt_sample_batch's order).
@@ -280,20 +234,9 @@ int trt_intersect_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_m
 int trt_occluded_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, uint8_t* d_occluded, void* stream) {
     return trt::query_device(s, d_rays, d_t_max, n, d_occluded, true, stream);
 }
-// How launch_query would launch n rays on this scene (host arithmetic only: works without a GPU when the CU count is given).
+// How launch_query would launch n rays on this scene.
 int trt_query_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    if (!s || !out) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    if (compute_units == 0u) {
-        const int rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        int dev = 0, cus = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess || cus <= 0) return trt::query_fail_hip(e, "compute unit count of the current device");
-        compute_units = (uint32_t)cus;
-    }
-    (void)trt::plan_query(trt::query_scene_layout(s), n, compute_units, *out);     // no instantiation: has_kernel = 0 says so
-    return TRT_OK;
+    return trt::batch_launch_plan(s, n, compute_units, trt::kQueryKernels[0], trt::kQueryShapes, out);
 }
 
 }  // extern "C"

@@ -25,14 +25,11 @@
 #include "kernels.h"
 #include "rt_path.h"
 #include "scene_query.h"
+#include "wave_run.h"
 
 namespace trt {
 
 constexpr uint32_t kBatchSpp = 8;            // samples per pixel in one batch
-
-TRT_DEV uint32_t st_rank(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 template <int MODE, bool STATS, int MINW = 1, int THREADS = 256, int WALK = WALK_RUNTIME, bool LAZY = false>
 __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev scd, CameraDev cam, RenderArgs ra,
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
     const uint32_t n_spp = ra.sample_end - ra.sample_begin;
     // postponed-leaf stack (rt_path.h walk_fast_lds): behind the scene copy, leaf_slots x 64 x 8 bytes per wave
     float2* const leaf_stack = (WALK != WALK_REGS && (WALK != WALK_RUNTIME || ra.lds_leaf_stack))
-        ? reinterpret_cast<float2*>(reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u)) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane
+        ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane
         : nullptr;
 
     // wave-uniform work cursor
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
             }
             if (!exhausted) {
                 const uint64_t want = __builtin_amdgcn_ballot_w64(!stocked);
-                const uint32_t item = cursor + st_rank(want);
+                const uint32_t item = cursor + wave_rank(want);
                 cursor += (uint32_t)__builtin_popcountll(want);
                 if (!stocked && item < items_per_batch) {
                     const uint32_t l = item & 63u, ds = ds0 + (item >> 6);         // neighbouring items = neighbouring pixels, same sample
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
     const SceneAcc<MODE> sc{scd.blob, scd.L};
     const uint32_t lane = threadIdx.x & 63u;
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
-    char* const lds_tail = reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u);
+    char* const lds_tail = lds_behind_scene(sc);
     float2* const leaf_stack = reinterpret_cast<float2*>(lds_tail) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane;
     // the pool: field f of entry e at pool[f * 64 + e]
     uint32_t* const pool = reinterpret_cast<uint32_t*>(lds_tail + (size_t)THREADS * ra.leaf_slots * sizeof(float2)) + (threadIdx.x >> 6) * (64u * kPoolDwords);
@@ -267,7 +264,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                     const uint32_t y = image_row(rr, row);
                     Rng rng = rng_seed(rr.seed_key, y * cam.width + x, rr.sample_begin + ds);        // cpu.rs:42-45
                     const Ray ray = primary_ray(cam, x, y, rng);
-                    const uint32_t e = st_rank(vmask);
+                    const uint32_t e = wave_rank(vmask);
                     pool[0u * 64u + e] = __float_as_uint(ray.o.x); pool[1u * 64u + e] = __float_as_uint(ray.o.y); pool[2u * 64u + e] = __float_as_uint(ray.o.z);
                     pool[3u * 64u + e] = __float_as_uint(ray.d.x); pool[4u * 64u + e] = __float_as_uint(ray.d.y); pool[5u * 64u + e] = __float_as_uint(ray.d.z);
                     pool[6u * 64u + e] = rng.s0; pool[7u * 64u + e] = rng.s1;
@@ -277,7 +274,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                 pool_count = (uint32_t)__builtin_popcountll(vmask);
                 if (pool_count == 0u) continue;                                           // a tile row entirely off the image
             }
-            const uint32_t rank = st_rank(need);
+            const uint32_t rank = wave_rank(need);
             if (!has_path && rank < pool_count) {
                 const uint32_t e = pool_head + rank;
                 p.ray.o = v3(__uint_as_float(pool[0u * 64u + e]), __uint_as_float(pool[1u * 64u + e]), __uint_as_float(pool[2u * 64u + e]));
@@ -396,7 +393,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_dual_kernel(SceneDev scd
                     const uint32_t y = image_row(ra, row);
                     Rng rng = rng_seed(ra.seed_key, y * cam.width + x, ra.sample_begin + ds);        // cpu.rs:42-45
                     const Ray ray = primary_ray(cam, x, y, rng);
-                    const uint32_t e = st_rank(vmask);
+                    const uint32_t e = wave_rank(vmask);
                     pool[0u * 64u + e] = __float_as_uint(ray.o.x); pool[1u * 64u + e] = __float_as_uint(ray.o.y); pool[2u * 64u + e] = __float_as_uint(ray.o.z);
                     pool[3u * 64u + e] = __float_as_uint(ray.d.x); pool[4u * 64u + e] = __float_as_uint(ray.d.y); pool[5u * 64u + e] = __float_as_uint(ray.d.z);
                     pool[6u * 64u + e] = rng.s0; pool[7u * 64u + e] = rng.s1;
@@ -406,7 +403,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_dual_kernel(SceneDev scd
                 pool_count = (uint32_t)__builtin_popcountll(vmask);
                 if (pool_count == 0u) continue;
             }
-            const uint32_t rank = st_rank(need);
+            const uint32_t rank = wave_rank(need);
             if (!S.has_path && rank < pool_count) {
                 const uint32_t e = pool_head + rank;
                 S.p.ray.o = v3(__uint_as_float(pool[0u * 64u + e]), __uint_as_float(pool[1u * 64u + e]), __uint_as_float(pool[2u * 64u + e]));

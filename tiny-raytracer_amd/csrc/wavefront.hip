@@ -28,6 +28,7 @@
 
 #include "kernels.h"
 #include "rt_path.h"
+#include "wave_run.h"
 
 namespace trt {
 
@@ -47,9 +48,6 @@ struct WfLds {                                                 // backend-privat
 };
 
 TRT_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
-TRT_DEV uint32_t rank_in(uint64_t mask) {                      // number of set bits below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 TRT_DEV uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
 
 // Append this lane's slot to an LDS queue if `push`: ballot, one LDS atomic per wave, prefix rank.
@@ -59,7 +57,7 @@ TRT_DEV void wave_push(uint16_t* q, uint32_t* count, bool push, uint32_t slot) {
     uint32_t base = 0;
     if (lane_id() == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(count, popc64(m));
     base = __shfl(base, __builtin_ctzll(m), 64);
-    if (push) q[base + rank_in(m)] = (uint16_t)slot;
+    if (push) q[base + wave_rank(m)] = (uint16_t)slot;
 }
 
 // local slot -> pixel of the tile: 8x8 sub-tiles so that the 64 slots a wave starts with are neighbours
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(kWfThreads, MINW) void wavefront_kernel(SceneDev sc
                     uint32_t b = 0;
                     if (lane == (uint32_t)__builtin_ctzll(free_m)) b = atomicAdd(&lds.head, n_free);
                     b = __shfl(b, __builtin_ctzll(free_m), 64);
-                    const uint32_t mine = b + rank_in(free_m);
+                    const uint32_t mine = b + wave_rank(free_m);
                     if (slot == kNone && mine < n) {
                         slot = q[mine];
                         const float4 a = st.s0[tile.slot0 + slot], d = st.s1[tile.slot0 + slot];
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(kWfThreads, MINW) void wavefront_kernel(SceneDev sc
                 uint32_t off = 0;
                 if (lane == (uint32_t)__builtin_ctzll(m)) off = atomicAdd(&lds.cursor[b], popc64(m));
                 off = __shfl(off, __builtin_ctzll(m), 64);
-                if (bin == b) lds.sorted[lds.base[b] + off + rank_in(m)] = (uint16_t)slot;
+                if (bin == b) lds.sorted[lds.base[b] + off + wave_rank(m)] = (uint16_t)slot;
             }
         }
         __syncthreads();
