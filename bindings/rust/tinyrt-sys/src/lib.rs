@@ -230,6 +230,21 @@ pub struct trt_query_plan {
     pub waves: u64,
 }
 
+/// Samples, depth, RNG numbering and sample range of `trt_radiance` (64 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_radiance_params {
+    pub samples_per_ray: u32,
+    pub max_bounces: u32,
+    pub background: trt_vec3,
+    pub seed: u32,
+    pub sample_begin: u32,
+    pub sample_end: u32,
+    pub accumulate: u32,
+    pub first_stream: u32,
+    pub reserved: [u32; 6],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -376,6 +391,12 @@ extern "C" {
                                     d_candidates: *const u32, n_candidates: u32, rel_tol: f32, abs_tol: f32, d_selected: *mut u32,
                                     d_count: *mut u32, d_scratch: *mut c_void, scratch_bytes: u64, stream: *mut c_void) -> c_int;
     pub fn trt_select_scratch_bytes(n_candidates: u32) -> u64;
+    pub fn trt_radiance_params_default(out: *mut trt_radiance_params);
+    pub fn trt_radiance(s: *mut trt_scene, rays: *const trt_ray, n: u32, p: *const trt_radiance_params, radiance: *mut f32,
+                        moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_radiance_device(s: *mut trt_scene, d_rays: *const trt_ray, n: u32, p: *const trt_radiance_params, d_radiance: *mut f32,
+                               d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_radiance_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

@@ -184,6 +184,32 @@ impl World {
         Ok(self.scene)
     }
 
+    /// The light that arrives along caller-supplied rays (`trt_radiance`): each `(origin, direction)` as six floats, used as given, is
+    /// path traced with `samples_per_ray` samples and folded with the imager's 1 / K rule.  Sample `s` of ray `i` uses RNG stream
+    /// `(seed, first_stream + i * samples_per_ray + s, 0)`.  Returns `(radiance, moment2)`, 3 floats per ray each: the mean colour and the
+    /// mean of its square, as `trt_variance` takes them.
+    pub fn radiance(&mut self, rays: &[[Float; 6]], samples_per_ray: u32, max_bounces: u32, background: Vec3, seed: u32,
+                    first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if rays.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 rays in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_radiance_params::default();
+        unsafe { sys::trt_radiance_params_default(&mut params) };
+        params.samples_per_ray = samples_per_ray;
+        params.max_bounces = max_bounces;
+        params.background = background.raw();
+        params.seed = seed;
+        params.first_stream = first_stream;
+        let mut radiance = vec![0.0 as Float; rays.len() * 3];
+        let mut moment2 = vec![0.0 as Float; rays.len() * 3];
+        check(unsafe {
+            sys::trt_radiance(scene, rays.as_ptr() as *const sys::trt_ray, rays.len() as u32, &params, radiance.as_mut_ptr(),
+                              moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.
     pub fn trim(&mut self) -> Result<(), Error> {
         if self.scene.is_null() {

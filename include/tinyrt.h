@@ -44,7 +44,8 @@ extern "C" {
  *              trt_denoise_device; trt_render_moments, trt_render_moments_device, trt_variance, trt_variance_device;
  *              trt_denoise_color, trt_denoise_color_default, trt_denoise_ex, trt_denoise_ex_device; trt_render_pixels,
  *              trt_render_pixels_device, trt_pixels_launch_plan, trt_select_pixels, trt_select_pixels_device,
- *              trt_select_scratch_bytes. */
+ *              trt_select_scratch_bytes; trt_radiance_params, trt_radiance_params_default, trt_radiance, trt_radiance_device,
+ *              trt_radiance_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -470,6 +471,58 @@ int trt_select_pixels_device(const float *d_accum, const float *d_moment2, uint3
                              uint32_t samples_done, const uint32_t *d_candidates, uint32_t n_candidates, float rel_tol, float abs_tol,
                              uint32_t *d_selected, uint32_t *d_count, void *d_scratch, uint64_t scratch_bytes, void *stream);
 uint64_t trt_select_scratch_bytes(uint32_t n_candidates);
+
+/* ---- Radiance queries: path tracing of caller-supplied rays ----
+ * The ray queries answer "what does this ray hit" for any ray; these answer "what light arrives along it": another camera (panorama,
+ * fisheye, orthographic, a lens model of the caller's own), baking (irradiance probes, lightmap texels: thousands of points with tens to
+ * hundreds of samples each), a sensor that is no image, or the render's own rays (trt_primary_rays) traced again with more samples.
+ *  - Path.  For ray i and sample s of 0..K, K = samples_per_ray, the colour c is CpuSampler::single_point_sampling (cpu.rs:39-65) for
+ *    ray i AS GIVEN: the direction is not normalised, as in trt_intersect and trt_sample_batch.
+ *  - RNG stream (seed, pixel = first_stream + i * K + s, sample = 0); no primary-ray draws are consumed.  This is trt_sample_batch's own
+ *    numbering (point j uses stream (seed, j, 0)) opened by an offset, and that is the reason for it: with K == 1 and first_stream == 0
+ *    radiance[i] is trt_sample_batch's out[i].color bit for bit, and every sample of any call can be checked against that entry point
+ *    (and the oracle's restatement of it) on a list with each ray repeated K times.
+ *  - Fold: the imager's own, per ray, in sample order, all f32, one IEEE operation per operator, nothing fused:
+ *      radiance.ch = radiance.ch + c.ch * inv_K;   moment2.ch = moment2.ch + (c.ch * c.ch) * inv_K;   inv_K = 1.0f / float(K)
+ *    `radiance` and `moment2` hold n x 3 f32; `moment2` may be NULL (not wanted).  trt_variance(radiance, moment2, n, K, ...) is then
+ *    the variance of each ray's estimate, and the pair feeds trt_select_pixels and the denoiser as a frame and its moments do.
+ *  - samples [sample_begin, sample_end) of 0..K are traced; sample_end == 0 means K.  accumulate == 0 starts the sums at 0, 1 continues
+ *    the ones in the buffers.  K fixes the 1 / K scale whatever the range, as samples_per_pixel does for a frame.
+ *  - Split invariance.  By samples: with K equal, [0, a) and then [a, K) with accumulate == 1 leave the bytes of one pass over [0, K).
+ *    By rays: rays [0, a) in one call and rays [a, n) in another with first_stream + a * K leave the bytes of one call over [0, n).
+ *  - Nothing to trace (an empty sample range, max_bounces == 0): the n entries are zeroed unless accumulate.  No byte outside [0, 12 n)
+ *    of either buffer is ever written.
+ *  - A ray with a NaN component hits nothing (the rule of the ray queries): its samples are `background`.
+ *  - stats / d_counters receive samples ([0]) and rays ([1]) only: there are no counting kernels.  `rays` counts the reference's
+ *    world.hit calls for these samples (cpu.rs:48) - what trt_sample_batch reports for the repeated list - whatever the kernel shares
+ *    between the samples of a ray (in most kernel shapes the closest hit of the caller's ray is found once per ray and call).  kernel_ms as in
+ *    trt_render_pixels.  `d_counters`: 16 uint64 as in trt_render_device, added to, or NULL.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL scene or params; with n > 0 a NULL `rays` or `radiance`;
+ *    samples_per_ray == 0; sample_begin > sample_end or sample_end > K (after the end == 0 rule); a non-zero reserved word;
+ *    first_stream + n * K > 2^32 (computed in 64 bits: the stream index must not wrap).  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the
+ *    host form's buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * trt_radiance: HOST buffers, synchronous; one device allocation for the call; the running sums are uploaded only when accumulate is set.
+ * trt_radiance_device: buffers in HBM on the calling thread's current device, asynchronous on `stream`; allocates nothing.
+ * Order, coherence and concurrency as for the ray queries: a wave works through a contiguous run of the caller's rays, each for all
+ * samples of the call; nothing is sorted. */
+typedef struct {
+    uint32_t samples_per_ray;     /* K >= 1: fixes the 1/K scale, as samples_per_pixel does for a frame */
+    uint32_t max_bounces;
+    trt_vec3 background;
+    uint32_t seed;
+    uint32_t sample_begin, sample_end;   /* samples [begin,end) of 0..K; end == 0 means K */
+    uint32_t accumulate;          /* 0: sums start at 0; 1: continue the sums in the buffers */
+    uint32_t first_stream;        /* RNG stream of sample 0 of ray 0 */
+    uint32_t reserved[6];         /* zero */
+} trt_radiance_params;            /* 64 B */
+void trt_radiance_params_default(trt_radiance_params *out);   /* K 1, max_bounces 50, background 0, seed 1, rest 0 */
+int trt_radiance(trt_scene *s, const trt_ray *rays, uint32_t n, const trt_radiance_params *p, float *radiance, float *moment2,
+                 trt_stats *stats);
+int trt_radiance_device(trt_scene *s, const trt_ray *d_rays, uint32_t n, const trt_radiance_params *p, float *d_radiance,
+                        float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_radiance[_device] launches n rays on this scene: trt_query_launch_plan's rule and fields (rays_per_wave = rays a wave owns, each
+ * for all samples of the call), over the radiance kernels' own table. */
+int trt_radiance_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

@@ -101,6 +101,15 @@ public:
         invalidate();
         return options_;
     }
+    // The light that arrives along caller-supplied rays (trt_radiance): each ray, used as given, is path traced with p.samples_per_ray
+    // samples and folded with the imager's 1 / K rule.  `radiance` and `moment2` (nullptr: not wanted) become 3 floats per ray, or
+    // continue the sums they hold when p.accumulate is set.  Start `p` from trt_radiance_params_default.
+    void radiance(const std::vector<trt_ray>& rays, const trt_radiance_params& p, std::vector<float>& radiance,
+                  std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(rays.size() * 3);
+        if (moment2) moment2->resize(rays.size() * 3);
+        check(trt_radiance(get_bvh(), rays.data(), (uint32_t)rays.size(), &p, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
     int num_geometries() const { return trt_world_num_geometries(w_); }
     const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).

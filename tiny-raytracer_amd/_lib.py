@@ -115,6 +115,14 @@ class DenoiseColor(C.Structure):
     _fields_ = [("variance", C.c_void_p), ("sigma_color", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class RadianceParams(C.Structure):
+    """tinyrt.h trt_radiance_params: samples, depth, RNG numbering and sample range of trt_radiance (64 bytes)."""
+    FIELDS = ("samples_per_ray", "max_bounces", "background", "seed", "sample_begin", "sample_end", "accumulate", "first_stream")
+    _fields_ = [("samples_per_ray", C.c_uint32), ("max_bounces", C.c_uint32), ("background", Vec3), ("seed", C.c_uint32),
+                ("sample_begin", C.c_uint32), ("sample_end", C.c_uint32), ("accumulate", C.c_uint32), ("first_stream", C.c_uint32),
+                ("reserved", C.c_uint32 * 6)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -203,6 +211,11 @@ SIGNATURES = {
     "trt_select_pixels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "trt_select_scratch_bytes": (C.c_uint64, [C.c_uint32]),
+    "trt_radiance_params_default": (None, [C.POINTER(RadianceParams)]),
+    "trt_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "trt_radiance_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -195,6 +195,55 @@ class Scene:
         check(lib.trt_pixels_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- radiance queries (tinyrt.h trt_radiance): path tracing of caller-supplied rays ----
+    @staticmethod
+    def _radiance_params(samples_per_ray, max_bounces=50, background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None,
+                         accumulate=False):
+        p = _lib.RadianceParams()
+        lib.trt_radiance_params_default(C.byref(p))
+        p.samples_per_ray, p.max_bounces, p.background, p.seed = int(samples_per_ray), int(max_bounces), _v(background), int(seed)
+        p.first_stream, p.sample_begin, p.sample_end = int(first_stream), int(sample_begin), 0 if sample_end is None else int(sample_end)
+        p.accumulate = 1 if accumulate else 0
+        if sample_end is not None and int(sample_end) == 0:
+            # tinyrt.h: sample_end == 0 means K; the empty range [0, 0) is asked for as begin == end elsewhere
+            raise ValueError("sample_end = 0 means samples_per_ray at the C boundary: pass None for that")
+        return p
+
+    def radiance(self, rays, samples_per_ray, max_bounces=50, background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0,
+                 sample_end=None, accumulate=False, radiance=None, moment2=None):
+        """trt_radiance: the light that arrives along rays float32 [n, 6] (origin, direction; used as given, never normalised), path
+        traced with samples [sample_begin, sample_end) of samples_per_ray = K per ray (None: K) and folded with the imager's 1 / K rule.
+        Sample s of ray i uses RNG stream (seed, first_stream + i * K + s, 0).  `radiance`, `moment2`: float32 [n, 3] to write or, with
+        accumulate, to continue (changed in place); radiance=None allocates one, moment2=None: True allocates one, None = not wanted.
+        Returns (radiance[n, 3], moment2 or None, stats with samples and rays)."""
+        r, _ = _rays_and_t_max(rays, None)
+        n = len(r)
+        p = self._radiance_params(samples_per_ray, max_bounces, background, seed, first_stream, sample_begin, sample_end, accumulate)
+        if radiance is None:
+            radiance = np.zeros((n, 3), np.float32)
+        if moment2 is True:
+            moment2 = np.zeros((n, 3), np.float32)
+        for a in (radiance, moment2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
+        st = Stats()
+        check(lib.trt_radiance(self._h, r.ctypes.data if n else None, n, C.byref(p), radiance.ctypes.data if n else None,
+                               moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        return radiance, moment2, st.as_dict()
+
+    def radiance_device(self, d_rays_ptr, n, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue radiance() on buffers already in HBM (device pointers as integers: n x 24 bytes of rays, n x 12 bytes of sums each) on
+        the current device; asynchronous on the stream, allocates nothing.  `params`: radiance()'s keywords, samples_per_ray included."""
+        p = self._radiance_params(**params)
+        check(lib.trt_radiance_device(self._h, C.c_void_p(d_rays_ptr), int(n), C.byref(p), C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr),
+                                      C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def radiance_plan(self, n, compute_units=0):
+        """trt_radiance_launch_plan: how radiance() launches n rays on this scene, as a dict with query_plan()'s fields (rays_per_wave =
+        rays a wave owns, each for all samples of the call)."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_radiance_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""

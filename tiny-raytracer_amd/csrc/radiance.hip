@@ -1,0 +1,344 @@
+// radiance.hip — radiance queries: path tracing of caller-supplied rays (tinyrt.h trt_radiance / trt_radiance_device), written for
+// gfx950 (CDNA4) only.
+//
+// The ray queries (query.hip) answer "what does this ray hit" for any ray; this unit answers "what light arrives along it": for ray i and
+// sample s the colour of CpuSampler::single_point_sampling (cpu.rs:39-65) for the ray as given, with RNG stream
+// (seed, first_stream + i * K + s, 0) - trt_sample_batch's numbering opened by an offset, so that every sample can be checked against the
+// oracle's restatement of that entry point on a list with each ray repeated K times - folded per ray with the imager's rule
+//   radiance.ch = radiance.ch + c.ch * inv_K;   moment2.ch = moment2.ch + (c.ch * c.ch) * inv_K
+// in sample order, one IEEE f32 operation per operator, in registers: a lane owns a ray for all samples of the call (pixels.hip's loop).
+//
+// There is no walk code in this file and no render kernel is touched: the kernel calls the entry points of rt_path.h with the dynamic LDS
+// laid out as the queries lay it out (scene copy | leaf stack: threads x slots x 8 bytes; the run, the place of the stack and the refill's
+// cursor step are wave_run.h's) and is launched by the rule of the queries (query_plan.h): a wave owns a contiguous run of the rays.
+//
+// Work: the wave runs in rounds - refill, start, SHADE what is pending, WALK what is alive.  A walk that ended in a round leaves its
+// (primitive, t) pending and is shaded at the top of the next, so shade_hit stays one call site.  The first segment of a ray is walked
+// once per ray and call, not once per sample (every walk but the lock-step list, where the two registers cost an occupancy step and
+// each sample walks): the closest hit of the caller's ray depends on nothing a sample draws, so when a ray's
+// first walk ends its (primitive, t) is kept in two registers and every later sample of that ray starts with it pending.  shade_hit
+// then receives the arguments a walk of its own would have given it, hence the same bits; the reference's world.hit call for that
+// segment (cpu.rs:48) is still counted once per sample.  TRT_RADIANCE_PLAIN_WALK = 1 builds the form in which every sample walks its
+// first segment (the A/B of tools/radiance_bench.py).
+#include "kernels.h"
+#include "query_plan.h"
+#include "rt_path.h"
+#include "scene_query.h"
+#include "wave_run.h"
+
+#ifndef TRT_RADIANCE_PLAIN_WALK
+#define TRT_RADIANCE_PLAIN_WALK 0
+#endif
+
+namespace trt {
+
+static_assert(sizeof(trt_radiance_params) == 64, "trt_radiance_params layout (tinyrt.h)");
+
+struct RadianceArgs {
+    const float* rays;               // n x (origin, direction), used as given
+    float* radiance;                 // n x 3
+    float* moment2;                  // n x 3, or nullptr: not wanted
+    unsigned long long* counters;    // nullptr, or [CTR_SAMPLES], [CTR_RAYS] are added to
+    uint32_t n, rays_per_wave;       // wave w owns rays [w * rays_per_wave, ...)
+    uint32_t slots, stragglers;      // as in query.hip QueryArgs
+    uint32_t samples_per_ray;        // K
+    uint32_t first_stream;           // first_stream + n * K <= 2^32 (radiance_check): the stream index never wraps
+};
+
+TRT_DEV Ray rad_load_ray(const float* __restrict__ rays, uint32_t idx) {
+    const float* r = rays + 6ull * idx;
+    Ray ray;
+    ray.o = v3(r[0], r[1], r[2]);
+    ray.d = v3(r[3], r[4], r[5]);
+    return ray;
+}
+
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_radiance: nothing to trace launches radiance_zero_kernel or nothing)
+template <int MODE, int WALK, int THREADS, int MINW>
+__global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, RenderArgs ra, RadianceArgs ga, const float4* __restrict__ leaf_list,
+                                                                      const uint4* __restrict__ nodes16) {
+    stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const float* __restrict__ const rays = ga.rays;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long begin64 = wave_begin<THREADS>(ga.rays_per_wave);
+    if (begin64 >= ga.n) return;                                            // (after the barriers above)
+    const uint32_t begin = (uint32_t)begin64;
+    const uint32_t count = wave_count(ga.n, ga.rays_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * ga.slots) + lane : nullptr;
+    const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
+    Counters<false> ctr;
+    constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
+    // the first segment is walked once per ray where keeping its (primitive, t) costs no occupancy: every walk but the lock-step list
+    constexpr bool kShareFirst = !TRT_RADIANCE_PLAIN_WALK && WALK != WALK_FLAT;
+
+    uint32_t cursor = 0;                                                    // wave-uniform
+    bool own = false, has_path = false, walking = false;                    // the lane owns a ray; a path of it is under way; its walk is parked
+    bool pending = false, have_first = false;                               // a finished walk waits for its shade; the ray's first hit is known
+    uint32_t idx = 0, s = 0;
+    uint32_t hit_prim = PRIM_NONE, first_prim = PRIM_NONE;
+    float hit_t = 0.0f, first_t = 0.0f;
+    uint32_t n_samples = 0, n_rays = 0;
+    V3 acc = v3(0.0f, 0.0f, 0.0f), m2 = v3(0.0f, 0.0f, 0.0f);
+    Path p;
+    p.ray.o = v3(0.0f, 0.0f, 0.0f); p.ray.d = v3(0.0f, 0.0f, 0.0f);
+    p.color = v3(0.0f, 0.0f, 0.0f); p.atten = v3(0.0f, 0.0f, 0.0f);
+    p.remain = 0u;
+    p.rng.s0 = 0u; p.rng.s1 = 0u;
+    for (;;) {
+        // ---- refill: every lane without a ray takes the next one of the run (begin + item < n: item < count <= n - begin) ----
+        const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
+        if (need != 0ull && cursor < count) {
+            const uint32_t item = cursor + wave_rank(need);
+            if (!own && item < count) {
+                idx = begin + item;
+                s = ra.sample_begin;
+                if (ra.accumulate) {
+                    const float* const a = ga.radiance + 3ull * idx;
+                    acc = v3(a[0], a[1], a[2]);
+                    if (ga.moment2) { const float* const m = ga.moment2 + 3ull * idx; m2 = v3(m[0], m[1], m[2]); }
+                } else {
+                    acc = v3(0.0f, 0.0f, 0.0f);
+                    m2 = v3(0.0f, 0.0f, 0.0f);
+                }
+                have_first = false;
+                own = true;
+            }
+            cursor = wave_advance(cursor, need, count);
+        }
+        if (__builtin_amdgcn_ballot_w64(own) == 0ull) break;                // every lane is free and none could take a ray: the run is done
+        if (own) {
+            // ---- start: the ray's next sample (cpu.rs:42-45 with the caller's ray; no primary-ray draws) ----
+            if (!has_path) {
+                p.rng = rng_seed(ra.seed_key, ga.first_stream + idx * ga.samples_per_ray + s, 0u);
+                p.ray = rad_load_ray(rays, idx);                            // re-read: 24 bytes per sample against six registers per lane
+                p.color = v3(0.0f, 0.0f, 0.0f);
+                p.atten = v3(1.0f, 1.0f, 1.0f);
+                p.remain = ra.max_bounces;
+                has_path = true;
+                n_samples++;
+                if (have_first) {                                           // the first segment's walk, done once for the ray
+                    hit_prim = first_prim; hit_t = first_t;
+                    pending = true;
+                    n_rays++;                                               // the reference's world.hit of this sample (cpu.rs:48)
+                }
+            }
+            // ---- shade what is pending ----
+            if (pending) {
+                pending = false;
+                if (shade_hit<MODE, false>(sc, p, hit_prim, hit_t, background, ctr)) {
+                    // imager.rs:35,50 and the second moment beside it, in the operation order of pixels_kernel
+                    acc = acc + p.color * ra.inv_spp;
+                    m2.x = m2.x + (p.color.x * p.color.x) * ra.inv_spp;
+                    m2.y = m2.y + (p.color.y * p.color.y) * ra.inv_spp;
+                    m2.z = m2.z + (p.color.z * p.color.z) * ra.inv_spp;
+                    has_path = false;
+                    s += 1u;
+                    if (s == ra.sample_end) {
+                        float* const a = ga.radiance + 3ull * idx;
+                        a[0] = acc.x; a[1] = acc.y; a[2] = acc.z;
+                        if (ga.moment2) { float* const m = ga.moment2 + 3ull * idx; m[0] = m2.x; m[1] = m2.y; m[2] = m2.z; }
+                        own = false;
+                    }
+                }
+            }
+            // ---- walk what is alive ----
+            if (has_path) {
+                bool done = true;
+                if constexpr (kResumable) {
+                    Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, p.ray, false);      // a new walk, or the frame of a parked one
+                    if (walking) trav_unpark(stack, tr); else { tr.t_best = __builtin_inff(); n_rays++; }
+                    const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+                    walking = !closest_hit_resume<MODE, false, WALK, false>(sc, p.ray, tr, ctr, ga.slots, stack, leaf_list, nodes16, ga.stragglers, entered);
+                    done = !walking;
+                    hit_prim = tr.prim_best; hit_t = tr.t_best;
+                } else {
+                    n_rays++;
+                    hit_prim = closest_hit<MODE, false, WALK, false>(sc, p.ray, false, hit_t, ctr, ga.slots, stack, leaf_list, nodes16, flat_reuse);
+                }
+                if (done) {
+                    pending = true;
+                    if constexpr (kShareFirst) {
+                        if (p.remain == ra.max_bounces) { first_prim = hit_prim; first_t = hit_t; have_first = true; }  // the caller's ray itself
+                    }
+                }
+            }
+        }
+    }
+    flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
+}
+
+// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the n entries become 0.
+__global__ __launch_bounds__(256) void radiance_zero_kernel(unsigned long long n3, float* __restrict__ radiance, float* __restrict__ moment2) {
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;         // n3 = 3 n: the floats of [0, 12 n)
+    if (i >= n3) return;
+    radiance[i] = 0.0f;
+    if (moment2) moment2[i] = 0.0f;
+}
+
+namespace {
+
+#define TRT_RADIANCE(MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&radiance_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// the (scene mode, walk, workgroup shape) set of the sparse render's table, with the register-slot fallback (query_plan.h), so that every
+// scene has a kernel.  A lane carries what a lane of pixels_kernel carries plus the pending and the first (primitive, t): the launch
+// bounds are the highest at which the instantiation uses no scratch memory (profiles/radiance_resource_usage.txt).  The plan reports
+// the bound (kernel_waves_per_simd).  The lock-step list keeps no first (primitive, t) (kShareFirst): with it that instantiation needs 76
+// registers and drops from 7 waves per SIMD to 6; without it all six shapes run at 7.
+const BatchKernel kRadianceKernels[] = {
+    TRT_RADIANCE(MODE_LDS, WALK_FLAT, 256, 7),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 256, 7),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 768, 7),
+    TRT_RADIANCE(MODE_LDS, WALK_REGS, 512, 7),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_COMPACT, 256, 7),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_REGS, 256, 7),
+};
+#undef TRT_RADIANCE
+constexpr size_t kRadianceShapes = sizeof(kRadianceKernels) / sizeof(kRadianceKernels[0]);
+
+hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_rays, uint32_t n, uint32_t samples_per_ray, uint32_t first_stream,
+                           float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
+        // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
+        if (ra.accumulate) return hipSuccess;
+        const unsigned long long n3 = 3ull * n;
+        hipLaunchKernelGGL(radiance_zero_kernel, dim3((uint32_t)((n3 + 255ull) / 256ull)), dim3(256), 0, stream, n3, d_radiance, d_moment2);
+        return hipGetLastError();
+    }
+    SceneDev scd = qs.scene;
+    BatchLaunch b;
+    const hipError_t e = batch_prepare(scd, n, kRadianceKernels, kRadianceShapes, b);
+    if (e != hipSuccess) return e;
+    const trt_query_plan& q = b.q;
+    ra.flat_reuse = qs.flat_reuse;
+    RadianceArgs ga{d_rays, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, samples_per_ray, first_stream};
+    void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
+    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
+    timing_mark(stream, true);
+    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    timing_mark(stream, false);
+    return le;
+}
+
+// What both forms check before any device work, and the kernel arguments of the parameters.
+int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, const float* radiance, RenderArgs& ra) {
+    if (!s || !p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (n > 0u && (!rays || !radiance)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
+    const uint32_t K = p->samples_per_ray;
+    if (K == 0u) return query_fail(TRT_ERR_INVALID_ARG, "samples_per_ray must be positive");
+    const uint32_t s1 = p->sample_end == 0u ? K : p->sample_end;
+    if (p->sample_begin > s1 || s1 > K) return query_fail(TRT_ERR_INVALID_ARG, "sample range must satisfy begin <= end <= samples_per_ray");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    // the last stream index, first_stream + n * K - 1, must fit 32 bits (n * K < 2^64: both are below 2^32)
+    if ((unsigned long long)p->first_stream + (unsigned long long)n * K > 0x100000000ull)
+        return query_fail(TRT_ERR_INVALID_ARG, "first_stream + n * samples_per_ray exceeds 2^32 RNG streams");
+    ra = RenderArgs{};
+    ra.background[0] = p->background.x; ra.background[1] = p->background.y; ra.background[2] = p->background.z;
+    ra.inv_spp = 1.0f / (float)K;
+    ra.max_bounces = p->max_bounces;
+    ra.seed_key = rng_seed_key(p->seed);
+    ra.sample_begin = p->sample_begin;
+    ra.sample_end = s1;
+    ra.accumulate = p->accumulate ? 1u : 0u;
+    return TRT_OK;
+}
+
+}  // namespace
+}  // namespace trt
+
+extern "C" {
+
+void trt_radiance_params_default(trt_radiance_params* out) {
+    if (!out) return;
+    *out = trt_radiance_params{};
+    out->samples_per_ray = 1u;
+    out->max_bounces = 50u;
+    out->seed = 1u;
+}
+
+int trt_radiance_device(trt_scene* s, const trt_ray* d_rays, uint32_t n, const trt_radiance_params* p, float* d_radiance, float* d_moment2,
+                        uint64_t* d_counters, void* stream) {
+    trt::RenderArgs ra;
+    int rc = trt::radiance_check(s, d_rays, n, p, d_radiance, ra);
+    if (rc != TRT_OK) return rc;
+    if (n == 0u) return TRT_OK;
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    trt::QueryScene qs;
+    rc = trt::query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = trt::launch_radiance(qs, ra, reinterpret_cast<const float*>(d_rays), n, p->samples_per_ray, p->first_stream, d_radiance,
+                                              d_moment2, reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return trt::query_fail_hip(e, "radiance query launch");
+    return TRT_OK;
+}
+
+// Host buffers: device copies of the rays and of the two sums are the call's own (one allocation), one stream-ordered sequence on the
+// default stream, complete when the call returns.  The running sums go up only when the call continues them.
+int trt_radiance(trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, float* radiance, float* moment2, trt_stats* stats) {
+    trt::RenderArgs ra;
+    int rc = trt::radiance_check(s, rays, n, p, radiance, ra);
+    if (rc != TRT_OK) return rc;
+    if (n == 0u) {
+        if (stats) *stats = trt_stats{};
+        return TRT_OK;
+    }
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    trt::QueryScene qs;
+    rc = trt::query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
+    const size_t off_rad = trt::q_align16(rays_b), off_m2 = off_rad + trt::q_align16(sums);
+    const size_t off_ctr = off_m2 + (moment2 ? trt::q_align16(sums) : 0u), total = off_ctr + trt::CTR_COUNT * sizeof(unsigned long long);
+    char* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
+    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("radiance query buffers: ") + hipGetErrorString(e)); }
+    float* const d_rad = reinterpret_cast<float*>(d + off_rad);
+    float* const d_m2 = moment2 ? reinterpret_cast<float*>(d + off_m2) : nullptr;
+    unsigned long long* const d_ctr = reinterpret_cast<unsigned long long*>(d + off_ctr);
+    unsigned long long h_ctr[trt::CTR_COUNT] = {0};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.0f;
+    const char* what = "hipMemcpy of the rays";
+    e = hipMemcpy(d, rays, rays_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { what = "hipMemset of the counters"; e = hipMemset(d_ctr, 0, sizeof(h_ctr)); }
+    // the running sums a pass continues go up; a pass that starts them reads nothing
+    if (e == hipSuccess && ra.accumulate) { what = "hipMemcpy of the sums"; e = hipMemcpy(d_rad, radiance, sums, hipMemcpyHostToDevice); }
+    if (e == hipSuccess && ra.accumulate && d_m2) { what = "hipMemcpy of the second moments"; e = hipMemcpy(d_m2, moment2, sums, hipMemcpyHostToDevice); }
+    if (e == hipSuccess) { what = "hipEventCreate"; e = hipEventCreate(&ev0); }
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev0, nullptr); }
+    if (e == hipSuccess) {
+        what = "radiance query launch";
+        e = trt::launch_radiance(qs, ra, reinterpret_cast<const float*>(d), n, p->samples_per_ray, p->first_stream, d_rad, d_m2, d_ctr, nullptr);
+    }
+    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev1, nullptr); }
+    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
+    if (e == hipSuccess && wrote) { what = "hipMemcpy of the results"; e = hipMemcpy(radiance, d_rad, sums, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
+    if (e == hipSuccess && wrote && d_m2) e = hipMemcpy(moment2, d_m2, sums, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) { what = "hipMemcpy of the counters"; e = hipMemcpy(h_ctr, d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost); }
+    if (e == hipSuccess) { what = "hipEventElapsedTime"; e = hipEventSynchronize(ev1); if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1); }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(d);
+    if (e != hipSuccess) return trt::query_fail_hip(e, what);
+    if (stats) {
+        *stats = trt_stats{};
+        stats->samples = h_ctr[trt::CTR_SAMPLES];
+        stats->rays = h_ctr[trt::CTR_RAYS];
+        stats->kernel_ms = ms;
+    }
+    return TRT_OK;
+}
+
+// How launch_radiance would launch n rays on this scene.
+int trt_radiance_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kRadianceKernels, trt::kRadianceShapes, out);
+}
+
+}  // extern "C"
