@@ -230,6 +230,13 @@ hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t s) {
     hipstub_enqueue(s, [=] { hipstub_log("memset", dst, nullptr, bytes, 1, bytes); memset(dst, value, bytes); });
     return hipSuccess;
 }
+hipError_t hipMemset(void* dst, int value, size_t bytes) {
+    if (inject("hipMemset")) return ret(hipErrorUnknown);
+    hipstub_stream* st = resolve(nullptr);
+    hipstub_enqueue(nullptr, [=] { memset(dst, value, bytes); });
+    st->drain();
+    return hipSuccess;
+}
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     if (inject("hipStreamCreate")) { *s = nullptr; return ret(hipErrorOutOfMemory); }
     hipstub_stream* st = make_stream(t_device);
@@ -317,6 +324,7 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
+    if (inject("hipEventElapsedTime")) return ret(hipErrorUnknown);
     if (!live_event(a) || !live_event(b)) return ret(hipErrorInvalidValue);
     if (a->device != b->device) return ret(hipErrorInvalidValue);          // the real runtime refuses events of two devices
     std::scoped_lock lock(a->mu, b->mu);

@@ -94,3 +94,18 @@ def test_capi_host_logic_under_asan_ubsan(tmp_path):
     exe = _build_capi_host_check(tmp_path, "address,undefined")
     r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
     assert r.returncode == 0 and "ok all" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def test_host_stage_under_asan_ubsan(tmp_path):
+    """The staging helper of the host-buffer forms (csrc/host_stage.h: trt_intersect, trt_radiance, trt_render_aov, ... go through it) and
+    their exception guard, on the simulated runtime: the layout against the forms' formulas, a form whose "kernel" is a task on the
+    default stream, every HIP call of the helper failing once at every position (status, message, no later step, no leak, the next
+    call works), and std::bad_alloc thrown with the allocation and the events alive."""
+    exe = str(tmp_path / "host_stage_check")
+    n = os.path.join(ROOT, "tests", "native")
+    c = os.path.join(ROOT, "tiny-raytracer_amd", "csrc")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(n, "hipstub"),
+                    "-x", "c++", os.path.join(c, "capi.hip"), os.path.join(c, "scene_host.cpp"), os.path.join(n, "launch_stub.cpp"),
+                    os.path.join(n, "hipstub", "hipstub.cpp"), os.path.join(n, "host_stage_check.cpp"), "-lpthread", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=120)
+    assert r.returncode == 0 and "ok all" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -273,22 +273,21 @@ int trt_primary_rays_device(const trt_camera* cam, const trt_render_params* p, u
 
 // Host buffer: a device copy of the call's own on the default stream, complete when the call returns.
 int trt_primary_rays(const trt_camera* cam, const trt_render_params* p, uint32_t s, trt_ray* rays) {
-    trt::RenderArgs ra;
-    trt::CameraDev cd;
-    uint32_t rows = 0;
-    const int rc = trt::rays_check(cam, p, s, rays, ra, rows, cd);
-    if (rc != TRT_OK) return rc;
-    const uint32_t n = rows * cam->width;
-    if (n == 0) return TRT_OK;
-    trt_ray* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * sizeof(trt_ray));
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("primary ray buffer: ") + hipGetErrorString(e)); }
-    const char* what = "primary ray launch";
-    e = trt::launch_primary_rays(cd, ra, s, n, d, nullptr);
-    if (e == hipSuccess) { what = "hipMemcpy of the rays"; e = hipMemcpy(rays, d, (size_t)n * sizeof(trt_ray), hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        trt::RenderArgs ra;
+        trt::CameraDev cd;
+        uint32_t rows = 0;
+        const int rc = trt::rays_check(cam, p, s, rays, ra, rows, cd);
+        if (rc != TRT_OK) return rc;
+        const uint32_t n = rows * cam->width;
+        if (n == 0) return TRT_OK;
+        trt::HostStage st("primary ray buffer");
+        const size_t r_rays = st.reserve((size_t)n * sizeof(trt_ray));
+        st.alloc();
+        if (st.ok()) st.run(trt::launch_primary_rays(cd, ra, s, n, st.ptr<trt_ray>(r_rays), nullptr), "primary ray launch");
+        st.down(rays, r_rays, (size_t)n * sizeof(trt_ray), "hipMemcpy of the rays");
+        return st.finish();
+    });
 }
 
 int trt_render_aov_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const trt_aov_buffers* d_buffers, void* stream) {
@@ -307,46 +306,32 @@ int trt_render_aov_device(trt_scene* s, const trt_camera* cam, const trt_render_
 
 // Host buffers: device copies of the ones wanted, one stream-ordered sequence on the default stream, complete when the call returns.
 int trt_render_aov(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const trt_aov_buffers* buffers) {
-    trt::RenderArgs ra;
-    trt::CameraDev cd;
-    uint32_t rows = 0;
-    int rc = trt::aov_check(s, cam, p, buffers, ra, rows, cd);
-    if (rc != TRT_OK) return rc;
-    const uint32_t n = rows * cam->width;
-    if (n == 0) return TRT_OK;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    void* const host[6] = {buffers->albedo, buffers->normal, buffers->depth, buffers->coverage, buffers->geometry, buffers->material};
-    const size_t item[6] = {12u, 12u, 4u, 4u, 4u, 4u};
-    size_t off[6], total = 0;
-    for (int i = 0; i < 6; i++) { off[i] = total; if (host[i]) total += trt::q_align16((size_t)n * item[i]); }
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("feature buffers: ") + hipGetErrorString(e)); }
-    // what the pass does not write goes up first: the running sums it continues, the indices if it does not hold sample 0
-    const bool up[6] = {ra.accumulate != 0u, ra.accumulate != 0u, ra.accumulate != 0u, ra.accumulate != 0u,
-                        !(ra.sample_begin == 0u && ra.sample_end > 0u), !(ra.sample_begin == 0u && ra.sample_end > 0u)};
-    const char* what = "hipMemcpy of the buffers";
-    for (int i = 0; i < 6 && e == hipSuccess; i++)
-        if (host[i] && up[i]) e = hipMemcpy(d + off[i], host[i], (size_t)n * item[i], hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        trt_aov_buffers db;
-        db.albedo = buffers->albedo ? reinterpret_cast<float*>(d + off[0]) : nullptr;
-        db.normal = buffers->normal ? reinterpret_cast<float*>(d + off[1]) : nullptr;
-        db.depth = buffers->depth ? reinterpret_cast<float*>(d + off[2]) : nullptr;
-        db.coverage = buffers->coverage ? reinterpret_cast<float*>(d + off[3]) : nullptr;
-        db.geometry = buffers->geometry ? reinterpret_cast<uint32_t*>(d + off[4]) : nullptr;
-        db.material = buffers->material ? reinterpret_cast<uint32_t*>(d + off[5]) : nullptr;
-        what = "feature buffer launch";
-        e = trt::launch_aov(qs, cd, ra, n, db, nullptr);
-    }
-    what = e == hipSuccess ? "hipMemcpy of the results" : what;
-    for (int i = 0; i < 6 && e == hipSuccess; i++)
-        if (host[i]) e = hipMemcpy(host[i], d + off[i], (size_t)n * item[i], hipMemcpyDeviceToHost);      // (waits for the kernel: same stream)
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        trt::RenderArgs ra;
+        trt::CameraDev cd;
+        uint32_t rows = 0;
+        int rc = trt::aov_check(s, cam, p, buffers, ra, rows, cd);
+        if (rc != TRT_OK) return rc;
+        const uint32_t n = rows * cam->width;
+        if (n == 0) return TRT_OK;
+        trt::QueryScene qs;
+        rc = trt::query_scene_on_device(s, qs);
+        if (rc != TRT_OK) return rc;
+        void* const host[6] = {buffers->albedo, buffers->normal, buffers->depth, buffers->coverage, buffers->geometry, buffers->material};
+        const size_t item[6] = {12u, 12u, 4u, 4u, 4u, 4u};
+        trt::HostStage st("feature buffers");
+        size_t r[6];
+        for (int i = 0; i < 6; i++) r[i] = st.reserve(trt::q_align16((size_t)n * item[i]), host[i] != nullptr);      // (whole 16s: the last one too)
+        st.alloc();
+        // what the pass does not write goes up first: the running sums it continues, the indices if it does not hold sample 0
+        const bool sums_up = ra.accumulate != 0u, indices_up = !(ra.sample_begin == 0u && ra.sample_end > 0u);
+        for (int i = 0; i < 6; i++)
+            if (i < 4 ? sums_up : indices_up) st.up(r[i], host[i], (size_t)n * item[i], "hipMemcpy of the buffers");
+        const trt_aov_buffers db{st.ptr<float>(r[0]), st.ptr<float>(r[1]), st.ptr<float>(r[2]), st.ptr<float>(r[3]), st.ptr<uint32_t>(r[4]), st.ptr<uint32_t>(r[5])};
+        if (st.ok()) st.run(trt::launch_aov(qs, cd, ra, n, db, nullptr), "feature buffer launch");
+        for (int i = 0; i < 6; i++) st.down(host[i], r[i], (size_t)n * item[i], "hipMemcpy of the results");
+        return st.finish();
+    });
 }
 
 // How launch_aov would launch a local image of n_pixels on this scene.

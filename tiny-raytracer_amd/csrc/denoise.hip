@@ -34,7 +34,7 @@
 #include <string>
 
 #include "../../include/tinyrt.h"
-#include "scene_query.h"
+#include "host_stage.h"
 
 namespace trt {
 namespace {
@@ -354,11 +354,9 @@ bool dn_choose_lds(DnVariant v, int step) {
         default: CALL(15u); break;                                                                 \
     }
 
-size_t dn_align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
-
 // The caller's scratch: up to 15 bytes to reach a 16-byte boundary, then four images of 16 bytes per pixel - colour A, colour B, G0, G1.
 // (The plain form uses the first two as 12-byte images and, with the colour term on, the first 4 bytes per pixel of the other two for v_i.)
-uint64_t dn_scratch_bytes(uint32_t width, uint32_t height) { return 16u + 4u * (uint64_t)dn_align16((size_t)width * height * 16u); }
+uint64_t dn_scratch_bytes(uint32_t width, uint32_t height) { return 16u + 4u * (uint64_t)q_align16((size_t)width * height * 16u); }
 
 struct DnPlan {
     trt_denoise_params p;
@@ -432,7 +430,7 @@ hipError_t dn_launch_lds(const DnPass& a, dim3 grid, uint32_t lds, const float4*
 // All passes on `stream`; every buffer is on the device.  Nothing is allocated.
 hipError_t dn_launch(const trt_denoise_inputs& in, uint32_t width, uint32_t height, const DnPlan& plan, float* d_out, void* d_scratch, hipStream_t stream) {
     const size_t n = (size_t)width * height;
-    const size_t image = dn_align16(n * 16u);
+    const size_t image = q_align16(n * 16u);
     char* const base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(d_scratch) + 15u) & ~(uintptr_t)15u);
     const DnVariant variant = dn_variant_from_env();
     const uint32_t flags = plan.flags;
@@ -559,44 +557,30 @@ int trt_denoise_device(const trt_denoise_inputs* d_in, uint32_t width, uint32_t 
 // Host buffers: device copies of the call's own, one stream-ordered sequence on the default stream, complete when the call returns.
 int trt_denoise_ex(const trt_denoise_inputs* in, const trt_denoise_color* color, uint32_t width, uint32_t height, const trt_denoise_params* params,
                    float* out) {
-    trt::DnPlan plan;
-    int rc = trt::dn_check(in, width, height, params, out, plan);
-    if (rc != TRT_OK) return rc;
-    rc = trt::dn_check_colour(color, width, height, out, plan);
-    if (rc != TRT_OK) return rc;
-    rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    const size_t n = (size_t)width * height;
-    const void* const host[5] = {in->color, (plan.flags & trt::kDnAlbedo) ? in->albedo : nullptr, (plan.flags & trt::kDnNormal) ? in->normal : nullptr,
-                                 (plan.flags & trt::kDnDepth) ? in->depth : nullptr, (plan.flags & trt::kDnColour) ? plan.variance : nullptr};
-    const size_t item[5] = {12u, 12u, 12u, 4u, 4u};
-    size_t off[5], total = 0;
-    for (int i = 0; i < 5; i++) { off[i] = total; if (host[i]) total += trt::dn_align16(n * item[i]); }
-    const size_t off_out = total;
-    total += trt::dn_align16(n * 12u);
-    const size_t off_scratch = total;
-    const uint64_t scratch = trt::dn_scratch_bytes(width, height);
-    total += (size_t)scratch;
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("denoise buffers: ") + hipGetErrorString(e)); }
-    const char* what = "hipMemcpy of the inputs";
-    for (int i = 0; i < 5 && e == hipSuccess; i++)
-        if (host[i]) e = hipMemcpy(d + off[i], host[i], n * item[i], hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        trt_denoise_inputs din;
-        din.color = reinterpret_cast<const float*>(d + off[0]);
-        din.albedo = host[1] ? reinterpret_cast<const float*>(d + off[1]) : nullptr;
-        din.normal = host[2] ? reinterpret_cast<const float*>(d + off[2]) : nullptr;
-        din.depth = host[3] ? reinterpret_cast<const float*>(d + off[3]) : nullptr;
-        plan.variance = host[4] ? reinterpret_cast<const float*>(d + off[4]) : nullptr;
-        what = "denoise launch";
-        e = trt::dn_launch(din, width, height, plan, reinterpret_cast<float*>(d + off_out), d + off_scratch, nullptr);
-    }
-    if (e == hipSuccess) { what = "hipMemcpy of the result"; e = hipMemcpy(out, d + off_out, n * 12u, hipMemcpyDeviceToHost); }      // (waits for the kernels: same stream)
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        trt::DnPlan plan;
+        int rc = trt::dn_check(in, width, height, params, out, plan);
+        if (rc != TRT_OK) return rc;
+        rc = trt::dn_check_colour(color, width, height, out, plan);
+        if (rc != TRT_OK) return rc;
+        rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        const size_t n = (size_t)width * height;
+        const void* const host[5] = {in->color, (plan.flags & trt::kDnAlbedo) ? in->albedo : nullptr, (plan.flags & trt::kDnNormal) ? in->normal : nullptr,
+                                     (plan.flags & trt::kDnDepth) ? in->depth : nullptr, (plan.flags & trt::kDnColour) ? plan.variance : nullptr};
+        const size_t item[5] = {12u, 12u, 12u, 4u, 4u};
+        trt::HostStage st("denoise buffers");
+        size_t r[5];
+        for (int i = 0; i < 5; i++) r[i] = st.reserve(n * item[i], host[i] != nullptr);
+        const size_t r_out = st.reserve(n * 12u), r_scratch = st.reserve((size_t)trt::dn_scratch_bytes(width, height));
+        st.alloc();
+        for (int i = 0; i < 5; i++) st.up(r[i], host[i], n * item[i], "hipMemcpy of the inputs");
+        const trt_denoise_inputs din{st.ptr<float>(r[0]), st.ptr<float>(r[1]), st.ptr<float>(r[2]), st.ptr<float>(r[3])};
+        plan.variance = st.ptr<float>(r[4]);
+        if (st.ok()) st.run(trt::dn_launch(din, width, height, plan, st.ptr<float>(r_out), st.ptr<char>(r_scratch), nullptr), "denoise launch");
+        st.down(out, r_out, n * 12u, "hipMemcpy of the result");
+        return st.finish();
+    });
 }
 
 int trt_denoise(const trt_denoise_inputs* in, uint32_t width, uint32_t height, const trt_denoise_params* params, float* out) {

@@ -371,81 +371,58 @@ int trt_render_pixels_device(trt_scene* s, const trt_camera* cam, const trt_rend
 // on the default stream, complete when the call returns.  Only the listed pixels are copied back into the caller's buffers.
 int trt_render_pixels(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const uint32_t* pixels, uint32_t n, float* accum,
                       float* moment2, trt_stats* stats) {
-    trt::RenderArgs ra;
-    trt::CameraDev cd;
-    uint32_t npixels = 0;
-    int rc = trt::pixels_check(s, cam, p, pixels, n, accum, ra, npixels, cd);
-    if (rc != TRT_OK) return rc;
-    {
-        std::vector<uint64_t> seen(((size_t)npixels + 63u) / 64u, 0ull);
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t pix = pixels[i];
-            if (pix >= npixels) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " at entry " + std::to_string(i) + " is outside the local image");
-            if (seen[pix >> 6] >> (pix & 63u) & 1ull) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " is listed twice");
-            seen[pix >> 6] |= 1ull << (pix & 63u);
+    return trt::host_form([&]() -> int {
+        trt::RenderArgs ra;
+        trt::CameraDev cd;
+        uint32_t npixels = 0;
+        int rc = trt::pixels_check(s, cam, p, pixels, n, accum, ra, npixels, cd);
+        if (rc != TRT_OK) return rc;
+        {
+            std::vector<uint64_t> seen(((size_t)npixels + 63u) / 64u, 0ull);
+            for (uint32_t i = 0; i < n; i++) {
+                const uint32_t pix = pixels[i];
+                if (pix >= npixels) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " at entry " + std::to_string(i) + " is outside the local image");
+                if (seen[pix >> 6] >> (pix & 63u) & 1ull) return trt::query_fail(TRT_ERR_INVALID_ARG, "pixel index " + std::to_string(pix) + " is listed twice");
+                seen[pix >> 6] |= 1ull << (pix & 63u);
+            }
         }
-    }
-    if (n == 0u) {
-        if (stats) *stats = trt_stats{};
-        return TRT_OK;
-    }
-    rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u;
-    const size_t off_list = 0, off_acc = trt::q_align16(list), off_m2 = off_acc + trt::q_align16(frame);
-    const size_t off_ctr = off_m2 + (moment2 ? trt::q_align16(frame) : 0u), total = off_ctr + trt::CTR_COUNT * sizeof(unsigned long long);
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("sparse render buffers: ") + hipGetErrorString(e)); }
-    float* const d_acc = reinterpret_cast<float*>(d + off_acc);
-    float* const d_m2 = moment2 ? reinterpret_cast<float*>(d + off_m2) : nullptr;
-    unsigned long long* const d_ctr = reinterpret_cast<unsigned long long*>(d + off_ctr);
-    unsigned long long h_ctr[trt::CTR_COUNT] = {0};
-    std::vector<float> back(3u * (size_t)npixels);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.0f;
-    const char* what = "hipMemcpy of the list";
-    e = hipMemcpy(d + off_list, pixels, list, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { what = "hipMemset of the counters"; e = hipMemset(d_ctr, 0, sizeof(h_ctr)); }
-    // the running sums a pass continues go up; a pass that starts them reads nothing
-    if (e == hipSuccess && ra.accumulate) { what = "hipMemcpy of the frame"; e = hipMemcpy(d_acc, accum, frame, hipMemcpyHostToDevice); }
-    if (e == hipSuccess && ra.accumulate && d_m2) { what = "hipMemcpy of the second moments"; e = hipMemcpy(d_m2, moment2, frame, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) { what = "hipEventCreate"; e = hipEventCreate(&ev0); }
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev0, nullptr); }
-    if (e == hipSuccess) {
-        what = "sparse render launch";
-        e = trt::launch_pixels(qs, cd, ra, npixels, reinterpret_cast<const uint32_t*>(d + off_list), n, nullptr, d_acc, d_m2, d_ctr, nullptr);
-    }
-    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev1, nullptr); }
-    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
-    for (int b = 0; b < 2 && e == hipSuccess && wrote; b++) {
-        float* const host = b == 0 ? accum : moment2;
-        if (!host) continue;
-        what = "hipMemcpy of the results";
-        e = hipMemcpy(back.data(), b == 0 ? d_acc : d_m2, frame, hipMemcpyDeviceToHost);       // (waits for the kernel: same stream)
-        if (e != hipSuccess) break;
-        for (uint32_t i = 0; i < n; i++) {
-            const size_t o = 3u * (size_t)pixels[i];
-            host[o] = back[o]; host[o + 1u] = back[o + 1u]; host[o + 2u] = back[o + 2u];
+        if (n == 0u) {
+            if (stats) *stats = trt_stats{};
+            return TRT_OK;
         }
-    }
-    if (e == hipSuccess) { what = "hipMemcpy of the counters"; e = hipMemcpy(h_ctr, d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost); }
-    if (e == hipSuccess) { what = "hipEventElapsedTime"; e = hipEventSynchronize(ev1); if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    if (stats) {
-        *stats = trt_stats{};
-        stats->samples = h_ctr[trt::CTR_SAMPLES];
-        stats->rays = h_ctr[trt::CTR_RAYS];
-        stats->kernel_ms = ms;
-    }
-    return TRT_OK;
+        rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        trt::QueryScene qs;
+        rc = trt::query_scene_on_device(s, qs);
+        if (rc != TRT_OK) return rc;
+        const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u;
+        trt::HostStage st("sparse render buffers");
+        const size_t r_list = st.reserve(list), r_acc = st.reserve(frame), r_m2 = st.reserve(frame, moment2 != nullptr);
+        st.reserve_counters();
+        st.alloc();
+        std::vector<float> back(3u * (size_t)npixels);
+        st.up(r_list, pixels, list, "hipMemcpy of the list");
+        st.zero_counters();
+        // the running sums a pass continues go up; a pass that starts them reads nothing
+        if (ra.accumulate) st.up(r_acc, accum, frame, "hipMemcpy of the frame");
+        if (ra.accumulate) st.up(r_m2, moment2, frame, "hipMemcpy of the second moments");
+        st.time_begin();
+        if (st.ok())
+            st.run(trt::launch_pixels(qs, cd, ra, npixels, st.ptr<uint32_t>(r_list), n, nullptr, st.ptr<float>(r_acc), st.ptr<float>(r_m2), st.counters(), nullptr),
+                   "sparse render launch");
+        const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
+        for (int b = 0; b < 2 && wrote; b++) {
+            float* const host = b == 0 ? accum : moment2;
+            if (!host) continue;
+            st.down(back.data(), b == 0 ? r_acc : r_m2, frame, "hipMemcpy of the results");
+            for (uint32_t i = 0; i < n && st.ok(); i++) {
+                const size_t o = 3u * (size_t)pixels[i];
+                host[o] = back[o]; host[o + 1u] = back[o + 1u]; host[o + 2u] = back[o + 2u];
+            }
+        }
+        st.read_stats(stats);
+        return st.finish();
+    });
 }
 
 // How launch_pixels would launch a list of n pixels on this scene.
@@ -488,38 +465,30 @@ int trt_select_pixels_device(const float* d_accum, const float* d_moment2, uint3
 // Host buffers: device copies of the call's own on the default stream, complete when the call returns.
 int trt_select_pixels(const float* accum, const float* moment2, uint32_t npixels, uint32_t samples_per_pixel, uint32_t samples_done,
                       const uint32_t* candidates, uint32_t n, float rel_tol, float abs_tol, uint32_t* selected, uint32_t* count) {
-    int rc = trt::select_check(accum, moment2, samples_per_pixel, samples_done, n, selected, count);
-    if (rc != TRT_OK) return rc;
-    if (n == 0u) { *count = 0u; return TRT_OK; }
-    rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u, scratch = (size_t)trt_select_scratch_bytes(n);
-    const size_t off_acc = 0, off_m2 = trt::q_align16(frame), off_cand = off_m2 + trt::q_align16(frame);
-    const size_t off_sel = off_cand + (candidates ? trt::q_align16(list) : 0u), off_scratch = off_sel + trt::q_align16(list);
-    const size_t off_count = off_scratch + scratch, total = off_count + 16u;
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("selection buffers: ") + hipGetErrorString(e)); }
-    const char* what = "hipMemcpy of the sums";
-    if (frame) e = hipMemcpy(d + off_acc, accum, frame, hipMemcpyHostToDevice);
-    if (e == hipSuccess && frame) e = hipMemcpy(d + off_m2, moment2, frame, hipMemcpyHostToDevice);
-    if (e == hipSuccess && candidates) { what = "hipMemcpy of the candidates"; e = hipMemcpy(d + off_cand, candidates, list, hipMemcpyHostToDevice); }
-    uint32_t kept = 0;
-    if (e == hipSuccess) {
-        const trt::SelectArgs sa = trt::select_args(reinterpret_cast<const float*>(d + off_acc), reinterpret_cast<const float*>(d + off_m2), npixels,
-                                                    samples_per_pixel, samples_done,
-                                                    candidates ? reinterpret_cast<const uint32_t*>(d + off_cand) : nullptr, n, rel_tol, abs_tol);
-        what = "selection launch";
-        e = trt::launch_select(sa, reinterpret_cast<uint32_t*>(d + off_sel), reinterpret_cast<uint32_t*>(d + off_count),
-                               reinterpret_cast<uint32_t*>(d + off_scratch), nullptr);
-    }
-    if (e == hipSuccess) { what = "hipMemcpy of the count"; e = hipMemcpy(&kept, d + off_count, sizeof(kept), hipMemcpyDeviceToHost); }      // (waits for the kernels: same stream)
-    if (e == hipSuccess && kept > n) { (void)hipFree(d); return trt::query_fail(TRT_ERR_HIP, "selection kept more candidates than it was given"); }
-    if (e == hipSuccess && kept) { what = "hipMemcpy of the selection"; e = hipMemcpy(selected, d + off_sel, (size_t)kept * 4u, hipMemcpyDeviceToHost); }
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    *count = kept;
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        int rc = trt::select_check(accum, moment2, samples_per_pixel, samples_done, n, selected, count);
+        if (rc != TRT_OK) return rc;
+        if (n == 0u) { *count = 0u; return TRT_OK; }
+        rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        const size_t frame = (size_t)npixels * 12u, list = (size_t)n * 4u;
+        trt::HostStage st("selection buffers");
+        const size_t r_acc = st.reserve(frame), r_m2 = st.reserve(frame), r_cand = st.reserve(list, candidates != nullptr), r_sel = st.reserve(list);
+        const size_t r_scratch = st.reserve((size_t)trt_select_scratch_bytes(n)), r_count = st.reserve(16u);
+        st.alloc();
+        if (frame) st.up(r_acc, accum, frame, "hipMemcpy of the sums");
+        if (frame) st.up(r_m2, moment2, frame, "hipMemcpy of the sums");
+        st.up(r_cand, candidates, list, "hipMemcpy of the candidates");
+        const trt::SelectArgs sa = trt::select_args(st.ptr<float>(r_acc), st.ptr<float>(r_m2), npixels, samples_per_pixel, samples_done,
+                                                    st.ptr<uint32_t>(r_cand), n, rel_tol, abs_tol);
+        if (st.ok()) st.run(trt::launch_select(sa, st.ptr<uint32_t>(r_sel), st.ptr<uint32_t>(r_count), st.ptr<uint32_t>(r_scratch), nullptr), "selection launch");
+        uint32_t kept = 0;
+        st.down(&kept, r_count, sizeof(kept), "hipMemcpy of the count");
+        if (st.ok() && kept > n) return trt::query_fail(TRT_ERR_HIP, "selection kept more candidates than it was given");
+        if (kept) st.down(selected, r_sel, (size_t)kept * 4u, "hipMemcpy of the selection");
+        if (st.ok()) *count = kept;
+        return st.finish();
+    });
 }
 
 }  // extern "C"

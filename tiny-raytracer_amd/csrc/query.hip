@@ -193,28 +193,22 @@ int query_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint
 }
 
 // Host buffers: device copies of the call's own, one stream-ordered sequence on the default stream, complete when the call returns.
+// (Runs inside host_form: the two entry points below.)
 int query_host(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, void* out, size_t out_stride, bool any) {
     int rc = query_check(s, rays, n, out);
     if (rc != TRT_OK || n == 0) return rc;
     QueryScene qs;
     rc = query_scene_on_device(s, qs);
     if (rc != TRT_OK) return rc;
-    const size_t rays_b = (size_t)n * sizeof(trt_ray), tmax_b = t_max ? (size_t)n * sizeof(float) : 0u, out_b = (size_t)n * out_stride;
-    const size_t off_tmax = q_align16(rays_b), off_out = off_tmax + q_align16(tmax_b);
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), off_out + out_b);
-    if (e != hipSuccess) { (void)hipGetLastError(); return query_fail(TRT_ERR_OOM, std::string("ray query buffers: ") + hipGetErrorString(e)); }
-    const char* what = "hipMemcpy of the rays";
-    e = hipMemcpy(d, rays, rays_b, hipMemcpyHostToDevice);
-    if (e == hipSuccess && t_max) { what = "hipMemcpy of t_max"; e = hipMemcpy(d + off_tmax, t_max, tmax_b, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) {
-        what = "ray query launch";
-        e = launch_query(qs, reinterpret_cast<const float*>(d), t_max ? reinterpret_cast<const float*>(d + off_tmax) : nullptr, n, d + off_out, any, nullptr);
-    }
-    if (e == hipSuccess) { what = "hipMemcpy of the answers"; e = hipMemcpy(out, d + off_out, out_b, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
-    (void)hipFree(d);
-    if (e != hipSuccess) return query_fail_hip(e, what);
-    return TRT_OK;
+    const size_t rays_b = (size_t)n * sizeof(trt_ray), tmax_b = (size_t)n * sizeof(float), out_b = (size_t)n * out_stride;
+    HostStage st("ray query buffers");
+    const size_t r_rays = st.reserve(rays_b), r_tmax = st.reserve(tmax_b, t_max != nullptr), r_out = st.reserve(out_b);
+    st.alloc();
+    st.up(r_rays, rays, rays_b, "hipMemcpy of the rays");
+    st.up(r_tmax, t_max, tmax_b, "hipMemcpy of t_max");
+    if (st.ok()) st.run(launch_query(qs, st.ptr<float>(r_rays), st.ptr<float>(r_tmax), n, st.ptr<void>(r_out), any, nullptr), "ray query launch");
+    st.down(out, r_out, out_b, "hipMemcpy of the answers");
+    return st.finish();
 }
 
 }  // namespace
@@ -223,10 +217,10 @@ int query_host(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n
 extern "C" {
 
 int trt_intersect(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, trt_hit* hits) {
-    return trt::query_host(s, rays, t_max, n, hits, sizeof(trt_hit), false);
+    return trt::host_form([&] { return trt::query_host(s, rays, t_max, n, hits, sizeof(trt_hit), false); });
 }
 int trt_occluded(trt_scene* s, const trt_ray* rays, const float* t_max, uint32_t n, uint8_t* occluded) {
-    return trt::query_host(s, rays, t_max, n, occluded, 1u, true);
+    return trt::host_form([&] { return trt::query_host(s, rays, t_max, n, occluded, 1u, true); });
 }
 int trt_intersect_device(trt_scene* s, const trt_ray* d_rays, const float* d_t_max, uint32_t n, trt_hit* d_hits, void* stream) {
     return trt::query_device(s, d_rays, d_t_max, n, d_hits, false, stream);

@@ -2,13 +2,15 @@
 // caller's rays), the feature buffers (aov.hip: a run of the local image's pixels) and the sparse render (pixels.hip: a run of the pixel
 // list).  ONE copy of the kernel table's entry, of the launch rule over the unit's own table (plan_batch: host arithmetic only), of what
 // a launch does before hipLaunchKernel (batch_prepare), of the launch-plan entry point (batch_launch_plan) and of the argument checks of
-// the units that trace camera rays (batch_render_args).  The device side of the same units is wave_run.h.
+// the units that trace camera rays (batch_render_args).  The device side of the same units is wave_run.h; their host-buffer forms stage
+// through host_stage.h, which also has q_align16.
 // For those three units only: batch_prepare and batch_launch_plan call the HIP runtime and scene_query.h's helpers, so capi.hip, whose
 // host-only build links without the units, must not include this header.
 #pragma once
 
 #include <stddef.h>
 
+#include "host_stage.h"
 #include "kernels.h"
 #include "rt_path.h"
 #include "scene_query.h"
@@ -22,7 +24,6 @@ struct BatchKernel {
 };
 
 constexpr size_t kQueryLdsPerCu = 160u * 1024u;
-inline size_t q_align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
 // How a batch of n items is launched on this scene with `cus` compute units.  The walk, workgroup shape and leaf-stack depth are those of
 // the streamed launch plan under the built-in tuning (streamed.hip streamed_launch_plan: that rule lives there and is not restated),

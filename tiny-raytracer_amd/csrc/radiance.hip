@@ -280,60 +280,39 @@ int trt_radiance_device(trt_scene* s, const trt_ray* d_rays, uint32_t n, const t
 // Host buffers: device copies of the rays and of the two sums are the call's own (one allocation), one stream-ordered sequence on the
 // default stream, complete when the call returns.  The running sums go up only when the call continues them.
 int trt_radiance(trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, float* radiance, float* moment2, trt_stats* stats) {
-    trt::RenderArgs ra;
-    int rc = trt::radiance_check(s, rays, n, p, radiance, ra);
-    if (rc != TRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) *stats = trt_stats{};
-        return TRT_OK;
-    }
-    rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
-    const size_t off_rad = trt::q_align16(rays_b), off_m2 = off_rad + trt::q_align16(sums);
-    const size_t off_ctr = off_m2 + (moment2 ? trt::q_align16(sums) : 0u), total = off_ctr + trt::CTR_COUNT * sizeof(unsigned long long);
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("radiance query buffers: ") + hipGetErrorString(e)); }
-    float* const d_rad = reinterpret_cast<float*>(d + off_rad);
-    float* const d_m2 = moment2 ? reinterpret_cast<float*>(d + off_m2) : nullptr;
-    unsigned long long* const d_ctr = reinterpret_cast<unsigned long long*>(d + off_ctr);
-    unsigned long long h_ctr[trt::CTR_COUNT] = {0};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.0f;
-    const char* what = "hipMemcpy of the rays";
-    e = hipMemcpy(d, rays, rays_b, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { what = "hipMemset of the counters"; e = hipMemset(d_ctr, 0, sizeof(h_ctr)); }
-    // the running sums a pass continues go up; a pass that starts them reads nothing
-    if (e == hipSuccess && ra.accumulate) { what = "hipMemcpy of the sums"; e = hipMemcpy(d_rad, radiance, sums, hipMemcpyHostToDevice); }
-    if (e == hipSuccess && ra.accumulate && d_m2) { what = "hipMemcpy of the second moments"; e = hipMemcpy(d_m2, moment2, sums, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) { what = "hipEventCreate"; e = hipEventCreate(&ev0); }
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev0, nullptr); }
-    if (e == hipSuccess) {
-        what = "radiance query launch";
-        e = trt::launch_radiance(qs, ra, reinterpret_cast<const float*>(d), n, p->samples_per_ray, p->first_stream, d_rad, d_m2, d_ctr, nullptr);
-    }
-    if (e == hipSuccess) { what = "hipEventRecord"; e = hipEventRecord(ev1, nullptr); }
-    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
-    if (e == hipSuccess && wrote) { what = "hipMemcpy of the results"; e = hipMemcpy(radiance, d_rad, sums, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
-    if (e == hipSuccess && wrote && d_m2) e = hipMemcpy(moment2, d_m2, sums, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) { what = "hipMemcpy of the counters"; e = hipMemcpy(h_ctr, d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost); }
-    if (e == hipSuccess) { what = "hipEventElapsedTime"; e = hipEventSynchronize(ev1); if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1); }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    if (stats) {
-        *stats = trt_stats{};
-        stats->samples = h_ctr[trt::CTR_SAMPLES];
-        stats->rays = h_ctr[trt::CTR_RAYS];
-        stats->kernel_ms = ms;
-    }
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        trt::RenderArgs ra;
+        int rc = trt::radiance_check(s, rays, n, p, radiance, ra);
+        if (rc != TRT_OK) return rc;
+        if (n == 0u) {
+            if (stats) *stats = trt_stats{};
+            return TRT_OK;
+        }
+        rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        trt::QueryScene qs;
+        rc = trt::query_scene_on_device(s, qs);
+        if (rc != TRT_OK) return rc;
+        const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
+        trt::HostStage st("radiance query buffers");
+        const size_t r_rays = st.reserve(rays_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
+        st.reserve_counters();
+        st.alloc();
+        st.up(r_rays, rays, rays_b, "hipMemcpy of the rays");
+        st.zero_counters();
+        // the running sums a pass continues go up; a pass that starts them reads nothing
+        if (ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
+        if (ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
+        st.time_begin();
+        if (st.ok())
+            st.run(trt::launch_radiance(qs, ra, st.ptr<float>(r_rays), n, p->samples_per_ray, p->first_stream, st.ptr<float>(r_rad), st.ptr<float>(r_m2),
+                                        st.counters(), nullptr), "radiance query launch");
+        const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
+        if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
+        if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
+        st.read_stats(stats);
+        return st.finish();
+    });
 }
 
 // How launch_radiance would launch n rays on this scene.

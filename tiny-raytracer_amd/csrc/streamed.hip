@@ -22,9 +22,9 @@
 // primary rays of a whole wave at once into an LDS pool.
 #include <string>
 
+#include "host_stage.h"
 #include "kernels.h"
 #include "rt_path.h"
-#include "scene_query.h"
 #include "wave_run.h"
 
 namespace trt {
@@ -566,7 +566,6 @@ uint32_t streamed_chunk_that_fits(uint32_t width, uint32_t rows, size_t bytes) {
 namespace {
 
 constexpr size_t kLdsPerCu = 160u * 1024u;
-inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
 // One kernel instantiation the launcher may pick.  Every instantiation has the same parameter list, so a launch is
 // hipLaunchKernel(fn, ...) with one argument array whichever entry is chosen.
@@ -639,7 +638,7 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
     // 8 waves per SIMD for scenes read from global memory
     int threads = 256;
     if (mode == MODE_LDS && L.hot_bytes > 20u * 1024u) {
-        threads = (align16(scene_bytes) + 768u * 4u * sizeof(float2)) * 2u <= kLdsPerCu && ra_all.lds_leaf_stack != 0u ? 768 : 512;
+        threads = (q_align16(scene_bytes) + 768u * 4u * sizeof(float2)) * 2u <= kLdsPerCu && ra_all.lds_leaf_stack != 0u ? 768 : 512;
         if (tn.stream_big_threads == 512u || tn.stream_big_threads == 768u) threads = (int)tn.stream_big_threads;
     }
     // LDS scenes: 6 waves per SIMD.  Scenes in global memory: rounds 1-4 ran them at 8 (100 k spheres: 2.03 Gray/s at 5 waves, 2.25 at 6, 2.29 at 8 -
@@ -671,13 +670,13 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
         // the default depth gives way to occupancy: the deepest stack (<= 7, >= 4) with which stack + ray pool + scene copy of
         // all the CU's workgroups fit its 160 KB of LDS (Cornell: 7 slots at 6 waves per SIMD, 5 at 7, 4 at 8)
         const size_t pool_b = (size_t)threads / 64u * 64u * kPoolDwords * sizeof(uint32_t);
-        while (slots > 4u && (align16(scene_bytes) + (size_t)threads * slots * sizeof(float2) + pool_b) * wg_per_cu > kLdsPerCu) slots--;
+        while (slots > 4u && (q_align16(scene_bytes) + (size_t)threads * slots * sizeof(float2) + pool_b) * wg_per_cu > kLdsPerCu) slots--;
     }
     if (threads > 512 && ra_all.leaf_slots == 0u) {
-        while (slots > 3u && (align16(scene_bytes) + (size_t)threads * slots * sizeof(float2)) * wg_per_cu > kLdsPerCu) slots--;
+        while (slots > 3u && (q_align16(scene_bytes) + (size_t)threads * slots * sizeof(float2)) * wg_per_cu > kLdsPerCu) slots--;
     }
     const size_t stack_bytes = (size_t)threads * slots * sizeof(float2);
-    const size_t with_stack = align16(scene_bytes) + stack_bytes;
+    const size_t with_stack = q_align16(scene_bytes) + stack_bytes;
     // LDS: scene copy + the postponed-leaf stack (8 bytes per lane and slot), the latter only where it does not cost a
     // resident workgroup (random-spheres: 49.6 KB scene copy, 3 workgroups of 512 lanes per CU without it, 2 with it:
     // measured 7 % slower than register slots); otherwise the slots are registers
@@ -706,8 +705,8 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
     bool dual = want_dual && specialise && compact && pool && threads == 256;
     if (dual) {
         uint32_t ds = ra_all.leaf_slots == 0u ? 4u : (ra_all.leaf_slots < 2u ? 2u : (ra_all.leaf_slots > kLdsLeafSlotsMax ? kLdsLeafSlotsMax : ra_all.leaf_slots));
-        while (ds > 2u && (align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) ds--;
-        if ((align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) dual = false;
+        while (ds > 2u && (q_align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) ds--;
+        if ((q_align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) dual = false;
         else slots = ds;
     }
     const size_t stack_total = dual ? 2u * (size_t)threads * slots * sizeof(float2) : stack_bytes;
@@ -741,7 +740,7 @@ StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra
         pool = kpool;
         if (kw >= 5 && kw < w) { w = kw; wg_per_cu = (uint32_t)(w * 4 * 64 / threads); }
     }
-    const size_t lds_bytes = lds_stack ? align16(scene_bytes) + (dual ? stack_total : stack_bytes) + (pool ? pool_bytes : 0u) : scene_bytes;
+    const size_t lds_bytes = lds_stack ? q_align16(scene_bytes) + (dual ? stack_total : stack_bytes) + (pool ? pool_bytes : 0u) : scene_bytes;
     if (lds_bytes) { const uint32_t by_lds = (uint32_t)(kLdsPerCu / lds_bytes); if (by_lds < wg_per_cu) wg_per_cu = by_lds ? by_lds : 1u; }
     pl.mode = mode; pl.threads = threads; pl.waves_per_simd = w; pl.wg_per_cu = wg_per_cu; pl.slots = slots;
     pl.lds_stack = lds_stack; pl.flat = flat && lds_stack; pl.compact = compact; pl.pool = pool; pl.walk = walk; pl.dual = dual;
@@ -780,7 +779,7 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
     // the kernel's assumptions about its dynamic LDS, checked where the launch is made (scene copy | leaf stack | ray pool)
     {
         size_t need = pl.scene_lds_bytes;
-        if (pl.lds_stack) need = align16(need) + (pl.dual ? 2u : 1u) * (size_t)pl.threads * pl.slots * sizeof(float2) + (pl.pool ? (size_t)pl.threads * kPoolDwords * sizeof(uint32_t) : 0u);
+        if (pl.lds_stack) need = q_align16(need) + (pl.dual ? 2u : 1u) * (size_t)pl.threads * pl.slots * sizeof(float2) + (pl.pool ? (size_t)pl.threads * kPoolDwords * sizeof(uint32_t) : 0u);
         if (need != pl.lds_bytes || pl.lds_bytes > kLdsPerCu || pl.kernel_threads != pl.threads || (pl.pool && !pl.lds_stack) ||
             (pl.flat && pl.slots < 2u) || (pl.kernel_pool != pl.pool)) return hipErrorInvalidConfiguration;
     }
@@ -872,25 +871,21 @@ int trt_variance_device(const float* d_accum, const float* d_moment2, uint32_t n
 
 // Host form: device copies of the call's own, the same kernel, complete when the call returns.  There is no CPU path.
 int trt_variance(const float* accum, const float* moment2, uint32_t npixels, uint32_t samples_per_pixel, float* variance) {
-    if (npixels && (!accum || !moment2 || !variance)) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    if (npixels == 0u) return TRT_OK;
-    const int rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    const size_t frame = ((size_t)npixels * 12u + 15u) & ~(size_t)15u;
-    char* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), 2u * frame + (size_t)npixels * 4u);
-    if (e != hipSuccess) { (void)hipGetLastError(); return trt::query_fail(TRT_ERR_OOM, std::string("variance buffers: ") + hipGetErrorString(e)); }
-    float* const d_s = reinterpret_cast<float*>(d);
-    float* const d_m = reinterpret_cast<float*>(d + frame);
-    float* const d_v = reinterpret_cast<float*>(d + 2u * frame);
-    const char* what = "hipMemcpy of the inputs";
-    e = hipMemcpy(d_s, accum, (size_t)npixels * 12u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_m, moment2, (size_t)npixels * 12u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { what = "variance launch"; e = trt::launch_variance(d_s, d_m, npixels, samples_per_pixel, d_v, nullptr); }
-    if (e == hipSuccess) { what = "hipMemcpy of the result"; e = hipMemcpy(variance, d_v, (size_t)npixels * 4u, hipMemcpyDeviceToHost); }      // (waits for the kernel: same stream)
-    (void)hipFree(d);
-    if (e != hipSuccess) return trt::query_fail_hip(e, what);
-    return TRT_OK;
+    return trt::host_form([&]() -> int {
+        if (npixels && (!accum || !moment2 || !variance)) return trt::query_fail(TRT_ERR_INVALID_ARG, "null argument");
+        if (npixels == 0u) return TRT_OK;
+        const int rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        const size_t frame = (size_t)npixels * 12u;
+        trt::HostStage st("variance buffers");
+        const size_t r_s = st.reserve(frame), r_m = st.reserve(frame), r_v = st.reserve((size_t)npixels * 4u);
+        st.alloc();
+        st.up(r_s, accum, frame, "hipMemcpy of the inputs");
+        st.up(r_m, moment2, frame, "hipMemcpy of the inputs");
+        if (st.ok()) st.run(trt::launch_variance(st.ptr<float>(r_s), st.ptr<float>(r_m), npixels, samples_per_pixel, st.ptr<float>(r_v), nullptr), "variance launch");
+        st.down(variance, r_v, (size_t)npixels * 4u, "hipMemcpy of the result");
+        return st.finish();
+    });
 }
 
 }  // extern "C"
