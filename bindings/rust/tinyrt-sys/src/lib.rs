@@ -245,6 +245,20 @@ pub struct trt_radiance_params {
     pub reserved: [u32; 6],
 }
 
+/// `enum trt_lobe`: the rule the first ray of a gather sample is drawn by.
+pub const TRT_LOBE_COSINE: u32 = 1;
+pub const TRT_LOBE_CONE: u32 = 2;
+
+/// `trt_radiance_params` and the lobe of `trt_gather` (96 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_gather_params {
+    pub path: trt_radiance_params,
+    pub lobe: u32,
+    pub spread: f32,
+    pub reserved: [u32; 6],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -397,6 +411,12 @@ extern "C" {
     pub fn trt_radiance_device(s: *mut trt_scene, d_rays: *const trt_ray, n: u32, p: *const trt_radiance_params, d_radiance: *mut f32,
                                d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_radiance_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_gather_params_default(out: *mut trt_gather_params);
+    pub fn trt_gather(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_gather_params, radiance: *mut f32,
+                      moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_gather_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_gather_params, d_radiance: *mut f32,
+                             d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_gather_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

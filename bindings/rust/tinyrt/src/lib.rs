@@ -114,6 +114,13 @@ impl Material for Light {
     }
 }
 
+/// The rule `World::gather` draws the first ray of a sample by (`enum trt_lobe`); `Cone` carries the spread.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum Lobe {
+    Cosine,
+    Cone(Float),
+}
+
 pub enum Geometry {
     Sphere { center: Vec3, radius: Float, material: MaterialHandle },
     Quad { corner: Vec3, u: Vec3, v: Vec3, material: MaterialHandle },
@@ -206,6 +213,40 @@ impl World {
         check(unsafe {
             sys::trt_radiance(scene, rays.as_ptr() as *const sys::trt_ray, rays.len() as u32, &params, radiance.as_mut_ptr(),
                               moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
+    /// The light gathered at caller-supplied surfels (`trt_gather`): each `(point, axis)` as six floats, used as given.  For every one of
+    /// `samples_per_item` samples the device draws a first ray about the axis - `Lobe::Cosine`: `Lambertian::scatter`'s rule, the result
+    /// is what a white diffuse surface there reflects (irradiance / pi); `Lobe::Cone(spread)`: axis + spread * (a point in the unit
+    /// sphere), `Metal::scatter`'s rule - from RNG stream `(seed, first_stream + i * samples_per_item + s, 1)`, traces its path on stream
+    /// `(.., 0)` and folds per item.  Returns `(radiance, moment2)` as `radiance` does.
+    pub fn gather(&mut self, items: &[[Float; 6]], samples_per_item: u32, lobe: Lobe, max_bounces: u32, background: Vec3, seed: u32,
+                  first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_gather_params::default();
+        unsafe { sys::trt_gather_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.max_bounces = max_bounces;
+        params.path.background = background.raw();
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        match lobe {
+            Lobe::Cosine => params.lobe = sys::TRT_LOBE_COSINE,
+            Lobe::Cone(spread) => {
+                params.lobe = sys::TRT_LOBE_CONE;
+                params.spread = spread;
+            }
+        }
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_gather(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, radiance.as_mut_ptr(),
+                            moment2.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((radiance, moment2))
     }

@@ -45,7 +45,8 @@ extern "C" {
  *              trt_denoise_color, trt_denoise_color_default, trt_denoise_ex, trt_denoise_ex_device; trt_render_pixels,
  *              trt_render_pixels_device, trt_pixels_launch_plan, trt_select_pixels, trt_select_pixels_device,
  *              trt_select_scratch_bytes; trt_radiance_params, trt_radiance_params_default, trt_radiance, trt_radiance_device,
- *              trt_radiance_launch_plan. */
+ *              trt_radiance_launch_plan; trt_lobe, trt_gather_params, trt_gather_params_default, trt_gather, trt_gather_device,
+ *              trt_gather_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -474,8 +475,9 @@ uint64_t trt_select_scratch_bytes(uint32_t n_candidates);
 
 /* ---- Radiance queries: path tracing of caller-supplied rays ----
  * The ray queries answer "what does this ray hit" for any ray; these answer "what light arrives along it": another camera (panorama,
- * fisheye, orthographic, a lens model of the caller's own), baking (irradiance probes, lightmap texels: thousands of points with tens to
- * hundreds of samples each), a sensor that is no image, or the render's own rays (trt_primary_rays) traced again with more samples.
+ * fisheye, orthographic, a lens model of the caller's own), a sensor that is no image, a probe along one fixed direction (K samples of
+ * one ray differ only after the first hit: texels and probes, which need K different first rays, are trt_gather's below), or the
+ * render's own rays (trt_primary_rays) traced again with more samples.
  *  - Path.  For ray i and sample s of 0..K, K = samples_per_ray, the colour c is CpuSampler::single_point_sampling (cpu.rs:39-65) for
  *    ray i AS GIVEN: the direction is not normalised, as in trt_intersect and trt_sample_batch.
  *  - RNG stream (seed, pixel = first_stream + i * K + s, sample = 0); no primary-ray draws are consumed.  This is trt_sample_batch's own
@@ -523,6 +525,46 @@ int trt_radiance_device(trt_scene *s, const trt_ray *d_rays, uint32_t n, const t
 /* How trt_radiance[_device] launches n rays on this scene: trt_query_launch_plan's rule and fields (rays_per_wave = rays a wave owns, each
  * for all samples of the call), over the radiance kernels' own table. */
 int trt_radiance_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Gather queries: radiance queries whose rays the device draws about caller-supplied surfels ----
+ * trt_radiance traces the SAME ray K times; a lightmap texel, an irradiance probe or a glossy gather needs K DIFFERENT first rays about
+ * a surface normal.  A gather query draws them on the device with one of the reference's two scatter rules, then traces and folds per
+ * item exactly as trt_radiance does: nothing per sample crosses the bus.  With the cosine lobe the result is the radiance a white
+ * Lambertian surface at the point would reflect (irradiance / pi: what a lightmap bakes); with the cone lobe a glossy or soft gather,
+ * and with a small spread the direction jitter that anti-aliases a camera of the caller's own.
+ *  - Item i is (origin = point, direction = axis), both used AS GIVEN: the axis is not normalised.
+ *  - First ray.  For sample s of 0..K, K = path.samples_per_ray, the stream index is j = path.first_stream + i * K + s (32 bits).  With
+ *    g = RNG (seed, pixel = j, sample = 1) and v = random_in_unit_sphere(g) (vec3extend.rs:15-30; three draws, nothing else is taken from g):
+ *      TRT_LOBE_COSINE, Lambertian::scatter (lambertian.rs:16-22):  dir = axis + normalize(v); if near_zero(dir) then dir = axis
+ *      TRT_LOBE_CONE, Metal::scatter with the axis as the mirror direction (metal.rs:18-25):  dir = axis + spread * v
+ *    and the ray is Ray::new(point, dir), which normalises dir.  `spread` is Metal's fuzz, not clamped; the cosine lobe ignores it.
+ *  - Path.  The sample's colour is CpuSampler::single_point_sampling (cpu.rs:39-65) for that ray with RNG (seed, j, 0) and the budget
+ *    max_bounces - what trt_radiance and trt_sample_batch do for stream j; the surfel is not a bounce.  Both streams start fresh, so the
+ *    draw can be restated with the reference's scatter functions and the path with trt_sample_batch, sample by sample.
+ *  - Fold, second moments, sample range, accumulate, split invariance by samples and by items (first_stream + a * K), "nothing to trace",
+ *    the output bounds [0, 12 n), stats / d_counters (samples and rays only; `rays` counts the reference's world.hit calls), kernel_ms,
+ *    order, coherence and concurrency: as in trt_radiance.
+ *  - A first ray with a NaN component hits nothing: its sample is `background`.  That includes a NaN or infinite axis or point, and a
+ *    draw with u3 == 0 under the cosine lobe, where the reference normalises a zero vector.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_radiance's own errors, applied to `path`; `lobe` not 1 or 2;
+ *    with TRT_LOBE_CONE a `spread` that is NaN, infinite or negative; a non-zero reserved word.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM
+ *    for the host form's buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * trt_gather: HOST buffers, synchronous, as trt_radiance.  trt_gather_device: buffers in HBM, asynchronous on `stream`; allocates nothing. */
+enum trt_lobe { TRT_LOBE_COSINE = 1, TRT_LOBE_CONE = 2 };
+typedef struct {
+    trt_radiance_params path;     /* every field as in trt_radiance, same rules, same errors; K = path.samples_per_ray */
+    uint32_t lobe;                /* enum trt_lobe */
+    float spread;                 /* CONE: radius of the sphere added to the axis (Metal's fuzz, not clamped); COSINE: ignored */
+    uint32_t reserved[6];         /* zero */
+} trt_gather_params;              /* 96 B */
+void trt_gather_params_default(trt_gather_params *out);   /* path = trt_radiance_params_default, lobe COSINE, spread 0 */
+int trt_gather(trt_scene *s, const trt_ray *items, uint32_t n, const trt_gather_params *p, float *radiance, float *moment2,
+               trt_stats *stats);
+int trt_gather_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_gather_params *p, float *d_radiance,
+                      float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_gather[_device] launches n items on this scene: trt_radiance_launch_plan's rule and fields over the gather kernels' own table
+ * (the same shapes; kernel_waves_per_simd is that table's bound). */
+int trt_gather_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

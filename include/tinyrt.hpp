@@ -110,6 +110,16 @@ public:
         if (moment2) moment2->resize(rays.size() * 3);
         check(trt_radiance(get_bvh(), rays.data(), (uint32_t)rays.size(), &p, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
     }
+    // The light gathered at caller-supplied surfels (trt_gather): item = (origin = point, direction = axis), used as given.  For each of
+    // p.path.samples_per_ray samples the device draws a first ray about the axis by p.lobe - cosine: what a white diffuse surface there
+    // reflects; cone: axis + p.spread * (a point in the unit sphere) - and traces and folds it as radiance() does.  Start `p` from
+    // trt_gather_params_default.
+    void gather(const std::vector<trt_ray>& items, const trt_gather_params& p, std::vector<float>& radiance,
+                std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_gather(get_bvh(), items.data(), (uint32_t)items.size(), &p, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
     int num_geometries() const { return trt_world_num_geometries(w_); }
     const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).

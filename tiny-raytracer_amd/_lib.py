@@ -123,6 +123,14 @@ class RadianceParams(C.Structure):
                 ("reserved", C.c_uint32 * 6)]
 
 
+LOBE_COSINE, LOBE_CONE = 1, 2                                                # tinyrt.h enum trt_lobe
+
+
+class GatherParams(C.Structure):
+    """tinyrt.h trt_gather_params: trt_radiance_params and the lobe the first ray of a sample is drawn from (96 bytes)."""
+    _fields_ = [("path", RadianceParams), ("lobe", C.c_uint32), ("spread", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -216,6 +224,11 @@ SIGNATURES = {
     "trt_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "trt_radiance_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_gather_params_default": (None, [C.POINTER(GatherParams)]),
+    "trt_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(GatherParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_gather_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(GatherParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "trt_gather_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -244,6 +244,54 @@ class Scene:
         check(lib.trt_radiance_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- gather queries (tinyrt.h trt_gather): radiance queries whose first rays the device draws about caller-supplied surfels ----
+    LOBES = {"cosine": _lib.LOBE_COSINE, "cone": _lib.LOBE_CONE}
+
+    @classmethod
+    def _gather_params(cls, samples_per_item, lobe="cosine", spread=0.0, **path):
+        if lobe not in cls.LOBES:
+            raise ValueError("lobe must be 'cosine' or 'cone'")
+        p = _lib.GatherParams()
+        lib.trt_gather_params_default(C.byref(p))
+        p.path = cls._radiance_params(samples_per_item, **path)
+        p.lobe, p.spread = cls.LOBES[lobe], float(spread)
+        return p
+
+    def gather(self, items, samples_per_item, lobe="cosine", spread=0.0, max_bounces=50, background=(0.0, 0.0, 0.0), seed=1, first_stream=0,
+               sample_begin=0, sample_end=None, accumulate=False, radiance=None, moment2=None):
+        """trt_gather: the light gathered at surfels float32 [n, 6] (point, axis; used as given, the axis is never normalised).  For each of
+        samples_per_item = K samples the device draws a first ray about the axis - lobe "cosine": Lambertian::scatter's rule, the result is
+        what a white diffuse surface there reflects (irradiance / pi); lobe "cone": axis + spread * (a point in the unit sphere), Metal's
+        rule - from RNG stream (seed, first_stream + i * K + s, 1), traces its path on stream (.., 0) and folds per item.  Everything else
+        - sample range, accumulate, `radiance`, `moment2`, the returns - as in radiance()."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        p = self._gather_params(samples_per_item, lobe, spread, max_bounces=max_bounces, background=background, seed=seed, first_stream=first_stream,
+                                sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
+        if radiance is None:
+            radiance = np.zeros((n, 3), np.float32)
+        if moment2 is True:
+            moment2 = np.zeros((n, 3), np.float32)
+        for a in (radiance, moment2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
+        st = Stats()
+        check(lib.trt_gather(self._h, r.ctypes.data if n else None, n, C.byref(p), radiance.ctypes.data if n else None,
+                             moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        return radiance, moment2, st.as_dict()
+
+    def gather_device(self, d_items_ptr, n, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue gather() on buffers already in HBM (device pointers as integers: n x 24 bytes of surfels, n x 12 bytes of sums each) on
+        the current device; asynchronous on the stream, allocates nothing.  `params`: gather()'s keywords, samples_per_item included."""
+        p = self._gather_params(**params)
+        check(lib.trt_gather_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr),
+                                    C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def gather_plan(self, n, compute_units=0):
+        """trt_gather_launch_plan: how gather() launches n surfels on this scene, as a dict with radiance_plan()'s fields."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_gather_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""

@@ -1,5 +1,5 @@
-// radiance.hip — radiance queries: path tracing of caller-supplied rays (tinyrt.h trt_radiance / trt_radiance_device), written for
-// gfx950 (CDNA4) only.
+// radiance.hip — radiance queries: path tracing of caller-supplied rays (tinyrt.h trt_radiance / trt_radiance_device), and gather
+// queries: the same from device-drawn rays about caller-supplied surfels (trt_gather / trt_gather_device), written for gfx950 (CDNA4) only.
 //
 // The ray queries (query.hip) answer "what does this ray hit" for any ray; this unit answers "what light arrives along it": for ray i and
 // sample s the colour of CpuSampler::single_point_sampling (cpu.rs:39-65) for the ray as given, with RNG stream
@@ -20,6 +20,11 @@
 // then receives the arguments a walk of its own would have given it, hence the same bits; the reference's world.hit call for that
 // segment (cpu.rs:48) is still counted once per sample.  TRT_RADIANCE_PLAIN_WALK = 1 builds the form in which every sample walks its
 // first segment (the A/B of tools/radiance_bench.py).
+//
+// Gather queries (tinyrt.h trt_gather / trt_gather_device) are the same kernel with LOBE != 0: an item is a surfel (point, axis), and the
+// start step DRAWS the sample's first ray about the axis - Lambertian::scatter's rule (cosine lobe) or Metal::scatter's with the axis as
+// the mirror direction (cone lobe), from stream (seed, j, 1) - where a radiance query loads it; the path then runs on stream (seed, j, 0)
+// as above.  The first segment differs per sample, so nothing of it is shared.
 #include "kernels.h"
 #include "query_plan.h"
 #include "rt_path.h"
@@ -33,6 +38,7 @@
 namespace trt {
 
 static_assert(sizeof(trt_radiance_params) == 64, "trt_radiance_params layout (tinyrt.h)");
+static_assert(sizeof(trt_gather_params) == 96, "trt_gather_params layout (tinyrt.h)");
 
 struct RadianceArgs {
     const float* rays;               // n x (origin, direction), used as given
@@ -44,6 +50,15 @@ struct RadianceArgs {
     uint32_t samples_per_ray;        // K
     uint32_t first_stream;           // first_stream + n * K <= 2^32 (radiance_check): the stream index never wraps
 };
+// The gather kernels' arguments: RadianceArgs and the lobe.  A derived struct, not two more fields above: a longer RadianceArgs moves the
+// kernel arguments behind it, and with them the scalar loads of every LOBE == 0 instantiation.
+struct GatherArgs : RadianceArgs {
+    uint32_t lobe;                   // TRT_LOBE_COSINE or TRT_LOBE_CONE (gather_check): the same for every lane of the launch
+    float spread;                    // the cone lobe's sphere radius
+};
+constexpr int LOBE_NONE = 0, LOBE_GATHER = 1;   // radiance_kernel's LOBE: the items are rays | surfels, the lobe is GatherArgs::lobe
+template <int LOBE> struct RadianceArgsOf { using type = RadianceArgs; };
+template <> struct RadianceArgsOf<LOBE_GATHER> { using type = GatherArgs; };
 
 TRT_DEV Ray rad_load_ray(const float* __restrict__ rays, uint32_t idx) {
     const float* r = rays + 6ull * idx;
@@ -53,10 +68,27 @@ TRT_DEV Ray rad_load_ray(const float* __restrict__ rays, uint32_t idx) {
     return ray;
 }
 
+// The first ray of a gather sample: the scatter rule of the lobe applied to the surfel (point, axis) = (item.o, item.d) with the draws
+// of g, in the operations of rt_path.h shade_hit (hence of the oracle's material_scatter).  Three draws are taken from g.
+// Cosine, lambertian.rs:16-22: axis + random_unit_vector, the axis itself if that is near zero; cone, metal.rs:18-25 with the axis in
+// the place of the reflected direction: axis + spread * random_in_unit_sphere.  Ray::new normalises (ray.rs:12-14).
+TRT_DEV Ray gather_ray(const float* __restrict__ items, uint32_t idx, uint32_t lobe, float spread, Rng& g) {
+    const V3 in_sphere = random_in_unit_sphere_unit(g);
+    const Ray item = rad_load_ray(items, idx);                              // after the draw: six registers less while it runs
+    V3 dir;
+    if (lobe == TRT_LOBE_COSINE) {
+        dir = item.d + normalized(in_sphere);
+        if (near_zero(dir)) dir = item.d;
+    } else {
+        dir = item.d + spread * in_sphere;
+    }
+    return ray_new(item.o, dir);
+}
+
 // ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_radiance: nothing to trace launches radiance_zero_kernel or nothing)
-template <int MODE, int WALK, int THREADS, int MINW>
-__global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, RenderArgs ra, RadianceArgs ga, const float4* __restrict__ leaf_list,
-                                                                      const uint4* __restrict__ nodes16) {
+template <int MODE, int WALK, int THREADS, int MINW, int LOBE>
+__global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, RenderArgs ra, typename RadianceArgsOf<LOBE>::type ga,
+                                                                      const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16) {
     stage_scene_to_lds<MODE>(scd);
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
     const SceneAcc<MODE> sc{scd.blob, scd.L};
@@ -71,8 +103,9 @@ __global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, R
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
     Counters<false> ctr;
     constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
-    // the first segment is walked once per ray where keeping its (primitive, t) costs no occupancy: every walk but the lock-step list
-    constexpr bool kShareFirst = !TRT_RADIANCE_PLAIN_WALK && WALK != WALK_FLAT;
+    // the first segment is walked once per ray where keeping its (primitive, t) costs no occupancy: every walk but the lock-step list;
+    // a gather sample draws its own first segment
+    constexpr bool kShareFirst = !TRT_RADIANCE_PLAIN_WALK && WALK != WALK_FLAT && LOBE == LOBE_NONE;
 
     uint32_t cursor = 0;                                                    // wave-uniform
     bool own = false, has_path = false, walking = false;                    // the lane owns a ray; a path of it is under way; its walk is parked
@@ -112,8 +145,16 @@ __global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, R
         if (own) {
             // ---- start: the ray's next sample (cpu.rs:42-45 with the caller's ray; no primary-ray draws) ----
             if (!has_path) {
-                p.rng = rng_seed(ra.seed_key, ga.first_stream + idx * ga.samples_per_ray + s, 0u);
-                p.ray = rad_load_ray(rays, idx);                            // re-read: 24 bytes per sample against six registers per lane
+                const uint32_t stream = ga.first_stream + idx * ga.samples_per_ray + s;
+                if constexpr (LOBE == LOBE_NONE) {
+                    p.rng = rng_seed(ra.seed_key, stream, 0u);
+                    p.ray = rad_load_ray(rays, idx);                        // re-read: 24 bytes per sample against six registers per lane
+                } else {
+                    // the surfel is re-read like a ray; its draw has a stream of its own (sample index 1), the path starts fresh at 0
+                    Rng g = rng_seed(ra.seed_key, stream, 1u);
+                    p.ray = gather_ray(rays, idx, ga.lobe, ga.spread, g);
+                    p.rng = rng_seed(ra.seed_key, stream, 0u);
+                }
                 p.color = v3(0.0f, 0.0f, 0.0f);
                 p.atten = v3(1.0f, 1.0f, 1.0f);
                 p.remain = ra.max_bounces;
@@ -180,26 +221,49 @@ __global__ __launch_bounds__(256) void radiance_zero_kernel(unsigned long long n
 
 namespace {
 
-#define TRT_RADIANCE(MODE, WALK, THREADS, MINW) \
-    BatchKernel{reinterpret_cast<const void*>(&radiance_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+#define TRT_RADIANCE(MODE, WALK, THREADS, MINW, LOBE) \
+    BatchKernel{reinterpret_cast<const void*>(&radiance_kernel<MODE, WALK, THREADS, MINW, LOBE>), MODE, WALK, THREADS, MINW}
 // the (scene mode, walk, workgroup shape) set of the sparse render's table, with the register-slot fallback (query_plan.h), so that every
 // scene has a kernel.  A lane carries what a lane of pixels_kernel carries plus the pending and the first (primitive, t): the launch
 // bounds are the highest at which the instantiation uses no scratch memory (profiles/radiance_resource_usage.txt).  The plan reports
 // the bound (kernel_waves_per_simd).  The lock-step list keeps no first (primitive, t) (kShareFirst): with it that instantiation needs 76
 // registers and drops from 7 waves per SIMD to 6; without it all six shapes run at 7.
 const BatchKernel kRadianceKernels[] = {
-    TRT_RADIANCE(MODE_LDS, WALK_FLAT, 256, 7),
-    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 256, 7),
-    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 768, 7),
-    TRT_RADIANCE(MODE_LDS, WALK_REGS, 512, 7),
-    TRT_RADIANCE(MODE_GLOBAL, WALK_COMPACT, 256, 7),
-    TRT_RADIANCE(MODE_GLOBAL, WALK_REGS, 256, 7),
+    TRT_RADIANCE(MODE_LDS, WALK_FLAT, 256, 7, LOBE_NONE),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 256, 7, LOBE_NONE),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 768, 7, LOBE_NONE),
+    TRT_RADIANCE(MODE_LDS, WALK_REGS, 512, 7, LOBE_NONE),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_COMPACT, 256, 7, LOBE_NONE),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_REGS, 256, 7, LOBE_NONE),
+};
+// The gather queries' table: the same six shapes, one instantiation each.  The lobe is a kernel argument, not a template parameter: it is
+// the same for every lane of a launch, so the choice is a scalar branch around a few vector instructions of the start step, the draw
+// itself is shared by both lobes as it is in shade_hit, and six more instantiations would buy nothing the register report shows - a lane
+// carries what a lane of the LOBE_NONE kernel carries less the first (primitive, t), and the draw's temporaries die before the walk; with
+// the lobe fixed at compile time every shape reports the registers it reports here.  Five shapes run at 7 waves per SIMD without scratch.
+// The lock-step list needs 74 registers, two more than 7 waves allow (the LOBE_NONE one needs exactly 72): at 7 the compiler spills two
+// in the leaf loop, so its bound is 6 (profiles/gather_resource_usage.txt; the render's lock-step kernel measured no slower at 6 than at 7,
+// profiles/r02_cornell_waves_sweep.txt).
+const BatchKernel kGatherKernels[] = {
+    TRT_RADIANCE(MODE_LDS, WALK_FLAT, 256, 6, LOBE_GATHER),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 256, 7, LOBE_GATHER),
+    TRT_RADIANCE(MODE_LDS, WALK_LDS_STACK, 768, 7, LOBE_GATHER),
+    TRT_RADIANCE(MODE_LDS, WALK_REGS, 512, 7, LOBE_GATHER),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_COMPACT, 256, 7, LOBE_GATHER),
+    TRT_RADIANCE(MODE_GLOBAL, WALK_REGS, 256, 7, LOBE_GATHER),
 };
 #undef TRT_RADIANCE
 constexpr size_t kRadianceShapes = sizeof(kRadianceKernels) / sizeof(kRadianceKernels[0]);
+static_assert(sizeof(kGatherKernels) == sizeof(kRadianceKernels), "one gather instantiation per radiance shape");
+
+// The lobe of a launch: 0 for a radiance query (the items are rays), else what GatherArgs carries.
+struct Lobe {
+    uint32_t lobe;                   // 0: a radiance query
+    float spread;
+};
 
 hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_rays, uint32_t n, uint32_t samples_per_ray, uint32_t first_stream,
-                           float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+                           float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream, Lobe lobe = Lobe{0u, 0.0f}) {
     if (n == 0) return hipSuccess;
     if (ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
@@ -210,11 +274,13 @@ hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_r
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, kRadianceKernels, kRadianceShapes, b);
+    const hipError_t e = batch_prepare(scd, n, lobe.lobe ? kGatherKernels : kRadianceKernels, kRadianceShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     ra.flat_reuse = qs.flat_reuse;
-    RadianceArgs ga{d_rays, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, samples_per_ray, first_stream};
+    // a radiance kernel reads the RadianceArgs in front, a gather kernel all of it
+    GatherArgs ga{{d_rays, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, samples_per_ray, first_stream},
+                  lobe.lobe, lobe.spread};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
     // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
     timing_mark(stream, true);
@@ -247,6 +313,70 @@ int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const tr
     return TRT_OK;
 }
 
+// What the gather forms check before any device work: trt_radiance's rules on p->path, then the lobe.
+int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* radiance, RenderArgs& ra, Lobe& lobe) {
+    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    const int rc = radiance_check(s, items, n, &p->path, radiance, ra);
+    if (rc != TRT_OK) return rc;
+    if (p->lobe != TRT_LOBE_COSINE && p->lobe != TRT_LOBE_CONE) return query_fail(TRT_ERR_INVALID_ARG, "lobe must be TRT_LOBE_COSINE or TRT_LOBE_CONE");
+    if (p->lobe == TRT_LOBE_CONE && !(p->spread >= 0.0f && p->spread < __builtin_inff()))
+        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    lobe = Lobe{p->lobe, p->spread};
+    return TRT_OK;
+}
+
+// The device form of both queries, after the checks: buffers in HBM, asynchronous on `stream`.
+int radiance_on_device(trt_scene* s, const RenderArgs& ra, const trt_radiance_params& p, Lobe lobe, const trt_ray* d_rays, uint32_t n, float* d_radiance,
+                       float* d_moment2, uint64_t* d_counters, void* stream, const char* what) {
+    if (n == 0u) return TRT_OK;
+    int rc = query_require_device();
+    if (rc != TRT_OK) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = launch_radiance(qs, ra, reinterpret_cast<const float*>(d_rays), n, p.samples_per_ray, p.first_stream, d_radiance, d_moment2,
+                                         reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream), lobe);
+    if (e != hipSuccess) return query_fail_hip(e, what);
+    return TRT_OK;
+}
+
+// The host form of both queries, after the checks (inside host_form).  Host buffers: device copies of the rays and of the two sums are
+// the call's own (one allocation), one stream-ordered sequence on the default stream, complete when the call returns.  The running sums
+// go up only when the call continues them.
+int radiance_on_host(trt_scene* s, const RenderArgs& ra, const trt_radiance_params& p, Lobe lobe, const trt_ray* rays, uint32_t n, float* radiance,
+                     float* moment2, trt_stats* stats, const char* buffers, const char* launch) {
+    if (n == 0u) {
+        if (stats) *stats = trt_stats{};
+        return TRT_OK;
+    }
+    int rc = query_require_device();
+    if (rc != TRT_OK) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
+    HostStage st(buffers);
+    const size_t r_rays = st.reserve(rays_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
+    st.reserve_counters();
+    st.alloc();
+    st.up(r_rays, rays, rays_b, "hipMemcpy of the rays");
+    st.zero_counters();
+    // the running sums a pass continues go up; a pass that starts them reads nothing
+    if (ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
+    if (ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
+    st.time_begin();
+    if (st.ok())
+        st.run(launch_radiance(qs, ra, st.ptr<float>(r_rays), n, p.samples_per_ray, p.first_stream, st.ptr<float>(r_rad), st.ptr<float>(r_m2),
+                               st.counters(), nullptr, lobe), launch);
+    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
+    if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
+    if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
+    st.read_stats(stats);
+    return st.finish();
+}
+
 }  // namespace
 }  // namespace trt
 
@@ -263,61 +393,54 @@ void trt_radiance_params_default(trt_radiance_params* out) {
 int trt_radiance_device(trt_scene* s, const trt_ray* d_rays, uint32_t n, const trt_radiance_params* p, float* d_radiance, float* d_moment2,
                         uint64_t* d_counters, void* stream) {
     trt::RenderArgs ra;
-    int rc = trt::radiance_check(s, d_rays, n, p, d_radiance, ra);
+    const int rc = trt::radiance_check(s, d_rays, n, p, d_radiance, ra);
     if (rc != TRT_OK) return rc;
-    if (n == 0u) return TRT_OK;
-    rc = trt::query_require_device();
-    if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_radiance(qs, ra, reinterpret_cast<const float*>(d_rays), n, p->samples_per_ray, p->first_stream, d_radiance,
-                                              d_moment2, reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "radiance query launch");
-    return TRT_OK;
+    return trt::radiance_on_device(s, ra, *p, trt::Lobe{0u, 0.0f}, d_rays, n, d_radiance, d_moment2, d_counters, stream, "radiance query launch");
 }
 
-// Host buffers: device copies of the rays and of the two sums are the call's own (one allocation), one stream-ordered sequence on the
-// default stream, complete when the call returns.  The running sums go up only when the call continues them.
 int trt_radiance(trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, float* radiance, float* moment2, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::RenderArgs ra;
-        int rc = trt::radiance_check(s, rays, n, p, radiance, ra);
+        const int rc = trt::radiance_check(s, rays, n, p, radiance, ra);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
-        trt::HostStage st("radiance query buffers");
-        const size_t r_rays = st.reserve(rays_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_rays, rays, rays_b, "hipMemcpy of the rays");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
-        if (ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
-        st.time_begin();
-        if (st.ok())
-            st.run(trt::launch_radiance(qs, ra, st.ptr<float>(r_rays), n, p->samples_per_ray, p->first_stream, st.ptr<float>(r_rad), st.ptr<float>(r_m2),
-                                        st.counters(), nullptr), "radiance query launch");
-        const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
-        if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
-        if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        return trt::radiance_on_host(s, ra, *p, trt::Lobe{0u, 0.0f}, rays, n, radiance, moment2, stats, "radiance query buffers", "radiance query launch");
     });
 }
 
 // How launch_radiance would launch n rays on this scene.
 int trt_radiance_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
     return trt::batch_launch_plan(s, n, compute_units, trt::kRadianceKernels, trt::kRadianceShapes, out);
+}
+
+void trt_gather_params_default(trt_gather_params* out) {
+    if (!out) return;
+    *out = trt_gather_params{};
+    trt_radiance_params_default(&out->path);
+    out->lobe = TRT_LOBE_COSINE;
+}
+
+int trt_gather_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_gather_params* p, float* d_radiance, float* d_moment2,
+                      uint64_t* d_counters, void* stream) {
+    trt::RenderArgs ra;
+    trt::Lobe lobe;
+    const int rc = trt::gather_check(s, d_items, n, p, d_radiance, ra, lobe);
+    if (rc != TRT_OK) return rc;
+    return trt::radiance_on_device(s, ra, p->path, lobe, d_items, n, d_radiance, d_moment2, d_counters, stream, "gather query launch");
+}
+
+int trt_gather(trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::RenderArgs ra;
+        trt::Lobe lobe;
+        const int rc = trt::gather_check(s, items, n, p, radiance, ra, lobe);
+        if (rc != TRT_OK) return rc;
+        return trt::radiance_on_host(s, ra, p->path, lobe, items, n, radiance, moment2, stats, "gather query buffers", "gather query launch");
+    });
+}
+
+// How launch_radiance would launch n surfels on this scene.
+int trt_gather_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kGatherKernels, trt::kRadianceShapes, out);
 }
 
 }  // extern "C"
