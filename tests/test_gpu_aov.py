@@ -48,26 +48,30 @@ INV = np.float32(1.0) / np.float32(SPP)                                     # im
 
 
 def restated_rays(orc, ocam, seed, s, rows=None):
-    """float32 [rows, W, 6]: SamplePointGenerator::generate's body (pointgen.rs:41-43) and Camera::get_ray (camera.rs:58-66) for sample
-    s of every pixel of the image rows `rows` (all by default).  The random numbers are drawn pixel by pixel from the oracle's functions
-    in the reference's order (u, v, the unit disk); the vector arithmetic is numpy's float32 (one IEEE operation per operator, no
-    fusing) in the reference's order; Ray::new is the oracle's."""
+    """float32 [rows, W, 6]: restated_rays_of_pixels for every pixel of the image rows `rows` (all by default), row by row."""
     width, height = ocam.width, ocam.height
     rows = list(range(height)) if rows is None else list(rows)
-    n = len(rows) * width
+    return restated_rays_of_pixels(orc, ocam, seed, s, [y * width + x for y in rows for x in range(width)]).reshape(len(rows), width, 6)
+
+
+def restated_rays_of_pixels(orc, ocam, seed, s, pixels):
+    """float32 [len(pixels), 6]: SamplePointGenerator::generate's body (pointgen.rs:41-43) and Camera::get_ray (camera.rs:58-66) for
+    sample s of the pixels `pixels` (y * W + x), in the order given.  The random numbers are drawn pixel by pixel from the oracle's
+    functions in the reference's order (u, v, the unit disk); the vector arithmetic is numpy's float32 (one IEEE operation per operator,
+    no fusing) in the reference's order; Ray::new is the oracle's."""
+    width, height = ocam.width, ocam.height
+    n = len(pixels)
     ru, rv, px, py = (np.zeros(n, np.float32) for _ in range(4))
     xs, ys = np.zeros(n, np.float32), np.zeros(n, np.float32)
     rng = (C.c_uint32 * 2)()
-    i = 0
-    for y in rows:
-        for x in range(width):
-            orc.lib.orc_rng_seed(seed, y * width + x, s, rng)
-            ru[i] = orc.lib.orc_rng_random(rng)
-            rv[i] = orc.lib.orc_rng_random(rng)
-            p = orc.lib.orc_random_in_unit_disk(rng)
-            px[i], py[i] = p.x, p.y
-            xs[i], ys[i] = x, y
-            i += 1
+    for i, pixel in enumerate(pixels):
+        y, x = divmod(int(pixel), width)
+        orc.lib.orc_rng_seed(seed, y * width + x, s, rng)
+        ru[i] = orc.lib.orc_rng_random(rng)
+        rv[i] = orc.lib.orc_rng_random(rng)
+        p = orc.lib.orc_random_in_unit_disk(rng)
+        px[i], py[i] = p.x, p.y
+        xs[i], ys[i] = x, y
     u = ((xs + ru) / np.float32(width - 1))[:, None]
     v = ((ys + rv) / np.float32(height - 1))[:, None]
     vec = lambda name: np.array(getattr(ocam, name).tolist(), np.float32)[None, :]          # noqa: E731
@@ -80,7 +84,7 @@ def restated_rays(orc, ocam, seed, s, rows=None):
         r = orc.lib.orc_ray_new(orc.Vec3(*origin[i]), orc.Vec3(*direction[i]))
         out[i, :3] = r.origin.tolist()
         out[i, 3:] = r.direction.tolist()
-    return out.reshape(len(rows), width, 6)
+    return out
 
 
 def fold(per_sample, hit=None, start=None):
