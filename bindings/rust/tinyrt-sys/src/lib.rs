@@ -259,6 +259,16 @@ pub struct trt_gather_params {
     pub reserved: [u32; 6],
 }
 
+/// `trt_gather_params` and the distance within which an occluder counts, for `trt_ambient` (128 bytes); `gather.path.max_bounces` and
+/// `gather.path.background` are not read; `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_ambient_params {
+    pub gather: trt_gather_params,
+    pub max_distance: f32,
+    pub reserved: [u32; 7],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -417,6 +427,12 @@ extern "C" {
     pub fn trt_gather_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_gather_params, d_radiance: *mut f32,
                              d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_gather_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_ambient_params_default(out: *mut trt_ambient_params);
+    pub fn trt_ambient(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_ambient_params, visibility: *mut f32,
+                       bent: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_ambient_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_ambient_params, d_visibility: *mut f32,
+                              d_bent: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_ambient_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

@@ -114,7 +114,7 @@ impl Material for Light {
     }
 }
 
-/// The rule `World::gather` draws the first ray of a sample by (`enum trt_lobe`); `Cone` carries the spread.
+/// The rule `World::gather` and `World::ambient` draw the first ray of a sample by (`enum trt_lobe`); `Cone` carries the spread.
 #[derive(Clone, Copy, Debug, PartialEq)]
 pub enum Lobe {
     Cosine,
@@ -249,6 +249,39 @@ impl World {
                             moment2.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((radiance, moment2))
+    }
+
+    /// How open the lobe about caller-supplied surfels is (`trt_ambient`): for every one of `samples_per_item` samples the device draws
+    /// the first ray `gather` would draw for the same `lobe`, `seed` and `first_stream`, and asks whether anything lies in
+    /// `[0.001, max_distance)` along it (`Float::INFINITY`: sky visibility).  An unoccluded sample adds 1 / K to the item's visibility
+    /// and its unit direction / K to the item's bent sum; an occluded one adds nothing.  Returns `(visibility, bent)`: one float and
+    /// three floats per item; `bent` is not renormalised.
+    pub fn ambient(&mut self, items: &[[Float; 6]], samples_per_item: u32, lobe: Lobe, max_distance: Float, seed: u32,
+                   first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_ambient_params::default();
+        unsafe { sys::trt_ambient_params_default(&mut params) };
+        params.gather.path.samples_per_ray = samples_per_item;
+        params.gather.path.seed = seed;
+        params.gather.path.first_stream = first_stream;
+        params.max_distance = max_distance;
+        match lobe {
+            Lobe::Cosine => params.gather.lobe = sys::TRT_LOBE_COSINE,
+            Lobe::Cone(spread) => {
+                params.gather.lobe = sys::TRT_LOBE_CONE;
+                params.gather.spread = spread;
+            }
+        }
+        let mut visibility = vec![0.0 as Float; items.len()];
+        let mut bent = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_ambient(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, visibility.as_mut_ptr(),
+                             bent.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((visibility, bent))
     }
 
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.

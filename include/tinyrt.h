@@ -46,7 +46,8 @@ extern "C" {
  *              trt_render_pixels_device, trt_pixels_launch_plan, trt_select_pixels, trt_select_pixels_device,
  *              trt_select_scratch_bytes; trt_radiance_params, trt_radiance_params_default, trt_radiance, trt_radiance_device,
  *              trt_radiance_launch_plan; trt_lobe, trt_gather_params, trt_gather_params_default, trt_gather, trt_gather_device,
- *              trt_gather_launch_plan. */
+ *              trt_gather_launch_plan; trt_ambient_params, trt_ambient_params_default, trt_ambient, trt_ambient_device,
+ *              trt_ambient_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -565,6 +566,54 @@ int trt_gather_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const tr
 /* How trt_gather[_device] launches n items on this scene: trt_radiance_launch_plan's rule and fields over the gather kernels' own table
  * (the same shapes; kernel_waves_per_simd is that table's bound). */
 int trt_gather_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Ambient queries: how open is the lobe about a surfel, and towards where ----
+ * Before "what light arrives here" (trt_gather) a baker or a probe system asks "how much of the hemisphere is open": ambient occlusion,
+ * sky visibility, and the bent normal - the mean unoccluded direction.  An ambient query draws trt_gather's first rays on the device and
+ * asks trt_occluded's question of each: nothing per sample crosses the bus, no closest hit is searched and nothing is shaded.
+ *  - Item i is a surfel (origin = point, direction = axis), both used AS GIVEN, as in trt_gather.
+ *  - First ray.  For sample s of 0..K, K = gather.path.samples_per_ray, the stream index is j = gather.path.first_stream + i * K + s, and
+ *    the ray is trt_gather's first ray for the same `gather` parameters, bit for bit: three draws from RNG (seed, pixel = j, sample = 1),
+ *    the cosine or the cone rule, Ray::new - which normalises, so the direction d below is a unit vector.  Stream (seed, j, 0) is not
+ *    touched: there is no path.  gather.path.max_bounces and gather.path.background are not read.
+ *  - Sample.  o = 1 if BVH::hit (hittable/bvh.rs:24-27,88-107) over [0.001, max_distance) finds anything for that ray, else 0: exactly
+ *    what trt_occluded answers for it with t_max = max_distance.  Every material occludes, lights and glass included.  A first ray with a
+ *    NaN component hits nothing (the rule of the ray queries).  If max_distance is not > 0.001 the range is empty: nothing is walked and
+ *    every sample is unoccluded.  max_distance = +inf asks for sky visibility.
+ *  - Fold, per item, in sample order, all f32, one IEEE operation per operator, nothing fused; inv_K = 1.0f / float(K).  An unoccluded
+ *    sample adds
+ *      visibility = visibility + inv_K;   bent.ch = bent.ch + d.ch * inv_K
+ *    and an occluded sample adds nothing (it does not add 0).  `visibility` holds n f32 and is required; `bent` holds n x 3 f32 and may
+ *    be NULL (not wanted; `visibility` is the same either way).  `bent` is not renormalised: its direction is the bent normal, its length
+ *    says how one-sided the opening is.  With the cosine lobe 1 - visibility is cosine-weighted ambient occlusion.
+ *  - Sample range, accumulate, the 1 / K scale fixed by K, and split invariance by samples (split the range, set accumulate) and by items
+ *    (first_stream + a * K): as in trt_radiance.  An empty sample range zeroes the n entries unless accumulate, which touches nothing;
+ *    max_bounces == 0 is NOT "nothing to trace" here.  No byte outside [0, 4 n) of `visibility` or [0, 12 n) of `bent` is ever written.
+ *  - stats / d_counters receive samples ([0]) and rays ([1]) only.  `rays` is the number of occlusion walks: one per traced sample when
+ *    max_distance > 0.001, else 0.  kernel_ms as in trt_radiance.  `d_counters`: 16 uint64 as in trt_render_device, added to, or NULL.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL scene or params; with n > 0 a NULL `items` or `visibility`; every error
+ *    trt_gather reports for `gather` (K == 0, a bad sample range, first_stream + n * K > 2^32, a bad lobe or spread, a non-zero reserved
+ *    word); a NaN max_distance; a non-zero reserved word of this struct.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's
+ *    buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * trt_ambient: HOST buffers, synchronous; one device allocation for the call; the sums are uploaded only when accumulate is set.
+ * trt_ambient_device: buffers in HBM on the calling thread's current device, asynchronous on `stream`; allocates nothing.
+ * Order, coherence and concurrency as in trt_gather: a wave works through a contiguous run of the items, each for all samples of the
+ * call.  The launch rule gives a wave 256 items whatever K is, as it does for trt_radiance and trt_gather. */
+typedef struct {
+    trt_gather_params gather;     /* lobe, spread and, of gather.path: samples_per_ray (K), seed, sample_begin, sample_end, accumulate,
+                                     first_stream - same rules, same errors as trt_gather.  gather.path.max_bounces and
+                                     gather.path.background are IGNORED (not read, not validated): there is no path. */
+    float max_distance;           /* occluders count in [0.001, max_distance) along the unit first ray; +inf: sky visibility */
+    uint32_t reserved[7];         /* zero */
+} trt_ambient_params;             /* 128 B: offsets 0, 96, 100 */
+void trt_ambient_params_default(trt_ambient_params *out);   /* gather = trt_gather_params_default, max_distance = +inf, rest 0; NULL tolerated */
+int trt_ambient(trt_scene *s, const trt_ray *items, uint32_t n, const trt_ambient_params *p, float *visibility, float *bent,
+                trt_stats *stats);
+int trt_ambient_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_ambient_params *p, float *d_visibility, float *d_bent,
+                       uint64_t *d_counters, void *stream);
+/* How trt_ambient[_device] launches n items on this scene: trt_query_launch_plan's rule and fields over the ambient kernels' own table
+ * (the same shapes; kernel_waves_per_simd is that table's bound). */
+int trt_ambient_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

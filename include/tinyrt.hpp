@@ -120,6 +120,17 @@ public:
         if (moment2) moment2->resize(items.size() * 3);
         check(trt_gather(get_bvh(), items.data(), (uint32_t)items.size(), &p, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
     }
+    // How open the lobe about caller-supplied surfels is (trt_ambient): for each of p.gather.path.samples_per_ray samples the device draws
+    // the first ray gather() would draw and asks whether anything lies in [0.001, p.max_distance) along it.  `visibility` becomes one
+    // float per item - the unoccluded share; with the cosine lobe 1 - visibility is ambient occlusion - and `bent` (nullptr: not wanted)
+    // three: the sum of the unoccluded unit directions / K, the bent normal, not renormalised.  Both continue the sums they hold when
+    // p.gather.path.accumulate is set.  Start `p` from trt_ambient_params_default.
+    void ambient(const std::vector<trt_ray>& items, const trt_ambient_params& p, std::vector<float>& visibility,
+                 std::vector<float>* bent = nullptr, trt_stats* stats = nullptr) {
+        visibility.resize(items.size());
+        if (bent) bent->resize(items.size() * 3);
+        check(trt_ambient(get_bvh(), items.data(), (uint32_t)items.size(), &p, visibility.data(), bent ? bent->data() : nullptr, stats));
+    }
     int num_geometries() const { return trt_world_num_geometries(w_); }
     const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).

@@ -131,6 +131,12 @@ class GatherParams(C.Structure):
     _fields_ = [("path", RadianceParams), ("lobe", C.c_uint32), ("spread", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
+class AmbientParams(C.Structure):
+    """tinyrt.h trt_ambient_params: trt_gather_params (its path's max_bounces and background are not read) and the distance within which
+    an occluder counts (128 bytes)."""
+    _fields_ = [("gather", GatherParams), ("max_distance", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -229,6 +235,11 @@ SIGNATURES = {
     "trt_gather_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(GatherParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "trt_gather_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_ambient_params_default": (None, [C.POINTER(AmbientParams)]),
+    "trt_ambient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(AmbientParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_ambient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(AmbientParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "trt_ambient_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -292,6 +292,61 @@ class Scene:
         check(lib.trt_gather_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- ambient queries (tinyrt.h trt_ambient): occlusion and bent normals from the first rays a gather query would draw ----
+    @classmethod
+    def _ambient_params(cls, samples_per_item, lobe="cosine", spread=0.0, max_distance=float("inf"), seed=1, first_stream=0, sample_begin=0,
+                        sample_end=0, accumulate=False):
+        """sample_end = 0 means samples_per_item, as at the C boundary."""
+        if lobe not in cls.LOBES:
+            raise ValueError("lobe must be 'cosine' or 'cone'")
+        p = _lib.AmbientParams()
+        lib.trt_ambient_params_default(C.byref(p))
+        path = p.gather.path
+        path.samples_per_ray, path.seed, path.first_stream = int(samples_per_item), int(seed), int(first_stream)
+        path.sample_begin, path.sample_end, path.accumulate = int(sample_begin), int(sample_end), 1 if accumulate else 0
+        p.gather.lobe, p.gather.spread, p.max_distance = cls.LOBES[lobe], float(spread), float(max_distance)
+        return p
+
+    def ambient(self, items, samples_per_item, lobe="cosine", spread=0.0, max_distance=float("inf"), seed=1, first_stream=0, sample_begin=0,
+                sample_end=0, accumulate=False, visibility=None, bent=False):
+        """trt_ambient: how open the lobe about surfels float32 [n, 6] (point, axis; used as given) is.  For each of samples_per_item = K
+        samples the device draws gather()'s first ray - the same lobe, spread, seed and first_stream give the same rays, bit for bit - and
+        asks occluded()'s question of it over [0.001, max_distance); an unoccluded sample adds 1 / K to visibility[i] and its unit
+        direction / K to bent[i], an occluded one nothing.  With the cosine lobe 1 - visibility is ambient occlusion; max_distance = inf
+        is sky visibility; bent is the bent normal, not renormalised.  Samples [sample_begin, sample_end) are traced (sample_end = 0: K).
+        `visibility`: float32 [n] to write or, with accumulate, to continue (changed in place); None allocates one.  `bent`: float32
+        [n, 3] likewise; True allocates one, False or None = not wanted.  Returns (visibility[n], bent[n, 3] or None, stats with samples
+        and rays = occlusion walks)."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        p = self._ambient_params(samples_per_item, lobe, spread, max_distance, seed, first_stream, sample_begin, sample_end, accumulate)
+        if visibility is None:
+            visibility = np.zeros(n, np.float32)
+        if bent is True:
+            bent = np.zeros((n, 3), np.float32)
+        elif bent is False:
+            bent = None
+        assert visibility.dtype == np.float32 and visibility.flags.c_contiguous and visibility.shape == (n,)
+        assert bent is None or (bent.dtype == np.float32 and bent.flags.c_contiguous and bent.shape == (n, 3))
+        st = Stats()
+        check(lib.trt_ambient(self._h, r.ctypes.data if n else None, n, C.byref(p), visibility.ctypes.data if n else None,
+                              bent.ctypes.data if bent is not None and n else None, C.byref(st)))
+        return visibility, bent, st.as_dict()
+
+    def ambient_device(self, d_items_ptr, n, d_visibility_ptr, d_bent_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue ambient() on buffers already in HBM (device pointers as integers: n x 24 bytes of surfels, n x 4 bytes of visibility,
+        n x 12 bytes of bent sums or 0) on the current device; asynchronous on the stream, allocates nothing.  `params`: ambient()'s
+        keywords, samples_per_item included."""
+        p = self._ambient_params(**params)
+        check(lib.trt_ambient_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_visibility_ptr), C.c_void_p(d_bent_ptr),
+                                     C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def ambient_plan(self, n, compute_units=0):
+        """trt_ambient_launch_plan: how ambient() launches n surfels on this scene, as a dict with gather_plan()'s fields."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_ambient_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""

@@ -1,0 +1,48 @@
+// gather_draw.h - what the units that draw a sample's first ray about a caller-supplied surfel share: the gather queries (radiance.hip:
+// the drawn ray starts a path) and the ambient queries (ambient.hip: the drawn ray is an occlusion query).  ONE copy of the item load and
+// of the draw on the device, and of the argument checks of trt_gather_params on the host.  The two device functions are pure functions
+// of values (wave_run.h says why): moved here from radiance.hip as they stood, radiance_kernel compiles to the registers it had.
+#pragma once
+
+#include "kernels.h"
+#include "rt_path.h"
+
+namespace trt {
+
+TRT_DEV Ray rad_load_ray(const float* __restrict__ rays, uint32_t idx) {
+    const float* r = rays + 6ull * idx;
+    Ray ray;
+    ray.o = v3(r[0], r[1], r[2]);
+    ray.d = v3(r[3], r[4], r[5]);
+    return ray;
+}
+
+// The first ray of a gather sample: the scatter rule of the lobe applied to the surfel (point, axis) = (item.o, item.d) with the draws
+// of g, in the operations of rt_path.h shade_hit (hence of the oracle's material_scatter).  Three draws are taken from g.
+// Cosine, lambertian.rs:16-22: axis + random_unit_vector, the axis itself if that is near zero; cone, metal.rs:18-25 with the axis in
+// the place of the reflected direction: axis + spread * random_in_unit_sphere.  Ray::new normalises (ray.rs:12-14).
+TRT_DEV Ray gather_ray(const float* __restrict__ items, uint32_t idx, uint32_t lobe, float spread, Rng& g) {
+    const V3 in_sphere = random_in_unit_sphere_unit(g);
+    const Ray item = rad_load_ray(items, idx);                              // after the draw: six registers less while it runs
+    V3 dir;
+    if (lobe == TRT_LOBE_COSINE) {
+        dir = item.d + normalized(in_sphere);
+        if (near_zero(dir)) dir = item.d;
+    } else {
+        dir = item.d + spread * in_sphere;
+    }
+    return ray_new(item.o, dir);
+}
+
+// The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.
+struct Lobe {
+    uint32_t lobe;                   // 0: a radiance query
+    float spread;
+};
+
+// Host side, declared here because the same two units need it and nothing else does: a header for one declaration would be a file more.
+// What the forms that take a trt_gather_params check before any device work: trt_radiance's rules on p->path, then the lobe; and the
+// kernel arguments of the parameters (radiance.hip).  `sums`: the required output buffer.
+int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* sums, RenderArgs& ra, Lobe& lobe);
+
+}  // namespace trt

@@ -4,6 +4,8 @@
 // a launch does before hipLaunchKernel (batch_prepare), of the launch-plan entry point (batch_launch_plan) and of the argument checks of
 // the units that trace camera rays (batch_render_args).  The device side of the same units is wave_run.h; their host-buffer forms stage
 // through host_stage.h, which also has q_align16.
+// The radiance and gather queries (radiance.hip: a run of the caller's rays or surfels) and the ambient queries (ambient.hip: a run of
+// surfels) use the same table entry, rule, preamble and plan entry point with tables of their own.
 // For those three units only: batch_prepare and batch_launch_plan call the HIP runtime and scene_query.h's helpers, so capi.hip, whose
 // host-only build links without the units, must not include this header.
 #pragma once

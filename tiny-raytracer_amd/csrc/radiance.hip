@@ -25,6 +25,7 @@
 // start step DRAWS the sample's first ray about the axis - Lambertian::scatter's rule (cosine lobe) or Metal::scatter's with the axis as
 // the mirror direction (cone lobe), from stream (seed, j, 1) - where a radiance query loads it; the path then runs on stream (seed, j, 0)
 // as above.  The first segment differs per sample, so nothing of it is shared.
+#include "gather_draw.h"
 #include "kernels.h"
 #include "query_plan.h"
 #include "rt_path.h"
@@ -60,30 +61,7 @@ constexpr int LOBE_NONE = 0, LOBE_GATHER = 1;   // radiance_kernel's LOBE: the i
 template <int LOBE> struct RadianceArgsOf { using type = RadianceArgs; };
 template <> struct RadianceArgsOf<LOBE_GATHER> { using type = GatherArgs; };
 
-TRT_DEV Ray rad_load_ray(const float* __restrict__ rays, uint32_t idx) {
-    const float* r = rays + 6ull * idx;
-    Ray ray;
-    ray.o = v3(r[0], r[1], r[2]);
-    ray.d = v3(r[3], r[4], r[5]);
-    return ray;
-}
-
-// The first ray of a gather sample: the scatter rule of the lobe applied to the surfel (point, axis) = (item.o, item.d) with the draws
-// of g, in the operations of rt_path.h shade_hit (hence of the oracle's material_scatter).  Three draws are taken from g.
-// Cosine, lambertian.rs:16-22: axis + random_unit_vector, the axis itself if that is near zero; cone, metal.rs:18-25 with the axis in
-// the place of the reflected direction: axis + spread * random_in_unit_sphere.  Ray::new normalises (ray.rs:12-14).
-TRT_DEV Ray gather_ray(const float* __restrict__ items, uint32_t idx, uint32_t lobe, float spread, Rng& g) {
-    const V3 in_sphere = random_in_unit_sphere_unit(g);
-    const Ray item = rad_load_ray(items, idx);                              // after the draw: six registers less while it runs
-    V3 dir;
-    if (lobe == TRT_LOBE_COSINE) {
-        dir = item.d + normalized(in_sphere);
-        if (near_zero(dir)) dir = item.d;
-    } else {
-        dir = item.d + spread * in_sphere;
-    }
-    return ray_new(item.o, dir);
-}
+// (rad_load_ray and gather_ray, the item load and the draw of a gather sample: gather_draw.h, shared with ambient.hip)
 
 // ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_radiance: nothing to trace launches radiance_zero_kernel or nothing)
 template <int MODE, int WALK, int THREADS, int MINW, int LOBE>
@@ -256,12 +234,6 @@ const BatchKernel kGatherKernels[] = {
 constexpr size_t kRadianceShapes = sizeof(kRadianceKernels) / sizeof(kRadianceKernels[0]);
 static_assert(sizeof(kGatherKernels) == sizeof(kRadianceKernels), "one gather instantiation per radiance shape");
 
-// The lobe of a launch: 0 for a radiance query (the items are rays), else what GatherArgs carries.
-struct Lobe {
-    uint32_t lobe;                   // 0: a radiance query
-    float spread;
-};
-
 hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_rays, uint32_t n, uint32_t samples_per_ray, uint32_t first_stream,
                            float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream, Lobe lobe = Lobe{0u, 0.0f}) {
     if (n == 0) return hipSuccess;
@@ -310,20 +282,6 @@ int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const tr
     ra.sample_begin = p->sample_begin;
     ra.sample_end = s1;
     ra.accumulate = p->accumulate ? 1u : 0u;
-    return TRT_OK;
-}
-
-// What the gather forms check before any device work: trt_radiance's rules on p->path, then the lobe.
-int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* radiance, RenderArgs& ra, Lobe& lobe) {
-    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    const int rc = radiance_check(s, items, n, &p->path, radiance, ra);
-    if (rc != TRT_OK) return rc;
-    if (p->lobe != TRT_LOBE_COSINE && p->lobe != TRT_LOBE_CONE) return query_fail(TRT_ERR_INVALID_ARG, "lobe must be TRT_LOBE_COSINE or TRT_LOBE_CONE");
-    if (p->lobe == TRT_LOBE_CONE && !(p->spread >= 0.0f && p->spread < __builtin_inff()))
-        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
-    for (uint32_t r : p->reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
-    lobe = Lobe{p->lobe, p->spread};
     return TRT_OK;
 }
 
@@ -378,6 +336,22 @@ int radiance_on_host(trt_scene* s, const RenderArgs& ra, const trt_radiance_para
 }
 
 }  // namespace
+
+// What the gather forms check before any device work: trt_radiance's rules on p->path, then the lobe (gather_draw.h: ambient.hip
+// applies the same rules to its own trt_gather_params).
+int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* radiance, RenderArgs& ra, Lobe& lobe) {
+    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    const int rc = radiance_check(s, items, n, &p->path, radiance, ra);
+    if (rc != TRT_OK) return rc;
+    if (p->lobe != TRT_LOBE_COSINE && p->lobe != TRT_LOBE_CONE) return query_fail(TRT_ERR_INVALID_ARG, "lobe must be TRT_LOBE_COSINE or TRT_LOBE_CONE");
+    if (p->lobe == TRT_LOBE_CONE && !(p->spread >= 0.0f && p->spread < __builtin_inff()))
+        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    lobe = Lobe{p->lobe, p->spread};
+    return TRT_OK;
+}
+
 }  // namespace trt
 
 extern "C" {

@@ -3,6 +3,8 @@
 // pixel list).  ONE copy of the lane rank, the run of a wave, the place of the leaf stacks, the cursor step of the round loop's refill
 // and the surface record of a closest hit; each kernel keeps its own loop body, because what a lane carries and does with a finished
 // walk differs.  The host side of the same units (kernel table, launch rule, launch preamble) is query_plan.h.
+// radiance.hip (radiance and gather queries: a run of the caller's rays or surfels) and ambient.hip (ambient queries: a run of surfels)
+// take the run, the leaf stacks and the refill step from here too.
 //
 // Every function here is a pure function of values, and that is deliberate: with these the device assembly of all kernels that use them
 // is, instruction for instruction, what their own copies gave.  Forms that did more were built and dropped because the compiler then
