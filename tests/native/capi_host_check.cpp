@@ -1,5 +1,6 @@
-// capi_host_check.cpp — drives the HOST logic of tiny-raytracer_amd/csrc/capi.hip (workspace / context pools, multi-GPU gather,
-// timing brackets, error paths) on a simulated HIP runtime (tests/native/hipstub) under ThreadSanitizer or ASan+UBSan.
+// capi_host_check.cpp — drives the HOST logic of tiny-raytracer_amd/csrc/capi.hip and scene_cache.h (the scene's device cache with its
+// workspace / context pools, the blocking calls' scaffold, multi-GPU gather, timing brackets, error paths) on a simulated HIP runtime
+// (tests/native/hipstub) under ThreadSanitizer or ASan+UBSan.
 // TEST INFRASTRUCTURE: built and run by tests/test_host_sanitizers.py; prints "ok ..." lines and returns 0, or says what failed.
 #include <hip/hip_runtime.h>
 
@@ -14,11 +15,17 @@
 #include <vector>
 
 #include "../../include/tinyrt.h"
+#include "../../tiny-raytracer_amd/csrc/scene_query.h"
 
 extern "C" long launch_stub_corruptions(void);
 extern "C" long launch_stub_launches(void);
 extern "C" long launch_stub_short_launches(void);
-namespace trt { float stub_pattern(uint32_t y, uint32_t x, int c, uint32_t seed_key, uint32_t s0, uint32_t s1); }
+namespace trt {
+float stub_pattern(uint32_t y, uint32_t x, int c, uint32_t seed_key, uint32_t s0, uint32_t s1);
+float stub_pattern2(uint32_t y, uint32_t x, int c, uint32_t seed_key, uint32_t s0, uint32_t s1);
+hipError_t stub_launch_moments(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                               float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats, hipStream_t stream);
+}
 
 static int g_failures = 0;
 #define CHECK(cond, ...)                                                                  \
@@ -31,13 +38,14 @@ static uint32_t seed_key(uint32_t seed) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }
-static std::vector<float> expected(uint32_t w, uint32_t h, uint32_t seed, uint32_t s0, uint32_t s1, int passes = 1) {
+static std::vector<float> expected(uint32_t w, uint32_t h, uint32_t seed, uint32_t s0, uint32_t s1, int passes = 1, bool second = false) {
     std::vector<float> f((size_t)w * h * 3);
+    const auto pattern = second ? trt::stub_pattern2 : trt::stub_pattern;      // second: the moments stub's other frame
     for (uint32_t y = 0; y < h; y++)
         for (uint32_t x = 0; x < w; x++)
             for (int c = 0; c < 3; c++) {
                 float v = 0.0f;
-                for (int k = 0; k < passes; k++) v = k == 0 ? trt::stub_pattern(y, x, c, seed_key(seed), s0, s1) : v + trt::stub_pattern(y, x, c, seed_key(seed), s0, s1);
+                for (int k = 0; k < passes; k++) v = k == 0 ? pattern(y, x, c, seed_key(seed), s0, s1) : v + pattern(y, x, c, seed_key(seed), s0, s1);
                 f[((size_t)y * w + x) * 3 + c] = v;
             }
     return f;
@@ -319,6 +327,117 @@ static void cap_and_trim() {
     printf("ok cap and trim\n");
 }
 
+// The blocking calls this file drives besides trt_render / trt_render_multi.  Each returns the status and says in `right` whether what came
+// back is what the stubs compute (looked at when the status is TRT_OK).
+static int call_sample_batch(trt_scene* s, trt_stats* st, bool& right) {
+    const uint32_t n = 65;
+    std::vector<trt_sample_point> in(n);
+    std::vector<trt_sampled_color> out(n);
+    memset(in.data(), 0, n * sizeof(trt_sample_point));
+    for (uint32_t i = 0; i < n; i++) { in[i].x = i; in[i].y = 1000u + i; out[i].x = out[i].y = ~0u; }
+    const int rc = trt_sample_batch(s, in.data(), n, out.data(), 4, trt_vec3{0.1f, 0.2f, 0.3f}, 9, st);
+    right = !st || st->samples == n;
+    for (uint32_t i = 0; i < n; i++) right = right && out[i].x == i && out[i].y == 1000u + i && out[i].color.x == 1.0f && out[i].color.y == 2.0f && out[i].color.z == 3.0f;
+    return rc;
+}
+static int call_moments(trt_scene* s, uint32_t acc, trt_stats* st, bool& right) {
+    trt_camera cam = make_camera(40, 36);
+    trt_render_params p = params(5, TRT_BACKEND_STREAMED, 0, 8, acc);
+    std::vector<float> f = acc ? expected(40, 36, 5, 0, 8) : std::vector<float>(40 * 36 * 3, -1.0f);
+    std::vector<float> m2 = acc ? expected(40, 36, 5, 0, 8, 1, true) : std::vector<float>(40 * 36 * 3, -1.0f);
+    const int rc = trt::query_render_moments(s, &cam, &p, f.data(), m2.data(), st, trt::stub_launch_moments);
+    right = f == expected(40, 36, 5, 0, 8, acc ? 2 : 1) && m2 == expected(40, 36, 5, 0, 8, acc ? 2 : 1, true) && (!st || st->samples == 40u * 36u * 8u);
+    return rc;
+}
+static int call_scene_on_device(trt_scene* s, bool& right) {
+    trt::QueryScene qs{};
+    const int rc = trt::query_scene_on_device(s, qs);
+    right = false;
+    if (rc != TRT_OK) return rc;
+    trt_scene_info info;
+    trt_scene_get_info(s, &info);
+    std::vector<uint8_t> packed(info.device_bytes);
+    trt_scene_get_packed(s, packed.data(), info.device_bytes);
+    right = qs.scene.blob && qs.geo_index && memcmp(qs.scene.blob, packed.data(), packed.size()) == 0;      // ("device memory" is the C heap)
+    uint32_t seen = 0;                                                        // the five spheres of make_scene, each insertion index once
+    for (int k = 0; right && k < 5; k++) { right = qs.geo_index[k] < 5u; if (right) seen |= 1u << qs.geo_index[k]; }
+    right = right && seen == 31u;
+    return rc;
+}
+
+// What each blocking entry point puts on its stream(s): per stream the ordered list of (kind, bytes per row, rows) the simulated runtime
+// EXECUTED during one call (copies, memsets and the stub kernels; allocations, events and synchronisation are not work on a stream and
+// not in the log).  A stream is named by its device; the shard threads of trt_render_multi race, so the streams' lists are compared
+// sorted.  The lists were written down from a run of this check on the code BEFORE the device cache and the blocking calls' scaffold
+// moved into csrc/scene_cache.h: they pin the call sequences of the entry points across that move.
+static std::vector<std::string> stream_sequences(const std::vector<hipstub_op>& log) {
+    std::vector<hipStream_t> streams;
+    for (const hipstub_op& op : log) if (std::find(streams.begin(), streams.end(), op.stream) == streams.end()) streams.push_back(op.stream);
+    std::vector<std::string> out;
+    for (hipStream_t sm : streams) {
+        std::string line;
+        for (const hipstub_op& op : log) {
+            if (op.stream != sm) continue;
+            // two shards on one device may be served by one context, one after the other: a shard's work begins with zeroing its counters
+            if (!line.empty() && !strcmp(op.kind, "memset")) { out.push_back(line); line.clear(); }
+            if (line.empty()) line = "dev" + std::to_string(op.device) + ":";
+            line += " " + std::string(op.kind) + " " + std::to_string(op.width) + "x" + std::to_string(op.height);
+        }
+        out.push_back(line);
+    }
+    std::sort(out.begin(), out.end());
+    return out;
+}
+static void check_sequences(const char* what, const std::vector<hipstub_op>& log, const std::vector<std::string>& want) {
+    const std::vector<std::string> got = stream_sequences(log);
+    CHECK(got == want, "%s: the streams' work differs", what);
+    if (got != want) for (const std::string& l : got) printf("    got  \"%s\"\n", l.c_str());
+}
+static void call_sequences() {
+    trt_scene* s = make_scene();
+    trt_camera cam = make_camera(40, 36);                                    // 17280 bytes; 480 a row; three bands for trt_render_multi, the last of 4 rows
+    hipSetDevice(0);
+    bool right = false;
+    trt_stats st;
+    {
+        std::vector<float> f = expected(40, 36, 5, 0, 8);
+        trt_render_params p = params(5, TRT_BACKEND_STREAMED, 0, 8, 1);
+        hipstub_oplog_start();
+        const int rc = trt_render(s, &cam, &p, f.data(), &st);
+        const std::vector<hipstub_op> log = hipstub_oplog_stop();
+        CHECK(rc == TRT_OK && f == expected(40, 36, 5, 0, 8, 2) && st.samples == 40u * 36u * 8u, "trt_render: %d %s", rc, trt_last_error());
+        check_sequences("trt_render", log, {"dev0: memset 128x1 copy 17280x1 kernel 480x36 copy 17280x1 copy 128x1"});
+    }
+    {
+        hipstub_oplog_start();
+        const int rc = call_moments(s, 1, &st, right);
+        const std::vector<hipstub_op> log = hipstub_oplog_stop();
+        CHECK(rc == TRT_OK && right, "moments host form: %d %s", rc, trt_last_error());
+        check_sequences("moments host form", log, {"dev0: memset 128x1 copy 17280x1 copy 17280x1 kernel 480x36 moments 480x36 copy 17280x1 copy 17280x1 copy 128x1"});
+    }
+    {
+        hipstub_oplog_start();
+        const int rc = call_sample_batch(s, &st, right);
+        const std::vector<hipstub_op> log = hipstub_oplog_stop();
+        CHECK(rc == TRT_OK && right, "trt_sample_batch: %d %s", rc, trt_last_error());
+        check_sequences("trt_sample_batch", log, {"dev0: memset 128x1 copy 2080x1 kernel 1300x1 copy 1300x1 copy 128x1"});
+    }
+    {
+        const int devs[3] = {0, 1, 0};
+        std::vector<float> f = expected(40, 36, 5, 0, 8);
+        trt_render_params p = params(5, TRT_BACKEND_STREAMED, 0, 8, 1);
+        hipstub_oplog_start();
+        const int rc = trt_render_multi(s, &cam, &p, devs, 3, f.data(), &st);
+        const std::vector<hipstub_op> log = hipstub_oplog_stop();
+        CHECK(rc == TRT_OK && f == expected(40, 36, 5, 0, 8, 2) && st.samples == 40u * 36u * 8u, "trt_render_multi: %d %s", rc, trt_last_error());
+        check_sequences("trt_render_multi", log, {"dev0: memset 128x1 copy 1920x1 kernel 480x4 copy 1920x1 copy 128x1",
+                                                  "dev0: memset 128x1 copy2d 7680x1 kernel 480x16 copy2d 7680x1 copy 128x1",
+                                                  "dev1: memset 128x1 copy2d 7680x1 kernel 480x16 copy2d 7680x1 copy 128x1"});
+    }
+    trt_scene_destroy(s);
+    printf("ok call sequences\n");
+}
+
 // every HIP call failing once, at every position: an error comes back, nothing leaks, nothing hangs, the next render works
 static void failure_injection() {
     const char* apis[] = {"hipMalloc", "hipEventCreate", "hipStreamCreate", "hipEventRecord", "hipMemcpyAsync", "hipMemsetAsync",
@@ -342,6 +461,25 @@ static void failure_injection() {
             int rc4 = trt_render_multi(s, &cam, &p, devs, 3, f.data(), nullptr);
             CHECK(rc4 == TRT_OK && f == expected(40, 36, 5, 0, 8), "%s@%ld: multi after the failure: %d %s", api, at, rc4, trt_last_error());
             trt_scene_destroy(s);
+            // the same for the other blocking calls, each on a fresh scene: trt_sample_batch, the moments host form, and the first
+            // query_scene_on_device (the two first-use uploads).  TRT_ERR_OOM: an allocation of the call's own failed.
+            for (int target = 0; target < 3; target++) {
+                const char* names[3] = {"trt_sample_batch", "moments host form", "query_scene_on_device"};
+                auto call = [&](trt_scene* sc, bool& right) {
+                    return target == 0 ? call_sample_batch(sc, nullptr, right) : target == 1 ? call_moments(sc, 0, nullptr, right) : call_scene_on_device(sc, right);
+                };
+                trt_scene* s2 = make_scene();
+                bool right = false;
+                hipstub_fail_after(api, at);
+                const int rc = call(s2, right);
+                hipstub_fail_after(api, -1);
+                if (rc != TRT_OK) failed_calls++;
+                CHECK(rc == TRT_ERR_HIP || (rc == TRT_OK && right) || (rc == TRT_ERR_OOM && !strcmp(api, "hipMalloc")), "%s, %s@%ld: rc %d right %d %s", names[target], api,
+                      at, rc, (int)right, trt_last_error());
+                const int rcn = call(s2, right);                                        // the next call works and is right
+                CHECK(rcn == TRT_OK && right, "%s, %s@%ld: the call after the failure: %d %s", names[target], api, at, rcn, trt_last_error());
+                trt_scene_destroy(s2);
+            }
         }
     }
     CHECK(failed_calls > 20, "only %d injected failures surfaced", failed_calls);
@@ -417,6 +555,7 @@ int main(int argc, char** argv) {
     trt_scene_destroy(s);
     CHECK(hipstub_live_allocations() == (long)base_allocs && hipstub_live_streams() == 0 && hipstub_live_events() == 0,
           "leak after destroy: %ld allocations, %ld streams, %ld events", hipstub_live_allocations(), hipstub_live_streams(), hipstub_live_events());
+    call_sequences();
     cap_and_trim();
     if (argc < 2 || strcmp(argv[1], "quick") != 0) failure_injection();
     CHECK(hipstub_live_allocations() == (long)base_allocs && hipstub_live_streams() == 0 && hipstub_live_events() == 0,

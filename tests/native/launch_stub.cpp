@@ -83,10 +83,34 @@ hipError_t launch_streamed(const SceneDev&, const CameraDev& cam, const RenderAr
     if (workspace_bytes < streamed_workspace_bytes(cam.width, ra.rows_local, ra.sample_end - ra.sample_begin, tn.radiance_gb)) g_stub_short_launches++;   // granted less than a full launch
     return stub_render(cam, ra, workspace, workspace_bytes, d_accum, d_counters, stream);
 }
+// trt_render_moments' launcher (scene_query.h MomentsLaunch): the streamed stub for the first frame, then a task that fills the second with a
+// pattern of its own (adding to the running sums when asked to, like the first)
+float stub_pattern2(uint32_t y, uint32_t x, int c, uint32_t seed_key, uint32_t s0, uint32_t s1) {
+    return 0.5f * stub_pattern(y, x, c, seed_key, s0, s1) + 1.0f;
+}
+hipError_t stub_launch_moments(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
+                               float* d_accum, float* d_moment2, unsigned long long* d_counters, bool stats, hipStream_t stream) {
+    const hipError_t e = launch_streamed(sc, cam, ra, tn, workspace, workspace_bytes, d_accum, d_counters, stats, stream);
+    if (e != hipSuccess || ra.rows_local == 0 || cam.width == 0) return e;
+    const CameraDev c = cam;
+    const RenderArgs a = ra;
+    hipstub_enqueue(stream, [=] {
+        hipstub_log("moments", d_moment2, nullptr, (size_t)c.width * 12u, a.rows_local, (size_t)c.width * 12u);
+        for (uint32_t row = 0; row < a.rows_local; row++)
+            for (uint32_t x = 0; x < c.width; x++)
+                for (int ch = 0; ch < 3; ch++) {
+                    float* o = d_moment2 + 3ull * ((unsigned long long)row * c.width + x) + ch;
+                    const float v = stub_pattern2(stub_image_row(a, row), x, ch, a.seed_key, a.sample_begin, a.sample_end);
+                    *o = a.accumulate ? *o + v : v;
+                }
+    });
+    return hipSuccess;
+}
 hipError_t launch_tonemap_u8(const float*, unsigned long long, float, uint8_t*, hipStream_t) { return hipSuccess; }
 hipError_t launch_sample_batch(const SceneDev&, const trt_sample_point* d_in, uint32_t n, trt_sampled_color* d_out, const RenderArgs&,
                                unsigned long long* d_counters, bool, hipStream_t stream) {
     hipstub_enqueue(stream, [=] {
+        hipstub_log("kernel", d_out, d_in, (size_t)n * sizeof(trt_sampled_color), 1, (size_t)n * sizeof(trt_sampled_color));
         for (uint32_t i = 0; i < n; i++) { d_out[i].x = d_in[i].x; d_out[i].y = d_in[i].y; d_out[i].color = trt_vec3{1.0f, 2.0f, 3.0f}; }
         if (d_counters) d_counters[CTR_SAMPLES] += n;
     });

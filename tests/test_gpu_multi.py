@@ -5,7 +5,7 @@ A GPU box has one MI355X, so the N-shard layout is exercised with the same ordin
 is driven by its own host thread on its own stream with its own device buffers, renders its round-robin bands and
 copies them to their place in the frame - everything the 8-GPU run does except that the copies stay on one device.
 Shards of one device render the same scene handle concurrently, which is exactly the case the per-render workspace
-pool (capi.hip workspace_acquire) exists for."""
+pool (scene_cache.h workspace_acquire) exists for."""
 import threading
 
 import numpy as np

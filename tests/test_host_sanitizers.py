@@ -66,8 +66,8 @@ int main(void) {
 
 
 def _build_capi_host_check(tmp_path, sanitizer):
-    """capi.hip's HOST logic (per-scene pools of workspaces and render contexts, multi-GPU gather, timing brackets, error paths)
-    compiled as plain C++ against the simulated HIP runtime under tests/native/hipstub (streams are worker threads, events complete
+    """capi.hip's and scene_cache.h's HOST logic (the per-scene device cache with its pools of workspaces and render contexts, the blocking
+    calls' scaffold, multi-GPU gather, timing brackets, error paths) compiled as plain C++ against the simulated HIP runtime under tests/native/hipstub (streams are worker threads, events complete
     in stream order, hipFree waits for the device, device memory is the C heap) with stub kernel launchers that stamp and re-check
     their workspace."""
     exe = str(tmp_path / ("capi_host_check_" + sanitizer.split(",")[0]))
@@ -82,7 +82,8 @@ def _build_capi_host_check(tmp_path, sanitizer):
 def test_capi_host_logic_under_thread_sanitizer(tmp_path):
     """Six threads x three repetitions rendering ONE scene (all three backends, mixed sizes), three un-synchronised device streams,
     1..13 shards over 4 simulated devices into host and device frames (peer access on and off, ragged heights, progressive),
-    timing brackets from five threads at once, the idle-scratch cap, and every HIP call failing once at every position: no data
+    timing brackets from five threads at once, the idle-scratch cap, the per-stream work of every blocking entry point, and every HIP
+    call failing once at every position of every blocking call and of the first-use uploads: no data
     race, no lost update, no leak, every frame right, every error recovered from (part of the audit of
     round 2's unexplained abort)."""
     exe = _build_capi_host_check(tmp_path, "thread")

@@ -6,17 +6,7 @@
 // C++ exception leaves this file.  There is no CPU fallback: without a gfx950 device every
 // compute entry point fails with TRT_ERR_NO_DEVICE.
 //
-// Host-side resources (round 3).  Everything a render needs on a device besides the caller's buffers is cached on the scene
-// handle, per device, and lives until trt_scene_destroy / trt_scene_trim:
-//   * the packed scene (uploaded on first use);
-//   * WORKSPACES: the device scratch of one render (streamed: radiance records of a chunk + batch counter; wavefront: path
-//     state).  A render owns its workspace from acquire to release; release records an event behind the render's last kernel
-//     and a workspace is handed out again only to a stream that first waits for that event;
-//   * RENDER CONTEXTS for the blocking entry points (trt_render, trt_render_multi*): a stream, two timing events, the device
-//     counters and a device frame buffer.  Streams are created once and never destroyed while the scene lives, so an event
-//     recorded on one (a workspace's `done`) never outlives its stream.
-// The scene mutex guards only the bookkeeping: an entry is marked busy under the lock and every HIP call that can block
-// (hipMalloc, hipFree, hipEventSynchronize, hipStreamSynchronize) runs with the lock released.
+// What a scene keeps on its devices, and the scaffold of the blocking entry points, are scene_cache.h.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -24,21 +14,21 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
-#include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "axis_quads.h"
 #include "nearest_first.h"
 #include "flat_reuse.h"
+#include "host_stage.h"
 #include "kernels.h"
 #include "scene.h"
 #include "scene_adopt.h"
+#include "scene_cache.h"
 #include "scene_query.h"
 
 using namespace trt;
@@ -93,47 +83,12 @@ void timing_mark(hipStream_t stream, bool begin) {
 }
 }  // namespace trt
 
-// Device scratch of one render.  busy: a host thread owns the entry (between acquire and release, or while the pool itself
-// regrows / frees it); recorded: `done` has been recorded behind the last kernel that used the buffer.
-struct Workspace {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;            // the stream `done` was recorded on (valid while recorded)
-    bool recorded = false;
-    bool busy = false;
-};
-// Everything a blocking render call needs on one device besides its workspace.  One call owns a context from acquire to
-// release and has synchronised `stream` before it releases, so an idle context has no work in flight.
-struct RenderCtx {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    unsigned long long* d_ctr = nullptr;          // CTR_COUNT counters
-    float* d_accum = nullptr;                     // device frame (or band) buffer, grown on demand
-    size_t accum_bytes = 0;
-    bool busy = false;
-};
-constexpr size_t kMaxWorkspacesPerDevice = 8;      // beyond that, renders queue behind each other on the device
-
-struct DeviceCache {
-    float4* blob = nullptr;                       // packed scene in HBM
-    bool blob_busy = false;                       // a thread is uploading it
-    uint32_t* geo_index = nullptr;                // trt_scene::geo_index in HBM (uploaded by the first ray query on the device)
-    bool geo_index_busy = false;                  // a thread is uploading it
-    std::vector<Workspace*> ws;
-    std::vector<RenderCtx*> ctx;
-    uint32_t short_samples = 0;                   // != 0: the last streamed render of a full-size launch was granted scratch for this many samples only
-};
-
 struct trt_scene {
     SceneHost host;
     FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h) and axis-exact-quads switch (axis_quads.h), derived once from host.blob
     std::vector<uint32_t> geo_index;              // ray queries: geometry insertion index of sphere k at [k], of quad k at [n_spheres + k] (the kernels know a
                                                   // primitive as kind bit | index within its kind); derived once from the reference tree, outside the packed scene
-    std::mutex mu;
-    std::condition_variable cv;
-    std::unordered_map<int, DeviceCache> dev;     // device ordinal -> cached device resources
-    size_t scratch_cap_bytes = (size_t)32 << 30;  // idle scratch (workspaces + context frames) kept per device: trt_scene_options.scratch_cap_bytes
+    SceneCache cache;                             // what the scene keeps on its devices (scene_cache.h); destroyed with the handle
 };
 
 namespace {
@@ -206,251 +161,10 @@ int require_device() {
     return TRT_OK;
 }
 
-// Uploads the packed scene to the current device on first use.  One thread uploads (lock released during the copy), the
-// others wait for it.
+// The packed scene on the current device, uploaded on first use.
 int scene_on_device(trt_scene* s, SceneDev& out) {
-    int dev = 0;
-    TRT_HIP(hipGetDevice(&dev));
-    std::unique_lock<std::mutex> lock(s->mu);
-    DeviceCache& dc = s->dev[dev];                              // references into an unordered_map stay valid across inserts
-    while (dc.blob == nullptr && dc.blob_busy) s->cv.wait(lock);
-    if (dc.blob == nullptr) {
-        dc.blob_busy = true;
-        lock.unlock();
-        float4* d = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), s->host.layout.blob_bytes);
-        if (e == hipSuccess) {
-            e = hipMemcpy(d, s->host.blob.data(), s->host.layout.blob_bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { (void)hipFree(d); d = nullptr; }
-        }
-        lock.lock();
-        dc.blob_busy = false;
-        dc.blob = d;
-        s->cv.notify_all();
-        if (e != hipSuccess) return fail_hip(e, "scene upload");
-    }
-    out.blob = dc.blob;
     out.L = s->host.layout;
-    return TRT_OK;
-}
-
-bool ws_finished(Workspace* w) {                                  // call with the scene lock held, entry not busy
-    if (!w->recorded) return true;
-    const bool done = hipEventQuery(w->done) == hipSuccess;
-    (void)hipGetLastError();                                      // hipErrorNotReady is not an error
-    return done;
-}
-
-// Frees idle scratch on `dc` until at most `cap` bytes of IDLE scratch stay cached (largest first).  Called with the lock held; the
-// hipFree calls run with the lock released (the entries are marked busy meanwhile).
-void trim_locked(trt_scene* s, std::unique_lock<std::mutex>& lock, DeviceCache& dc, size_t cap) {
-    for (;;) {
-        size_t total = 0;                                         // idle entries only: a busy entry's fields belong to its owner
-        for (Workspace* w : dc.ws) if (!w->busy) total += w->bytes;
-        for (RenderCtx* c : dc.ctx) if (!c->busy) total += c->accum_bytes;
-        if (total <= cap) return;
-        Workspace* bw = nullptr;
-        RenderCtx* bc = nullptr;
-        for (Workspace* w : dc.ws) if (!w->busy && w->bytes && ws_finished(w) && (!bw || w->bytes > bw->bytes)) bw = w;
-        for (RenderCtx* c : dc.ctx) if (!c->busy && c->accum_bytes && (!bc || c->accum_bytes > bc->accum_bytes)) bc = c;
-        if (!bw && !bc) return;                                   // everything left is in use
-        void* victim;
-        if (bw && (!bc || bw->bytes >= bc->accum_bytes)) { bw->busy = true; victim = bw->ptr; bw->ptr = nullptr; bw->bytes = 0; bw->recorded = false; bc = nullptr; }
-        else { bc->busy = true; victim = bc->d_accum; bc->d_accum = nullptr; bc->accum_bytes = 0; bw = nullptr; }
-        lock.unlock();
-        (void)hipFree(victim);
-        (void)hipGetLastError();
-        lock.lock();
-        if (bw) bw->busy = false; else bc->busy = false;
-        s->cv.notify_all();
-    }
-}
-
-// Takes a workspace of at least `need` bytes for a render that will be enqueued on `stream` of device `dev`.
-int workspace_acquire(trt_scene* s, int dev, size_t need, hipStream_t stream, Workspace** out) {
-    std::unique_lock<std::mutex> lock(s->mu);
-    DeviceCache& dc = s->dev[dev];
-    bool may_grow = true;
-    for (;;) {
-        // 1. an idle one whose last render has finished (no dependency at all): the smallest that fits, else one to regrow
-        Workspace* pick = nullptr;
-        Workspace* regrow = nullptr;
-        for (Workspace* w : dc.ws) {
-            if (w->busy || !ws_finished(w)) continue;
-            if (w->bytes >= need) { if (!pick || w->bytes < pick->bytes) pick = w; }
-            else if (!regrow) regrow = w;
-        }
-        enum { USE, REGROW, CREATE, QUEUE, DRAIN } what = USE;
-        // 1b. one whose last render is still in flight ON THIS STREAM: stream order already puts this render behind it - no wait, no second
-        //     buffer.  (Back-to-back renders enqueued on one stream - bench.py's steps, a progressive viewer - otherwise grew the pool to its
-        //     eight workspaces, 16 GB each at full size, and sent the idle ones through the byte cap: a 13 GB hipMalloc + hipFree per render.)
-        //     hipStreamPerThread is one handle for many streams and never matches.
-        //     The wait on `done` is still enqueued (SAME_STREAM below): behind its own stream's work it costs nothing, and it keeps the reuse
-        //     safe should a caller destroy a stream with work pending and get the same handle back for a new one.
-        bool same_stream = false;
-        if (!pick && stream != hipStreamPerThread) {
-            for (Workspace* w : dc.ws) if (!w->busy && w->recorded && w->last_stream == stream && w->bytes >= need && (!pick || w->bytes < pick->bytes)) pick = w;
-            same_stream = pick != nullptr;
-        }
-        if (same_stream) what = QUEUE;
-        if (!pick && regrow) { pick = regrow; what = REGROW; }
-        // 2. a new one while the pool may grow
-        if (!pick && may_grow && dc.ws.size() < kMaxWorkspacesPerDevice) {
-            pick = new (std::nothrow) Workspace();
-            if (!pick) return fail(TRT_ERR_OOM, "out of memory");
-            dc.ws.push_back(pick);
-            what = CREATE;
-        }
-        // 3. an idle one that is still in flight and large enough: this render queues behind it on the device
-        if (!pick) {
-            for (Workspace* w : dc.ws) if (!w->busy && w->bytes >= need) { pick = w; what = QUEUE; break; }
-        }
-        if (!pick) {
-            // 4. every workspace is owned by another host thread: wait for a release
-            bool any_busy = false;
-            for (Workspace* w : dc.ws) any_busy = any_busy || w->busy;
-            if (any_busy) { s->cv.wait(lock); continue; }
-            if (dc.ws.empty()) return fail(TRT_ERR_OOM, "no device memory for a render workspace");
-            // 5. all idle, all in flight, all too small: wait for the first to finish, then regrow it
-            pick = dc.ws.front();
-            what = DRAIN;
-        }
-        pick->busy = true;
-        lock.unlock();
-        // ---- HIP calls, lock released; `pick` is ours ----
-        hipError_t e = hipSuccess;
-        const char* where = "";
-        if (what == CREATE) {
-            e = hipEventCreateWithFlags(&pick->done, hipEventDisableTiming); where = "hipEventCreate(workspace)";
-            if (e == hipSuccess) { e = hipMalloc(&pick->ptr, need); where = "hipMalloc(workspace)"; if (e == hipSuccess) pick->bytes = need; else pick->ptr = nullptr; }
-        } else if (what == DRAIN || what == REGROW) {
-            if (what == DRAIN) { e = hipEventSynchronize(pick->done); where = "hipEventSynchronize(workspace)"; }
-            if (e == hipSuccess && pick->ptr) { e = hipFree(pick->ptr); where = "hipFree(workspace)"; pick->ptr = nullptr; pick->bytes = 0; }
-            if (e == hipSuccess) { e = hipMalloc(&pick->ptr, need); where = "hipMalloc(workspace)"; if (e == hipSuccess) pick->bytes = need; else pick->ptr = nullptr; }
-            if (e == hipSuccess) pick->recorded = false;
-        } else if (what == QUEUE) {
-            e = hipStreamWaitEvent(stream, pick->done, 0); where = "hipStreamWaitEvent(workspace)";
-        }
-        if (e == hipSuccess) { *out = pick; return TRT_OK; }
-        (void)hipGetLastError();
-        lock.lock();
-        if (what == CREATE) {
-            dc.ws.erase(std::find(dc.ws.begin(), dc.ws.end(), pick));
-            if (pick->done) (void)hipEventDestroy(pick->done);
-            delete pick;
-            s->cv.notify_all();
-            if (e == hipErrorOutOfMemory) {
-                // out of HBM for another copy: queue behind a running render whose buffer is large enough, if there is one; else the caller
-                // may ask for less (TRT_ERR_OOM: enqueue_render halves the samples per launch)
-                bool fits = false;                                 // (a busy entry's fields belong to its owner: it may fit once released)
-                for (Workspace* w : dc.ws) fits = fits || w->busy || w->bytes >= need;
-                if (fits) { may_grow = false; continue; }
-                return fail(TRT_ERR_OOM, std::string(where) + ": " + hipGetErrorString(e));
-            }
-            return fail_hip(e, where);
-        }
-        pick->busy = false;                                       // (a failed regrow leaves an empty, reusable entry)
-        s->cv.notify_all();
-        if (e == hipErrorOutOfMemory) return fail(TRT_ERR_OOM, std::string(where) + ": " + hipGetErrorString(e));
-        return fail_hip(e, where);
-    }
-}
-
-// Gives the workspace back; `stream` has all of the render's launches enqueued.
-int workspace_release(trt_scene* s, int dev, Workspace* w, hipStream_t stream) {
-    hipError_t e = hipEventRecord(w->done, stream);
-    bool recorded = e == hipSuccess;
-    if (!recorded) {
-        // without the event nothing orders the next user behind this render: wait for the render itself
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(stream);
-        (void)hipGetLastError();
-    }
-    {
-        std::unique_lock<std::mutex> lock(s->mu);
-        w->recorded = recorded;
-        w->last_stream = stream;
-        w->busy = false;
-        trim_locked(s, lock, s->dev[dev], s->scratch_cap_bytes);
-    }
-    s->cv.notify_all();
-    if (e != hipSuccess) return fail_hip(e, "hipEventRecord(workspace)");
-    return TRT_OK;
-}
-
-// A render context on the current device with a device frame of at least `accum_bytes` (0: none needed).
-int context_acquire(trt_scene* s, int dev, size_t accum_bytes, RenderCtx** out) {
-    RenderCtx* c = nullptr;
-    bool fresh = false;
-    {
-        std::lock_guard<std::mutex> lock(s->mu);
-        DeviceCache& dc = s->dev[dev];
-        RenderCtx* fits = nullptr;                                 // the smallest idle frame that fits, else the largest idle one (regrown)
-        RenderCtx* any = nullptr;
-        for (RenderCtx* k : dc.ctx) {
-            if (k->busy) continue;
-            if (k->accum_bytes >= accum_bytes && (!fits || k->accum_bytes < fits->accum_bytes)) fits = k;
-            if (!any || k->accum_bytes > any->accum_bytes) any = k;
-        }
-        c = fits ? fits : any;
-        if (!c) {
-            c = new (std::nothrow) RenderCtx();
-            if (!c) return fail(TRT_ERR_OOM, "out of memory");
-            dc.ctx.push_back(c);
-            fresh = true;
-        }
-        c->busy = true;
-    }
-    hipError_t e = hipSuccess;
-    const char* where = "";
-    if (fresh) {
-        e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking); where = "hipStreamCreate";
-        if (e == hipSuccess) { e = hipEventCreate(&c->ev0); where = "hipEventCreate"; }
-        if (e == hipSuccess) { e = hipEventCreate(&c->ev1); where = "hipEventCreate"; }
-        if (e == hipSuccess) { e = hipMalloc(reinterpret_cast<void**>(&c->d_ctr), CTR_COUNT * sizeof(unsigned long long)); where = "hipMalloc(counters)"; }
-    }
-    if (e == hipSuccess && c->accum_bytes < accum_bytes) {
-        if (c->d_accum) { e = hipFree(c->d_accum); where = "hipFree(frame)"; c->d_accum = nullptr; c->accum_bytes = 0; }
-        if (e == hipSuccess) { e = hipMalloc(reinterpret_cast<void**>(&c->d_accum), accum_bytes); where = "hipMalloc(frame)"; if (e == hipSuccess) c->accum_bytes = accum_bytes; else c->d_accum = nullptr; }
-    }
-    if (e == hipSuccess) { *out = c; return TRT_OK; }
-    (void)hipGetLastError();
-    const int rc = fail_hip(e, where);
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (fresh) {                                                  // half-built: take it out of the pool again
-        DeviceCache& dc = s->dev[dev];
-        dc.ctx.erase(std::find(dc.ctx.begin(), dc.ctx.end(), c));
-        if (c->d_ctr) (void)hipFree(c->d_ctr);
-        if (c->ev0) (void)hipEventDestroy(c->ev0);
-        if (c->ev1) (void)hipEventDestroy(c->ev1);
-        if (c->stream) (void)hipStreamDestroy(c->stream);
-        delete c;
-    } else {
-        c->busy = false;
-    }
-    return rc;
-}
-
-void context_destroy(RenderCtx* c) {                              // idle context: nothing in flight on its stream
-    if (c->d_accum) (void)hipFree(c->d_accum);
-    if (c->d_ctr) (void)hipFree(c->d_ctr);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    (void)hipGetLastError();
-    delete c;
-}
-
-// The caller has synchronised c->stream (or nothing was enqueued on it).  The context stays in the pool whatever the pool's size:
-// its stream and events live until trt_scene_destroy (a workspace's `done` event may have been recorded on that stream and is
-// queried by later acquires, so destroying the stream here - round 3 did, beyond 16 idle contexts - brought back the very pattern
-// DESIGN.md's audit of round 2's abort removed).  What a burst of shards leaves behind is bounded by the byte cap: idle contexts'
-// frames are freed largest first by trim_locked; a context without a frame is a stream, two events and 128 bytes of counters.
-void context_release(trt_scene* s, int dev, RenderCtx* c) {
-    std::unique_lock<std::mutex> lock(s->mu);
-    DeviceCache& dc = s->dev[dev];
-    c->busy = false;
-    trim_locked(s, lock, dc, s->scratch_cap_bytes);
+    return s->cache.on_device(SceneCache::PACKED_SCENE, s->host.blob.data(), s->host.layout.blob_bytes, "scene upload", out.blob);
 }
 
 void to_camera_dev(const trt_camera& c, CameraDev& d) {
@@ -505,6 +219,13 @@ int to_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs
     return TRT_OK;
 }
 
+// The argument errors of to_render_args alone.  rows = rows the call owns.
+int check_render_args(const trt_camera* cam, const trt_render_params* p, uint32_t& rows) {
+    RenderArgs ra;
+    trt_tuning tn;
+    return to_render_args(cam, p, ra, rows, tn);
+}
+
 // `d_moment2` with `launch_moments` (trt_render_moments*, streamed backend only - query_render_moments* refuse every other): a second
 // frame-shaped buffer for the second moments and the launcher that fills both (scene_query.h MomentsLaunch).
 int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params* p, float* d_accum, uint64_t* d_counters,
@@ -532,12 +253,12 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
     const bool streamed = p->backend == TRT_BACKEND_STREAMED || p->backend == TRT_BACKEND_AUTO;     // fastest on every scene measured
     if (wavefront || streamed) {
         // Device workspace (wavefront: 72 B of path state per pixel; streamed: 12 B per pixel and sample of a launch), private
-        // to this render until its last kernel has run (workspace_acquire): concurrent renders of one scene are safe.
+        // to this render until its last kernel has run (SceneCache::workspace_acquire): concurrent renders of one scene are safe.
         int dev = 0;
         TRT_HIP(hipGetDevice(&dev));
         Workspace* ws = nullptr;
         if (wavefront) {
-            rc = workspace_acquire(s, dev, wavefront_workspace_bytes(cam->width, rows), stream, &ws);
+            rc = s->cache.workspace_acquire(dev, wavefront_workspace_bytes(cam->width, rows), stream, &ws);
         } else {
             // The streamed launch is sized for 288 GB (up to 16 GB of records).  If the device cannot give that much right now - HBM held by
             // another scene's cached scratch, by the host application, by torch - ask for half the samples per launch, and half again: the
@@ -549,39 +270,27 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
             // Lasting pressure: while the device still cannot hold the full request, start where the last render ended up instead
             // of freeing the cached shorter workspace, failing the full-size hipMalloc and allocating the shorter one again on every render.
             // hipMemGetInfo says when the pressure is gone: free memory + this scene's own idle scratch (a regrow frees it first) covers the request.
-            {
-                uint32_t short_samples = 0;
-                size_t idle = 0;
-                {
-                    std::lock_guard<std::mutex> lock(s->mu);
-                    DeviceCache& dc = s->dev[dev];
-                    short_samples = dc.short_samples;
-                    for (Workspace* w : dc.ws) if (!w->busy) idle += w->bytes;
-                }
-                if (short_samples != 0u && short_samples < samples) {
-                    size_t free_b = 0, total_b = 0;
-                    const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-                    (void)hipGetLastError();
-                    if (!known || free_b + idle < streamed_workspace_bytes(cam->width, rows, samples, tn.radiance_gb)) samples = short_samples;
-                }
+            const uint32_t short_samples = s->cache.short_samples(dev);
+            if (short_samples != 0u && short_samples < samples) {
+                const size_t idle = s->cache.idle_workspace_bytes(dev);
+                size_t free_b = 0, total_b = 0;
+                const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+                (void)hipGetLastError();
+                if (!known || free_b + idle < streamed_workspace_bytes(cam->width, rows, samples, tn.radiance_gb)) samples = short_samples;
             }
             bool trimmed = false;
             for (;;) {
-                rc = workspace_acquire(s, dev, streamed_workspace_bytes(cam->width, rows, samples, tn.radiance_gb), stream, &ws);
+                rc = s->cache.workspace_acquire(dev, streamed_workspace_bytes(cam->width, rows, samples, tn.radiance_gb), stream, &ws);
                 if (rc != TRT_ERR_OOM) break;
                 if (!trimmed) {                      // first give back what this scene itself keeps idle on the device (frames of idle contexts, other workspaces), then ask again
                     trimmed = true;
-                    std::unique_lock<std::mutex> lock(s->mu);
-                    trim_locked(s, lock, s->dev[dev], 0);
+                    s->cache.trim(dev, 0);
                     continue;
                 }
                 if (samples <= 1u) break;
                 samples = (samples + 1u) / 2u;
             }
-            {
-                std::lock_guard<std::mutex> lock(s->mu);
-                s->dev[dev].short_samples = (rc == TRT_OK && samples < wanted) ? samples : 0u;
-            }
+            s->cache.set_short_samples(dev, (rc == TRT_OK && samples < wanted) ? samples : 0u);
         }
         if (rc != TRT_OK) return rc;
         hipError_t le;
@@ -594,19 +303,12 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
         } else {
             le = launch_wavefront(sc, cd, ra, tn, ws->ptr, d_accum, reinterpret_cast<unsigned long long*>(d_counters), p->collect_stats != 0, stream);
         }
-        rc = workspace_release(s, dev, ws, stream);
+        rc = s->cache.workspace_release(dev, ws, stream);
         if (le != hipSuccess) return fail_hip(le, streamed ? "launch_streamed" : "launch_wavefront");
         return rc;
     }
     TRT_HIP(launch_megakernel(sc, cd, ra, tn, d_accum, reinterpret_cast<unsigned long long*>(d_counters), p->collect_stats != 0, stream));
     return TRT_OK;
-}
-
-void counters_to_stats(const unsigned long long* c, trt_stats* st) {
-    st->samples = c[CTR_SAMPLES]; st->rays = c[CTR_RAYS]; st->node_tests = c[CTR_NODE]; st->sphere_tests = c[CTR_SPHERE];
-    st->quad_plane_tests = c[CTR_QUAD_PLANE]; st->quad_inside_tests = c[CTR_QUAD_INSIDE]; st->shades = c[CTR_SHADE];
-    for (int i = 0; i < 4; i++) st->wave_trips[i] = c[CTR_W_ROUNDS + i];
-    st->gather_per_band = 0;
 }
 
 // The reuse schedule of a flat-walk scene's leaf list and its axis-exact-quads switch, from the host copy of its blob (both scene compilers leave one).
@@ -646,6 +348,16 @@ void set_geo_index(trt_scene* s) {
     }
 }
 
+// The handle of a compiled scene: what both scene compilers' entry points end in.  May throw std::bad_alloc.
+trt_scene* scene_from_host(SceneHost&& host, const trt_scene_options& opt) {
+    std::unique_ptr<trt_scene> s(new trt_scene());
+    s->host = std::move(host);
+    set_flat_reuse(s.get());
+    set_geo_index(s.get());
+    s->cache.set_cap((size_t)opt.scratch_cap_bytes);
+    return s.release();
+}
+
 }  // namespace
 
 // The ray-query unit's view of this layer (scene_query.h)
@@ -654,34 +366,12 @@ int query_fail(int code, const std::string& msg) { return fail(code, msg); }
 int query_fail_hip(hipError_t e, const char* what) { return fail_hip(e, what); }
 int query_require_device() { return require_device(); }
 const SceneLayout& query_scene_layout(const trt_scene* s) { return s->host.layout; }
-// The scene and its index table on the current device, both uploaded on first use (one thread uploads, the others wait: scene_on_device).
+// The scene and its index table on the current device, both uploaded on first use (SceneCache::on_device).
 int query_scene_on_device(trt_scene* s, QueryScene& out) {
     int rc = scene_on_device(s, out.scene);
     if (rc != TRT_OK) return rc;
-    int dev = 0;
-    TRT_HIP(hipGetDevice(&dev));
-    std::unique_lock<std::mutex> lock(s->mu);
-    DeviceCache& dc = s->dev[dev];
-    while (dc.geo_index == nullptr && dc.geo_index_busy) s->cv.wait(lock);
-    if (dc.geo_index == nullptr) {
-        dc.geo_index_busy = true;
-        lock.unlock();
-        uint32_t* d = nullptr;
-        const size_t bytes = s->geo_index.size() * sizeof(uint32_t);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), bytes ? bytes : sizeof(uint32_t));
-        if (e == hipSuccess && bytes) {
-            e = hipMemcpy(d, s->geo_index.data(), bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { (void)hipFree(d); d = nullptr; }
-        }
-        lock.lock();
-        dc.geo_index_busy = false;
-        dc.geo_index = d;
-        s->cv.notify_all();
-        if (e != hipSuccess) return fail_hip(e, "geometry index upload");
-    }
-    out.geo_index = dc.geo_index;
     out.flat_reuse = s->flat_reuse;
-    return TRT_OK;
+    return s->cache.on_device(SceneCache::GEO_INDEX, s->geo_index.data(), s->geo_index.size() * sizeof(uint32_t), "geometry index upload", out.geo_index);
 }
 int query_render_args(const trt_camera* cam, const trt_render_params* p, RenderArgs& ra, uint32_t& rows) {
     trt_render_params q = *p;
@@ -704,12 +394,8 @@ int scene_fail(int code, const std::string& msg) { return fail(code, msg); }
 const World& world_of(const trt_world* w) { return w->w; }
 trt_scene* scene_adopt(SceneHost&& host, const trt_scene_options& opt, int device, void* d_blob) {
     try {
-        trt_scene* s = new trt_scene();
-        s->host = std::move(host);
-        set_flat_reuse(s);
-        set_geo_index(s);
-        s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
-        if (d_blob) s->dev[device].blob = static_cast<float4*>(d_blob);      // the first render on `device` does not upload again
+        trt_scene* s = scene_from_host(std::move(host), opt);
+        if (d_blob) s->cache.adopt_packed_scene(device, d_blob);             // the first render on `device` does not upload again
         return s;
     } catch (const std::bad_alloc&) {
         fail(TRT_ERR_OOM, "out of memory");
@@ -816,13 +502,10 @@ int trt_scene_create_ex(const trt_world* w, const trt_scene_options* options, tr
     try {
         const trt_scene_options opt = scene_options_or_defaults(options);
         if (scene_options_check(opt) != TRT_OK) return TRT_ERR_INVALID_ARG;
-        trt_scene* s = new trt_scene();
+        SceneHost host;
         std::string msg;
-        if (!compile_scene(w->w, opt, s->host, msg)) { delete s; return fail(TRT_ERR_INVALID_ARG, msg); }
-        set_flat_reuse(s);
-        set_geo_index(s);
-        s->scratch_cap_bytes = (size_t)opt.scratch_cap_bytes;
-        *out = s;
+        if (!compile_scene(w->w, opt, host, msg)) return fail(TRT_ERR_INVALID_ARG, msg);
+        *out = scene_from_host(std::move(host), opt);
     } catch (const std::bad_alloc&) {
         return fail(TRT_ERR_OOM, "out of memory");
     } catch (const std::exception& e) {                         // (the scene compiler builds its trees on several threads: nothing may leave the C ABI)
@@ -835,44 +518,16 @@ int trt_scene_create(const trt_world* w, trt_scene** out) { return trt_scene_cre
 // packed scene stays.  Safe while renders of the scene run: what they own is skipped.
 int trt_scene_trim(trt_scene* s) {
     if (!s) return fail(TRT_ERR_INVALID_ARG, "scene is null");
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-    std::vector<int> devices;
-    {
-        std::lock_guard<std::mutex> lock(s->mu);
-        for (auto& kv : s->dev) devices.push_back(kv.first);
-    }
-    for (int d : devices) {
-        if (hipSetDevice(d) != hipSuccess) continue;
-        std::unique_lock<std::mutex> lock(s->mu);
-        trim_locked(s, lock, s->dev[d], 0);
-    }
-    if (have_prev) (void)hipSetDevice(prev);
+    s->cache.trim_all();
     (void)hipGetLastError();
     return TRT_OK;
 }
 // Must not run while another host thread is inside a render call on this scene.  Renders enqueued through trt_render_device
-// that are still running on the device are waited for (their workspace events) before anything is freed.
+// that are still running on the device are waited for (their workspace events) before anything is freed (~SceneCache).
 void trt_scene_destroy(trt_scene* s) {
     if (!s) return;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-    for (auto& kv : s->dev) {
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        DeviceCache& dc = kv.second;
-        for (Workspace* w : dc.ws) {
-            if (w->recorded) (void)hipEventSynchronize(w->done);      // a render may still be using it
-            if (w->ptr) (void)hipFree(w->ptr);
-            if (w->done) (void)hipEventDestroy(w->done);
-            delete w;
-        }
-        for (RenderCtx* c : dc.ctx) context_destroy(c);               // after the workspaces: their events were recorded on these streams
-        if (dc.blob) (void)hipFree(dc.blob);
-        if (dc.geo_index) (void)hipFree(dc.geo_index);
-    }
-    if (have_prev) (void)hipSetDevice(prev);
-    (void)hipGetLastError();
     delete s;
+    (void)hipGetLastError();
 }
 int trt_scene_get_info(const trt_scene* s, trt_scene_info* out) {
     if (!s || !out) return fail(TRT_ERR_INVALID_ARG, "null argument");
@@ -954,58 +609,23 @@ int render_host(trt_scene* s, const trt_camera* cam, const trt_render_params* p,
                 MomentsLaunch launch_moments) {
     int rc = require_device();
     if (rc != TRT_OK) return rc;
-    RenderArgs probe;
-    trt_tuning probe_tn;
     uint32_t rows = 0;
-    rc = to_render_args(cam, p, probe, rows, probe_tn);
+    rc = check_render_args(cam, p, rows);
     if (rc != TRT_OK) return rc;
     const size_t bytes = (size_t)rows * cam->width * 3 * sizeof(float);
-    int dev = 0;
-    TRT_HIP(hipGetDevice(&dev));
-    RenderCtx* c = nullptr;
-    rc = context_acquire(s, dev, bytes ? bytes : 16, &c);
-    if (rc != TRT_OK) return rc;
-    unsigned long long h_ctr[CTR_COUNT] = {0};
-    float ms = 0.0f;
+    CtxRun run(s->cache);
+    run.acquire(bytes ? bytes : 16);
     float* d_m2 = nullptr;
-    if (moment2) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_m2), bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            context_release(s, dev, c);
-            return fail(TRT_ERR_OOM, std::string("second-moment frame: ") + hipGetErrorString(e));
-        }
-    }
-    // from here on every exit drains the context's stream before the context goes back to the pool
-    auto finish = [&](int code) {
-        (void)hipStreamSynchronize(c->stream);
-        if (d_m2) (void)hipFree(d_m2);
-        (void)hipGetLastError();
-        context_release(s, dev, c);
-        return code;
-    };
-#define TRT_HIP_C(call)                                                          \
-    do {                                                                         \
-        hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) return finish(fail_hip(e_, #call));                \
-    } while (0)
-    TRT_HIP_C(hipMemsetAsync(c->d_ctr, 0, sizeof(h_ctr), c->stream));
-    if (p->accumulate && bytes) TRT_HIP_C(hipMemcpyAsync(c->d_accum, accum, bytes, hipMemcpyHostToDevice, c->stream));
-    if (p->accumulate && bytes && d_m2) TRT_HIP_C(hipMemcpyAsync(d_m2, moment2, bytes, hipMemcpyHostToDevice, c->stream));
-    TRT_HIP_C(hipEventRecord(c->ev0, c->stream));
-    rc = enqueue_render(s, cam, p, c->d_accum, reinterpret_cast<uint64_t*>(c->d_ctr), c->stream, nullptr, d_m2, launch_moments);
-    if (rc != TRT_OK) return finish(rc);
-    TRT_HIP_C(hipEventRecord(c->ev1, c->stream));
-    if (bytes) TRT_HIP_C(hipMemcpyAsync(accum, c->d_accum, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (bytes && d_m2) TRT_HIP_C(hipMemcpyAsync(moment2, d_m2, bytes, hipMemcpyDeviceToHost, c->stream));
-    TRT_HIP_C(hipMemcpyAsync(h_ctr, c->d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
-    TRT_HIP_C(hipStreamSynchronize(c->stream));
-    TRT_HIP_C(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-#undef TRT_HIP_C
-    if (d_m2) (void)hipFree(d_m2);
-    context_release(s, dev, c);
-    if (stats) { counters_to_stats(h_ctr, stats); stats->kernel_ms = ms; }
-    return TRT_OK;
+    if (moment2) run.alloc(&d_m2, bytes ? bytes : 16, "second-moment frame", TRT_ERR_OOM);
+    run.zero_counters();
+    if (run.ok() && p->accumulate && bytes) run.step(hipMemcpyAsync(run.frame(), accum, bytes, hipMemcpyHostToDevice, run.stream()), "hipMemcpyAsync(frame to device)");
+    if (run.ok() && p->accumulate && bytes && d_m2) run.step(hipMemcpyAsync(d_m2, moment2, bytes, hipMemcpyHostToDevice, run.stream()), "hipMemcpyAsync(second moments to device)");
+    run.time_begin();
+    if (run.ok()) run.step(enqueue_render(s, cam, p, run.frame(), reinterpret_cast<uint64_t*>(run.counters()), run.stream(), nullptr, d_m2, launch_moments));
+    run.time_end();
+    if (run.ok() && bytes) run.step(hipMemcpyAsync(accum, run.frame(), bytes, hipMemcpyDeviceToHost, run.stream()), "hipMemcpyAsync(frame to host)");
+    if (run.ok() && bytes && d_m2) run.step(hipMemcpyAsync(moment2, d_m2, bytes, hipMemcpyDeviceToHost, run.stream()), "hipMemcpyAsync(second moments to host)");
+    return run.finish(stats);
 }
 
 }  // namespace
@@ -1130,42 +750,25 @@ hipError_t copy_bands(const trt_band_copy& pl, char* local, char* frame, bool to
 }
 
 // One device's share.  dst: the whole frame, on the host (dst_device < 0) or on device dst_device.
-void render_shard(trt_scene* s, const trt_camera* cam, const trt_render_params* p, uint32_t ndev, MultiShard* sh, float* dst,
-                  int dst_device) {
+int render_shard(trt_scene* s, const trt_camera* cam, const trt_render_params* p, uint32_t ndev, MultiShard* sh, float* dst, int dst_device) {
     hipError_t e = hipSetDevice(sh->device);
-    if (e != hipSuccess) { sh->rc = fail_hip(e, "hipSetDevice"); sh->error = g_last_error; return; }
-    if (sh->rows_local == 0) return;                                        // more shards than bands
+    if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+    if (sh->rows_local == 0) return TRT_OK;                                 // more shards than bands
     trt_band_copy pl;
     band_copy_plan(cam->width, cam->height, ndev, sh->rank, &pl);
     trt_render_params q = *p;
     q.band_rows = kMultiBandRows; q.band_stride = ndev; q.band_offset = sh->rank; q.rows_local = sh->rows_local;
-    RenderCtx* c = nullptr;
-    sh->rc = context_acquire(s, sh->device, (size_t)pl.rows_local * cam->width * 3 * sizeof(float), &c);
-    if (sh->rc != TRT_OK) { sh->error = g_last_error; return; }
-    auto finish = [&]() {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipGetLastError();
-        context_release(s, sh->device, c);
-    };
-#define TRT_HIP_S(call)                                                                                         \
-    do {                                                                                                        \
-        hipError_t e_ = (call);                                                                                 \
-        if (e_ != hipSuccess) { sh->rc = fail_hip(e_, #call); sh->error = g_last_error; finish(); return; }     \
-    } while (0)
-    char* local = reinterpret_cast<char*>(c->d_accum);
+    CtxRun run(s->cache, sh->device);
+    run.acquire((size_t)pl.rows_local * cam->width * 3 * sizeof(float));
+    char* local = reinterpret_cast<char*>(run.frame());
     char* frame = reinterpret_cast<char*>(dst);
-    TRT_HIP_S(hipMemsetAsync(c->d_ctr, 0, sizeof(sh->ctr), c->stream));
-    if (p->accumulate) TRT_HIP_S(copy_bands(pl, local, frame, false, sh->device, dst_device, sh->peer_ok, c->stream));   // continue the frame's running sums
-    TRT_HIP_S(hipEventRecord(c->ev0, c->stream));
-    sh->rc = enqueue_render(s, cam, &q, c->d_accum, reinterpret_cast<uint64_t*>(c->d_ctr), c->stream, nullptr);
-    if (sh->rc != TRT_OK) { sh->error = g_last_error; finish(); return; }
-    TRT_HIP_S(hipEventRecord(c->ev1, c->stream));
-    TRT_HIP_S(copy_bands(pl, local, frame, true, sh->device, dst_device, sh->peer_ok, c->stream, &sh->per_band));        // the gather
-    TRT_HIP_S(hipMemcpyAsync(sh->ctr, c->d_ctr, sizeof(sh->ctr), hipMemcpyDeviceToHost, c->stream));
-    TRT_HIP_S(hipStreamSynchronize(c->stream));
-    TRT_HIP_S(hipEventElapsedTime(&sh->ms, c->ev0, c->ev1));
-#undef TRT_HIP_S
-    context_release(s, sh->device, c);
+    run.zero_counters();
+    if (run.ok() && p->accumulate) run.step(copy_bands(pl, local, frame, false, sh->device, dst_device, sh->peer_ok, run.stream()), "copy_bands: hipMemcpy*Async of the running sums");   // continue the frame's running sums
+    run.time_begin();
+    if (run.ok()) run.step(enqueue_render(s, cam, &q, run.frame(), reinterpret_cast<uint64_t*>(run.counters()), run.stream(), nullptr));
+    run.time_end();
+    if (run.ok()) run.step(copy_bands(pl, local, frame, true, sh->device, dst_device, sh->peer_ok, run.stream(), &sh->per_band), "copy_bands: hipMemcpy*Async of the gather");
+    return run.finish(sh->ctr, &sh->ms);
 }
 
 int render_multi(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const int* devices, uint32_t ndev, float* dst,
@@ -1185,44 +788,42 @@ int render_multi(trt_scene* s, const trt_camera* cam, const trt_render_params* p
         shards[r].rank = r;
         shards[r].rows_local = band_rows_local(cam->height, ndev, r, kMultiBandRows);
     }
-    {   // validate once on the calling thread, so argument errors do not depend on a device
-        RenderArgs probe;
-        trt_tuning probe_tn;
-        uint32_t rows = 0;
-        rc = to_render_args(cam, p, probe, rows, probe_tn);
-        if (rc != TRT_OK) return rc;
-    }
-    int prev = 0;
-    TRT_HIP(hipGetDevice(&prev));
+    uint32_t rows = 0;                                                      // validate once on the calling thread, so argument errors do not depend on a device
+    rc = check_render_args(cam, p, rows);
+    if (rc != TRT_OK) return rc;
+    DeviceRestore restore;                                                  // the shards and the peer-access loop set other devices
+    if (restore.error() != hipSuccess) return fail_hip(restore.error(), "hipGetDevice");
     const int dst_device = dst_on_device ? shards[0].device : -1;
     if (dst_on_device) {
         for (uint32_t r = 0; r < ndev; r++) {                               // peer access for the gather (xGMI)
             if (shards[r].device == dst_device) continue;
             int can = 0;
             hipError_t e = hipDeviceCanAccessPeer(&can, shards[r].device, dst_device);
-            if (e != hipSuccess) { (void)hipSetDevice(prev); return fail_hip(e, "hipDeviceCanAccessPeer"); }
+            if (e != hipSuccess) return fail_hip(e, "hipDeviceCanAccessPeer");
             if (!can) { shards[r].peer_ok = false; continue; }             // hipMemcpyPeerAsync then stages through the host
             e = hipSetDevice(shards[r].device);
             if (e == hipSuccess) e = hipDeviceEnablePeerAccess(dst_device, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipSetDevice(prev); return fail_hip(e, "hipDeviceEnablePeerAccess"); }
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail_hip(e, "hipDeviceEnablePeerAccess");
             (void)hipGetLastError();
         }
-        TRT_HIP(hipSetDevice(prev));
+        TRT_HIP(hipSetDevice(restore.device()));
     }
+    auto shard = [&](MultiShard* sh) {                                     // (on a worker thread: the message is thread-local)
+        sh->rc = render_shard(s, cam, p, ndev, sh, dst, dst_device);
+        if (sh->rc != TRT_OK) sh->error = g_last_error;
+    };
     if (ndev == 1) {
-        render_shard(s, cam, p, 1, &shards[0], dst, dst_device);
+        shard(&shards[0]);
     } else {
         std::vector<std::thread> workers;
         try {
-            for (uint32_t r = 0; r < ndev; r++) workers.emplace_back(render_shard, s, cam, p, ndev, &shards[r], dst, dst_device);
+            for (uint32_t r = 0; r < ndev; r++) workers.emplace_back(shard, &shards[r]);
         } catch (...) {
             for (auto& t : workers) t.join();
-            (void)hipSetDevice(prev);
             return fail(TRT_ERR_OOM, "could not start a host thread per device");
         }
         for (auto& t : workers) t.join();
     }
-    (void)hipSetDevice(prev);
     unsigned long long total[CTR_COUNT] = {0};
     float ms = 0.0f;
     uint64_t per_band = 0;
@@ -1240,20 +841,12 @@ int render_multi(trt_scene* s, const trt_camera* cam, const trt_render_params* p
 
 int trt_render_multi(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const int* devices, uint32_t ndev, float* accum,
                      trt_stats* stats) {
-    try {
-        return render_multi(s, cam, p, devices, ndev, accum, false, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(TRT_ERR_OOM, "out of memory");
-    }
+    return host_form([&] { return render_multi(s, cam, p, devices, ndev, accum, false, stats); });
 }
 
 int trt_render_multi_device(trt_scene* s, const trt_camera* cam, const trt_render_params* p, const int* devices, uint32_t ndev,
                             float* d_accum, trt_stats* stats) {
-    try {
-        return render_multi(s, cam, p, devices, ndev, d_accum, true, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(TRT_ERR_OOM, "out of memory");
-    }
+    return host_form([&] { return render_multi(s, cam, p, devices, ndev, d_accum, true, stats); });
 }
 
 int trt_band_rows_local(uint32_t height, uint32_t ndev, uint32_t rank, uint32_t* rows_local) {
@@ -1294,43 +887,19 @@ int trt_sample_batch(trt_scene* s, const trt_sample_point* in, uint32_t n, trt_s
     const bool counting = stats != nullptr;
     ra.ref_tree = counting ? 1u : 0u;
     ra.leaf_slots = counting ? 1u : 4u;
-    int dev = 0;
-    TRT_HIP(hipGetDevice(&dev));
-    RenderCtx* c = nullptr;
-    rc = context_acquire(s, dev, 0, &c);
-    if (rc != TRT_OK) return rc;
+    CtxRun run(s->cache);
+    run.acquire(0);
     trt_sample_point* d_in = nullptr;
     trt_sampled_color* d_out = nullptr;
-    unsigned long long h_ctr[CTR_COUNT] = {0};
-    float ms = 0.0f;
-    auto finish = [&](int code) {
-        (void)hipStreamSynchronize(c->stream);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        (void)hipGetLastError();
-        context_release(s, dev, c);
-        return code;
-    };
-#define TRT_HIP_C(call)                                                          \
-    do {                                                                         \
-        hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) return finish(fail_hip(e_, #call));                \
-    } while (0)
-    TRT_HIP_C(hipMalloc(reinterpret_cast<void**>(&d_in), (size_t)n * sizeof(trt_sample_point)));
-    TRT_HIP_C(hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)n * sizeof(trt_sampled_color)));
-    TRT_HIP_C(hipMemsetAsync(c->d_ctr, 0, sizeof(h_ctr), c->stream));
-    TRT_HIP_C(hipMemcpyAsync(d_in, in, (size_t)n * sizeof(trt_sample_point), hipMemcpyHostToDevice, c->stream));
-    TRT_HIP_C(hipEventRecord(c->ev0, c->stream));
-    TRT_HIP_C(launch_sample_batch(sc, d_in, n, d_out, ra, c->d_ctr, counting, c->stream));
-    TRT_HIP_C(hipEventRecord(c->ev1, c->stream));
-    TRT_HIP_C(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(trt_sampled_color), hipMemcpyDeviceToHost, c->stream));
-    TRT_HIP_C(hipMemcpyAsync(h_ctr, c->d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
-    TRT_HIP_C(hipStreamSynchronize(c->stream));
-    TRT_HIP_C(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-#undef TRT_HIP_C
-    (void)finish(TRT_OK);
-    if (stats) { counters_to_stats(h_ctr, stats); stats->kernel_ms = ms; }
-    return TRT_OK;
+    run.alloc(&d_in, (size_t)n * sizeof(trt_sample_point), "hipMalloc(sample points)", TRT_ERR_HIP);
+    run.alloc(&d_out, (size_t)n * sizeof(trt_sampled_color), "hipMalloc(sampled colours)", TRT_ERR_HIP);
+    run.zero_counters();
+    if (run.ok()) run.step(hipMemcpyAsync(d_in, in, (size_t)n * sizeof(trt_sample_point), hipMemcpyHostToDevice, run.stream()), "hipMemcpyAsync(sample points to device)");
+    run.time_begin();
+    if (run.ok()) run.step(launch_sample_batch(sc, d_in, n, d_out, ra, run.counters(), counting, run.stream()), "launch_sample_batch");
+    run.time_end();
+    if (run.ok()) run.step(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(trt_sampled_color), hipMemcpyDeviceToHost, run.stream()), "hipMemcpyAsync(sampled colours to host)");
+    return run.finish(stats);
 }
 
 uint32_t trt_streamed_chunk_spp(uint32_t width, uint32_t rows) { return streamed_chunk_spp(width, rows, defaults().tuning.radiance_gb); }
@@ -1386,19 +955,19 @@ int trt_kernel_timing_end(double* total_ms, uint32_t* launches) {
     double sum = 0.0;
     uint32_t n = 0;
     int rc = TRT_OK;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-    for (const trt::TimingPair& pr : pairs) {
-        float ms = 0.0f;
-        hipError_t e = hipSetDevice(pr.device);
-        if (e == hipSuccess) e = hipEventSynchronize(pr.end);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.begin, pr.end);
-        if (e != hipSuccess) { if (rc == TRT_OK) rc = fail_hip(e, "kernel timing events"); continue; }
-        sum += ms;
-        n++;
+    {
+        DeviceRestore restore;
+        for (const trt::TimingPair& pr : pairs) {
+            float ms = 0.0f;
+            hipError_t e = hipSetDevice(pr.device);
+            if (e == hipSuccess) e = hipEventSynchronize(pr.end);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.begin, pr.end);
+            if (e != hipSuccess) { if (rc == TRT_OK) rc = fail_hip(e, "kernel timing events"); continue; }
+            sum += ms;
+            n++;
+        }
+        for (const trt::TimingPair& pr : pairs) { (void)hipEventDestroy(pr.begin); (void)hipEventDestroy(pr.end); }
     }
-    for (const trt::TimingPair& pr : pairs) { (void)hipEventDestroy(pr.begin); (void)hipEventDestroy(pr.end); }
-    if (have_prev) (void)hipSetDevice(prev);
     (void)hipGetLastError();
     if (total_ms) *total_ms = sum;
     if (launches) *launches = n;
