@@ -714,8 +714,8 @@ int trt_tonemap_u8_device(const float *d_accum, uint32_t npixels, float gamma, u
 
 /* How the streamed backend launches a render of this scene with these settings (host arithmetic only: works without a GPU).
  * The kernels' view of their dynamic LDS - scene copy | postponed-leaf stack (threads x leaf_slots x 8 B) | ray pool (36 B per
- * lane) - is decided in ONE place (streamed.hip streamed_launch_plan) and reported here, so that its invariants can be checked
- * for every scene size and every tuning knob without a device (tests/test_host_boundary.py). */
+ * lane) - is decided in ONE place (csrc/stream_plan.h: LdsLayout and the stages of streamed_launch_plan) and reported here, so that its
+ * invariants can be checked for every scene size and every tuning knob without a device (tests/test_host_boundary.py, tests/test_stream_plan.py). */
 typedef struct {
     uint32_t scene_mode;              /* 0 scene read from global memory, 1 whole hot scene copied into LDS */
     uint32_t threads_per_workgroup, waves_per_simd, workgroups_per_cu;

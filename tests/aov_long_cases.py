@@ -1,7 +1,7 @@
 """The image sizes, the pixels around the run boundaries and the oracle's fold of the feature-buffer test at frame size
 (tests/test_gpu_aov_long.py on the GPU; tests/test_aov_long_cases.py runs the same arithmetic and the same oracle without one).
 
-The feature buffers are launched by the rule of the queries (query_plan.h plan_batch): a wave owns a run of 256 local pixels until the
+The feature buffers are launched by the rule of the queries (stream_plan.h plan_batch): a wave owns a run of 256 local pixels until the
 image has more than n0 = 256 x wave_slots pixels, then of roundup64(ceil(n / wave_slots)).  Everything here is derived from
 Scene.aov_plan for a given compute-unit count (0: the device at hand), never assumed:
 

@@ -74,8 +74,6 @@ size_t streamed_workspace_bytes(uint32_t width, uint32_t rows, uint32_t samples,
     return (size_t)width * rows * (samples < chunk ? (samples ? samples : 1u) : chunk) * 12u + 256u;
 }
 uint32_t streamed_chunk_that_fits(uint32_t width, uint32_t rows, size_t bytes) { return bytes > 256u ? (uint32_t)((bytes - 256u) / ((size_t)width * rows * 12u)) : 0u; }
-const char* streamed_kernel_name(const SceneLayout&, const RenderArgs&, const trt_tuning&) { return "stub"; }
-StreamLaunchPlan streamed_launch_plan(const SceneLayout&, const RenderArgs&, const trt_tuning&, bool) { return StreamLaunchPlan{}; }
 std::atomic<long> g_stub_short_launches{0};
 hipError_t launch_streamed(const SceneDev&, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
                            float* d_accum, unsigned long long* d_counters, bool, hipStream_t stream) {

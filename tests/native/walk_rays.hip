@@ -3,7 +3,7 @@
 // - prim_best, the bits of t_best, and the fast / ref flags trav_begin gave the ray - for the Python side to compare with the
 // oracle's closest hit.  There is no walk code in this file: the kernels call the entry points streamed.hip calls (trav_begin,
 // closest_hit, closest_hit_resume, walk_compact2, trav_park / trav_unpark, stage_scene_to_lds) with the LDS laid out as
-// streamed.hip lays it out (scene copy | leaf stack: threads x slots x 8 bytes, two stacks per lane in the two-path kernel), and the
+// stream_plan.h LdsLayout lays it out (scene copy | leaf stack: threads x slots x 8 bytes, two stacks per lane in the two-path kernel), and the
 // resumable kernels mirror the round structure of stream_sample_kernel / stream_dual_kernel: a lane whose walk completed takes the
 // next ray of its wave's list, a parked one resumes beside it.
 //
@@ -222,14 +222,13 @@ struct Run {
 
 template <typename K>
 void set_lds(K kernel, size_t bytes) {
-    if (bytes > 160u * 1024u) { std::printf("LDS plan of %zu bytes\n", bytes); std::exit(3); }
+    if (bytes > kLdsPerCu) { std::printf("LDS plan of %zu bytes\n", bytes); std::exit(3); }
     CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
 template <int MODE, int WALK>
 void launch_direct(const Run& r, const Variant& v, const SceneDev& scd, const float4* list, const uint4* nodes, FlatReuse reuse) {
-    const size_t scene_b = MODE == MODE_LDS ? ((size_t)r.L->hot_bytes + 15u) & ~(size_t)15u : 0u;
-    const size_t lds = scene_b + (v.stack ? (size_t)kThreads * v.slots * sizeof(float2) : 0u);
+    const size_t lds = LdsLayout{MODE == MODE_LDS ? r.L->hot_bytes : 0u, kThreads, v.stack ? v.slots : 0u, 1u, false}.total();
     set_lds(direct_kernel<MODE, WALK>, lds);
     const uint32_t blocks = (r.n_tasks + 3u) / 4u;
     hipLaunchKernelGGL((direct_kernel<MODE, WALK>), dim3(blocks), dim3(kThreads), lds, 0, scd, r.d_rays, r.d_tasks, r.n_tasks, r.d_out, v.slots,
@@ -237,8 +236,7 @@ void launch_direct(const Run& r, const Variant& v, const SceneDev& scd, const fl
 }
 template <int MODE, int WALK>
 void launch_resume(const Run& r, const Variant& v, const SceneDev& scd, const float4* list, const uint4* nodes) {
-    const size_t scene_b = MODE == MODE_LDS ? ((size_t)r.L->hot_bytes + 15u) & ~(size_t)15u : 0u;
-    const size_t lds = scene_b + (size_t)kThreads * v.slots * sizeof(float2);
+    const size_t lds = LdsLayout{MODE == MODE_LDS ? r.L->hot_bytes : 0u, kThreads, v.slots, 1u, false}.total();
     set_lds(resume_kernel<MODE, WALK>, lds);
     const uint32_t blocks = (r.n_tasks + 3u) / 4u;
     hipLaunchKernelGGL((resume_kernel<MODE, WALK>), dim3(blocks), dim3(kThreads), lds, 0, scd, r.d_rays, r.d_tasks, r.n_tasks, r.d_out, v.slots,
@@ -260,7 +258,7 @@ void run_variant(const Run& r, const Variant& v) {
     }
     CHECK(hipMemset(r.d_out, 0xCD, 12ull * r.n_rays));
     if (v.kind == DUAL) {
-        const size_t lds = 2u * (size_t)kThreads * v.slots * sizeof(float2);
+        const size_t lds = LdsLayout{0u, kThreads, v.slots, 2u, false}.total();
         set_lds(dual_kernel, lds);
         hipLaunchKernelGGL(dual_kernel, dim3((r.n_tasks + 3u) / 4u), dim3(kThreads), lds, 0, scd, r.d_rays, r.d_tasks, r.n_tasks, r.d_out, v.slots,
                            v.stragglers, list, nodes);

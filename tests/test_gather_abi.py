@@ -219,7 +219,7 @@ def test_the_plan_symbol_checks_its_arguments(trt):
 
 
 RAY_COUNTS = (1, 64, 257, 324, 100003, 2 ** 32 - 1)                          # test_radiance_abi.py's
-# what plan_batch (query_plan.h) derives from the kernel's launch bound: the resident workgroups and wave slots, and through them the runs
+# what plan_batch (stream_plan.h) derives from the kernel's launch bound: the resident workgroups and wave slots, and through them the runs
 # of a batch too long for 256 items per wave
 FROM_THE_BOUND = ("kernel_waves_per_simd", "workgroups_per_cu", "wave_slots")
 FROM_THE_SLOTS = ("rays_per_wave", "waves", "workgroups")

@@ -1,5 +1,5 @@
 """The feature buffers (trt_render_aov_device) and the primary-ray export (trt_primary_rays_device) at frame size: images of more pixels
-than 256 x wave_slots, where a wave's run of pixels grows beyond 256 (query_plan.h plan_batch) - wave w no longer begins at a multiple of
+than 256 x wave_slots, where a wave's run of pixels grows beyond 256 (stream_plan.h plan_batch) - wave w no longer begins at a multiple of
 256, the refill cursor of the resumable walks and the `base += 64` loop of the others run more than four rounds, and the last wave owns a
 ragged rest - against the same frame folded on the device from the exported rays and trt_intersect_device, and, around the run
 boundaries, against the CPU oracle.

@@ -30,6 +30,7 @@
 #include "scene_adopt.h"
 #include "scene_cache.h"
 #include "scene_query.h"
+#include "stream_plan.h"
 
 using namespace trt;
 
@@ -925,7 +926,7 @@ int trt_streamed_launch_plan(const trt_scene* s, const trt_camera* cam, const tr
     out->ray_pool = pl.pool ? 1u : 0u;
     out->walk = (uint32_t)pl.walk;
     out->specialised = pl.specialised ? 1u : 0u;
-    out->has_kernel = pl.kernel != nullptr ? 1u : 0u;
+    out->has_kernel = pl.kernel_index >= 0 ? 1u : 0u;
     out->kernel_waves_per_simd = (uint32_t)pl.kernel_minw;
     out->kernel_threads = (uint32_t)pl.kernel_threads;
     out->kernel_walk = (uint32_t)pl.kernel_walk;

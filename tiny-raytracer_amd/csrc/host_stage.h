@@ -11,8 +11,6 @@
 
 namespace trt {
 
-inline size_t q_align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
-
 // Runs the body of a host form: no std::bad_alloc leaves the C ABI (if even the message cannot be set, the old one stays).
 template <class Body>
 int host_form(Body&& body) {

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "scene.h"
@@ -90,6 +91,8 @@ enum { CTR_SAMPLES = 0, CTR_RAYS, CTR_NODE, CTR_SPHERE, CTR_QUAD_PLANE, CTR_QUAD
 // scene.h kLdsSceneMaxBytes: hot blobs up to that size are copied whole into LDS; larger scenes are read from global memory.
 inline int scene_mode(const SceneLayout& L) { return L.hot_bytes <= kLdsSceneMaxBytes ? 1 : 0; }
 inline uint32_t scene_lds_bytes(const SceneLayout& L) { return scene_mode(L) == 1 ? L.hot_bytes : 0u; }
+// Regions of LDS and of staged device buffers begin at multiples of 16 bytes.
+inline size_t q_align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
 // Optional device timing of the dominant kernel (trt_kernel_timing_begin / _end, capi.hip): while enabled, a launcher
 // brackets every launch of its dominant kernel with timing_mark(stream, true) / timing_mark(stream, false), which record
@@ -117,10 +120,10 @@ uint32_t streamed_chunk_spp(uint32_t width, uint32_t rows, uint32_t radiance_gb)
 size_t streamed_workspace_bytes(uint32_t width, uint32_t rows, uint32_t samples, uint32_t radiance_gb);   // samples = sample_end - sample_begin of the render
 // Samples per pixel a workspace of `bytes` holds for this image (what launch_streamed may trace per launch with the scratch it was granted).
 uint32_t streamed_chunk_that_fits(uint32_t width, uint32_t rows, size_t bytes);
-const char* streamed_kernel_name(const SceneLayout& L, const RenderArgs& ra, const trt_tuning& tn);
-// How launch_streamed runs a scene with these settings (streamed.hip; also what trt_streamed_launch_plan reports).  The
-// kernel's view of its dynamic LDS - scene copy | leaf stack (threads x slots x 8 B) | ray pool (36 B per lane) - is fixed
-// here and nowhere else; launch_streamed refuses a plan whose parts do not add up (hipErrorInvalidConfiguration).
+// How launch_streamed runs a scene with these settings: the result of stream_plan.h streamed_launch_plan (host arithmetic only; also
+// what trt_streamed_launch_plan reports).  The kernel's view of its dynamic LDS - scene copy | leaf stack (threads x slots x 8 B) | ray
+// pool (36 B per lane) - is stream_plan.h LdsLayout and nothing else; launch_streamed refuses a plan whose parts do not add up
+// (hipErrorInvalidConfiguration).
 struct StreamLaunchPlan {
     int mode, threads, waves_per_simd;      // scene mode, lanes per workgroup, waves per SIMD the grid is sized for
     uint32_t wg_per_cu, slots;              // resident workgroups per CU; postponed-leaf slots per lane
@@ -128,12 +131,11 @@ struct StreamLaunchPlan {
     bool dual;                              // two paths per lane (stream_dual_kernel): two leaf stacks per lane
     int walk;                               // WALK_* the kernel will run
     size_t lds_bytes, scene_lds_bytes;      // dynamic LDS per workgroup; the scene copy's share of it
-    const void* kernel;                     // the instantiation (nullptr: none - a bug, launch_streamed fails)
+    int kernel_index;                       // the instantiation: its row of stream_plan.h kStreamKernels (-1: none - a bug, launch_streamed fails)
     int kernel_minw, kernel_threads, kernel_walk;      // its template arguments (launch bound, lanes, WALK_RUNTIME = chooses at run time)
     bool kernel_pool, kernel_stats;
     const char* kernel_name;
 };
-StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra, const trt_tuning& tn, bool stats);
 // `workspace_bytes`: what the caller was granted (at least streamed_workspace_bytes for one sample): the launches are sized to it.
 hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
                            float* d_accum, unsigned long long* d_counters, bool stats, hipStream_t stream);

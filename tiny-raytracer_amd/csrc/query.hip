@@ -145,7 +145,7 @@ namespace {
 // no resident 512-lane workgroup (scene copies of roughly 56 to 64 KB) is planned as LDS tree / 512 lanes, which is not here, and
 // neither are the plans only scene options reach (a tree walk from global memory with the 16-byte nodes switched off; the lock-step
 // list forced on a scene of more than 32 primitives that is in LDS at 768 lanes or in global memory).  Those run the register-slot
-// instantiation of their scene mode (query_plan.h plan_batch: fallback), which walks the culling tree every compiled scene carries and
+// instantiation of their scene mode (stream_plan.h plan_batch: fallback), which walks the culling tree every compiled scene carries and
 // needs neither the leaf list nor the 16-byte nodes.  Row 0: the closest-hit form, row 1: the occlusion form of the same shapes.
 #define TRT_QUERY_TABLE(ANY)                                \
     {                                                       \

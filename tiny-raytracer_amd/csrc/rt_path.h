@@ -9,6 +9,7 @@
 #include "nearest_first.h"
 #include "kernels.h"
 #include "rt_device.h"
+#include "stream_plan.h"
 
 namespace trt {
 
@@ -17,8 +18,7 @@ extern __shared__ float4 g_lds[];          // dynamic LDS: [scene copy (LDS vari
 // ------------------------------------------------------------------------------------------------
 // Scene access: LDS copy or global blob, same element offsets (scene.h).
 // ------------------------------------------------------------------------------------------------
-enum { MODE_GLOBAL = 0,      // scene read through L1/L2
-       MODE_LDS = 1 };       // the whole hot part of the blob (culling tree, primitives, materials) copied into LDS
+// MODE_GLOBAL / MODE_LDS: stream_plan.h, with the launch rule that chooses between them.
 // (A third mode - the upper part of a large scene's tree in LDS - was built twice and lost twice: round 4's level-order top levels of the 32-byte
 // tree, "slower at every size", and round 5's split of the 16-byte tree with a hand-written exec-mask loop, 7-10 % slower one step per trip and twice
 // as slow with LDS lanes running ahead.  The walk of a scene in global memory is bound by VALU issue; LDS hits spare it nothing and the split
@@ -989,13 +989,7 @@ TRT_DEV void walk_compact2(const SceneAcc<MODE>& sc, const uint4* __restrict__ n
     doneA = iA >= n; doneB = iB >= n;
 }
 
-constexpr uint32_t kLdsLeafSlotsMax = 16; // most slots per lane of the LDS leaf stack (8 bytes each)
-
-// Which walk a kernel instantiation runs.  WALK_RUNTIME picks by the launch arguments (every knob combination; counting
-// kernels); the others fix the walk at compile time, which is what the production launches use: the kernel then holds ONE
-// walk instead of five, with the SGPRs, VGPRs and instruction-cache footprint of one (stream_pool_kernel on Cornell:
-// 6849 lines of ISA, 44 spilled SGPRs and 16 spilled VGPRs with the runtime choice).
-enum { WALK_RUNTIME = 0, WALK_LDS_STACK = 1, WALK_FLAT = 2, WALK_COMPACT = 3, WALK_REGS = 5 };
+// kLdsLeafSlotsMax and the WALK_* a kernel instantiation runs: stream_plan.h.
 
 // Axis-exact quads (axis_quads.h).  Only the production lock-step kernel on an LDS scene copy takes the switch: the counting kernels,
 // the kernels that choose their walk at run time, the megakernel and the wavefront backend keep the generic test on the packed records

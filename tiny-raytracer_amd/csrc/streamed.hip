@@ -25,11 +25,10 @@
 #include "host_stage.h"
 #include "kernels.h"
 #include "rt_path.h"
+#include "stream_plan.h"
 #include "wave_run.h"
 
 namespace trt {
-
-constexpr uint32_t kBatchSpp = 8;            // samples per pixel in one batch
 
 template <int MODE, bool STATS, int MINW = 1, int THREADS = 256, int WALK = WALK_RUNTIME, bool LAZY = false>
 __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev scd, CameraDev cam, RenderArgs ra,
@@ -162,8 +161,6 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
 // (RNG keyed by pixel and sample, radiance stored per sample, folded in order).  Used where the pool costs no resident
 // workgroup (small LDS scene copies, scenes in global memory).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kPoolDwords = 9u;         // origin, direction, rng state, radiance slot
-
 // The streamed kernels' argument list as the kernel-argument segment lays it out (every argument at its natural alignment, in order).
 // stream_pool_kernel reads the arguments that only its refill branch needs - the camera, the band layout, the tile arithmetic: ~40 words,
 // used once per ~7 rounds - from that segment INSIDE the branch instead of taking them from the by-value parameters: those are loaded at
@@ -206,7 +203,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
     const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
     char* const lds_tail = lds_behind_scene(sc);
     float2* const leaf_stack = reinterpret_cast<float2*>(lds_tail) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane;
-    // the pool: field f of entry e at pool[f * 64 + e]
+    // the pool: field f of entry e at pool[f * 64 + e]; behind the leaf stack (stream_plan.h LdsLayout::stack_bytes, one stack)
     uint32_t* const pool = reinterpret_cast<uint32_t*>(lds_tail + (size_t)THREADS * ra.leaf_slots * sizeof(float2)) + (threadIdx.x >> 6) * (64u * kPoolDwords);
 
     uint32_t tile_x0 = 0, tile_row0 = 0, tile_slot0 = 0, ds0 = 0, items_per_batch = 0, cursor = 0;    // wave-uniform work cursor
@@ -353,7 +350,7 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_dual_kernel(SceneDev scd
     char* const lds_tail = reinterpret_cast<char*>(g_lds);
     float2* const stkA = reinterpret_cast<float2*>(lds_tail) + (2u * wave) * (64u * ra.leaf_slots) + lane;
     float2* const stkB = stkA + 64u * ra.leaf_slots;
-    uint32_t* const pool = reinterpret_cast<uint32_t*>(lds_tail + (size_t)THREADS * 2u * ra.leaf_slots * sizeof(float2)) + wave * (64u * kPoolDwords);
+    uint32_t* const pool = reinterpret_cast<uint32_t*>(lds_tail + (size_t)THREADS * 2u * ra.leaf_slots * sizeof(float2)) + wave * (64u * kPoolDwords);      // behind the two leaf stacks (stream_plan.h LdsLayout::stack_bytes)
 
     uint32_t tile_x0 = 0, tile_row0 = 0, tile_slot0 = 0, ds0 = 0, items_per_batch = 0, cursor = 0;    // wave-uniform work cursor
     uint32_t pool_head = 0, pool_count = 0;                                            // wave-uniform
@@ -565,195 +562,21 @@ uint32_t streamed_chunk_that_fits(uint32_t width, uint32_t rows, size_t bytes) {
 
 namespace {
 
-constexpr size_t kLdsPerCu = 160u * 1024u;
-
-// One kernel instantiation the launcher may pick.  Every instantiation has the same parameter list, so a launch is
-// hipLaunchKernel(fn, ...) with one argument array whichever entry is chosen.
-struct KernelEntry {
-    const void* fn;
-    int mode, threads, minw;        // template arguments: scene mode, lanes per workgroup, launch bound (waves per SIMD)
-    int walk;                       // WALK_RUNTIME: the kernel picks the walk from its arguments (every knob, counting variants)
-    bool pool, stats, lazy;
-    bool dual = false;              // stream_dual_kernel: two paths per lane (MODE_GLOBAL, 16-byte nodes, ray pool)
+// The kernels' addresses, row for row the shapes of stream_plan.h kStreamKernels: the same two lists, expanded into the instantiations.
+// Every instantiation has the same parameter list, so a launch is hipLaunchKernel(fn, ...) with one argument array whichever row is chosen.
+#define TRT_FN_POOL(MODE, STATS, MINW, THREADS, WALK, LAZY) reinterpret_cast<const void*>(&stream_pool_kernel<MODE, STATS, MINW, THREADS, WALK, LAZY>),
+#define TRT_FN_SAMPLE(MODE, STATS, MINW, THREADS, WALK, LAZY) reinterpret_cast<const void*>(&stream_sample_kernel<MODE, STATS, MINW, THREADS, WALK, LAZY>),
+#define TRT_FN_DUAL(MINW) reinterpret_cast<const void*>(&stream_dual_kernel<MINW, 256>),
+const void* const kStreamKernelFns[] = {
+    TRT_STREAM_SPECIALISED(TRT_FN_POOL, TRT_FN_SAMPLE, TRT_FN_DUAL)
+    TRT_STREAM_GENERAL(TRT_FN_POOL, TRT_FN_SAMPLE, TRT_FN_DUAL)
 };
-#define TRT_POOL(MODE, STATS, MINW, THREADS, WALK, LAZY) \
-    KernelEntry{reinterpret_cast<const void*>(&stream_pool_kernel<MODE, STATS, MINW, THREADS, WALK, LAZY>), MODE, THREADS, MINW, WALK, true, STATS, LAZY}
-#define TRT_SAMPLE(MODE, STATS, MINW, THREADS, WALK, LAZY) \
-    KernelEntry{reinterpret_cast<const void*>(&stream_sample_kernel<MODE, STATS, MINW, THREADS, WALK, LAZY>), MODE, THREADS, MINW, WALK, false, STATS, LAZY}
-
-#define TRT_DUAL(MINW) \
-    KernelEntry{reinterpret_cast<const void*>(&stream_dual_kernel<MINW, 256>), MODE_GLOBAL, 256, MINW, WALK_COMPACT, true, false, true, true}
-
-// production launches: walk fixed at compile time, lazy colour, no counters
-const KernelEntry kSpecialised[] = {
-    TRT_POOL(MODE_LDS, false, 6, 256, WALK_FLAT, true),
-    TRT_POOL(MODE_LDS, false, 7, 256, WALK_FLAT, true),
-    TRT_POOL(MODE_LDS, false, 8, 256, WALK_FLAT, true),
-    TRT_POOL(MODE_LDS, false, 6, 256, WALK_LDS_STACK, true),
-    TRT_SAMPLE(MODE_LDS, false, 6, 512, WALK_REGS, true),
-    TRT_SAMPLE(MODE_LDS, false, 6, 768, WALK_LDS_STACK, true),
-    TRT_POOL(MODE_GLOBAL, false, 8, 256, WALK_COMPACT, true),
-    TRT_POOL(MODE_GLOBAL, false, 7, 256, WALK_COMPACT, true),     // 72 VGPRs: nothing spilled (at 8 waves the fused slab arithmetic spills ten registers)
-    TRT_DUAL(4), TRT_DUAL(5), TRT_DUAL(6), TRT_DUAL(7), TRT_DUAL(8),
-};
-// every other knob combination and the counting variants: runtime choice of the walk
-const KernelEntry kGeneral[] = {
-    TRT_SAMPLE(MODE_LDS, false, 6, 768, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 6, 768, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_LDS, false, 6, 512, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 6, 512, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_LDS, false, 5, 512, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 5, 512, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_LDS, false, 7, 256, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 7, 256, WALK_RUNTIME, false),
-    TRT_POOL(MODE_LDS, false, 6, 256, WALK_RUNTIME, false),      TRT_POOL(MODE_LDS, true, 6, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_LDS, false, 6, 256, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 6, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_LDS, false, 5, 256, WALK_RUNTIME, false),    TRT_SAMPLE(MODE_LDS, true, 5, 256, WALK_RUNTIME, false),
-    TRT_POOL(MODE_GLOBAL, false, 8, 256, WALK_RUNTIME, false),   TRT_POOL(MODE_GLOBAL, true, 8, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_GLOBAL, false, 8, 256, WALK_RUNTIME, false), TRT_SAMPLE(MODE_GLOBAL, true, 8, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_GLOBAL, false, 7, 256, WALK_RUNTIME, false), TRT_SAMPLE(MODE_GLOBAL, true, 7, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_GLOBAL, false, 6, 256, WALK_RUNTIME, false), TRT_SAMPLE(MODE_GLOBAL, true, 6, 256, WALK_RUNTIME, false),
-    TRT_SAMPLE(MODE_GLOBAL, false, 1, 256, WALK_RUNTIME, false), TRT_SAMPLE(MODE_GLOBAL, true, 1, 256, WALK_RUNTIME, false),
-};
-#undef TRT_POOL
-#undef TRT_SAMPLE
-#undef TRT_DUAL
-
-const KernelEntry* find_general(int mode, int threads, int minw, bool pool, bool stats) {
-    for (const KernelEntry& k : kGeneral)
-        if (k.mode == mode && k.threads == threads && k.minw == minw && k.pool == pool && k.stats == stats && !k.dual) return &k;
-    return nullptr;
-}
+#undef TRT_FN_POOL
+#undef TRT_FN_SAMPLE
+#undef TRT_FN_DUAL
+static_assert(sizeof(kStreamKernelFns) / sizeof(kStreamKernelFns[0]) == kStreamKernelCount, "one address per shape row");
 
 }  // namespace
-
-// How a scene is launched: workgroup shape, waves per SIMD, where the postponed leaves live, which walk, which kernel.
-// Everything the kernel assumes about its LDS (scene copy | leaf stack: threads x slots x 8 bytes | ray pool: 36 bytes per lane)
-// is decided HERE and nowhere else; trt_streamed_launch_plan exposes the result, and the CPU tests check its invariants for
-// every scene size and every knob (tests/test_host_boundary.py).
-StreamLaunchPlan streamed_launch_plan(const SceneLayout& L, const RenderArgs& ra_all, const trt_tuning& tn, bool stats) {
-    StreamLaunchPlan pl{};
-    const size_t scene_bytes = scene_lds_bytes(L);
-    const int mode = scene_mode(L);
-    // waves per SIMD / lanes per workgroup: 256-lane workgroups for small LDS copies; a big LDS copy (> 20 KB) is shared by
-    // more waves: 768 lanes (12 waves, two workgroups per CU = 6 waves per SIMD) if the copy and a 4-slot LDS leaf stack
-    // fit twice into the CU's 160 KB (random-spheres: 49.6 + 24 KB; 19.0 Gray/s against 18.0 for 512 lanes with register
-    // slots and 18.7 for 1024 lanes at 8 waves per SIMD, one box: tools/sweep_rs.sh), else 512 lanes with the slots in registers;
-    // 8 waves per SIMD for scenes read from global memory
-    int threads = 256;
-    if (mode == MODE_LDS && L.hot_bytes > 20u * 1024u) {
-        threads = (q_align16(scene_bytes) + 768u * 4u * sizeof(float2)) * 2u <= kLdsPerCu && ra_all.lds_leaf_stack != 0u ? 768 : 512;
-        if (tn.stream_big_threads == 512u || tn.stream_big_threads == 768u) threads = (int)tn.stream_big_threads;
-    }
-    // LDS scenes: 6 waves per SIMD.  Scenes in global memory: rounds 1-4 ran them at 8 (100 k spheres: 2.03 Gray/s at 5 waves, 2.25 at 6, 2.29 at 8 -
-    // measured with NaN rays walking the whole tree in every launch: rt_path.h ray_has_nan)
-    // (round 5, without the NaN-ray tail and with the fused slab arithmetic: a tree that fits the chip's 32 MiB of L2 runs 5 % faster at 7 waves
-    // with no spilled register than at 8 with ten; a scene whose walk waits for memory - sphere_field, 1 M spheres and up - wants the eighth wave:
-    // profiles/r05_waves7_ab.txt)
-    // Two paths per lane (stream_dual_kernel; trt_tuning.dual_walk: 0 by scene, 1 wherever the kernel exists, 2 never): with the fused box step in its loop
-    // it LOSES 2.6 % where the tree fits L2 and WINS 2.7 % / 4.2 % on sphere_field 1 M / 4 M at 6 waves - where the walk's loads really miss, a second
-    // node load in flight per lane pays (profiles/r05_dual_walk_fused_ab.txt): by scene = beyond L2, when nothing else about the launch was asked for.
-    const bool beyond_l2 = mode == MODE_GLOBAL && L.hot_bytes > (32u << 20);
-    const bool want_dual = mode == MODE_GLOBAL && (tn.dual_walk == 1u || (tn.dual_walk == 0u && beyond_l2 && tn.stream_waves_per_simd == 0u && !stats && !ra_all.ref_tree &&
-                                                                           L.lazy_color && tn.runtime_walk == 0u && tn.ray_pool != 0u && ra_all.lds_leaf_stack != 0u &&
-                                                                           L.off_compact != 0u));
-    int w = mode == MODE_LDS ? 6 : (beyond_l2 ? (want_dual ? 6 : 8) : 7);
-    if (tn.stream_waves_per_simd) w = (int)tn.stream_waves_per_simd;
-    if (w < 5 && !(want_dual && w == 4)) w = 5;      // (4: the two-path kernel only - eight rays per SIMD like 8 x 1)
-    if (w > 8) w = 8;
-    if (threads == 512 && w > 6) w = 6;
-    if (threads == 768) w = 6;
-    uint32_t wg_per_cu = (uint32_t)(w * 4 * 64 / threads);
-    // slots of the LDS stack: 4 for tree walks (5 in the 768-lane plan if they fit: random-spheres +3 %, profiles/r03_defaults_sweep.txt);
-    // 7 for the lock-step leaf list, whose t_best stays stale for a whole walk (Cornell 34.0 Gray/s at 4, 35.1 at 6..12) and which
-    // steps two leaves per trip, so a lane must have two free
-    const bool flat = L.flat_walk && !ra_all.ref_tree;
-    uint32_t slots = ra_all.leaf_slots == 0u ? (flat ? 7u : (threads == 768 ? 5u : 4u)) : (ra_all.leaf_slots > kLdsLeafSlotsMax ? kLdsLeafSlotsMax : ra_all.leaf_slots);
-    if (flat && slots < 2u) slots = 2u;                                         // walk_flat pushes up to two leaves per trip
-    if (flat && ra_all.leaf_slots == 0u && mode == MODE_LDS && threads == 256) {
-        // the default depth gives way to occupancy: the deepest stack (<= 7, >= 4) with which stack + ray pool + scene copy of
-        // all the CU's workgroups fit its 160 KB of LDS (Cornell: 7 slots at 6 waves per SIMD, 5 at 7, 4 at 8)
-        const size_t pool_b = (size_t)threads / 64u * 64u * kPoolDwords * sizeof(uint32_t);
-        while (slots > 4u && (q_align16(scene_bytes) + (size_t)threads * slots * sizeof(float2) + pool_b) * wg_per_cu > kLdsPerCu) slots--;
-    }
-    if (threads > 512 && ra_all.leaf_slots == 0u) {
-        while (slots > 3u && (q_align16(scene_bytes) + (size_t)threads * slots * sizeof(float2)) * wg_per_cu > kLdsPerCu) slots--;
-    }
-    const size_t stack_bytes = (size_t)threads * slots * sizeof(float2);
-    const size_t with_stack = q_align16(scene_bytes) + stack_bytes;
-    // LDS: scene copy + the postponed-leaf stack (8 bytes per lane and slot), the latter only where it does not cost a
-    // resident workgroup (random-spheres: 49.6 KB scene copy, 3 workgroups of 512 lanes per CU without it, 2 with it:
-    // measured 7 % slower than register slots); otherwise the slots are registers
-    bool lds_stack = ra_all.lds_leaf_stack != 0u && with_stack <= kLdsPerCu;
-    if (lds_stack && ra_all.lds_leaf_stack != 2u) {
-        const uint32_t fit_plain = scene_bytes ? (uint32_t)(kLdsPerCu / scene_bytes) : wg_per_cu;
-        const uint32_t fit_stack = (uint32_t)(kLdsPerCu / with_stack);
-        lds_stack = (fit_stack < wg_per_cu ? fit_stack : wg_per_cu) >= (fit_plain < wg_per_cu ? fit_plain : wg_per_cu);
-    }
-    // few primitives: lock-step leaf list (rt_path.h walk_flat); scenes read from global memory: 16-byte culling nodes
-    // (walk_compact).  Both need the LDS stack.
-    const bool compact = lds_stack && mode == MODE_GLOBAL && L.off_compact != 0u && !ra_all.ref_tree;
-    // per-wave pool of primary rays (stream_pool_kernel): needs the LDS stack and 256-lane workgroups (LDS scenes at 6
-    // waves per SIMD and more, global-memory scenes at 8), and must not cost a resident workgroup either
-    const size_t pool_bytes = (size_t)threads / 64u * 64u * kPoolDwords * sizeof(uint32_t);
-    bool pool = lds_stack && threads == 256 && !ra_all.ref_tree && ((mode == MODE_LDS && w >= 6) || (mode == MODE_GLOBAL && (w >= 7 || want_dual)));
-    pool = pool && tn.ray_pool != 0u;
-    if (pool) pool = (uint32_t)(kLdsPerCu / (with_stack + pool_bytes)) >= wg_per_cu;
-
-    // ---- the kernel instantiation ----
-    const int walk = compact ? WALK_COMPACT : (flat && lds_stack) ? WALK_FLAT : lds_stack ? WALK_LDS_STACK : WALK_REGS;
-    const bool slots_ok = lds_stack || ra_all.leaf_slots == 0u || ra_all.leaf_slots >= 4u;      // WALK_REGS has 4 register slots
-    const bool specialise = !stats && slots_ok && L.lazy_color && tn.runtime_walk == 0u;
-    // two paths per lane (stream_dual_kernel): scenes in global memory on 16-byte nodes with the ray pool; two leaf stacks per lane, as deep
-    // as fit beside the pool (2..4 slots: a parked walk needs two)
-    bool dual = want_dual && specialise && compact && pool && threads == 256;
-    if (dual) {
-        uint32_t ds = ra_all.leaf_slots == 0u ? 4u : (ra_all.leaf_slots < 2u ? 2u : (ra_all.leaf_slots > kLdsLeafSlotsMax ? kLdsLeafSlotsMax : ra_all.leaf_slots));
-        while (ds > 2u && (q_align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) ds--;
-        if ((q_align16(scene_bytes) + 2u * (size_t)threads * ds * sizeof(float2) + pool_bytes) * wg_per_cu > kLdsPerCu) dual = false;
-        else slots = ds;
-    }
-    const size_t stack_total = dual ? 2u * (size_t)threads * slots * sizeof(float2) : stack_bytes;
-    const KernelEntry* k = nullptr;
-    if (specialise) {
-        for (const KernelEntry& e : kSpecialised)
-            if (e.mode == mode && e.threads == threads && e.minw == w && e.pool == pool && e.walk == walk && e.dual == dual) { k = &e; break; }
-    }
-    if (!k) dual = false;
-    if (!dual && w < 5) { w = 5; wg_per_cu = (uint32_t)(w * 4 * 64 / threads); }             // four waves per SIMD exist for the two-path kernel only
-    if (!dual && want_dual && tn.dual_walk == 0u) { w = 8; wg_per_cu = (uint32_t)(w * 4 * 64 / threads); }      // the plan's own wish fell through: the one-path shape of a scene beyond L2
-    pl.specialised = k != nullptr;
-    if (!k) {
-        // the general instantiations exist for fewer (waves, pool) combinations than the knobs can ask for: take the nearest one
-        // BELOW the request and make the plan follow the kernel, so that grid and LDS are sized for what really runs
-        bool kpool = pool;
-        int kw = w;
-        if (mode == MODE_LDS && threads == 256) {
-            if (w >= 7) { kw = 7; kpool = false; }                  // 7 waves: sample kernel only
-            else if (w == 6) kw = 6;
-            else { kw = 5; kpool = false; }
-        } else if (mode == MODE_LDS && threads == 512) { kw = w >= 6 ? 6 : 5; kpool = false; }
-        else if (mode == MODE_LDS) { kw = 6; kpool = false; }
-        else {                                                      // MODE_GLOBAL
-            if (w >= 8) kw = 8;
-            else if (w == 7) { kw = 7; kpool = false; }
-            else if (w == 6) { kw = 6; kpool = false; }
-            else { kw = 1; kpool = false; }
-        }
-        k = find_general(mode, threads, kw, kpool, stats);
-        pool = kpool;
-        if (kw >= 5 && kw < w) { w = kw; wg_per_cu = (uint32_t)(w * 4 * 64 / threads); }
-    }
-    const size_t lds_bytes = lds_stack ? q_align16(scene_bytes) + (dual ? stack_total : stack_bytes) + (pool ? pool_bytes : 0u) : scene_bytes;
-    if (lds_bytes) { const uint32_t by_lds = (uint32_t)(kLdsPerCu / lds_bytes); if (by_lds < wg_per_cu) wg_per_cu = by_lds ? by_lds : 1u; }
-    pl.mode = mode; pl.threads = threads; pl.waves_per_simd = w; pl.wg_per_cu = wg_per_cu; pl.slots = slots;
-    pl.lds_stack = lds_stack; pl.flat = flat && lds_stack; pl.compact = compact; pl.pool = pool; pl.walk = walk; pl.dual = dual;
-    pl.lds_bytes = lds_bytes; pl.scene_lds_bytes = scene_bytes;
-    pl.kernel = k ? k->fn : nullptr;
-    pl.kernel_minw = k ? k->minw : 0; pl.kernel_threads = k ? k->threads : 0; pl.kernel_walk = k ? k->walk : 0; pl.kernel_pool = k ? k->pool : false;
-    pl.kernel_stats = k ? k->stats : false;
-    pl.kernel_name = dual ? "trt::stream_dual_kernel" : pool ? "trt::stream_pool_kernel" : "trt::stream_sample_kernel";
-    return pl;
-}
-
-// Name of the kernel that dominates a streamed render of this scene (for profiles and bench.py's roofline line).
-const char* streamed_kernel_name(const SceneLayout& L, const RenderArgs& ra, const trt_tuning& tn) { return streamed_launch_plan(L, ra, tn, false).kernel_name; }
 
 // d_moment2 == nullptr: the frame only.
 static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra_all, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
@@ -775,14 +598,12 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
     if (e != hipSuccess) return e;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const StreamLaunchPlan pl = streamed_launch_plan(sc.L, ra_all, tn, stats);
-    if (pl.kernel == nullptr) return hipErrorInvalidDeviceFunction;               // no instantiation for this plan: a bug, never a fallback
+    if (pl.kernel_index < 0 || (size_t)pl.kernel_index >= kStreamKernelCount) return hipErrorInvalidDeviceFunction;      // no instantiation for this plan: a bug, never a fallback
+    const void* const kernel = kStreamKernelFns[pl.kernel_index];
     // the kernel's assumptions about its dynamic LDS, checked where the launch is made (scene copy | leaf stack | ray pool)
-    {
-        size_t need = pl.scene_lds_bytes;
-        if (pl.lds_stack) need = q_align16(need) + (pl.dual ? 2u : 1u) * (size_t)pl.threads * pl.slots * sizeof(float2) + (pl.pool ? (size_t)pl.threads * kPoolDwords * sizeof(uint32_t) : 0u);
-        if (need != pl.lds_bytes || pl.lds_bytes > kLdsPerCu || pl.kernel_threads != pl.threads || (pl.pool && !pl.lds_stack) ||
-            (pl.flat && pl.slots < 2u) || (pl.kernel_pool != pl.pool)) return hipErrorInvalidConfiguration;
-    }
+    const LdsLayout lds = plan_lds_layout(pl);
+    if (lds.total() != pl.lds_bytes || !lds.fits(1u) || pl.kernel_threads != pl.threads || (pl.pool && !pl.lds_stack) ||
+        (pl.flat && pl.slots < 2u) || (pl.kernel_pool != pl.pool)) return hipErrorInvalidConfiguration;
     SceneDev scd = sc;
     CameraDev camd = cam;
     const float4* leaf_list = (pl.flat || pl.compact) ? sc.blob + sc.L.off_leaf_list : nullptr;
@@ -791,7 +612,7 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
     const uint32_t resident = (uint32_t)cus * pl.wg_per_cu;
     const uint32_t waves_per_wg = (uint32_t)pl.threads / 64u;
     if (pl.lds_bytes > 48u * 1024u) {
-        e = hipFuncSetAttribute(pl.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
         if (e != hipSuccess) return e;
     }
     bool first = true;
@@ -814,7 +635,7 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
         if (e != hipSuccess) return e;
         void* args[] = {&scd, &camd, &ra, &colors, &batch_counter, &d_counters, &tiles_x, &n_tiles, &n_batches, &batch_spp, &leaf_list, &nodes16};
         timing_mark(stream, true);
-        e = hipLaunchKernel(pl.kernel, dim3(grid_x), dim3((uint32_t)pl.threads), args, pl.lds_bytes, stream);
+        e = hipLaunchKernel(kernel, dim3(grid_x), dim3((uint32_t)pl.threads), args, pl.lds_bytes, stream);
         timing_mark(stream, false);
         if (e != hipSuccess) return e;
         const uint32_t fold_blocks = (n_tiles + 3u) / 4u;                           // four tiles (waves) per workgroup

@@ -2,7 +2,7 @@
 // of the caller's rays), the feature buffers (aov.hip: a run of the local image's pixels) and the sparse render (pixels.hip: a run of the
 // pixel list).  ONE copy of the lane rank, the run of a wave, the place of the leaf stacks, the cursor step of the round loop's refill
 // and the surface record of a closest hit; each kernel keeps its own loop body, because what a lane carries and does with a finished
-// walk differs.  The host side of the same units (kernel table, launch rule, launch preamble) is query_plan.h.
+// walk differs.  The host side of the same units is stream_plan.h (kernel table entry, launch rule) and query_plan.h (launch preamble).
 // radiance.hip (radiance and gather queries: a run of the caller's rays or surfels) and ambient.hip (ambient queries: a run of surfels)
 // take the run, the leaf stacks and the refill step from here too.
 //
@@ -33,7 +33,8 @@ TRT_DEV unsigned long long wave_begin(uint32_t per_wave) {
 TRT_DEV uint32_t wave_count(uint32_t n, uint32_t per_wave, uint32_t begin) { return n - begin < per_wave ? n - begin : per_wave; }
 
 // The dynamic LDS behind the scene copy (16-byte aligned): the backend-private area.  The postponed-leaf stacks (rt_path.h
-// walk_fast_lds) begin here: slots x 64 x 8 bytes per wave, a lane's entries 64 apart.
+// walk_fast_lds) begin here: slots x 64 x 8 bytes per wave, a lane's entries 64 apart.  The sizes of these parts, for the host: stream_plan.h
+// LdsLayout (scene copy aligned to 16 | stacks); the address stays written out here and in the kernels (see the head of this file).
 template <int MODE>
 TRT_DEV char* lds_behind_scene(const SceneAcc<MODE>& sc) {
     return reinterpret_cast<char*>(g_lds) + ((sc.lds_bytes() + 15u) & ~15u);
