@@ -269,6 +269,20 @@ pub struct trt_ambient_params {
     pub reserved: [u32; 7],
 }
 
+/// `enum trt_probe_domain`: the directions the first ray of a probe sample is drawn over.
+pub const TRT_PROBE_SPHERE: u32 = 1;
+pub const TRT_PROBE_HEMISPHERE: u32 = 2;
+
+/// `trt_radiance_params`, the domain and the number of spherical-harmonic bands of `trt_probe` (96 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_probe_params {
+    pub path: trt_radiance_params,
+    pub domain: u32,
+    pub bands: u32,
+    pub reserved: [u32; 6],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -433,6 +447,12 @@ extern "C" {
     pub fn trt_ambient_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_ambient_params, d_visibility: *mut f32,
                               d_bent: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_ambient_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_probe_params_default(out: *mut trt_probe_params);
+    pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
+                     stats: *mut trt_stats) -> c_int;
+    pub fn trt_probe_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_probe_params, d_sh: *mut f32,
+                            d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_probe_launch_plan(s: *const trt_scene, n: u32, bands: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

@@ -121,6 +121,13 @@ pub enum Lobe {
     Cone(Float),
 }
 
+/// The directions `World::probe` draws the first ray of a sample over (`enum trt_probe_domain`).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum ProbeDomain {
+    Sphere,
+    Hemisphere,
+}
+
 pub enum Geometry {
     Sphere { center: Vec3, radius: Float, material: MaterialHandle },
     Quad { corner: Vec3, u: Vec3, v: Vec3, material: MaterialHandle },
@@ -282,6 +289,40 @@ impl World {
                              bent.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((visibility, bent))
+    }
+
+    /// The radiance arriving at caller-supplied points as a function of direction (`trt_probe`): each `(point, axis)` as six floats, used
+    /// as given.  For every one of `samples_per_item` samples the device draws a first ray uniformly over the sphere
+    /// (`ProbeDomain::Sphere`) or over the hemisphere about the axis (`ProbeDomain::Hemisphere`) from RNG stream
+    /// `(seed, first_stream + i * samples_per_item + s, 1)`, traces its path on stream `(.., 0)` and adds colour * Y_k(direction) / K to
+    /// coefficient `k` of the item.  Returns `bands * bands * 3` floats per item: real spherical harmonics, coefficient `l (l + 1) + m`,
+    /// then channel.
+    pub fn probe(&mut self, items: &[[Float; 6]], samples_per_item: u32, bands: u32, domain: ProbeDomain, max_bounces: u32,
+                 background: Vec3, seed: u32, first_stream: u32) -> Result<Vec<Float>, Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        if !(1..=3).contains(&bands) {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "bands must be 1, 2 or 3".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_probe_params::default();
+        unsafe { sys::trt_probe_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.max_bounces = max_bounces;
+        params.path.background = background.raw();
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        params.bands = bands;
+        params.domain = match domain {
+            ProbeDomain::Sphere => sys::TRT_PROBE_SPHERE,
+            ProbeDomain::Hemisphere => sys::TRT_PROBE_HEMISPHERE,
+        };
+        let mut sh = vec![0.0 as Float; items.len() * (bands * bands) as usize * 3];
+        check(unsafe {
+            sys::trt_probe(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, sh.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok(sh)
     }
 
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.

@@ -47,7 +47,8 @@ extern "C" {
  *              trt_select_scratch_bytes; trt_radiance_params, trt_radiance_params_default, trt_radiance, trt_radiance_device,
  *              trt_radiance_launch_plan; trt_lobe, trt_gather_params, trt_gather_params_default, trt_gather, trt_gather_device,
  *              trt_gather_launch_plan; trt_ambient_params, trt_ambient_params_default, trt_ambient, trt_ambient_device,
- *              trt_ambient_launch_plan. */
+ *              trt_ambient_launch_plan; trt_probe_domain, trt_probe_params, trt_probe_params_default, trt_probe, trt_probe_device,
+ *              trt_probe_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -614,6 +615,63 @@ int trt_ambient_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const t
 /* How trt_ambient[_device] launches n items on this scene: trt_query_launch_plan's rule and fields over the ambient kernels' own table
  * (the same shapes; kernel_waves_per_simd is that table's bound). */
 int trt_ambient_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Probe queries: the radiance arriving at a point as a function of direction, in spherical harmonics ----
+ * trt_gather returns ONE colour per (point, axis): a lightmap texel.  A light probe, or a directional lightmap texel, stores the incoming
+ * radiance as a function of direction, so that a dynamic object or a normal-mapped surface can be lit from it afterwards.  A probe query
+ * draws K first rays uniformly over the sphere (or the hemisphere about the axis) on the device, traces each as trt_gather does, and folds
+ * the colours against the real spherical-harmonic (SH) basis at the ray's direction: 1, 4 or 9 coefficients per colour channel come back
+ * per item and nothing per sample crosses the bus.
+ *  - Item i is (origin = point, direction = axis), both used AS GIVEN.  The axis is read only by the hemisphere domain.
+ *  - First ray.  For sample s of 0..K, K = path.samples_per_ray, the stream index is j = path.first_stream + i * K + s (32 bits).  With
+ *    g = RNG (seed, pixel = j, sample = 1) and u = normalize(random_in_unit_sphere(g)) (Vec3::new_random_unit_vector, vec3extend.rs:32-34;
+ *    three draws, nothing else is taken from g):
+ *      TRT_PROBE_SPHERE:      dir = u
+ *      TRT_PROBE_HEMISPHERE:  dir = dot(u, axis) > 0 ? u : -u   (Vec3::new_random_on_hemisphere, vec3extend.rs:36-43; a zero or NaN dot flips)
+ *    and the ray is Ray::new(point, dir), which normalises AGAIN.  d below is that ray's stored direction, not u: the second normalisation
+ *    changes the bits of about a quarter of the directions.
+ *  - Path.  The sample's colour c is CpuSampler::single_point_sampling (cpu.rs:39-65) for that ray with RNG (seed, j, 0) and the budget
+ *    max_bounces, exactly as trt_gather traces its drawn ray.  stats / d_counters (samples and rays only; `rays` counts the reference's
+ *    world.hit calls) and kernel_ms: as in trt_gather.
+ *  - Basis.  Real SH in the graphics convention: no Condon-Shortley sign, coefficient index k = l (l + 1) + m.  With (x, y, z) = d, all f32,
+ *    one IEEE operation per operator, nothing fused, in exactly this parenthesisation:
+ *      c0 = 0.282094792f  c1 = 0.488602512f  c2 = 1.092548431f  c3 = 0.315391565f  c4 = 0.546274215f
+ *      b0 = c0            b1 = c1*y          b2 = c1*z          b3 = c1*x
+ *      b4 = c2*(x*y)      b5 = c2*(y*z)      b6 = c3*((3.0f*(z*z)) - 1.0f)           b7 = c2*(x*z)      b8 = c4*((x*x) - (y*y))
+ *  - Fold, per item, in sample order, inv_K = 1.0f / float(K): for k < C = bands * bands
+ *      t = b_k * inv_K;   sh[k].ch = sh[k].ch + c.ch * t     per channel
+ *    `sh` holds n x C x 3 f32: item-major, then coefficient, then channel.  The bytes of coefficient k do not depend on `bands`.
+ *  - A sample whose first ray has a NaN component (a NaN point; the draw with u3 == 0, where the reference normalises a zero vector) is
+ *    traced and counted as trt_gather counts it and ADDS NOTHING to the sums - neither 0 nor NaN: one such draw in 2^23 must not poison a
+ *    probe.
+ *  - Meaning.  The sums are the plain mean of c * Y_k(d).  4 pi sh[k] (SPHERE) or 2 pi sh[k] (HEMISPHERE: the function is 0 in the other
+ *    half-space) estimates the integral of L Y_k over the directions, and the irradiance about a unit normal n is
+ *    sum_k A_l(k) * (4 pi sh[k]) * Y_k(n) with A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4.
+ *  - Sample range, accumulate (the C x 3 sums per item are read back), the 1 / K scale fixed by K, split invariance by samples (split the
+ *    range, set accumulate) and by items (first_stream + a * K), order, coherence and concurrency: as in trt_radiance.  "Nothing to
+ *    trace" - an empty sample range or max_bounces == 0 - zeroes [0, 12 C n) unless accumulate, which touches nothing.  No byte outside
+ *    [0, 12 C n) of `sh` is ever written.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_radiance's own errors, applied to `path` with `sh` as the
+ *    required buffer; a `domain` that is not 1 or 2; `bands` outside 1..3; a non-zero reserved word.  Then TRT_ERR_NO_DEVICE, then
+ *    TRT_ERR_OOM for the host form's buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * trt_probe: HOST buffers, synchronous, as trt_gather.  trt_probe_device: buffers in HBM, asynchronous on `stream`; allocates nothing. */
+enum trt_probe_domain { TRT_PROBE_SPHERE = 1, TRT_PROBE_HEMISPHERE = 2 };
+typedef struct {
+    trt_radiance_params path;     /* every field as in trt_radiance, same rules, same errors; K = path.samples_per_ray */
+    uint32_t domain;              /* enum trt_probe_domain */
+    uint32_t bands;               /* 1, 2 or 3: SH bands l = 0 .. bands-1, C = bands*bands coefficients (1, 4, 9) */
+    uint32_t reserved[6];         /* zero */
+} trt_probe_params;               /* 96 B: offsets 0, 64, 68, 72 */
+void trt_probe_params_default(trt_probe_params *out);   /* path = trt_radiance_params_default, SPHERE, bands 3; NULL tolerated */
+int trt_probe(trt_scene *s, const trt_ray *items, uint32_t n, const trt_probe_params *p, float *sh, trt_stats *stats);
+int trt_probe_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_probe_params *p, float *d_sh, uint64_t *d_counters,
+                     void *stream);
+/* How trt_probe[_device] launches n items on this scene: trt_gather_launch_plan's rule and fields over the probe kernels' own table for
+ * that `bands` (the same shapes; kernel_waves_per_simd is that table's bound, lower than the gather's: a lane carries 3 C sums more).
+ * `bands` outside 1..3 is TRT_ERR_INVALID_ARG.  The rule gives a wave 256 items whatever K is, as it does for trt_radiance and
+ * trt_gather: a few probes with many samples fill few lanes.  The exact workaround: list such a probe m times with K / m samples each and
+ * distinct first_streams, then average the m rows - every row is a plain mean over its own samples. */
+int trt_probe_launch_plan(const trt_scene *s, uint32_t n, uint32_t bands, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

@@ -131,6 +131,15 @@ public:
         if (bent) bent->resize(items.size() * 3);
         check(trt_ambient(get_bvh(), items.data(), (uint32_t)items.size(), &p, visibility.data(), bent ? bent->data() : nullptr, stats));
     }
+    // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
+    // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
+    // gather() does and adds colour * Y_k(direction) / K to coefficient k of the item.  `sh` becomes p.bands^2 x 3 floats per item - real
+    // spherical harmonics, coefficient l (l + 1) + m, then channel - and continues the sums it holds when p.path.accumulate is set.
+    // Start `p` from trt_probe_params_default.
+    void probe(const std::vector<trt_ray>& items, const trt_probe_params& p, std::vector<float>& sh, trt_stats* stats = nullptr) {
+        sh.resize(items.size() * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);   // (bands out of range: trt_probe says so)
+        check(trt_probe(get_bvh(), items.data(), (uint32_t)items.size(), &p, sh.data(), stats));
+    }
     int num_geometries() const { return trt_world_num_geometries(w_); }
     const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).

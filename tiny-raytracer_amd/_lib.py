@@ -137,6 +137,15 @@ class AmbientParams(C.Structure):
     _fields_ = [("gather", GatherParams), ("max_distance", C.c_float), ("reserved", C.c_uint32 * 7)]
 
 
+PROBE_SPHERE, PROBE_HEMISPHERE = 1, 2                                        # tinyrt.h enum trt_probe_domain
+
+
+class ProbeParams(C.Structure):
+    """tinyrt.h trt_probe_params: trt_radiance_params, the domain the first ray of a sample is drawn over and the number of spherical-
+    harmonic bands the colours are folded into (96 bytes)."""
+    _fields_ = [("path", RadianceParams), ("domain", C.c_uint32), ("bands", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -240,6 +249,10 @@ SIGNATURES = {
     "trt_ambient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(AmbientParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "trt_ambient_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
+    "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
+    "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_probe_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -347,6 +347,53 @@ class Scene:
         check(lib.trt_ambient_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- probe queries (tinyrt.h trt_probe): spherical-harmonic radiance from first rays the device draws over the sphere ----
+    DOMAINS = {"sphere": _lib.PROBE_SPHERE, "hemisphere": _lib.PROBE_HEMISPHERE}
+
+    @classmethod
+    def _probe_params(cls, samples_per_item, bands=3, domain="sphere", **path):
+        if domain not in cls.DOMAINS:
+            raise ValueError("domain must be 'sphere' or 'hemisphere'")
+        p = _lib.ProbeParams()
+        lib.trt_probe_params_default(C.byref(p))
+        p.path = cls._radiance_params(samples_per_item, **path)
+        p.domain, p.bands = cls.DOMAINS[domain], int(bands)
+        return p
+
+    def probe(self, items, samples_per_item, bands=3, domain="sphere", max_bounces=50, background=(0.0, 0.0, 0.0), seed=1, first_stream=0,
+              sample_begin=0, sample_end=None, accumulate=False, sh=None):
+        """trt_probe: the radiance arriving at items float32 [n, 6] (point, axis; used as given) as a function of direction.  For each of
+        samples_per_item = K samples the device draws a first ray uniformly over the sphere (domain "sphere") or over the hemisphere about
+        the axis ("hemisphere") from RNG stream (seed, first_stream + i * K + s, 1), traces its path on stream (.., 0) as gather() does and
+        adds colour * Y_k(direction) / K to coefficient k of the item, for the C = bands ** 2 real spherical-harmonic basis functions of
+        tiny-raytracer_amd.sh.  Sample range and accumulate as in radiance().  `sh`: float32 [n, C, 3] to write or, with accumulate, to
+        continue (changed in place); None allocates one.  Returns (sh[n, C, 3], stats with samples and rays)."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        p = self._probe_params(samples_per_item, bands, domain, max_bounces=max_bounces, background=background, seed=seed, first_stream=first_stream,
+                               sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
+        coeffs = int(bands) ** 2
+        if sh is None:
+            sh = np.zeros((n, coeffs, 3), np.float32)
+        assert sh.dtype == np.float32 and sh.flags.c_contiguous and sh.shape == (n, coeffs, 3)
+        st = Stats()
+        check(lib.trt_probe(self._h, r.ctypes.data if n else None, n, C.byref(p), sh.ctypes.data if n else None, C.byref(st)))
+        return sh, st.as_dict()
+
+    def probe_device(self, d_items_ptr, n, d_sh_ptr, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue probe() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n x bands ** 2 x 12 bytes of
+        sums) on the current device; asynchronous on the stream, allocates nothing.  `params`: probe()'s keywords, samples_per_item
+        included."""
+        p = self._probe_params(**params)
+        check(lib.trt_probe_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_sh_ptr), C.c_void_p(d_counters_ptr),
+                                   C.c_void_p(stream_ptr)))
+
+    def probe_plan(self, n, bands=3, compute_units=0):
+        """trt_probe_launch_plan: how probe() launches n items with this many bands on this scene, as a dict with gather_plan()'s fields."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_probe_launch_plan(self._h, int(n), int(bands), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""

@@ -34,6 +34,21 @@ TRT_DEV Ray gather_ray(const float* __restrict__ items, uint32_t idx, uint32_t l
     return ray_new(item.o, dir);
 }
 
+// The first ray of a probe sample (probe.hip): a direction uniform over the sphere, Vec3::new_random_unit_vector (vec3extend.rs:32-34), or
+// over the hemisphere about the item's axis, Vec3::new_random_on_hemisphere (vec3extend.rs:36-43: the unit vector itself where its dot
+// with the axis is > 0, else its negation - a zero or NaN dot flips).  Three draws are taken from g.  Ray::new normalises again
+// (ray.rs:12-14), which changes the bits of about a quarter of the directions.  The axis is read by the hemisphere domain only.
+TRT_DEV Ray probe_ray(const float* __restrict__ items, uint32_t idx, bool hemisphere, Rng& g) {
+    const V3 u = normalized(random_in_unit_sphere_unit(g));
+    const float* it = items + 6ull * idx;                                   // after the draw, as in gather_ray
+    V3 dir = u;
+    if (hemisphere) {
+        const V3 axis = v3(it[3], it[4], it[5]);
+        if (!(dot(u, axis) > 0.0f)) dir = -u;
+    }
+    return ray_new(v3(it[0], it[1], it[2]), dir);
+}
+
 // The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.
 struct Lobe {
     uint32_t lobe;                   // 0: a radiance query
@@ -44,5 +59,7 @@ struct Lobe {
 // What the forms that take a trt_gather_params check before any device work: trt_radiance's rules on p->path, then the lobe; and the
 // kernel arguments of the parameters (radiance.hip).  `sums`: the required output buffer.
 int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* sums, RenderArgs& ra, Lobe& lobe);
+// trt_radiance's own rules on a trt_radiance_params, which gather_check applies to p->path and the probe queries (probe.hip) to theirs.
+int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, const float* sums, RenderArgs& ra);
 
 }  // namespace trt

@@ -261,30 +261,6 @@ hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_r
     return le;
 }
 
-// What both forms check before any device work, and the kernel arguments of the parameters.
-int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, const float* radiance, RenderArgs& ra) {
-    if (!s || !p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    if (n > 0u && (!rays || !radiance)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
-    const uint32_t K = p->samples_per_ray;
-    if (K == 0u) return query_fail(TRT_ERR_INVALID_ARG, "samples_per_ray must be positive");
-    const uint32_t s1 = p->sample_end == 0u ? K : p->sample_end;
-    if (p->sample_begin > s1 || s1 > K) return query_fail(TRT_ERR_INVALID_ARG, "sample range must satisfy begin <= end <= samples_per_ray");
-    for (uint32_t r : p->reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
-    // the last stream index, first_stream + n * K - 1, must fit 32 bits (n * K < 2^64: both are below 2^32)
-    if ((unsigned long long)p->first_stream + (unsigned long long)n * K > 0x100000000ull)
-        return query_fail(TRT_ERR_INVALID_ARG, "first_stream + n * samples_per_ray exceeds 2^32 RNG streams");
-    ra = RenderArgs{};
-    ra.background[0] = p->background.x; ra.background[1] = p->background.y; ra.background[2] = p->background.z;
-    ra.inv_spp = 1.0f / (float)K;
-    ra.max_bounces = p->max_bounces;
-    ra.seed_key = rng_seed_key(p->seed);
-    ra.sample_begin = p->sample_begin;
-    ra.sample_end = s1;
-    ra.accumulate = p->accumulate ? 1u : 0u;
-    return TRT_OK;
-}
-
 // The device form of both queries, after the checks: buffers in HBM, asynchronous on `stream`.
 int radiance_on_device(trt_scene* s, const RenderArgs& ra, const trt_radiance_params& p, Lobe lobe, const trt_ray* d_rays, uint32_t n, float* d_radiance,
                        float* d_moment2, uint64_t* d_counters, void* stream, const char* what) {
@@ -336,6 +312,31 @@ int radiance_on_host(trt_scene* s, const RenderArgs& ra, const trt_radiance_para
 }
 
 }  // namespace
+
+// What both forms check before any device work, and the kernel arguments of the parameters (declared in gather_draw.h: the probe queries
+// apply the same rules to their path).
+int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, const float* radiance, RenderArgs& ra) {
+    if (!s || !p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (n > 0u && (!rays || !radiance)) return query_fail(TRT_ERR_INVALID_ARG, "null buffer");
+    const uint32_t K = p->samples_per_ray;
+    if (K == 0u) return query_fail(TRT_ERR_INVALID_ARG, "samples_per_ray must be positive");
+    const uint32_t s1 = p->sample_end == 0u ? K : p->sample_end;
+    if (p->sample_begin > s1 || s1 > K) return query_fail(TRT_ERR_INVALID_ARG, "sample range must satisfy begin <= end <= samples_per_ray");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    // the last stream index, first_stream + n * K - 1, must fit 32 bits (n * K < 2^64: both are below 2^32)
+    if ((unsigned long long)p->first_stream + (unsigned long long)n * K > 0x100000000ull)
+        return query_fail(TRT_ERR_INVALID_ARG, "first_stream + n * samples_per_ray exceeds 2^32 RNG streams");
+    ra = RenderArgs{};
+    ra.background[0] = p->background.x; ra.background[1] = p->background.y; ra.background[2] = p->background.z;
+    ra.inv_spp = 1.0f / (float)K;
+    ra.max_bounces = p->max_bounces;
+    ra.seed_key = rng_seed_key(p->seed);
+    ra.sample_begin = p->sample_begin;
+    ra.sample_end = s1;
+    ra.accumulate = p->accumulate ? 1u : 0u;
+    return TRT_OK;
+}
 
 // What the gather forms check before any device work: trt_radiance's rules on p->path, then the lobe (gather_draw.h: ambient.hip
 // applies the same rules to its own trt_gather_params).
