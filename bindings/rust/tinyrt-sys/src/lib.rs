@@ -283,6 +283,21 @@ pub struct trt_probe_params {
     pub reserved: [u32; 6],
 }
 
+/// `enum trt_passes_source`: where the first ray of a passes sample comes from; 1 and 2 are `enum trt_lobe`.
+pub const TRT_PASSES_RAYS: u32 = 0;
+pub const TRT_PASSES_COSINE: u32 = 1;
+pub const TRT_PASSES_CONE: u32 = 2;
+
+/// `trt_gather_params`, whose `lobe` is read as `enum trt_passes_source`, and the number of depth bins of `trt_passes` (128 bytes);
+/// `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_passes_params {
+    pub gather: trt_gather_params,
+    pub depth_bins: u32,
+    pub reserved: [u32; 7],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -453,6 +468,12 @@ extern "C" {
     pub fn trt_probe_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_probe_params, d_sh: *mut f32,
                             d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_probe_launch_plan(s: *const trt_scene, n: u32, bands: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_passes_params_default(out: *mut trt_passes_params);
+    pub fn trt_passes(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_passes_params, passes: *mut f32, spent: *mut f32,
+                      stats: *mut trt_stats) -> c_int;
+    pub fn trt_passes_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_passes_params, d_passes: *mut f32,
+                             d_spent: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_passes_launch_plan(s: *const trt_scene, n: u32, depth_bins: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_sample_batch(s: *mut trt_scene, input: *const trt_sample_point, n: u32, out: *mut trt_sampled_color,
                             max_bounces: u32, background: trt_vec3, seed: u32, stats: *mut trt_stats) -> c_int;
     pub fn trt_intersect(s: *mut trt_scene, rays: *const trt_ray, t_max: *const f32, n: u32, hits: *mut trt_hit) -> c_int;

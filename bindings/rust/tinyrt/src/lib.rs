@@ -128,6 +128,14 @@ pub enum ProbeDomain {
     Hemisphere,
 }
 
+/// Where `World::passes` takes the first ray of a sample from (`enum trt_passes_source`): the items are rays, or surfels the device draws
+/// `World::gather`'s first rays about.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum PassesSource {
+    Rays,
+    Lobe(Lobe),
+}
+
 pub enum Geometry {
     Sphere { center: Vec3, radius: Float, material: MaterialHandle },
     Quad { corner: Vec3, u: Vec3, v: Vec3, material: MaterialHandle },
@@ -323,6 +331,45 @@ impl World {
             sys::trt_probe(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, sh.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok(sh)
+    }
+
+    /// The light `radiance` or `gather` folds into one colour, split by how each path ended and after how many scatters (`trt_passes`).
+    /// With `PassesSource::Rays` each item is a ray used as given; with `PassesSource::Lobe` a surfel `(point, axis)` about which the
+    /// device draws `gather`'s first rays, bit for bit.  With `B = depth_bins` (1 to 4) and `b = min(depth, B - 1)` a sample that ended
+    /// at a light adds colour / K to slot `b`, one that missed everything to slot `B + b`, and one that ran out of bounces adds 1 / K
+    /// to the item's spent share.  Returns `(passes, spent)`: `2 * depth_bins * 3` floats per item and one float per item.
+    pub fn passes(&mut self, items: &[[Float; 6]], samples_per_item: u32, depth_bins: u32, source: PassesSource, max_bounces: u32,
+                  background: Vec3, seed: u32, first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        if !(1..=4).contains(&depth_bins) {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "depth_bins must be 1, 2, 3 or 4".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_passes_params::default();
+        unsafe { sys::trt_passes_params_default(&mut params) };
+        params.gather.path.samples_per_ray = samples_per_item;
+        params.gather.path.max_bounces = max_bounces;
+        params.gather.path.background = background.raw();
+        params.gather.path.seed = seed;
+        params.gather.path.first_stream = first_stream;
+        params.depth_bins = depth_bins;
+        match source {
+            PassesSource::Rays => params.gather.lobe = sys::TRT_PASSES_RAYS,
+            PassesSource::Lobe(Lobe::Cosine) => params.gather.lobe = sys::TRT_PASSES_COSINE,
+            PassesSource::Lobe(Lobe::Cone(spread)) => {
+                params.gather.lobe = sys::TRT_PASSES_CONE;
+                params.gather.spread = spread;
+            }
+        }
+        let mut passes = vec![0.0 as Float; items.len() * 2 * depth_bins as usize * 3];
+        let mut spent = vec![0.0 as Float; items.len()];
+        check(unsafe {
+            sys::trt_passes(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, passes.as_mut_ptr(), spent.as_mut_ptr(),
+                            ptr::null_mut())
+        })?;
+        Ok((passes, spent))
     }
 
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.

@@ -48,7 +48,8 @@ extern "C" {
  *              trt_radiance_launch_plan; trt_lobe, trt_gather_params, trt_gather_params_default, trt_gather, trt_gather_device,
  *              trt_gather_launch_plan; trt_ambient_params, trt_ambient_params_default, trt_ambient, trt_ambient_device,
  *              trt_ambient_launch_plan; trt_probe_domain, trt_probe_params, trt_probe_params_default, trt_probe, trt_probe_device,
- *              trt_probe_launch_plan. */
+ *              trt_probe_launch_plan; trt_passes_source, trt_passes_params, trt_passes_params_default, trt_passes, trt_passes_device,
+ *              trt_passes_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -672,6 +673,68 @@ int trt_probe_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt
  * trt_gather: a few probes with many samples fill few lanes.  The exact workaround: list such a probe m times with K / m samples each and
  * distinct first_streams, then average the m rows - every row is a plain mean over its own samples. */
 int trt_probe_launch_plan(const trt_scene *s, uint32_t n, uint32_t bands, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Light-path passes: the gathered radiance split by the depth and the end of each path ----
+ * trt_radiance and trt_gather say how much light arrives; a passes query says by what kind of path.  A baker that lights directly at run
+ * time bakes only the indirect part; a frame filters emitters seen directly apart from smooth indirect light; a probe placer asks what
+ * share of a probe's paths die by their budget, the sign of a probe inside geometry.  The split is exact, not a difference of two noisy
+ * runs: in CpuSampler::single_point_sampling (cpu.rs:39-65) a sample's colour comes from exactly one terminal event - Light::scatter
+ * returns None, or a miss adds the background and breaks - and every other hit adds +0, so each sample belongs to exactly one class and
+ * the same paths, on the same RNG draws, are folded per class.
+ *  - First ray.  With gather.lobe == TRT_PASSES_RAYS item i is a ray used AS GIVEN, as in trt_radiance: not normalised, nothing is drawn,
+ *    and gather.spread is ignored (not read, not validated).  With TRT_PASSES_COSINE or TRT_PASSES_CONE (the values of enum trt_lobe) item
+ *    i is a surfel (point, axis) and the first ray of sample s is trt_gather's for the same `gather`, bit for bit: three draws from RNG
+ *    (seed, pixel = j, sample = 1), j = gather.path.first_stream + i * K + s, K = gather.path.samples_per_ray, the cosine or the cone rule,
+ *    Ray::new.
+ *  - Path.  The sample's colour c is CpuSampler::single_point_sampling (cpu.rs:39-65) for that ray with RNG (seed, j, 0) and the budget
+ *    max_bounces - exactly what trt_radiance (RAYS) or trt_gather (COSINE, CONE) folds for stream j.
+ *  - Class of a sample.  d is the number of scatters before the path ended (the times cpu.rs:52-54 ran), and the end is one of
+ *      LIGHT: the path hit a TRT_LIGHT material (scatter returned None, cpu.rs:55-57);
+ *      SKY:   the ray missed (cpu.rs:58-61);
+ *      SPENT: the budget ran out (d == max_bounces), so c is 0.
+ *    With B = depth_bins and b = min(d, B - 1) the sample's slot is b for LIGHT and B + b for SKY.  SPENT has no slot.
+ *  - Fold, per item, in sample order, all f32, one IEEE operation per operator, nothing fused; inv_K = 1.0f / float(K):
+ *      passes[i][slot].ch = passes[i][slot].ch + c.ch * inv_K          (LIGHT, SKY)
+ *      spent[i] = spent[i] + inv_K                                     (SPENT)
+ *    A sample touches its own slot only: the other slots of the item are NOT touched by it, which is not the same as adding 0 (a slot
+ *    that holds -0 or NaN keeps it).  `passes` holds n x 2B x 3 f32: item-major, then slot (LIGHT 0..B-1, SKY 0..B-1), then channel.
+ *    `spent` holds n f32 and may be NULL (not wanted; `passes` is the same either way).
+ *  - A first ray with a NaN component hits nothing (the rule of the queries): the sample is SKY at d = 0, slot B receives `background`.
+ *  - Identities.  (1) On a scene whose light colours and albedos are non-negative, with background == 0 and B == 1, slot 0 is
+ *    trt_gather's `radiance` (RAYS: trt_radiance's) byte for byte: there every sample adds c.ch * inv_K to the one sum, here the LIGHT
+ *    samples do, and every other sample's c is +0, which changes no sum that started at +0 (x + (+0) == x for every x but -0, and no sum
+ *    is -0).  (2) The LIGHT and SKY slots at depth d < B - 1 do not depend on B: LIGHT slot d of a call with B bins equals LIGHT slot d
+ *    of a call with B' bins, and SKY slot B + d equals SKY slot B' + d, for d < min(B, B') - 1.
+ *  - Meaning.  For a surfel, LIGHT and SKY at d = 0 are its direct light (the first ray reached an emitter or the sky); everything at
+ *    d >= 1 is indirect.  For a camera ray, d = 0 is what is seen directly.  The sum of all slots is trt_gather's radiance up to the
+ *    rounding of a different summation order; `spent` is the share of the K samples that ended by their budget.
+ *  - Sample range, accumulate (the 2B x 3 sums per item and `spent` are read back), the 1 / K scale fixed by K, split invariance by
+ *    samples (split the range, set accumulate) and by items (first_stream + a * K), order, coherence and concurrency: as in trt_radiance.
+ *    "Nothing to trace" - an empty sample range or max_bounces == 0 - zeroes [0, 24 B n) of `passes` and [0, 4 n) of `spent` unless
+ *    accumulate, which touches nothing.  No byte outside those ranges is ever written.
+ *  - stats / d_counters receive samples ([0]) and rays ([1]) only; `rays` counts the reference's world.hit calls for these samples,
+ *    as in trt_radiance.  kernel_ms as in trt_radiance.  `d_counters`: 16 uint64 as in trt_render_device, added to, or NULL.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_radiance's own errors, applied to gather.path with `passes`
+ *    as the required buffer; gather.lobe not 0, 1 or 2; with TRT_PASSES_CONE a `spread` that is NaN, infinite or negative; depth_bins
+ *    outside 1..4; a non-zero reserved word of `gather` or of this struct.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's
+ *    buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * trt_passes: HOST buffers, synchronous, as trt_gather.  trt_passes_device: buffers in HBM, asynchronous on `stream`; allocates nothing.
+ * A frame in passes: for sample s take trt_primary_rays_device for s, then trt_passes_device with K = spp, the sample range [s, s + 1)
+ * and accumulate (from s = 1 on).  Such a frame uses the query stream numbering (seed, first_stream + pixel * K + s, 0), not trt_render's. */
+enum trt_passes_source { TRT_PASSES_RAYS = 0, TRT_PASSES_COSINE = 1, TRT_PASSES_CONE = 2 };   /* 1, 2 = enum trt_lobe */
+typedef struct {
+    trt_gather_params gather;     /* path, lobe (read as enum trt_passes_source) and spread: trt_gather's rules and errors */
+    uint32_t depth_bins;          /* B = 1..4: depths 0 .. B-2 have a slot each, depths >= B-1 share the last */
+    uint32_t reserved[7];         /* zero */
+} trt_passes_params;              /* 128 B: offsets 0, 96, 100 */
+void trt_passes_params_default(trt_passes_params *out);   /* gather = trt_gather_params_default (source COSINE), depth_bins 3; NULL tolerated */
+int trt_passes(trt_scene *s, const trt_ray *items, uint32_t n, const trt_passes_params *p, float *passes, float *spent, trt_stats *stats);
+int trt_passes_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_passes_params *p, float *d_passes, float *d_spent,
+                      uint64_t *d_counters, void *stream);
+/* How trt_passes[_device] launches n items on this scene: trt_gather_launch_plan's rule and fields over the passes kernels' own table for
+ * that `depth_bins` (the same shapes; B = 1 and 2 run the kernels that carry 2 bins, B = 3 and 4 those that carry 4;
+ * kernel_waves_per_simd is that table's bound: a lane carries 6 sums per bin).  `depth_bins` outside 1..4 is TRT_ERR_INVALID_ARG. */
+int trt_passes_launch_plan(const trt_scene *s, uint32_t n, uint32_t depth_bins, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

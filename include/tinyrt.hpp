@@ -140,6 +140,17 @@ public:
         sh.resize(items.size() * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);   // (bands out of range: trt_probe says so)
         check(trt_probe(get_bvh(), items.data(), (uint32_t)items.size(), &p, sh.data(), stats));
     }
+    // The light radiance() or gather() folds into one colour, split by how each path ended and after how many scatters (trt_passes):
+    // p.gather.lobe is the source of the first ray (TRT_PASSES_RAYS: the items are rays; TRT_PASSES_COSINE, TRT_PASSES_CONE: surfels,
+    // gather()'s draws).  `sums` becomes 2 x p.depth_bins x 3 floats per item - the paths that ended at a light by depth bin, then those
+    // that ended in the background, then channel - and `spent`, if wanted, the share of each item's samples that ended by their bounce
+    // budget; both continue the sums they hold when p.gather.path.accumulate is set.  Start `p` from trt_passes_params_default.
+    void passes(const std::vector<trt_ray>& items, const trt_passes_params& p, std::vector<float>& sums, std::vector<float>* spent = nullptr,
+                trt_stats* stats = nullptr) {
+        sums.resize(items.size() * (p.depth_bins <= 4u ? 2u * (size_t)p.depth_bins : 0u) * 3);   // (bins out of range: trt_passes says so)
+        if (spent) spent->resize(items.size());
+        check(trt_passes(get_bvh(), items.data(), (uint32_t)items.size(), &p, sums.data(), spent ? spent->data() : nullptr, stats));
+    }
     int num_geometries() const { return trt_world_num_geometries(w_); }
     const trt_world* handle() const { return w_; }
     // Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders (trt_scene_trim).

@@ -146,6 +146,15 @@ class ProbeParams(C.Structure):
     _fields_ = [("path", RadianceParams), ("domain", C.c_uint32), ("bands", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
+PASSES_RAYS, PASSES_COSINE, PASSES_CONE = 0, 1, 2                           # tinyrt.h enum trt_passes_source (1, 2 = enum trt_lobe)
+
+
+class PassesParams(C.Structure):
+    """tinyrt.h trt_passes_params: trt_gather_params, whose lobe is read as the source of the first ray, and the number of depth bins
+    the samples are split into (128 bytes)."""
+    _fields_ = [("gather", GatherParams), ("depth_bins", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -253,6 +262,11 @@ SIGNATURES = {
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_probe_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_passes_params_default": (None, [C.POINTER(PassesParams)]),
+    "trt_passes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_passes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "trt_passes_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, Vec3, C.c_uint32,
                                    C.POINTER(Stats)]),
     "trt_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

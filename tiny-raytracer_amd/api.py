@@ -394,6 +394,62 @@ class Scene:
         check(lib.trt_probe_launch_plan(self._h, int(n), int(bands), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- passes queries (tinyrt.h trt_passes): the gathered radiance split by the depth and the end of each path ----
+    SOURCES = {"rays": _lib.PASSES_RAYS, "cosine": _lib.PASSES_COSINE, "cone": _lib.PASSES_CONE}
+
+    @classmethod
+    def _passes_params(cls, samples_per_item, depth_bins=3, source="cosine", spread=0.0, **path):
+        if source not in cls.SOURCES:
+            raise ValueError("source must be 'rays', 'cosine' or 'cone'")
+        p = _lib.PassesParams()
+        lib.trt_passes_params_default(C.byref(p))
+        p.gather.path = cls._radiance_params(samples_per_item, **path)
+        p.gather.lobe, p.gather.spread, p.depth_bins = cls.SOURCES[source], float(spread), int(depth_bins)
+        return p
+
+    def passes(self, items, samples_per_item, depth_bins=3, source="cosine", spread=0.0, max_bounces=50, background=(0.0, 0.0, 0.0), seed=1,
+               first_stream=0, sample_begin=0, sample_end=None, accumulate=False, passes=None, spent=None):
+        """trt_passes: the light radiance() (source "rays": items float32 [n, 6] are rays, used as given) or gather() (source "cosine" or
+        "cone": items are surfels, the device draws gather()'s first rays bit for bit) folds into one colour, split by how each path ended
+        and after how many scatters.  With B = depth_bins (1 .. 4) and b = min(depth, B - 1) a sample that ended at a light adds
+        colour / K to slot b, one that missed everything to slot B + b, and one that ran out of bounces adds 1 / K to spent[i]; a sample
+        touches no other slot (tiny-raytracer_amd.passes names the slots and sums them).  Sample range and accumulate as in radiance().
+        `passes`: float32 [n, 2 B, 3] to write or, with accumulate, to continue (changed in place); None allocates one.  `spent`:
+        float32 [n] likewise; None allocates one, False = not wanted.  Returns (passes[n, 2 B, 3], spent[n] or None, stats with samples
+        and rays)."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        p = self._passes_params(samples_per_item, depth_bins, source, spread, max_bounces=max_bounces, background=background, seed=seed,
+                                first_stream=first_stream, sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
+        slots = 2 * int(depth_bins)
+        if passes is None:
+            passes = np.zeros((n, slots, 3), np.float32)
+        if spent is None:
+            spent = np.zeros(n, np.float32)
+        elif spent is False:
+            spent = None
+        assert passes.dtype == np.float32 and passes.flags.c_contiguous and passes.shape == (n, slots, 3)
+        assert spent is None or (spent.dtype == np.float32 and spent.flags.c_contiguous and spent.shape == (n,))
+        st = Stats()
+        check(lib.trt_passes(self._h, r.ctypes.data if n else None, n, C.byref(p), passes.ctypes.data if n else None,
+                             spent.ctypes.data if spent is not None and n else None, C.byref(st)))
+        return passes, spent, st.as_dict()
+
+    def passes_device(self, d_items_ptr, n, d_passes_ptr, d_spent_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue passes() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n x 2 depth_bins x 12 bytes of
+        sums, n x 4 bytes of spent shares or 0) on the current device; asynchronous on the stream, allocates nothing.  `params`: passes()'s
+        keywords, samples_per_item included."""
+        p = self._passes_params(**params)
+        check(lib.trt_passes_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_passes_ptr), C.c_void_p(d_spent_ptr),
+                                    C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def passes_plan(self, n, depth_bins=3, compute_units=0):
+        """trt_passes_launch_plan: how passes() launches n items with this many depth bins on this scene, as a dict with gather_plan()'s
+        fields."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_passes_launch_plan(self._h, int(n), int(depth_bins), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""
