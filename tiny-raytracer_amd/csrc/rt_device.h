@@ -65,6 +65,36 @@ TRT_DEV float refined_rcp(float b) {
     const float e = __builtin_fmaf(-b, r0, 1.0f);
     return __builtin_fmaf(e, r0, r0);
 }
+// 1.0f / d for 2^-40 <= |d| <= 2^40: refined_rcp and div_by_refined_rcp(1.0f, d, r1) with the first product left out - q0 = 1.0f * r1 is
+// r1 exactly, so the residuals and corrections see the same operands and the bits are the same.  7 instructions and one transcendental
+// instead of hipcc's 11 per 1 / d.  The quotient lies in [2^-40, 2^40] too: finite, non-zero, normal.
+// tests/native/recip_exhaustive.hip compares it with `/` on every float of the range, both signs: no mismatch.
+TRT_DEV float recip_in_range(float d) {
+    const float r1 = refined_rcp(d);
+    const float e1 = __builtin_fmaf(-d, r1, 1.0f);
+    const float q1 = __builtin_fmaf(e1, r1, r1);
+    const float e2 = __builtin_fmaf(-d, q1, 1.0f);
+    return __builtin_fmaf(e2, r1, q1);
+}
+constexpr float kRecipLo = 9.094947017729282e-13f, kRecipHi = 1099511627776.0f;          // 2^-40, 2^40
+// The range test for three operands at once: abs min3, abs max3 and two compares.  The maximum is the NaN-propagating one (IEEE 754-2019
+// `maximum`, v_maximum3_f32 on gfx950; fmaxf would drop a NaN and let the other two components answer), so a NaN component fails `<=`.
+// (A host compiler without that builtin - the host-side checks of this header under tests/native - gets the same truth value from three compares.)
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_elementwise_maximum)
+#define TRT_HAVE_MAXIMUM 1
+#endif
+#endif
+TRT_DEV bool recip_in_range3(float x, float y, float z) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y), az = __builtin_fabsf(z);
+    const float mn = __builtin_fminf(__builtin_fminf(ax, ay), az);
+#ifdef TRT_HAVE_MAXIMUM
+    const float mx = __builtin_elementwise_maximum(__builtin_elementwise_maximum(ax, ay), az);
+    return (mn >= kRecipLo) & (mx <= kRecipHi);
+#else
+    return (mn >= kRecipLo) & (ax <= kRecipHi) & (ay <= kRecipHi) & (az <= kRecipHi);
+#endif
+}
 // The primary ray's image coordinates (pointgen.rs:41-43): u = nu / (width - 1), v = nv / (height - 1) with nu = x + random, nv = y + random.
 // The two denominators are the same for every ray of a launch.  For a width and a height of 2 or more they are floats in [1, 2^32] and
 // a numerator is +0 (column or row 0 with a draw of 0) or lies in [2^-23, 2^32]: inside div_by_refined_rcp's range, so each quotient is
@@ -429,9 +459,16 @@ TRT_DEV bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }
 // Primitive tests.  Range<f32>::contains is half open: t0 <= t < t1.
 // ------------------------------------------------------------------------------------------------
 // Sphere::hit (hittable/sphere.rs:29-54).  sp = (center.xyz, radius).
+// COLD: the call sits in code a wave seldom reaches (the reference walk, the lock-step walk's generic leaf phase on a scene of quads).
+// `a = d.d` depends on the ray alone, so the compiler computes it once in front of the walk's loop - five vector instructions for every
+// ray on behalf of a test that almost none runs.  The empty asm makes the direction opaque HERE, so a is formed where it is read.  The
+// per-lane tree walks test spheres all the time and keep the hoisted form (COLD = false): there it is a gain.
+template <bool COLD = false>
 TRT_DEV bool sphere_test(float4 sp, const Ray& ray, float t0, float t1, float& t_out) {
     V3 oc = ray.o - v3(sp.x, sp.y, sp.z);
-    float a = sqlen(ray.d);
+    V3 d = ray.d;
+    if constexpr (COLD) asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
+    float a = sqlen(d);
     float half_b = dot(oc, ray.d);
     float c = sqlen(oc) - sp.w * sp.w;
     float disc = half_b * half_b - a * c;

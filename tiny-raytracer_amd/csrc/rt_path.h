@@ -114,7 +114,26 @@ struct Trav {
     uint32_t n;             // node count of the tree this lane walks; i >= n means the walk is over
     bool fast;              // slab_fast is exact for this ray (see rt_device.h)
     bool ref;               // walk the reference tree instead of the culling tree
+    bool nf;                // 2^-60 <= |inv| <= 2^60 on every axis: the ray domain of the nearest-first leaf phase (nearest_first.h nf_in_domain)
 };
+
+// What a walk needs of the three 1/d, in the plain form: hipcc's full divisions and every test on their results.  Lanes whose direction
+// is outside recip_in_range's range take it (trav_begin); out of line only in tools/micro/event_costs.hip (TRT_COLD, rt_device.h).
+struct InvSetup {
+    V3 inv;
+    bool finite;            // every 1/d is finite
+    bool compact;           // every |1/d| <= 2^60 (box_loop_compact's domain)
+    bool nf;                // nf_in_domain
+};
+TRT_COLD InvSetup inv_setup_plain(V3 d) {
+    const float big = 1152921504606846976.0f;                        // 2^60
+    InvSetup s;
+    s.inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    s.finite = finite_f(s.inv.x) && finite_f(s.inv.y) && finite_f(s.inv.z);
+    s.compact = __builtin_fabsf(s.inv.x) <= big && __builtin_fabsf(s.inv.y) <= big && __builtin_fabsf(s.inv.z) <= big;
+    s.nf = nf_in_domain(s.inv.x, s.inv.y, s.inv.z);
+    return s;
+}
 
 // ref_tree: walk the reference tree whatever the ray (counting kernels: their counters then equal the oracle's).
 // A ray whose slab arithmetic can produce NaN (zero / non-finite direction component, non-finite origin) always
@@ -124,15 +143,34 @@ struct Trav {
 // conservative - |o| <= SceneLayout::compact_origin_limit per axis and |1/d| <= 2^60 (box_loop_compact).
 template <int MODE, bool COMPACT_DOMAIN = false>
 TRT_DEV Trav trav_begin(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_tree, bool compact_domain = false) {
+    // SHORT SETUP.  One guard, 2^-40 <= min |d_axis| and max |d_axis| <= 2^40 with a NaN failing it (recip_in_range3: four instructions),
+    // and for the lanes that pass it the three 1/d are recip_in_range's 7 instructions each instead of hipcc's 11; every bench scene's
+    // rays pass (unit directions whose smallest component is above 2^-40).  For such a lane, per axis:
+    //  * inv = fl(1 / d) bit for bit (recip_in_range), and 2^-40 <= |1 / d| <= 2^40 in real numbers; both ends are floats and rounding is
+    //    monotonic, so 2^-40 <= |inv| <= 2^40: finite, non-zero, normal;
+    //  * finite_f(inv) is true - the three tests on inv are implied;
+    //  * 2^-60 < 2^-40 <= |inv| <= 2^40 < 2^60: nf_in_domain(inv) is true (closest_hit reads it as tr.nf), and so is the compact walk's
+    //    |inv| <= 2^60.
+    // None of them is evaluated for these lanes.  Every other lane (a zero, subnormal, tiny, huge, infinite or NaN component) runs the plain
+    // divisions and all of those tests as before (inv_setup_plain), behind a branch the wave skips when no lane needs it.  The tests on the
+    // origin and on the scene are the same for both kinds of lane.  (An earlier note here said the short division gained nothing: it
+    // was measured with its own range test and the product by 1.0, when the kernel was not yet bound by instruction issue outside the walk.)
     Trav tr;
-    tr.inv = v3(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);     // (the short division of rt_device.h gains nothing here: measured)
-    tr.fast = sc.L.all_finite && finite_f(tr.inv.x) && finite_f(tr.inv.y) && finite_f(tr.inv.z) && finite_f(ray.o.x) &&
-              finite_f(ray.o.y) && finite_f(ray.o.z);
+    bool inv_finite = true, inv_compact = true;
+    tr.nf = true;
+    if (__builtin_expect(recip_in_range3(ray.d.x, ray.d.y, ray.d.z), 1)) {
+        tr.inv = v3(recip_in_range(ray.d.x), recip_in_range(ray.d.y), recip_in_range(ray.d.z));
+    } else {
+        const InvSetup s = inv_setup_plain(ray.d);
+        tr.inv = s.inv;
+        inv_finite = s.finite;
+        inv_compact = s.compact;
+        tr.nf = s.nf;
+    }
+    tr.fast = sc.L.all_finite && inv_finite && finite_f(ray.o.x) && finite_f(ray.o.y) && finite_f(ray.o.z);
     if (COMPACT_DOMAIN || compact_domain) {
-        const float big = 1152921504606846976.0f;                    // 2^60
         tr.fast = tr.fast && __builtin_fabsf(ray.o.x) <= sc.L.compact_origin_limit[0] && __builtin_fabsf(ray.o.y) <= sc.L.compact_origin_limit[1] &&
-                  __builtin_fabsf(ray.o.z) <= sc.L.compact_origin_limit[2] && __builtin_fabsf(tr.inv.x) <= big && __builtin_fabsf(tr.inv.y) <= big &&
-                  __builtin_fabsf(tr.inv.z) <= big;
+                  __builtin_fabsf(ray.o.z) <= sc.L.compact_origin_limit[2] && inv_compact;
     }
     tr.ref = ref_tree || !tr.fast;
     tr.n = tr.ref ? sc.L.n_nodes : sc.L.n_cull_nodes;
@@ -170,7 +208,8 @@ TRT_DEV uint32_t trav_box_step(const SceneAcc<MODE>& sc, const Ray& ray, Trav& t
 // s_cbranch_execz.  Forcing a scalar branch with readfirstlane, and compiling the kernel's tracing loop once per value of the flag, were
 // both measured: +0.1 % and +1.8 % against this form's +1.8 to +1.9 % - 47 and 21 spilled SGPRs against 26, the second with 69 VGPRs:
 // profiles/aq_axis_quads_ab.txt.)
-template <int MODE, bool STATS>
+// COLD: the call is seldom reached, see sphere_test.
+template <int MODE, bool STATS, bool COLD = false>
 TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint32_t leaf, Counters<STATS>& ctr, uint32_t axis_quads = 0u) {
     const uint32_t idx = leaf & PRIM_INDEX_MASK;
     if (axis_quads != 0u && (leaf & PRIM_QUAD_BIT)) {
@@ -217,7 +256,7 @@ TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint3
     } else {                                                           // Sphere::hit, sphere.rs:29-54
         if constexpr (STATS) ctr.sphere++;
         float t;
-        if (sphere_test(sc.sphere(idx), ray, kTMin, tr.t_best, t)) {
+        if (sphere_test<COLD>(sc.sphere(idx), ray, kTMin, tr.t_best, t)) {
             tr.t_best = t;
             tr.prim_best = leaf;
         }
@@ -255,7 +294,7 @@ TRT_DEV void closest_hit_ref(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr,
         }
         if (leaf == PRIM_NONE) break;
         if constexpr (STATS) { if (first_active_lane()) ctr.w_leaf++; }
-        trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, axis_quads);
+        trav_leaf<MODE, STATS, !STATS>(sc, ray, tr, leaf, ctr, axis_quads);     // (cold unless a counting kernel walks the reference tree by request)
         if constexpr (ANY) { if (tr.prim_best != PRIM_NONE) { tr.i = tr.n; break; } }
     }
 }
@@ -670,7 +709,9 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
         if constexpr (!STATS && !ANY) {
             if (nearest) { leaf_phase_nearest<MODE>(sc, ray, stk, top, tr, margin); return; }
         }
-        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
+        // (the sphere test's d.d stays in here: on a scene of quads nothing reads it, and a lock-step scene with spheres runs one or two
+        // sphere tests per ray, so forming it per test costs what forming it per ray did)
+        leaf_phase<MODE, STATS>(stk, top, tr, ctr, [&](uint32_t leaf) { trav_leaf<MODE, STATS, !STATS>(sc, ray, tr, leaf, ctr, reuse.axis_quads); });
     };
     if constexpr (kAsmBoxLoop && !STATS) {
         float2* const lim = stk + 64u * (slots - 2u);
@@ -1040,7 +1081,8 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
     if constexpr (!kAxisQuadsKernel<MODE, STATS, WALK>) { flat_reuse.axis_quads = 0u; flat_reuse.nearest_first = 0u; }      // (axis_quads_to_lds: no other kernel rewrites its records)
     if constexpr (kAxisQuadsKernel<MODE, STATS, WALK> && !ANY) {
         // the nearest-first leaf phase's margin holds for 2^-60 <= |1/d| <= 2^60 (nearest_first.h); any other ray walks the reference tree
-        if (flat_reuse.nearest_first != 0u && !nf_in_domain(tr.inv.x, tr.inv.y, tr.inv.z)) { tr.ref = true; tr.n = sc.L.n_nodes; }
+        // (tr.nf: nf_in_domain of the three 1/d, evaluated by trav_begin only for the lanes its range guard does not already answer for)
+        if (flat_reuse.nearest_first != 0u && !tr.nf) tr.ref = true;
     }
     if (__builtin_expect(!tr.ref, 1)) {
         if constexpr (WALK == WALK_COMPACT) {
@@ -1060,6 +1102,7 @@ TRT_DEV uint32_t closest_hit(const SceneAcc<MODE>& sc, const Ray& ray, bool ref_
             else walk_fast<MODE, STATS, 1, ANY>(sc, ray, tr, ctr);
         }
     } else {
+        tr.n = sc.L.n_nodes;                       // what trav_begin chose for a lane with tr.ref; said here, no walk above carries the per-lane choice
         closest_hit_ref<MODE, STATS, ANY>(sc, ray, tr, ctr, flat_reuse.axis_quads);
     }
     t_hit = tr.t_best;
