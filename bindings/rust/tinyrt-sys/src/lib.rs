@@ -259,6 +259,32 @@ pub struct trt_gather_params {
     pub reserved: [u32; 6],
 }
 
+/// One light of the table `trt_direct` samples (80 bytes): made by `trt_scene_emitters`, `trt_emitter_init_quad` or
+/// `trt_emitter_init_sphere`; `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_emitter {
+    pub kind: u32,
+    pub geometry: u32,
+    pub a: trt_vec3,
+    pub b: trt_vec3,
+    pub c: trt_vec3,
+    pub normal: trt_vec3,
+    pub color: trt_vec3,
+    pub area: f32,
+    pub reserved: [u32; 2],
+}
+
+/// `trt_radiance_params` (its `max_bounces` and `background` are not read) and the share of the distance to the emitter point the
+/// shadow ray covers, for `trt_direct` (96 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_direct_params {
+    pub path: trt_radiance_params,
+    pub shadow_end: f32,
+    pub reserved: [u32; 7],
+}
+
 /// `trt_gather_params` and the distance within which an occluder counts, for `trt_ambient` (128 bytes); `gather.path.max_bounces` and
 /// `gather.path.background` are not read; `reserved` stays zero.
 #[repr(C)]
@@ -462,6 +488,16 @@ extern "C" {
     pub fn trt_ambient_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_ambient_params, d_visibility: *mut f32,
                               d_bent: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_ambient_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_scene_emitters(s: *const trt_scene, out: *mut trt_emitter, cap: u32, count: *mut u32) -> c_int;
+    pub fn trt_emitter_init_quad(out: *mut trt_emitter, corner: trt_vec3, u: trt_vec3, v: trt_vec3, color: trt_vec3);
+    pub fn trt_emitter_init_sphere(out: *mut trt_emitter, centre: trt_vec3, radius: f32, color: trt_vec3);
+    pub fn trt_direct_params_default(out: *mut trt_direct_params);
+    pub fn trt_direct(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, n_emitters: u32,
+                      p: *const trt_direct_params, radiance: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_direct_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter, n_emitters: u32,
+                             p: *const trt_direct_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
+                             stream: *mut c_void) -> c_int;
+    pub fn trt_direct_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_probe_params_default(out: *mut trt_probe_params);
     pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
                      stats: *mut trt_stats) -> c_int;

@@ -154,6 +154,19 @@ impl Quad {
     }
 }
 
+/// A quad lamp that is no geometry of the scene, for the table of `World::direct` (`trt_emitter_init_quad`): it emits `color` from both faces.
+pub fn quad_emitter(corner: Vec3, u: Vec3, v: Vec3, color: Vec3) -> sys::trt_emitter {
+    let mut e = sys::trt_emitter::default();
+    unsafe { sys::trt_emitter_init_quad(&mut e, corner.raw(), u.raw(), v.raw(), color.raw()) };
+    e
+}
+/// A sphere lamp that is no geometry of the scene (`trt_emitter_init_sphere`).
+pub fn sphere_emitter(centre: Vec3, radius: Float, color: Vec3) -> sys::trt_emitter {
+    let mut e = sys::trt_emitter::default();
+    unsafe { sys::trt_emitter_init_sphere(&mut e, centre.raw(), radius, color.raw()) };
+    e
+}
+
 pub struct World {
     handle: *mut sys::trt_world,
     scene: *mut sys::trt_scene, // World::get_bvh(), cached until the world changes
@@ -297,6 +310,46 @@ impl World {
                              bent.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((visibility, bent))
+    }
+
+    /// The scene's own lights (`trt_scene_emitters`): the geometries whose material is a `Light`, in insertion order - a table for
+    /// `direct`.  Needs no device.
+    pub fn emitters(&mut self) -> Result<Vec<sys::trt_emitter>, Error> {
+        let scene = self.get_bvh()?;
+        let mut count = 0u32;
+        check(unsafe { sys::trt_scene_emitters(scene, ptr::null_mut(), 0, &mut count) })?;
+        let mut table = vec![sys::trt_emitter::default(); count as usize];
+        if count > 0 {
+            check(unsafe { sys::trt_scene_emitters(scene, table.as_mut_ptr(), count, &mut count) })?;
+        }
+        Ok(table)
+    }
+
+    /// The light that reaches caller-supplied surfels straight from the emitters of a table (`trt_direct`): `emitters()`, a part of it,
+    /// or lights that are no geometry of the scene (`quad_emitter`, `sphere_emitter`).  Every one of `samples_per_item` samples picks an
+    /// emitter uniformly and a point on it from RNG stream `(seed, first_stream + i * samples_per_item + s, 1)` and asks whether
+    /// anything lies in `[0.001, distance * shadow_end)` along the normalised ray towards it; an unoccluded sample that faces the point
+    /// adds its weighted colour / K.  With a unit axis the result is what a white diffuse surface reflects from those emitters alone:
+    /// `gather`'s convention.  Returns `(radiance, moment2)` as `radiance` does.
+    pub fn direct(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], samples_per_item: u32, shadow_end: Float, seed: u32,
+                  first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_direct_params::default();
+        unsafe { sys::trt_direct_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        params.shadow_end = shadow_end;
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_direct(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32,
+                            &params, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
     }
 
     /// The radiance arriving at caller-supplied points as a function of direction (`trt_probe`): each `(point, axis)` as six floats, used

@@ -49,7 +49,8 @@ extern "C" {
  *              trt_gather_launch_plan; trt_ambient_params, trt_ambient_params_default, trt_ambient, trt_ambient_device,
  *              trt_ambient_launch_plan; trt_probe_domain, trt_probe_params, trt_probe_params_default, trt_probe, trt_probe_device,
  *              trt_probe_launch_plan; trt_passes_source, trt_passes_params, trt_passes_params_default, trt_passes, trt_passes_device,
- *              trt_passes_launch_plan. */
+ *              trt_passes_launch_plan; trt_emitter, trt_scene_emitters, trt_emitter_init_quad, trt_emitter_init_sphere, trt_direct_params,
+ *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -735,6 +736,98 @@ int trt_passes_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const tr
  * that `depth_bins` (the same shapes; B = 1 and 2 run the kernels that carry 2 bins, B = 3 and 4 those that carry 4;
  * kernel_waves_per_simd is that table's bound: a lane carries 6 sums per bin).  `depth_bins` outside 1..4 is TRT_ERR_INVALID_ARG. */
 int trt_passes_launch_plan(const trt_scene *s, uint32_t n, uint32_t depth_bins, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Direct-light queries: shadow rays the device draws towards a table of emitters ----
+ * trt_gather, trt_probe and trt_passes find the lights as the reference does, by chance: in the Cornell box the lamp covers about 0.5 % of
+ * a floor texel's cosine lobe, so the d = 0 LIGHT slot of trt_passes - the texel's direct light - holds about K / 200 samples worth 15
+ * each.  A direct-light query aims: every sample picks an emitter of a caller-supplied table, a point on it, and asks trt_occluded's
+ * question of the segment between the surfel and that point.  A baker, a probe placer or an engine that lights a surfel at run time
+ * gets the same mean from about a hundredth of the samples.
+ *
+ * The emitter table is the caller's: trt_scene_emitters lists the scene's own lights, and the table handed to trt_direct may be that
+ * list, a part of it, or lights that are no geometry of the scene at all (trt_emitter_init_quad, trt_emitter_init_sphere) - a scene
+ * without a TRT_LIGHT material can be lit by a virtual lamp.
+ *  - trt_scene_emitters: the geometries whose material kind is TRT_LIGHT, in insertion order.  Host only, needs no device.  *count
+ *    receives their number; the first min(cap, *count) are written to `out` (which may be NULL with cap == 0).  A NULL scene or count is
+ *    TRT_ERR_INVALID_ARG.
+ *  - The two init functions fill geometry = 0xFFFFFFFF, reserved = 0 and compute `normal` and `area` with the host code
+ *    trt_scene_emitters uses, all f32, one IEEE operation per operator, nothing fused:
+ *      cross = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x);  length = sqrt((c.x*c.x + c.y*c.y) + c.z*c.z)
+ *      quad:   normal = cross / length (what Ray::new makes of the cross product, ray.rs:12-14; the value the packed scene holds,
+ *              quad.rs:20-29), area = length;      sphere:  area = 12.566371f * (r * r), normal = 0 (unread)
+ *    A NULL `out` is tolerated.
+ *
+ * Contract of a sample.  Item i is a surfel (x = origin, n = direction), both used AS GIVEN.  K = path.samples_per_ray, E = n_emitters;
+ * sample s of 0..K has stream index j = path.first_stream + i * K + s (32 bits).  All f32, one IEEE operation per operator, nothing fused:
+ *  1. g = RNG (seed, pixel = j, sample = 1).  Stream (seed, j, 0) is not touched; path.max_bounces and path.background are not read.
+ *  2. u0 = random(g) (utils/random.rs:11-13);  e = min(uint32(u0 * float(E)), E - 1): emitters are chosen uniformly.
+ *  3. Quad:    a = random(g), then b = random(g);  y = (corner + u * a) + v * b;  nl = normal.
+ *     Sphere:  nl = Vec3::new_random_unit_vector(g) (vec3extend.rs:32-34: three draws, as trt_probe draws it);  y = centre + nl * radius.
+ *  4. w = y - x;  d2 = dot(w, w);  cs = dot(n, w);  cl = |dot(nl, w)|.  Emitters shine from both faces, as Light::emitted ignores the
+ *     face (light.rs).
+ *  5. scale = (area * float(E)) * 0.318309886f;  geom = (cs * cl) / (d2 * d2);  wgt = geom * scale.
+ *  6. The sample is LIVE iff cs > 0 and d2 > 0 and wgt is finite.  A NaN in the item, the record or the draw fails one of the three.  A
+ *     dead sample is counted in `samples`, walks nothing and adds nothing.
+ *  7. Shadow ray: ray = Ray::new(x, w), which normalises (ray.rs:12-14);  t_max = sqrt(d2) * shadow_end.  The sample is occluded iff
+ *     BVH::hit (hittable/bvh.rs:24-27,88-107) over [0.001, t_max) finds anything: exactly what trt_occluded answers for that ray and
+ *     t_max.  Every material occludes, lights and glass included.  If t_max is not > 0.001 the range is empty: nothing is walked, the
+ *     sample is unoccluded and is not counted in `rays`.
+ *  8. Fold, per item, in sample order, inv_K = 1.0f / float(K).  A live, unoccluded sample has c.ch = color.ch * wgt and adds
+ *       radiance.ch = radiance.ch + c.ch * inv_K;   moment2.ch = moment2.ch + (c.ch * c.ch) * inv_K
+ *     Every other sample adds nothing (it does not add 0).  `radiance` and `moment2` hold n x 3 f32; `moment2` may be NULL (not wanted).
+ * Meaning.  With a unit axis the mean is the radiance a white Lambertian surfel reflects from the table's emitters alone - direct
+ * irradiance / pi: trt_gather's convention, so the two are comparable, and this result plus trt_passes' indirect slots is a full bake.
+ * trt_variance(radiance, moment2, n, K, ...) is the variance of each estimate.
+ * Limits.  (1) Emitters are chosen with probability 1 / E whatever their power: where powers differ much, split the table over calls and
+ * add the results.  (2) An occluder within (1 - shadow_end) of the distance to the emitter point is not seen; shadow_end < 1 keeps the
+ * emitter's own surface, which is geometry of the scene, from shadowing itself.  The ray is normalised and t_max is a SHARE of the
+ * distance on purpose: an un-normalised segment to t = 1 would put the walks' fixed lower end 0.001 at 0.1 % of the lamp's distance and
+ * leak light at contact corners.  (3) A non-unit axis is used as given: the result scales linearly with its length.  (4) An emitter
+ * coplanar with other geometry - the stock Cornell box's lamp lies in the ceiling's plane, both y = 100 - is seen fully by the shadow
+ * ray, while the reference's own paths (trt_gather, trt_passes) see it only where rounding lets the lamp win the tie with the ceiling
+ * (about a quarter of the time in one measurement: 0.038 against 0.128 over 40 surfels of the box).  That is a property of that scene, not
+ * of this query: compare the two on a lamp lowered to y = 99.
+ *  - Sample range, accumulate, the 1 / K scale fixed by K, split invariance by samples (split the range, set accumulate) and by items
+ *    (first_stream + a * K), order, coherence and concurrency: as in trt_radiance.  An empty sample range zeroes the n entries unless
+ *    accumulate, which touches nothing; max_bounces == 0 is NOT "nothing to trace" here.  No byte outside [0, 12 n) of either buffer is
+ *    ever written.
+ *  - stats / d_counters receive samples ([0]: every sample of the range) and rays ([1]: the occlusion walks made) only.  kernel_ms as
+ *    in trt_radiance.  `d_counters`: 16 uint64 as in trt_render_device, added to, or NULL.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_radiance's own errors, applied to `path`; with n > 0 a NULL
+ *    `emitters` or n_emitters outside 1 .. 2^20; shadow_end NaN, <= 0 or > 1; a non-zero reserved word; and, host form only (the
+ *    device form cannot read the table), an emitter whose kind is above 1 or that has a non-zero reserved word.  The device form reads
+ *    any kind other than 1 as a sphere.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's buffers.  n == 0 succeeds and
+ *    touches nothing, with or without a device.
+ * trt_direct: HOST buffers, synchronous; one device allocation for the call (items, table, sums); the sums are uploaded only when
+ * accumulate is set.  trt_direct_device: buffers in HBM on the calling thread's current device - the table included, n_emitters x 80
+ * bytes, 4-byte aligned - asynchronous on `stream`; allocates nothing.  The launch rule gives a wave 256 items whatever K is, as it does
+ * for trt_radiance and trt_gather. */
+typedef struct {
+    uint32_t kind;                /* 0 sphere, 1 quad */
+    uint32_t geometry;            /* insertion index in the world, or 0xFFFFFFFF: a light of the caller's own that is not in the scene; not read by trt_direct */
+    trt_vec3 a, b, c;             /* sphere: a = centre, b.x = radius; quad: a = corner, b = u, c = v */
+    trt_vec3 normal;              /* quad: Quad::new's unit normal (quad.rs:20-29); sphere: unread */
+    trt_vec3 color;               /* emitted colour (Light::emitted) */
+    float area;                   /* quad: length(cross(u, v)); sphere: 12.566371f * (r * r) */
+    uint32_t reserved[2];         /* zero */
+} trt_emitter;                    /* 80 B: offsets 0, 4, 8, 20, 32, 44, 56, 68, 72 */
+int trt_scene_emitters(const trt_scene *s, trt_emitter *out, uint32_t cap, uint32_t *count);
+void trt_emitter_init_quad(trt_emitter *out, trt_vec3 corner, trt_vec3 u, trt_vec3 v, trt_vec3 color);
+void trt_emitter_init_sphere(trt_emitter *out, trt_vec3 centre, float radius, trt_vec3 color);
+typedef struct {
+    trt_radiance_params path;     /* samples_per_ray (K), seed, sample_begin, sample_end, accumulate, first_stream: trt_radiance's rules and
+                                     errors.  max_bounces and background are IGNORED (not read): there is no path. */
+    float shadow_end;             /* the shadow ray covers [0.001, distance * shadow_end): in (0, 1] */
+    uint32_t reserved[7];         /* zero */
+} trt_direct_params;              /* 96 B: offsets 0, 64, 68 */
+void trt_direct_params_default(trt_direct_params *out);   /* path = trt_radiance_params_default, shadow_end = 0.999f; NULL tolerated */
+int trt_direct(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, uint32_t n_emitters,
+               const trt_direct_params *p, float *radiance, float *moment2, trt_stats *stats);
+int trt_direct_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, uint32_t n_emitters,
+                      const trt_direct_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_direct[_device] launches n items on this scene: trt_ambient_launch_plan's rule and fields over the direct-light kernels' own
+ * table (the same shapes; kernel_waves_per_simd is that table's bound). */
+int trt_direct_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

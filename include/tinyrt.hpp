@@ -131,6 +131,27 @@ public:
         if (bent) bent->resize(items.size() * 3);
         check(trt_ambient(get_bvh(), items.data(), (uint32_t)items.size(), &p, visibility.data(), bent ? bent->data() : nullptr, stats));
     }
+    // The scene's own lights (trt_scene_emitters): the geometries whose material is a Light, in insertion order - a table for direct().
+    std::vector<trt_emitter> emitters() {
+        uint32_t count = 0;
+        check(trt_scene_emitters(get_bvh(), nullptr, 0, &count));
+        std::vector<trt_emitter> table(count);
+        if (count) check(trt_scene_emitters(get_bvh(), table.data(), count, &count));
+        return table;
+    }
+    // The light that reaches caller-supplied surfels straight from the emitters of a table (trt_direct): emitters(), a part of it, or
+    // lights that are no geometry of the scene (trt_emitter_init_quad, trt_emitter_init_sphere).  Each of p.path.samples_per_ray samples
+    // picks an emitter and a point on it and asks whether anything lies in [0.001, distance * p.shadow_end) along the normalised ray
+    // towards it.  `radiance` becomes three floats per item - with a unit axis what a white diffuse surface reflects from those emitters
+    // alone, gather()'s convention - and `moment2` (nullptr: not wanted) the second moments.  Both continue the sums they hold when
+    // p.path.accumulate is set.  Start `p` from trt_direct_params_default.
+    void direct(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_direct_params& p, std::vector<float>& radiance,
+                std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_direct(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
+                         moment2 ? moment2->data() : nullptr, stats));
+    }
     // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
     // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
     // gather() does and adds colour * Y_k(direction) / K to coefficient k of the item.  `sh` becomes p.bands^2 x 3 floats per item - real

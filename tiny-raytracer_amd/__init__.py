@@ -3,7 +3,7 @@ World / Camera / Renderer surface.  All compute is in libtinyrt.so (HIP, gfx950)
 package fails if that library is not built.  The directory name has a hyphen, so import it with
 importlib.import_module("tiny-raytracer_amd") or through the top-level alias module `tinyrt_amd`.
 """
-from . import bake, passes, scenes, sh  # noqa: F401
+from . import bake, lights, passes, scenes, sh  # noqa: F401
 from ._lib import (BACKEND_AUTO, BACKEND_MEGAKERNEL, BACKEND_STREAMED, BACKEND_WAVEFRONT, DIELECTRIC, LAMBERTIAN, LIGHT, METAL, CameraPOD,  # noqa: F401
                    Hit, Material, Ray, RenderParams, SampledColor, SamplePoint, SceneOptions, Stats, TinyRTError, Tuning, Vec3, lib)
 from .api import (AOV_CHANNELS, HIT_DTYPE, Camera, Dielectric, Image, Lambertian, Light, Metal, Quad, Renderer, Scene, Sphere, World,  # noqa: F401

@@ -137,7 +137,23 @@ class AmbientParams(C.Structure):
     _fields_ = [("gather", GatherParams), ("max_distance", C.c_float), ("reserved", C.c_uint32 * 7)]
 
 
-PROBE_SPHERE, PROBE_HEMISPHERE = 1, 2                                        # tinyrt.h enum trt_probe_domain
+EMITTER_SPHERE, EMITTER_QUAD = 0, 1                                         # tinyrt.h trt_emitter.kind
+NO_GEOMETRY = 0xFFFFFFFF                                                    # trt_emitter.geometry of a light that is not in the scene
+
+
+class Emitter(C.Structure):
+    """tinyrt.h trt_emitter: one light of the table a direct-light query samples (80 bytes)."""
+    _fields_ = [("kind", C.c_uint32), ("geometry", C.c_uint32), ("a", Vec3), ("b", Vec3), ("c", Vec3), ("normal", Vec3), ("color", Vec3),
+                ("area", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class DirectParams(C.Structure):
+    """tinyrt.h trt_direct_params: trt_radiance_params (its max_bounces and background are not read) and the share of the distance to
+    the emitter point the shadow ray covers (96 bytes)."""
+    _fields_ = [("path", RadianceParams), ("shadow_end", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+
+PROBE_SPHERE, PROBE_HEMISPHERE = 1, 2                                       # tinyrt.h enum trt_probe_domain
 
 
 class ProbeParams(C.Structure):
@@ -258,6 +274,15 @@ SIGNATURES = {
     "trt_ambient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(AmbientParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "trt_ambient_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_scene_emitters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "trt_emitter_init_quad": (None, [C.POINTER(Emitter), Vec3, Vec3, Vec3, Vec3]),
+    "trt_emitter_init_sphere": (None, [C.POINTER(Emitter), Vec3, C.c_float, Vec3]),
+    "trt_direct_params_default": (None, [C.POINTER(DirectParams)]),
+    "trt_direct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectParams), C.c_void_p, C.c_void_p,
+                             C.POINTER(Stats)]),
+    "trt_direct_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectParams), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "trt_direct_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

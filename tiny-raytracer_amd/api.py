@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import (BACKEND_MEGAKERNEL, BACKEND_WAVEFRONT, DIELECTRIC, LAMBERTIAN, LIGHT, METAL, CameraPOD, Material,
                    RenderParams, SampledColor, SamplePoint, SceneInfo, SceneOptions, Stats, TinyRTError, Tuning, Vec3, check, lib)
+from .lights import EMITTER_DTYPE
 
 
 def _v(v):
@@ -345,6 +346,75 @@ class Scene:
         """trt_ambient_launch_plan: how ambient() launches n surfels on this scene, as a dict with gather_plan()'s fields."""
         plan = _lib.QueryPlan()
         check(lib.trt_ambient_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
+    # ---- direct-light queries (tinyrt.h trt_direct): shadow rays the device draws towards a table of emitters ----
+    def emitters(self):
+        """trt_scene_emitters: the scene's own lights - the geometries whose material is a Light, in insertion order - as a record array
+        of lights.EMITTER_DTYPE; needs no device.  A table for direct(): use it whole, slice it, or join it with lights.quad(...) /
+        lights.sphere(...) records (lights.table)."""
+        count = C.c_uint32(0)
+        check(lib.trt_scene_emitters(self._h, None, 0, C.byref(count)))
+        out = np.zeros(count.value, EMITTER_DTYPE)
+        if count.value:
+            check(lib.trt_scene_emitters(self._h, out.ctypes.data, count.value, C.byref(count)))
+        return out
+
+    @staticmethod
+    def _direct_params(samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0, accumulate=False):
+        """sample_end = 0 means samples_per_item, as at the C boundary; shadow_end = None: the library's default (0.999)."""
+        p = _lib.DirectParams()
+        lib.trt_direct_params_default(C.byref(p))
+        path = p.path
+        path.samples_per_ray, path.seed, path.first_stream = int(samples_per_item), int(seed), int(first_stream)
+        path.sample_begin, path.sample_end, path.accumulate = int(sample_begin), int(sample_end), 1 if accumulate else 0
+        if shadow_end is not None:
+            p.shadow_end = float(shadow_end)
+        return p
+
+    @staticmethod
+    def _emitter_table(emitters):
+        e = np.ascontiguousarray(emitters)
+        if e.dtype != EMITTER_DTYPE or e.ndim != 1:
+            raise ValueError("emitters must be a one-dimensional record array of lights.EMITTER_DTYPE")
+        return e
+
+    def direct(self, items, emitters, samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0,
+               accumulate=False, radiance=None, moment2=None):
+        """trt_direct: the light that reaches surfels float32 [n, 6] (point, axis; used as given) straight from the emitters of a table
+        (emitters(), lights.quad / lights.sphere records, or any mix).  Each of samples_per_item = K samples picks an emitter uniformly and
+        a point on it from RNG stream (seed, first_stream + i * K + s, 1), and asks occluded()'s question of the normalised ray towards
+        it over [0.001, distance * shadow_end); an unoccluded sample that faces the point adds colour * cos * |cos_l| * area * E /
+        (pi * distance^2) / K.  With a unit axis the result is what a white diffuse surface reflects from those emitters alone -
+        gather()'s convention, with far less noise.  Sample range, accumulate, `radiance`, `moment2` and the returns as in radiance()
+        (sample_end = 0: K); stats carry samples and rays = the occlusion walks made."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        e = self._emitter_table(emitters)
+        p = self._direct_params(samples_per_item, shadow_end, seed, first_stream, sample_begin, sample_end, accumulate)
+        if radiance is None:
+            radiance = np.zeros((n, 3), np.float32)
+        if moment2 is True:
+            moment2 = np.zeros((n, 3), np.float32)
+        for a in (radiance, moment2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
+        st = Stats()
+        check(lib.trt_direct(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
+                             radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        return radiance, moment2, st.as_dict()
+
+    def direct_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue direct() on buffers already in HBM (device pointers as integers: n x 24 bytes of surfels, n_emitters x 80 bytes of
+        trt_emitter records, n x 12 bytes of sums each) on the current device; asynchronous on the stream, allocates nothing.  `params`:
+        direct()'s keywords, samples_per_item included."""
+        p = self._direct_params(**params)
+        check(lib.trt_direct_device(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
+                                    C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def direct_plan(self, n, compute_units=0):
+        """trt_direct_launch_plan: how direct() launches n surfels on this scene, as a dict with ambient_plan()'s fields."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_direct_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
     # ---- probe queries (tinyrt.h trt_probe): spherical-harmonic radiance from first rays the device draws over the sphere ----

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -572,6 +573,44 @@ int trt_scene_get_packed(const trt_scene* s, uint8_t* bytes, uint32_t cap) {
     if (cap < n) return fail(TRT_ERR_INVALID_ARG, "cap is smaller than the packed scene (trt_scene_info.device_bytes)");
     memcpy(bytes, s->host.blob.data(), n);
     return TRT_OK;
+}
+// The scene's own lights for trt_direct, read back from the packed scene: primitive k of a kind names its material (spheres in the u32
+// plane, quads in their record), the material its kind and colour, geo_index its insertion index.  Host only.
+int trt_scene_emitters(const trt_scene* s, trt_emitter* out, uint32_t cap, uint32_t* count) {
+    if (!s || !count) return fail(TRT_ERR_INVALID_ARG, "null argument");
+    if (cap > 0u && !out) return fail(TRT_ERR_INVALID_ARG, "out is null");
+    const SceneLayout& L = s->host.layout;
+    const F4* const f4 = reinterpret_cast<const F4*>(s->host.blob.data());
+    const uint32_t* const u32 = reinterpret_cast<const uint32_t*>(s->host.blob.data());
+    try {
+        std::vector<trt_emitter> lights;
+        for (uint32_t k = 0; k < L.n_spheres + L.n_quads; k++) {
+            const bool quad = k >= L.n_spheres;
+            const F4* const q = f4 + L.off_quad + 5u * (size_t)(k - L.n_spheres);         // (read only where quad)
+            uint32_t material;
+            if (quad) memcpy(&material, &q[1].w, 4); else material = u32[L.off_sphere_mat + k];
+            if (material >= L.n_materials || u32[L.off_material_kind + material] != TRT_LIGHT) continue;
+            const F4 m = f4[L.off_material + material];
+            const trt_vec3 color{m.x, m.y, m.z};
+            trt_emitter e;
+            if (quad) emitter_init_quad(e, trt_vec3{q[1].x, q[1].y, q[1].z}, trt_vec3{q[3].z, q[3].w, q[4].x}, trt_vec3{q[2].x, q[2].y, q[2].z}, color);
+            else emitter_init_sphere(e, trt_vec3{f4[L.off_sphere + k].x, f4[L.off_sphere + k].y, f4[L.off_sphere + k].z}, f4[L.off_sphere + k].w, color);
+            e.geometry = s->geo_index[k];
+            lights.push_back(e);
+        }
+        std::sort(lights.begin(), lights.end(), [](const trt_emitter& a, const trt_emitter& b) { return a.geometry < b.geometry; });
+        *count = (uint32_t)lights.size();
+        for (uint32_t i = 0; i < cap && i < lights.size(); i++) out[i] = lights[i];
+    } catch (const std::bad_alloc&) {
+        return fail(TRT_ERR_OOM, "out of memory");
+    }
+    return TRT_OK;
+}
+void trt_emitter_init_quad(trt_emitter* out, trt_vec3 corner, trt_vec3 u, trt_vec3 v, trt_vec3 color) {
+    if (out) emitter_init_quad(*out, corner, u, v, color);
+}
+void trt_emitter_init_sphere(trt_emitter* out, trt_vec3 centre, float radius, trt_vec3 color) {
+    if (out) emitter_init_sphere(*out, centre, radius, color);
 }
 
 // ---- Camera ----

@@ -1,5 +1,6 @@
 // gather_draw.h - what the units that draw a sample's first ray about a caller-supplied surfel share: the gather queries (radiance.hip:
-// the drawn ray starts a path) and the ambient queries (ambient.hip: the drawn ray is an occlusion query).  ONE copy of the item load and
+// the drawn ray starts a path), the ambient queries (ambient.hip: the drawn ray is an occlusion query), the probe queries (probe.hip) and the
+// direct-light queries (direct.hip: the drawn ray is a shadow ray towards a drawn point on an emitter).  ONE copy of the item load and
 // of the draw on the device, and of the argument checks of trt_gather_params on the host.  The two device functions are pure functions
 // of values (wave_run.h says why): moved here from radiance.hip as they stood, radiance_kernel compiles to the registers it had.
 #pragma once
@@ -47,6 +48,51 @@ TRT_DEV Ray probe_ray(const float* __restrict__ items, uint32_t idx, bool hemisp
         if (!(dot(u, axis) > 0.0f)) dir = -u;
     }
     return ray_new(v3(it[0], it[1], it[2]), dir);
+}
+
+// The shadow ray of a direct-light sample (direct.hip): a point y on one emitter of the caller's table (tinyrt.h trt_emitter: 20 words a
+// record, read through the lane's own index - vector loads - once the first draw has chosen it), the ray from the surfel towards it and what
+// an unoccluded sample folds.  In tinyrt.h's operation order, one IEEE f32 operation per operator:
+//   u0 = random; e = min(uint32(u0 * float(E)), E - 1)
+//   quad:    a = random; b = random; y = (corner + u * a) + v * b; nl = normal
+//   sphere:  nl = random_unit_vector (probe_ray's); y = centre + nl * radius
+//   w = y - x; d2 = w.w; cs = n.w; cl = |nl.w|; wgt = ((cs * cl) / (d2 * d2)) * ((area * float(E)) * (1 / pi))
+// live: cs > 0, d2 > 0 and wgt finite - a NaN anywhere fails one of the three.  Three draws (quad) or four (sphere) are taken from g.
+struct DirectSample {
+    Ray ray;                         // Ray::new(x, w): normalised
+    V3 c;                            // colour * wgt
+    float t_max;                     // sqrt(d2) * shadow_end: the walk covers [0.001, t_max)
+    bool live;
+};
+TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters, uint32_t n_emitters,
+                                 float shadow_end, Rng& g) {
+    const float fe = (float)n_emitters;
+    const uint32_t pick = (uint32_t)(rng_random(g) * fe);
+    const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
+    const V3 a = v3(em[2], em[3], em[4]);
+    V3 y, nl;
+    if (__float_as_uint(em[0]) == 1u) {
+        const float ra = rng_random(g);
+        const float rb = rng_random(g);
+        y = (a + v3(em[5], em[6], em[7]) * ra) + v3(em[8], em[9], em[10]) * rb;
+        nl = v3(em[11], em[12], em[13]);
+    } else {
+        nl = normalized(random_in_unit_sphere_unit(g));
+        y = a + nl * em[5];
+    }
+    const Ray item = rad_load_ray(items, idx);                              // after the draws, as in gather_ray
+    const V3 w = y - item.o;
+    const float d2 = dot(w, w);
+    const float cs = dot(item.d, w);
+    const float cl = __builtin_fabsf(dot(nl, w));
+    const float scale = (em[17] * fe) * 0.318309886f;
+    const float wgt = ((cs * cl) / (d2 * d2)) * scale;
+    DirectSample smp;
+    smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
+    smp.ray = ray_new(item.o, w);
+    smp.t_max = __builtin_sqrtf(d2) * shadow_end;
+    smp.c = v3(em[14], em[15], em[16]) * wgt;
+    return smp;
 }
 
 // The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.

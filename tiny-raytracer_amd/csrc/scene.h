@@ -118,6 +118,11 @@ trt_scene_options scene_options_builtin();
 void camera_init(trt_camera& out, float focus_distance, float defocus_angle_deg, trt_vec3 position, trt_vec3 look_at,
                  trt_vec3 up, float vertical_fov_deg, uint32_t width, uint32_t height);
 
+// tinyrt.h trt_emitter_init_quad / trt_emitter_init_sphere: the record of a light that is no geometry of a scene; trt_scene_emitters
+// fills the records of a scene's own lights with the same two functions.
+void emitter_init_quad(trt_emitter& out, trt_vec3 corner, trt_vec3 u, trt_vec3 v, trt_vec3 color);
+void emitter_init_sphere(trt_emitter& out, trt_vec3 centre, float radius, trt_vec3 color);
+
 // Image finalisation (imager.rs:52-53; utils/image.rs:92-111)
 void tonemap_u8(const float* accum, uint32_t npixels, float gamma, uint8_t* rgb);
 

@@ -542,6 +542,30 @@ void camera_init(trt_camera& out, float focus_distance, float defocus_angle_deg,
     out.height = height;
 }
 
+// tinyrt.h trt_emitter of a quad: n = u x v, the unit normal Quad::new keeps (quad.rs:20-29; the value compile_scene packs, by the same
+// two functions) and the area |n|.  geometry = 0xFFFFFFFF: trt_scene_emitters overwrites it.
+void emitter_init_quad(trt_emitter& out, trt_vec3 corner, trt_vec3 u, trt_vec3 v, trt_vec3 color) {
+    const H3 n = hcross(h3(u), h3(v));
+    const H3 nu = hnormalized(n);
+    out = trt_emitter{};
+    out.kind = 1u;
+    out.geometry = 0xFFFFFFFFu;
+    out.a = corner; out.b = u; out.c = v;
+    out.normal = trt_vec3{nu.x, nu.y, nu.z};
+    out.color = color;
+    out.area = sqrtf(hdot(n, n));
+}
+// ... of a sphere: area = 4 pi r^2 with the f32 constant of the header.
+void emitter_init_sphere(trt_emitter& out, trt_vec3 centre, float radius, trt_vec3 color) {
+    out = trt_emitter{};
+    out.kind = 0u;
+    out.geometry = 0xFFFFFFFFu;
+    out.a = centre;
+    out.b = trt_vec3{radius, 0.0f, 0.0f};
+    out.color = color;
+    out.area = 12.566371f * (radius * radius);
+}
+
 // Imager: set_pixel applies gamma (imager.rs:52-53, image.rs:38-44,92-98); RgbImage conversion clamps
 // to [0, 0.999], scales by 255 and truncates (image.rs:101-111; Rust's `as u8` saturates, NaN -> 0).
 void tonemap_u8(const float* accum, uint32_t npixels, float gamma, uint8_t* rgb) {
