@@ -324,6 +324,17 @@ pub struct trt_passes_params {
     pub reserved: [u32; 7],
 }
 
+/// `trt_gather_params`, whose `lobe` is read as `enum trt_passes_source`, the share of the distance to the emitter point a shadow ray
+/// covers and whether the first hit counts as reached by a diffuse scatter, for `trt_nee` (128 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_nee_params {
+    pub gather: trt_gather_params,
+    pub shadow_end: f32,
+    pub source_is_diffuse: u32,
+    pub reserved: [u32; 6],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -498,6 +509,13 @@ extern "C" {
                              p: *const trt_direct_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
                              stream: *mut c_void) -> c_int;
     pub fn trt_direct_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_nee_params_default(out: *mut trt_nee_params);
+    pub fn trt_nee(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, n_emitters: u32,
+                   p: *const trt_nee_params, radiance: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_nee_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter, n_emitters: u32,
+                          p: *const trt_nee_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
+                          stream: *mut c_void) -> c_int;
+    pub fn trt_nee_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_probe_params_default(out: *mut trt_probe_params);
     pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
                      stats: *mut trt_stats) -> c_int;

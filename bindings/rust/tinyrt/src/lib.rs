@@ -425,6 +425,45 @@ impl World {
         Ok((passes, spent))
     }
 
+    /// What `radiance` (`PassesSource::Rays`) or `gather` (`PassesSource::Lobe`) estimates, with the lights aimed at (`trt_nee`): the
+    /// path of every sample is theirs bit for bit, at every Lambertian hit that leaves bounce budget one shadow ray goes to the emitter
+    /// table as in `direct`, and a light the path then reaches by a diffuse scatter counts as black.  `emitters` should be
+    /// `emitters()`: a light left out is still hidden.  With `source_is_diffuse` the first hit counts as diffusely reached too: for a
+    /// cosine source the result is the surfel's indirect light, and `direct` + `nee` is a full bake.  Returns `(radiance, moment2)` as
+    /// `radiance` does.
+    pub fn nee(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], samples_per_item: u32, source: PassesSource,
+               source_is_diffuse: bool, shadow_end: Float, max_bounces: u32, background: Vec3, seed: u32, first_stream: u32)
+               -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_nee_params::default();
+        unsafe { sys::trt_nee_params_default(&mut params) };
+        params.gather.path.samples_per_ray = samples_per_item;
+        params.gather.path.max_bounces = max_bounces;
+        params.gather.path.background = background.raw();
+        params.gather.path.seed = seed;
+        params.gather.path.first_stream = first_stream;
+        params.shadow_end = shadow_end;
+        params.source_is_diffuse = source_is_diffuse as u32;
+        match source {
+            PassesSource::Rays => params.gather.lobe = sys::TRT_PASSES_RAYS,
+            PassesSource::Lobe(Lobe::Cosine) => params.gather.lobe = sys::TRT_PASSES_COSINE,
+            PassesSource::Lobe(Lobe::Cone(spread)) => {
+                params.gather.lobe = sys::TRT_PASSES_CONE;
+                params.gather.spread = spread;
+            }
+        }
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_nee(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32, &params,
+                         radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.
     pub fn trim(&mut self) -> Result<(), Error> {
         if self.scene.is_null() {

@@ -1,0 +1,55 @@
+#!/usr/bin/env python3
+"""Bake the full light of the Cornell box's floor with the lights aimed at at every bounce -> nee.png, beside the same light found by
+chance -> gather.png.
+   python examples/bake_nee.py [SIZE K]
+bake.quad_texels lays SIZE x SIZE surfels over the floor quad.  Scene.direct (trt_direct) aims every sample at the lamp from the texel
+itself; Scene.nee (trt_nee) with source_is_diffuse=True traces the cosine-distributed paths Scene.gather traces, hides the lamp where a
+path reaches it by a diffuse bounce and sends one shadow ray to it from every diffuse vertex instead: the texel's indirect light.  Their sum
+and Scene.gather at the same K estimate the same integral; the standard error of a texel says at what price.
+
+The lamp is lowered from y = 100 to y = 99 here, as in examples/bake_direct.py: in the stock box it lies in the ceiling's plane."""
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tinyrt_amd as trt
+
+argv = sys.argv[1:]
+size, spp = (int(a) for a in argv[:2]) if len(argv) >= 2 else (256, 64)
+desc = trt.scenes.cornell(2, 2)                                              # the camera of the description is not used
+geos = list(desc["geometries"])
+kind, corner, u, v, material = geos[2]
+assert kind == "quad" and material == "light"
+geos[2] = (kind, (corner[0], 99.0, corner[2]), u, v, material)
+desc = dict(desc, geometries=geos)
+scene = trt.world_from_description(desc)[0].get_bvh()
+kind, corner, u, v, _ = desc["geometries"][3]
+assert kind == "quad"
+items = trt.bake.quad_texels(corner, u, v, size, size, flip=True)            # the axis points up, into the box
+table = scene.emitters()
+path = dict(max_bounces=5, background=(0.0, 0.0, 0.0))
+t0 = time.perf_counter()
+direct, d_m2, dst = scene.direct(items, table, spp, moment2=True)
+indirect, i_m2, ist = scene.nee(items, table, spp, source="cosine", source_is_diffuse=True, moment2=True, **path)
+t1 = time.perf_counter()
+gather, g_m2, gst = scene.gather(items, spp, lobe="cosine", moment2=True, **path)
+t2 = time.perf_counter()
+full = direct + indirect
+trt.Image(full.reshape(size, size, 3)).save("nee.png")
+trt.Image(gather.reshape(size, size, 3)).save("gather.png")
+
+
+def texel_error(mean, m2):
+    return np.sqrt(np.maximum(m2 - mean * mean, 0.0) / max(spp - 1, 1))[:, 0]
+
+
+# the two estimates are drawn from different streams of a sample: their variances add
+err_nee = np.sqrt(texel_error(direct, d_m2) ** 2 + texel_error(indirect, i_m2) ** 2)
+err_gather = texel_error(gather, g_m2)
+print(f"{size}x{size} texels of the floor, {spp} samples each: direct + nee mean {float(full[:, 0].mean()):.4f} "
+      f"(standard error of a texel {float(err_nee.mean()):.4f}; {dst['rays'] + ist['rays']} rays, {(t1 - t0) * 1e3:.1f} ms) -> nee.png; "
+      f"gather mean {float(gather[:, 0].mean()):.4f} (standard error {float(err_gather.mean()):.4f}; {gst['rays']} rays, "
+      f"{(t2 - t1) * 1e3:.1f} ms) -> gather.png")

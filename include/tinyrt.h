@@ -50,7 +50,8 @@ extern "C" {
  *              trt_ambient_launch_plan; trt_probe_domain, trt_probe_params, trt_probe_params_default, trt_probe, trt_probe_device,
  *              trt_probe_launch_plan; trt_passes_source, trt_passes_params, trt_passes_params_default, trt_passes, trt_passes_device,
  *              trt_passes_launch_plan; trt_emitter, trt_scene_emitters, trt_emitter_init_quad, trt_emitter_init_sphere, trt_direct_params,
- *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan. */
+ *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan; trt_nee_params, trt_nee_params_default,
+ *              trt_nee, trt_nee_device, trt_nee_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -828,6 +829,71 @@ int trt_direct_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const tr
 /* How trt_direct[_device] launches n items on this scene: trt_ambient_launch_plan's rule and fields over the direct-light kernels' own
  * table (the same shapes; kernel_waves_per_simd is that table's bound). */
 int trt_direct_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Next-event queries: the paths of trt_radiance / trt_gather with a shadow ray to the emitter table at every diffuse hit ----
+ * trt_direct aims at the lights for the surfel itself; every query that carries light along a path (trt_radiance, trt_gather, trt_probe,
+ * trt_passes) still finds them by chance at every later bounce.  A next-event query traces the same path - the same vertices, bit for
+ * bit - and at every Lambertian vertex sends one device-drawn shadow ray to a caller-supplied emitter table (trt_direct's table and
+ * draw).  A light the path then reaches by a diffuse scatter is hidden, so nothing is counted twice: the expectation is the
+ * reference's at the same max_bounces, the variance is not.
+ *
+ * Contract of a sample.  Item i is a ray (source RAYS) or a surfel (COSINE, CONE), used AS GIVEN.  E = n_emitters,
+ * K = gather.path.samples_per_ray, B = gather.path.max_bounces; sample s of 0..K has stream index j = first_stream + i * K + s (32 bits).
+ * All f32, one IEEE operation per operator, nothing fused:
+ *  1. First ray: exactly trt_passes' for the source.  RAYS: the item.  COSINE, CONE: trt_gather's draw on stream (seed, j, 1).
+ *  2. The path runs on stream (seed, j, 0) and makes exactly the draws of CpuSampler::single_point_sampling (cpu.rs:39-65): its vertices
+ *     are those of trt_radiance / trt_gather for the same j, bit for bit.  color = 0, atten = 1, remain = B;
+ *     after_diffuse = (source_is_diffuse != 0).
+ *  3. At a hit (cpu.rs:49-50) color = color + atten * emission, where emission is the light's colour, except that it is Vec3::zero()
+ *     when the material is a light AND after_diffuse is set.  This is the only change to the reference's loop body.
+ *  4. Scatter, atten = atten * attenuation and remain -= 1 as in the reference (cpu.rs:51-54).  after_diffuse becomes (material kind ==
+ *     TRT_LAMBERTIAN): metal of any fuzz and dielectric count as specular, a light they lead to is seen by the path itself.
+ *  5. Next event.  If the hit was Lambertian AND remain > 0 after the decrement, the sample at that vertex is trt_direct's contract
+ *     steps 2-7 with x = rec.p (the new ray's origin), n = rec.normal (unit, facing against the incoming ray), g = RNG (seed, j, 2 + d)
+ *     where d = scatters made before this vertex, the same shadow_end and the same "an empty range walks nothing, is unoccluded".  A
+ *     live, unoccluded sample has c.ch = emitter colour.ch * wgt and adds  color = color + atten * c  with atten as step 4 left it;
+ *     every other sample adds nothing.  The term is added before the next vertex's emission.  The shadow ray stands for the emission
+ *     the reference would find at hit number h + 1 <= B, hence the condition on remain.
+ *  6. Miss: color = color + atten * background, as in the reference (cpu.rs:58-61).  The sky is never hidden.
+ *  7. The fold (radiance.ch = radiance.ch + color.ch * inv_K, moment2.ch = moment2.ch + (color.ch * color.ch) * inv_K; moment2 may be
+ *     NULL), the sample range, accumulate, split invariance by samples and by items (first_stream + a * K), "nothing to trace" (an empty
+ *     range or B == 0 zeroes the n entries unless accumulate, which touches nothing), the NaN-first-ray rule and the output bounds
+ *     ([0, 12 n) of either buffer): trt_radiance's, unchanged.
+ *  8. stats / d_counters: samples ([0]) counts the samples of the range, rays ([1]) the world.hit calls (cpu.rs:48) plus the shadow
+ *     walks made.  kernel_ms and `d_counters` as in trt_radiance.
+ *  9. Errors, before any device work, TRT_ERR_INVALID_ARG: trt_passes' own on `gather` (trt_radiance's on the path, a source other than
+ *     0, 1, 2, a cone spread that is negative or not finite, a non-zero reserved word); trt_direct's on the table (with n > 0 a NULL
+ *     table or n_emitters outside 1 .. 2^20; host form only: a record whose kind is above 1 or with a non-zero reserved word) and on
+ *     shadow_end (NaN, <= 0, > 1); source_is_diffuse above 1; a non-zero reserved word.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the
+ *     host form's buffers.  n == 0 succeeds and touches nothing, with or without a device.
+ * Meaning of source_is_diffuse = 1.  The first hit is treated as reached by a diffuse scatter: with the COSINE source the result is the
+ * surfel's INDIRECT light only, and trt_direct(surfel) + trt_nee(surfel) is a full bake with aimed light at every bounce.  With 0 the
+ * first hit's emission counts, as for a camera ray: the result estimates what trt_radiance / trt_gather estimate.
+ * Identities.  (1) With B == 1 there is no next event and, with source_is_diffuse == 0, nothing is hidden: the result is trt_radiance's
+ * (RAYS) / trt_gather's (COSINE, CONE), byte for byte.  (2) On a scene without a Lambertian material the result is trt_radiance's /
+ * trt_gather's for any B (source_is_diffuse == 0).
+ * Limits.  (1) The table should list every TRT_LIGHT geometry of the scene, which trt_scene_emitters does: a light left out of the table
+ * is still hidden after a diffuse scatter, so its bounced light is lost.  (2) Virtual emitters (trt_emitter_init_*) add light no path can
+ * hit: the result is then no estimate of trt_gather's.  (3) trt_direct's limits are inherited: the uniform choice among emitters,
+ * shadow_end, and the lamp coplanar with other geometry (the stock Cornell box: compare on a lamp lowered to y = 99).
+ * trt_nee: HOST buffers, synchronous; one device allocation for the call.  trt_nee_device: buffers in HBM (the table included),
+ * asynchronous on `stream`; allocates nothing.  A frame: per sample s, trt_primary_rays_device for s, then trt_nee_device with source
+ * RAYS, K = spp, the sample range [s, s + 1) and accumulate from the second pass on, as trt_passes' frame.  The launch rule gives a wave
+ * 256 items whatever K is, as it does for every query. */
+typedef struct {
+    trt_gather_params gather;     /* path, lobe read as enum trt_passes_source (RAYS 0, COSINE 1, CONE 2), spread: trt_passes' rules and errors */
+    float shadow_end;             /* as trt_direct: in (0, 1] */
+    uint32_t source_is_diffuse;   /* 0 or 1: after_diffuse at the first hit */
+    uint32_t reserved[6];         /* zero */
+} trt_nee_params;                 /* 128 B: offsets 0, 96, 100, 104 */
+void trt_nee_params_default(trt_nee_params *out);   /* gather = trt_passes_params_default's (source COSINE), shadow_end 0.999f, source_is_diffuse 0; NULL tolerated */
+int trt_nee(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, uint32_t n_emitters, const trt_nee_params *p,
+            float *radiance, float *moment2, trt_stats *stats);
+int trt_nee_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, uint32_t n_emitters,
+                   const trt_nee_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_nee[_device] launches n items on this scene: trt_passes_launch_plan's rule and fields over the next-event kernels' own table
+ * (the same shapes; kernel_waves_per_simd is that table's bound, the same for every source). */
+int trt_nee_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

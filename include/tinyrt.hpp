@@ -152,6 +152,19 @@ public:
         check(trt_direct(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
                          moment2 ? moment2->data() : nullptr, stats));
     }
+    // What radiance() / gather() estimate, with the lights aimed at (trt_nee): the path of every sample is theirs bit for bit (p.gather:
+    // path, source - TRT_PASSES_RAYS, _COSINE, _CONE - and spread), at every Lambertian hit that leaves bounce budget one shadow ray goes
+    // to `table` as in direct(), and a light the path then reaches by a diffuse scatter counts as black.  `table` should be emitters():
+    // a light left out is still hidden.  With p.source_is_diffuse the first hit counts as diffusely reached too: for a cosine source the
+    // result is the surfel's indirect light, and direct() + nee() is a full bake.  Buffers as in direct().  Start `p` from
+    // trt_nee_params_default.
+    void nee(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_nee_params& p, std::vector<float>& radiance,
+             std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_nee(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
+                      moment2 ? moment2->data() : nullptr, stats));
+    }
     // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
     // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
     // gather() does and adds colour * Y_k(direction) / K to coefficient k of the item.  `sh` becomes p.bands^2 x 3 floats per item - real

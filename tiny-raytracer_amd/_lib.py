@@ -171,6 +171,12 @@ class PassesParams(C.Structure):
     _fields_ = [("gather", GatherParams), ("depth_bins", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class NeeParams(C.Structure):
+    """tinyrt.h trt_nee_params: trt_gather_params, whose lobe is read as the source of the first ray (PASSES_*), the share of the distance
+    to the emitter point a shadow ray covers and whether the first hit counts as reached by a diffuse scatter (128 bytes)."""
+    _fields_ = [("gather", GatherParams), ("shadow_end", C.c_float), ("source_is_diffuse", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -283,6 +289,12 @@ SIGNATURES = {
     "trt_direct_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectParams), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "trt_direct_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_nee_params_default": (None, [C.POINTER(NeeParams)]),
+    "trt_nee": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeParams), C.c_void_p, C.c_void_p,
+                          C.POINTER(Stats)]),
+    "trt_nee_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeParams), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "trt_nee_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

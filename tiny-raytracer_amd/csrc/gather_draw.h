@@ -1,6 +1,7 @@
 // gather_draw.h - what the units that draw a sample's first ray about a caller-supplied surfel share: the gather queries (radiance.hip:
 // the drawn ray starts a path), the ambient queries (ambient.hip: the drawn ray is an occlusion query), the probe queries (probe.hip) and the
-// direct-light queries (direct.hip: the drawn ray is a shadow ray towards a drawn point on an emitter).  ONE copy of the item load and
+// direct-light queries (direct.hip: the drawn ray is a shadow ray towards a drawn point on an emitter; nee.hip draws the same from a path's
+// vertices).  ONE copy of the item load and
 // of the draw on the device, and of the argument checks of trt_gather_params on the host.  The two device functions are pure functions
 // of values (wave_run.h says why): moved here from radiance.hip as they stood, radiance_kernel compiles to the registers it had.
 #pragma once
@@ -90,6 +91,38 @@ TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, 
     DirectSample smp;
     smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
     smp.ray = ray_new(item.o, w);
+    smp.t_max = __builtin_sqrtf(d2) * shadow_end;
+    smp.c = v3(em[14], em[15], em[16]) * wgt;
+    return smp;
+}
+
+// The same sample for a surfel held in registers (nee.hip: a vertex of a path): x the point, n the unit normal on the side the light is
+// gathered on.  A copy of direct_draw's body less the item load, beside it and not under it: as a helper that direct_draw calls, the
+// compiler's output for direct.hip differs from what it was in its block labels.
+TRT_DEV DirectSample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
+    const float fe = (float)n_emitters;
+    const uint32_t pick = (uint32_t)(rng_random(g) * fe);
+    const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
+    const V3 a = v3(em[2], em[3], em[4]);
+    V3 y, nl;
+    if (__float_as_uint(em[0]) == 1u) {
+        const float ra = rng_random(g);
+        const float rb = rng_random(g);
+        y = (a + v3(em[5], em[6], em[7]) * ra) + v3(em[8], em[9], em[10]) * rb;
+        nl = v3(em[11], em[12], em[13]);
+    } else {
+        nl = normalized(random_in_unit_sphere_unit(g));
+        y = a + nl * em[5];
+    }
+    const V3 w = y - x;
+    const float d2 = dot(w, w);
+    const float cs = dot(n, w);
+    const float cl = __builtin_fabsf(dot(nl, w));
+    const float scale = (em[17] * fe) * 0.318309886f;
+    const float wgt = ((cs * cl) / (d2 * d2)) * scale;
+    DirectSample smp;
+    smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
+    smp.ray = ray_new(x, w);
     smp.t_max = __builtin_sqrtf(d2) * shadow_end;
     smp.c = v3(em[14], em[15], em[16]) * wgt;
     return smp;

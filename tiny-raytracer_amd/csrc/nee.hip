@@ -1,0 +1,394 @@
+// nee.hip — next-event queries: the paths of the radiance and gather queries with a device-drawn shadow ray to a caller-supplied emitter
+// table at every diffuse vertex (tinyrt.h trt_nee / trt_nee_device), written for gfx950 (CDNA4) only.
+//
+// The gather queries (radiance.hip) find the lights by chance at every bounce; the direct-light queries (direct.hip) aim at them, for the
+// surfel itself only.  This unit puts the two together.  Sample j of an item runs the path of CpuSampler::single_point_sampling
+// (cpu.rs:39-65) on RNG stream (seed, j, 0) with exactly the reference's draws, so its vertices are trt_radiance's / trt_gather's bit for
+// bit, and changes the loop body in two places:
+//   * at a hit a light's emission is Vec3::zero() when the path came there by a Lambertian scatter (after_diffuse);
+//   * after a Lambertian scatter that leaves bounce budget, gather_draw.h direct_draw_at on stream (seed, j, 2 + d) - d scatters before
+//     this vertex - draws an emitter point for the surfel (rec.p, rec.normal); a live sample whose shadow ray finds nothing in
+//     [0.001, t_max) adds  color = color + atten * c,  atten being the attenuation after the vertex's albedo.
+// The shadow ray stands for the emission the reference would find one hit later, which is why a light reached diffusely is hidden and why
+// the last vertex of the budget draws none: the expectation is the reference's at the same max_bounces.  The fold per item is
+// trt_radiance's, in registers: a lane owns an item for all samples of the call.
+//
+// The round loop is radiance_kernel's - refill, start, SHADE what is pending, WALK what is alive - with one more lane state: a shadow
+// ray is outstanding.  Its origin is the continuation ray's, so the lane keeps its direction, its t_max and what it would add.  There
+// is ONE walk call site: a round walks the lane's shadow ray if one is outstanding, else its path ray, through the same closest_hit /
+// closest_hit_resume call with a per-lane first t_best of t_max or +inf; "anything in [0.001, t_max)" is prim_best != PRIM_NONE after a
+// closest-hit walk that starts at t_max (rt_path.h: up to the first acceptance t_best is the caller's t_max).  A lane with a shadow ray
+// walks its continuation ray in the next round.  Every sample walks its own first segment (no kShareFirst): the two registers are
+// needed elsewhere.  There is no walk code in this file; the dynamic LDS is the queries' (wave_run.h), the launch rule too (query_plan.h).
+#include "gather_draw.h"
+#include "host_stage.h"
+#include "kernels.h"
+#include "query_plan.h"
+#include "rt_path.h"
+#include "scene_query.h"
+#include "wave_run.h"
+
+namespace trt {
+
+static_assert(sizeof(trt_nee_params) == 128 && offsetof(trt_nee_params, gather) == 0 && offsetof(trt_nee_params, shadow_end) == 96 &&
+              offsetof(trt_nee_params, source_is_diffuse) == 100 && offsetof(trt_nee_params, reserved) == 104, "trt_nee_params layout (tinyrt.h)");
+
+struct NeeArgs {
+    const float* items;              // n x (origin, direction) or n x (point, axis), used as given
+    const float* emitters;           // n_emitters x 20 words (trt_emitter)
+    float* radiance;                 // n x 3
+    float* moment2;                  // n x 3, or nullptr: not wanted
+    unsigned long long* counters;    // nullptr, or [CTR_SAMPLES], [CTR_RAYS] are added to
+    uint32_t n, rays_per_wave;       // wave w owns items [w * rays_per_wave, ...)
+    uint32_t slots, stragglers;      // as in query.hip QueryArgs
+    uint32_t samples_per_item;       // K
+    uint32_t first_stream;           // first_stream + n * K <= 2^32 (radiance_check): the stream index never wraps
+    uint32_t source;                 // enum trt_passes_source of the lobe kernels (the RAYS kernels do not read it)
+    float spread;                    // the cone lobe's sphere radius
+    uint32_t n_emitters;             // E: 1 .. 2^20
+    float shadow_end;                // in (0, 1]
+    uint32_t source_is_diffuse;      // after_diffuse at the first hit
+};
+constexpr int NEE_RAYS = 0, NEE_LOBE = 1;      // nee_kernel's SOURCE: the items are rays | surfels whose lobe is NeeArgs::source
+
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches nee_zero_kernel or nothing)
+template <int MODE, int WALK, int THREADS, int MINW, int SOURCE>
+__global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, RenderArgs ra, NeeArgs ga, const float4* __restrict__ leaf_list,
+                                                                 const uint4* __restrict__ nodes16) {
+    stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const float* __restrict__ const items = ga.items;
+    const float* __restrict__ const emitters = ga.emitters;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long begin64 = wave_begin<THREADS>(ga.rays_per_wave);
+    if (begin64 >= ga.n) return;                                            // (after the barriers above)
+    const uint32_t begin = (uint32_t)begin64;
+    const uint32_t count = wave_count(ga.n, ga.rays_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * ga.slots) + lane : nullptr;
+    const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
+    Counters<false> ctr;
+    constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
+
+    uint32_t cursor = 0;                                                    // wave-uniform
+    bool own = false, has_path = false, walking = false;                    // the lane owns an item; a path of it is under way; its walk is parked
+    bool pending = false, shadow = false;                                   // a finished path walk waits for its shade; a shadow ray is outstanding
+    bool after_diffuse = false;                                             // the path's last scatter was Lambertian (or the source counts as one)
+    uint32_t idx = 0, s = 0;
+    uint32_t hit_prim = PRIM_NONE;
+    float hit_t = 0.0f;
+    uint32_t n_samples = 0, n_rays = 0;
+    V3 acc = v3(0.0f, 0.0f, 0.0f), m2 = v3(0.0f, 0.0f, 0.0f);
+    V3 sh_d = v3(0.0f, 0.0f, 0.0f), sh_c = v3(0.0f, 0.0f, 0.0f);            // of the outstanding shadow ray: direction, atten * c
+    float sh_t = 0.0f;                                                      // and its t_max
+    Path p;
+    p.ray.o = v3(0.0f, 0.0f, 0.0f); p.ray.d = v3(0.0f, 0.0f, 0.0f);
+    p.color = v3(0.0f, 0.0f, 0.0f); p.atten = v3(0.0f, 0.0f, 0.0f);
+    p.remain = 0u;
+    p.rng.s0 = 0u; p.rng.s1 = 0u;
+    for (;;) {
+        // ---- refill: every lane without an item takes the next one of the run (begin + item < n: item < count <= n - begin) ----
+        const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
+        if (need != 0ull && cursor < count) {
+            const uint32_t item = cursor + wave_rank(need);
+            if (!own && item < count) {
+                idx = begin + item;
+                s = ra.sample_begin;
+                if (ra.accumulate) {
+                    const float* const a = ga.radiance + 3ull * idx;
+                    acc = v3(a[0], a[1], a[2]);
+                    if (ga.moment2) { const float* const m = ga.moment2 + 3ull * idx; m2 = v3(m[0], m[1], m[2]); }
+                } else {
+                    acc = v3(0.0f, 0.0f, 0.0f);
+                    m2 = v3(0.0f, 0.0f, 0.0f);
+                }
+                own = true;
+            }
+            cursor = wave_advance(cursor, need, count);
+        }
+        if (__builtin_amdgcn_ballot_w64(own) == 0ull) break;                // every lane is free and none could take an item: the run is done
+        if (own) {
+            // ---- start: the item's next sample; a drawn first ray has stream (seed, j, 1), the path starts fresh on (seed, j, 0) ----
+            if (!has_path) {
+                const uint32_t stream = ga.first_stream + idx * ga.samples_per_item + s;
+                if constexpr (SOURCE == NEE_RAYS) {
+                    p.ray = rad_load_ray(items, idx);                       // re-read: 24 bytes per sample against six registers per lane
+                } else {
+                    Rng g = rng_seed(ra.seed_key, stream, 1u);
+                    p.ray = gather_ray(items, idx, ga.source, ga.spread, g);
+                }
+                p.rng = rng_seed(ra.seed_key, stream, 0u);
+                p.color = v3(0.0f, 0.0f, 0.0f);
+                p.atten = v3(1.0f, 1.0f, 1.0f);
+                p.remain = ra.max_bounces;
+                after_diffuse = ga.source_is_diffuse != 0u;
+                has_path = true;
+                n_samples++;
+            }
+            // ---- shade what is pending ----
+            if (pending) {
+                pending = false;
+                ShadeInfo info;
+                info.hide_light = after_diffuse;
+                info.kind = SHADE_KIND_MISS;
+                info.normal = v3(0.0f, 0.0f, 0.0f);
+                if (shade_hit_info<MODE, false>(sc, p, hit_prim, hit_t, background, ctr, info)) {
+                    // imager.rs:35,50 and the second moment beside it, in the operation order of pixels_kernel
+                    acc = acc + p.color * ra.inv_spp;
+                    m2.x = m2.x + (p.color.x * p.color.x) * ra.inv_spp;
+                    m2.y = m2.y + (p.color.y * p.color.y) * ra.inv_spp;
+                    m2.z = m2.z + (p.color.z * p.color.z) * ra.inv_spp;
+                    has_path = false;
+                    s += 1u;
+                    if (s == ra.sample_end) {
+                        float* const a = ga.radiance + 3ull * idx;
+                        a[0] = acc.x; a[1] = acc.y; a[2] = acc.z;
+                        if (ga.moment2) { float* const m = ga.moment2 + 3ull * idx; m[0] = m2.x; m[1] = m2.y; m[2] = m2.z; }
+                        own = false;
+                    }
+                } else {
+                    // the path goes on (p.remain > 0 after the decrement): metal and glass are specular, a light they lead to is the path's own
+                    after_diffuse = info.kind == TRT_LAMBERTIAN;
+                    if (after_diffuse) {
+                        // ---- next event: the surfel is (the new ray's origin, the record's normal); d = max_bounces - remain - 1 scatters before ----
+                        const uint32_t stream = ga.first_stream + idx * ga.samples_per_item + s;
+                        Rng g = rng_seed(ra.seed_key, stream, 1u + (ra.max_bounces - p.remain));
+                        const DirectSample smp = direct_draw_at(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
+                        const V3 term = p.atten * smp.c;
+                        if (smp.live) {
+                            if (smp.t_max > kTMin) {
+                                shadow = true;
+                                sh_d = smp.ray.d; sh_t = smp.t_max; sh_c = term;
+                            } else {
+                                p.color = p.color + term;                   // an empty range: nothing is walked, the sample is unoccluded
+                            }
+                        }
+                    }
+                }
+            }
+            // ---- walk what is alive: the shadow ray first, the path ray in a round after it ----
+            if (has_path) {
+                Ray ray = p.ray;
+                if (shadow) ray.d = sh_d;
+                const float t_first = shadow ? sh_t : __builtin_inff();
+                bool done = true;
+                uint32_t prim;
+                float t;
+                if constexpr (kResumable) {
+                    Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, ray, false);        // a new walk, or the frame of a parked one
+                    if (walking) trav_unpark(stack, tr); else { tr.t_best = t_first; n_rays++; }
+                    const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+                    walking = !closest_hit_resume<MODE, false, WALK, false>(sc, ray, tr, ctr, ga.slots, stack, leaf_list, nodes16, ga.stragglers, entered);
+                    done = !walking;
+                    prim = tr.prim_best; t = tr.t_best;
+                } else {
+                    n_rays++;
+                    prim = closest_hit<MODE, false, WALK, false>(sc, ray, false, t, ctr, ga.slots, stack, leaf_list, nodes16, flat_reuse, t_first);
+                }
+                if (done) {
+                    if (shadow) {
+                        if (prim == PRIM_NONE) p.color = p.color + sh_c;
+                        shadow = false;
+                    } else {
+                        hit_prim = prim; hit_t = t;
+                        pending = true;
+                    }
+                }
+            }
+        }
+    }
+    flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
+}
+
+// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the 3 n floats of each buffer become 0.
+__global__ __launch_bounds__(256) void nee_zero_kernel(unsigned long long floats, float* __restrict__ radiance, float* __restrict__ moment2) {
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    if (i < floats) {
+        radiance[i] = 0.0f;
+        if (moment2) moment2[i] = 0.0f;
+    }
+}
+
+namespace {
+
+#define TRT_NEE(MODE, WALK, THREADS, MINW, SOURCE) \
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE>), MODE, WALK, THREADS, MINW}
+// The (scene mode, walk, workgroup shape) set of the other batch units, with the register-slot fallback (query_plan.h), so that every
+// scene has a kernel; one set for rays as given, one for the drawn lobes, as radiance.hip has.  A lane carries what a lane of the gather
+// kernel carries plus the outstanding shadow ray (direction, t_max, colour) and two flags: the launch bounds are the highest at which
+// the instantiation uses no scratch memory and spills no vector register (profiles/nee_resource_usage.txt).  The plan reports the bound
+// (kernel_waves_per_simd).
+const BatchKernel kNeeRayKernels[] = {
+    TRT_NEE(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
+    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_RAYS),
+    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_RAYS),
+    TRT_NEE(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
+    TRT_NEE(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
+    TRT_NEE(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
+};
+const BatchKernel kNeeLobeKernels[] = {
+    TRT_NEE(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
+    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_LOBE),
+    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_LOBE),
+    TRT_NEE(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
+    TRT_NEE(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
+    TRT_NEE(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
+};
+#undef TRT_NEE
+constexpr size_t kNeeShapes = sizeof(kNeeRayKernels) / sizeof(kNeeRayKernels[0]);
+static_assert(sizeof(kNeeLobeKernels) == sizeof(kNeeRayKernels), "one lobe instantiation per shape");
+
+// What a call asks of the device, after the checks.
+struct NeeCall {
+    RenderArgs ra;                   // of the path parameters (radiance_check)
+    uint32_t samples_per_item, first_stream;
+    uint32_t source;
+    float spread;
+    uint32_t n_emitters;
+    float shadow_end;
+    uint32_t source_is_diffuse;
+    bool nothing() const { return ra.sample_begin == ra.sample_end || ra.max_bounces == 0u; }
+};
+
+hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_items, uint32_t n, const float* d_emitters, float* d_radiance,
+                      float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (c.nothing()) {
+        // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
+        if (c.ra.accumulate) return hipSuccess;
+        const unsigned long long floats = 3ull * n;
+        hipLaunchKernelGGL(nee_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, floats, d_radiance, d_moment2);
+        return hipGetLastError();
+    }
+    SceneDev scd = qs.scene;
+    BatchLaunch b;
+    const hipError_t e = batch_prepare(scd, n, c.source == TRT_PASSES_RAYS ? kNeeRayKernels : kNeeLobeKernels, kNeeShapes, b);
+    if (e != hipSuccess) return e;
+    const trt_query_plan& q = b.q;
+    RenderArgs ra = c.ra;
+    ra.flat_reuse = qs.flat_reuse;
+    NeeArgs ga{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
+               c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse};
+    void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
+    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
+    timing_mark(stream, true);
+    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    timing_mark(stream, false);
+    return le;
+}
+
+constexpr uint32_t kMaxEmitters = 1u << 20;
+
+// What both forms check before any device work: trt_passes' rules on p->gather (radiance_check on the path, the source, the cone's spread,
+// the reserved words), trt_direct's on the table's size and on shadow_end, then this struct's own fields.  The table's entries are the
+// host form's to check: the device form cannot read them.
+int nee_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_params* p,
+              const float* radiance, NeeCall& c) {
+    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    const trt_gather_params& g = p->gather;
+    const int rc = radiance_check(s, items, n, &g.path, radiance, c.ra);
+    if (rc != TRT_OK) return rc;
+    if (g.lobe != TRT_PASSES_RAYS && g.lobe != TRT_PASSES_COSINE && g.lobe != TRT_PASSES_CONE)
+        return query_fail(TRT_ERR_INVALID_ARG, "source must be TRT_PASSES_RAYS, TRT_PASSES_COSINE or TRT_PASSES_CONE");
+    if (g.lobe == TRT_PASSES_CONE && !(g.spread >= 0.0f && g.spread < __builtin_inff()))
+        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
+    for (uint32_t r : g.reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    if (n > 0u && !emitters) return query_fail(TRT_ERR_INVALID_ARG, "null emitter table");
+    if (n > 0u && (n_emitters < 1u || n_emitters > kMaxEmitters)) return query_fail(TRT_ERR_INVALID_ARG, "n_emitters must be in 1 .. 2^20");
+    if (!(p->shadow_end > 0.0f && p->shadow_end <= 1.0f)) return query_fail(TRT_ERR_INVALID_ARG, "shadow_end must be in (0, 1]");
+    if (p->source_is_diffuse > 1u) return query_fail(TRT_ERR_INVALID_ARG, "source_is_diffuse must be 0 or 1");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    c.samples_per_item = g.path.samples_per_ray;
+    c.first_stream = g.path.first_stream;
+    c.source = g.lobe;
+    c.spread = g.lobe == TRT_PASSES_RAYS ? 0.0f : g.spread;
+    c.n_emitters = n_emitters;
+    c.shadow_end = p->shadow_end;
+    c.source_is_diffuse = p->source_is_diffuse;
+    return TRT_OK;
+}
+
+}  // namespace
+}  // namespace trt
+
+extern "C" {
+
+void trt_nee_params_default(trt_nee_params* out) {
+    if (!out) return;
+    *out = trt_nee_params{};
+    trt_gather_params_default(&out->gather);
+    out->gather.lobe = TRT_PASSES_COSINE;
+    out->shadow_end = 0.999f;
+}
+
+int trt_nee_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters, const trt_nee_params* p,
+                   float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::NeeCall c;
+    int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK || n == 0u) return rc;
+    rc = trt::query_require_device();
+    if (rc != TRT_OK) return rc;
+    trt::QueryScene qs;
+    rc = trt::query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = trt::launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance,
+                                         d_moment2, reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return trt::query_fail_hip(e, "next-event query launch");
+    return TRT_OK;
+}
+
+// Host buffers: device copies of the items, of the table and of the sums are the call's own (one allocation), one stream-ordered sequence
+// on the default stream, complete when the call returns.  The running sums go up only when the call continues them.
+int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_params* p, float* radiance,
+            float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::NeeCall c;
+        int rc = trt::nee_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        if (n == 0u) {
+            if (stats) *stats = trt_stats{};
+            return TRT_OK;
+        }
+        for (uint32_t k = 0; k < n_emitters; k++) {
+            if (emitters[k].kind > 1u) return trt::query_fail(TRT_ERR_INVALID_ARG, "emitter kind must be 0 (sphere) or 1 (quad)");
+            if (emitters[k].reserved[0] != 0u || emitters[k].reserved[1] != 0u)
+                return trt::query_fail(TRT_ERR_INVALID_ARG, "reserved words of an emitter must be zero");
+        }
+        rc = trt::query_require_device();
+        if (rc != TRT_OK) return rc;
+        trt::QueryScene qs;
+        rc = trt::query_scene_on_device(s, qs);
+        if (rc != TRT_OK) return rc;
+        const size_t items_b = (size_t)n * sizeof(trt_ray), table_b = (size_t)n_emitters * sizeof(trt_emitter), sums = (size_t)n * 12u;
+        trt::HostStage st("next-event query buffers");
+        const size_t r_items = st.reserve(items_b), r_table = st.reserve(table_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
+        st.reserve_counters();
+        st.alloc();
+        st.up(r_items, items, items_b, "hipMemcpy of the items");
+        st.up(r_table, emitters, table_b, "hipMemcpy of the emitters");
+        st.zero_counters();
+        // the running sums a pass continues go up; a pass that starts them reads nothing
+        if (c.ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
+        if (c.ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
+        st.time_begin();
+        if (st.ok())
+            st.run(trt::launch_nee(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_table), st.ptr<float>(r_rad), st.ptr<float>(r_m2), st.counters(),
+                                   nullptr),
+                   "next-event query launch");
+        const bool wrote = !(c.ra.accumulate && c.nothing());
+        if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
+        if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
+        st.read_stats(stats);
+        return st.finish();
+    });
+}
+
+// How launch_nee would launch n items on this scene: the two tables share their shapes and bounds, so the source does not enter.
+int trt_nee_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeLobeKernels, trt::kNeeShapes, out);
+}
+
+}  // extern "C"
