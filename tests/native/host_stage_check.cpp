@@ -1,6 +1,7 @@
 // host_stage_check.cpp — drives tiny-raytracer_amd/csrc/host_stage.h (the staging helper of the host-buffer forms of the C ABI and their
 // exception guard) on the simulated HIP runtime (tests/native/hipstub) under ASan+UBSan: the layout, a form that succeeds, every HIP call
-// of the helper failing once at every position, and the guard.  The "kernel" is a task on the default stream.
+// of the helper failing once at every position, and the guard.  The "kernel" is a task on the default stream.  Then the scaffold that
+// the sample queries' two forms share (sample_query_on_host, sample_query_on_device) with a fake launcher on a real scene handle.
 // TEST INFRASTRUCTURE: built and run by tests/test_host_sanitizers.py; prints "ok ..." lines and returns 0, or says what failed.
 #include <hip/hip_runtime.h>
 
@@ -232,11 +233,178 @@ static void guard() {
     printf("ok guard\n");
 }
 
+// ---- the sample queries' scaffold: what goes up, what comes down, what a failure says and leaves ----
+constexpr uint32_t kItems = 5;                  // items of 24 bytes: 120, a multiple of 8 and not of 16
+constexpr float kScribble = -777.0f;
+struct SampleIo {
+    float items[kItems * 6], table[20], sums[kItems * 3], sums2[kItems];
+    trt_stats stats;
+    SampleIo() {
+        for (uint32_t i = 0; i < kItems * 6; i++) items[i] = 0.5f * (float)i;
+        for (uint32_t i = 0; i < 20; i++) table[i] = 100.0f + (float)i;
+        for (uint32_t i = 0; i < kItems * 3; i++) sums[i] = 1000.0f + (float)i;
+        for (uint32_t i = 0; i < kItems; i++) sums2[i] = 2000.0f + (float)i;
+        memset(&stats, kSentinel, sizeof(stats));
+    }
+    // what the fake kernel leaves: (the sums as they went up | 0) + the item's first word (+ the table's first word); sums2 + 1
+    float want_sum(uint32_t i, bool accumulate, bool with_table) const { return (accumulate ? 1000.0f + (float)i : 0.0f) + items[6 * (i / 3)] + (with_table ? table[0] : 0.0f); }
+    float want_sum2(uint32_t i, bool accumulate) const { return (accumulate ? 2000.0f + (float)i : 0.0f) + 1.0f; }
+};
+struct SampleSeen { int calls = 0; bool table = false, sums2 = false, counters = false; };
+
+// One call of the host form as a unit makes it.  The fake launcher behaves as the units' launchers do: with nothing to trace it launches
+// nothing under accumulate - here it writes kScribble over the device sums instead, so that a download would show.
+static int sample_form(trt_scene* s, uint32_t n, SampleIo& io, bool with_table, bool with_sums2, bool accumulate, bool nothing, hipError_t refuse, SampleSeen& seen,
+                       trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        const trt::SampleHost h{io.items, (size_t)n * 24u, "copy of the items", with_table ? io.table : nullptr, sizeof(io.table), "copy of the table",
+                                io.sums, (size_t)n * 12u, with_sums2 ? io.sums2 : nullptr, (size_t)n * 4u, "copy of the second sums"};
+        return trt::sample_query_on_host(s, n, h, accumulate, nothing, "fake buffers", "fake launch", stats, [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+            seen.calls++;
+            seen.table = d.table != nullptr; seen.sums2 = d.sums2 != nullptr; seen.counters = d.counters != nullptr;
+            if (refuse != hipSuccess) return refuse;
+            CHECK(qs.scene.blob != nullptr, "the launcher got no scene");
+            const trt::SampleDev dev = d;
+            hipstub_enqueue(nullptr, [=] {
+                g_ran++;
+                for (uint32_t i = 0; i < 3u * n; i++) {
+                    if (nothing) { dev.sums[i] = kScribble; continue; }
+                    dev.sums[i] = (accumulate ? dev.sums[i] : 0.0f) + dev.items[6 * (i / 3)] + (dev.table ? dev.table[0] : 0.0f);
+                }
+                for (uint32_t i = 0; dev.sums2 && i < n; i++) dev.sums2[i] = nothing ? kScribble : (accumulate ? dev.sums2[i] : 0.0f) + 1.0f;
+                if (!nothing) for (int c = 0; c < trt::CTR_COUNT; c++) dev.counters[c] += 100ull + (unsigned)c;
+            });
+            return hipSuccess;
+        });
+    });
+}
+
+static trt_scene* sample_scene() {
+    trt_world* w = nullptr;
+    trt_world_create(&w);
+    trt_material m{TRT_LAMBERTIAN, {0.5f, 0.5f, 0.5f}, 0.0f};
+    trt_world_add_material(w, "m", &m);
+    for (int i = 0; i < 5; i++) trt_world_add_sphere(w, trt_vec3{(float)i, 0.0f, -3.0f}, 0.4f, 0);
+    trt_scene* s = nullptr;
+    if (trt_scene_create(w, &s) != TRT_OK) { printf("scene: %s\n", trt_last_error()); exit(2); }
+    trt_world_destroy(w);
+    return s;
+}
+
+static void sample_scaffold() {
+    trt_scene* s = sample_scene();
+    {
+        SampleIo io;                                                // the first call uploads the scene: its allocations stay with the handle
+        SampleSeen seen;
+        const int rc = sample_form(s, kItems, io, false, false, false, false, hipSuccess, seen, &io.stats);
+        CHECK(rc == TRT_OK, "first call: rc %d %s", rc, trt_last_error());
+    }
+    const long allocs = hipstub_live_allocations(), events = hipstub_live_events();
+    const SampleIo fresh;
+    // the second output and the table, wanted or not; a call that starts the sums and one that continues them
+    for (int with_table = 0; with_table < 2; with_table++)
+        for (int with_sums2 = 0; with_sums2 < 2; with_sums2++)
+            for (int accumulate = 0; accumulate < 2; accumulate++) {
+                SampleIo io;
+                SampleSeen seen;
+                g_ran = 0;
+                const int rc = sample_form(s, kItems, io, with_table != 0, with_sums2 != 0, accumulate != 0, false, hipSuccess, seen, &io.stats);
+                CHECK(rc == TRT_OK && g_ran == 1 && seen.calls == 1, "table %d sums2 %d accumulate %d: rc %d %s, ran %d", with_table, with_sums2, accumulate, rc, trt_last_error(), g_ran.load());
+                CHECK(seen.table == (with_table != 0) && seen.sums2 == (with_sums2 != 0) && seen.counters, "table %d sums2 %d: the launcher saw table %d sums2 %d counters %d",
+                      with_table, with_sums2, seen.table, seen.sums2, seen.counters);
+                bool right = true;
+                for (uint32_t i = 0; i < kItems * 3; i++) right = right && io.sums[i] == fresh.want_sum(i, accumulate != 0, with_table != 0);
+                for (uint32_t i = 0; i < kItems; i++) right = right && io.sums2[i] == (with_sums2 ? fresh.want_sum2(i, accumulate != 0) : fresh.sums2[i]);
+                CHECK(right, "table %d sums2 %d accumulate %d: the sums differ from the task's", with_table, with_sums2, accumulate);
+                CHECK(io.stats.samples == 100u + trt::CTR_SAMPLES && io.stats.rays == 100u + trt::CTR_RAYS && io.stats.kernel_ms >= 0.0, "stats: samples %llu rays %llu",
+                      (unsigned long long)io.stats.samples, (unsigned long long)io.stats.rays);
+                CHECK(hipstub_live_allocations() == allocs && hipstub_live_events() == events, "leak: %ld allocations, %ld events", hipstub_live_allocations() - allocs,
+                      hipstub_live_events() - events);
+            }
+    // the copies of a call, in order: the k-th hipMemcpy failing names the k-th of them, one past the last fails nothing
+    for (int cfg = 0; cfg < 16; cfg++) {
+        const bool with_table = cfg & 1, with_sums2 = cfg & 2, accumulate = cfg & 4, nothing = cfg & 8;
+        std::vector<const char*> want = {"copy of the items"};
+        if (with_table) want.push_back("copy of the table");
+        if (accumulate) want.push_back("hipMemcpy of the sums");
+        if (accumulate && with_sums2) want.push_back("copy of the second sums");
+        if (!(accumulate && nothing)) want.push_back("hipMemcpy of the results");
+        if (!(accumulate && nothing) && with_sums2) want.push_back("hipMemcpy of the results");
+        want.push_back("hipMemcpy of the counters");
+        for (size_t k = 0; k <= want.size(); k++) {
+            SampleIo io;
+            SampleSeen seen;
+            hipstub_fail_after("hipMemcpy", (long)k);
+            const int rc = sample_form(s, kItems, io, with_table, with_sums2, accumulate, nothing, hipSuccess, seen, &io.stats);
+            hipstub_fail_after("hipMemcpy", -1);
+            if (k == want.size()) CHECK(rc == TRT_OK, "copies of configuration %d: more than %zu", cfg, want.size());
+            else CHECK(rc == TRT_ERR_HIP && !strncmp(trt_last_error(), want[k], strlen(want[k])), "configuration %d, copy %zu: rc %d '%s', expected '%s'", cfg, k, rc, trt_last_error(), want[k]);
+            CHECK(hipstub_live_allocations() == allocs && hipstub_live_events() == events, "configuration %d, copy %zu: leak", cfg, k);
+        }
+    }
+    printf("ok sample scaffold: outputs and copies\n");
+    // accumulate with nothing to trace: both sums go up, nothing comes down, the host buffers keep their bytes (the device copies were scribbled over)
+    for (int nothing_accumulates = 0; nothing_accumulates < 2; nothing_accumulates++) {
+        SampleIo io;
+        SampleSeen seen;
+        const int rc = sample_form(s, kItems, io, true, true, nothing_accumulates != 0, true, hipSuccess, seen, &io.stats);
+        CHECK(rc == TRT_OK && seen.calls == 1, "nothing, accumulate %d: rc %d %s", nothing_accumulates, rc, trt_last_error());
+        if (nothing_accumulates) {
+            CHECK(!memcmp(io.sums, fresh.sums, sizeof(io.sums)) && !memcmp(io.sums2, fresh.sums2, sizeof(io.sums2)), "accumulate with nothing: the host sums were written");
+        } else {
+            CHECK(io.sums[0] == kScribble && io.sums2[kItems - 1] == kScribble, "nothing without accumulate: what the launcher wrote did not arrive");
+        }
+        CHECK(io.stats.samples == 0u && io.stats.rays == 0u, "nothing: stats %llu %llu", (unsigned long long)io.stats.samples, (unsigned long long)io.stats.rays);
+        CHECK(hipstub_live_allocations() == allocs && hipstub_live_events() == events, "nothing: leak");
+    }
+    printf("ok sample scaffold: nothing to trace\n");
+    {
+        SampleIo io;                                                // a failing launch: its label, no download, no stats, the allocation freed
+        SampleSeen seen;
+        g_ran = 0;
+        const int rc = sample_form(s, kItems, io, true, true, true, false, hipErrorInvalidConfiguration, seen, &io.stats);
+        CHECK(rc == TRT_ERR_HIP && !strncmp(trt_last_error(), "fake launch", 11) && seen.calls == 1 && g_ran == 0, "failing launch: rc %d '%s'", rc, trt_last_error());
+        CHECK(!memcmp(io.sums, fresh.sums, sizeof(io.sums)) && !memcmp(io.sums2, fresh.sums2, sizeof(io.sums2)) && Buffers::untouched(&io.stats, sizeof(io.stats)),
+              "failing launch: the outputs or the stats were written");
+        CHECK(hipstub_live_allocations() == allocs && hipstub_live_events() == events, "failing launch: %ld allocations, %ld events left", hipstub_live_allocations() - allocs,
+              hipstub_live_events() - events);
+    }
+    {
+        SampleIo io;                                                // a failing allocation: TRT_ERR_OOM under the buffers' label, no launch
+        SampleSeen seen;
+        hipstub_fail_after("hipMalloc", 0);
+        const int rc = sample_form(s, kItems, io, true, true, false, false, hipSuccess, seen, &io.stats);
+        hipstub_fail_after("hipMalloc", -1);
+        CHECK(rc == TRT_ERR_OOM && !strncmp(trt_last_error(), "fake buffers: ", 14) && seen.calls == 0, "failing allocation: rc %d '%s', %d launches", rc, trt_last_error(), seen.calls);
+        CHECK(!memcmp(io.sums, fresh.sums, sizeof(io.sums)) && Buffers::untouched(&io.stats, sizeof(io.stats)), "failing allocation: the outputs or the stats were written");
+        CHECK(hipstub_live_allocations() == allocs && hipstub_live_events() == events, "failing allocation: leak");
+    }
+    {
+        SampleIo io;                                                // n == 0: no device work at all, stats zeroed
+        SampleSeen seen;
+        const long mallocs = hipstub_malloc_calls();
+        const int rc = sample_form(s, 0, io, true, true, true, false, hipSuccess, seen, &io.stats);
+        CHECK(rc == TRT_OK && seen.calls == 0 && hipstub_malloc_calls() == mallocs && io.stats.samples == 0u && io.stats.kernel_ms == 0.0, "n == 0: rc %d, %d launches", rc, seen.calls);
+        CHECK(sample_form(s, 0, io, true, true, true, false, hipSuccess, seen, nullptr) == TRT_OK, "n == 0 without stats");
+    }
+    // the device form: n == 0 launches nothing; a launch's error comes back under its label
+    int launches = 0;
+    CHECK(trt::sample_query_on_device(s, 0, "fake launch", [&](const trt::QueryScene&) { launches++; return hipSuccess; }) == TRT_OK && launches == 0, "device form, n == 0");
+    CHECK(trt::sample_query_on_device(s, 3, "fake launch", [&](const trt::QueryScene& qs) { launches += qs.scene.blob != nullptr; return hipSuccess; }) == TRT_OK && launches == 1,
+          "device form: %s", trt_last_error());
+    CHECK(trt::sample_query_on_device(s, 3, "fake launch", [&](const trt::QueryScene&) { return hipErrorInvalidConfiguration; }) == TRT_ERR_HIP &&
+              !strncmp(trt_last_error(), "fake launch", 11), "device form, failing launch: '%s'", trt_last_error());
+    CHECK(hipstub_errors() == 0, "%ld protocol violations", hipstub_errors());
+    trt_scene_destroy(s);
+    printf("ok sample scaffold: failures and the device form\n");
+}
+
 int main() {
     layout();
     success();
     failure_injection();
     guard();
+    sample_scaffold();
     if (g_failures) { printf("%d check(s) failed\n", g_failures); return 1; }
     printf("ok all\n");
     return 0;

@@ -1,5 +1,5 @@
 // Test program (tests/test_gpu_shade.py builds and runs it on the GPU box): the shade cases of tests/shade_cases.py through the
-// product's shade_hit (rt_path.h), one case per lane, and a list of vectors through the helpers of rt_device.h (normalized, ray_new,
+// product's shade_hit and shade_hit_info (rt_path.h: two forwarders to one body), one case per lane, and a list of vectors through the helpers of rt_device.h (normalized, ray_new,
 // reflect, refract, near_zero, ray_at).  There is no shading or vector code in this file: the kernels load a Path, call shade_hit /
 // the helpers and write every word back for the Python side to compare with the oracle, bit for bit.
 //
@@ -14,6 +14,9 @@
 //            (shade, lambertian, metal, dielectric, light; zero without STATS).
 //            lds_carried <LDS, false, false>   lds_lazy <LDS, false, true>   lds_stats <LDS, true, false>
 //            global_carried <GLOBAL, false, false>   global_lazy <GLOBAL, false, true>
+//            lds_info, lds_info_hidden <LDS, false>   global_info, global_info_hidden <GLOBAL, false>: shade_hit_info, the forwarder
+//            the next-event queries call, with hide_light = 0 and = 1.  Words 16 .. 19 of a record are info.kind and info.normal as
+//            the call left them (set beforehand to 0x5EEDC0DE and to three floats of those bits), word 20 is 0.
 //            The GLOBAL forms read the same packed scene through SceneAcc<MODE_GLOBAL> (same element offsets, rt_path.h), whatever its size.
 //            The LAZY forms run only the cases flagged lazy_ok and leave the others' records unwritten (0xCDCDCDCD); a flagged case whose
 //            incoming colour is not +0, or a flag on a scene without SceneLayout::lazy_color, is refused (exit status 3).
@@ -76,6 +79,47 @@ __global__ __launch_bounds__(kThreads) void shade_kernel(SceneDev scd, const uin
     }
 }
 
+// The same cases through shade_hit_info<MODE, false>: the 16 words above, then what the call left in `info`.
+constexpr uint32_t kInfoUnset = 0x5EEDC0DEu;
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void shade_info_kernel(SceneDev scd, const uint32_t* __restrict__ cases, const uint2* __restrict__ tasks,
+                                                              uint32_t n_tasks, uint32_t hide_light, uint32_t* __restrict__ out) {
+    stage_scene_to_lds<MODE>(scd);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    if (wave >= n_tasks) return;
+    const uint2 task = tasks[wave];
+    for (uint32_t base = 0; base < task.y; base += 64u) {
+        if (base + lane >= task.y) continue;
+        const uint32_t idx = task.x + base + lane;
+        const uint32_t* c = cases + (size_t)kCaseWords * idx;
+        auto f = [&](uint32_t k) { return __uint_as_float(c[k]); };
+        Path p;
+        p.ray.o = v3(f(0), f(1), f(2));
+        p.ray.d = v3(f(3), f(4), f(5));
+        p.color = v3(f(6), f(7), f(8));
+        p.atten = v3(f(9), f(10), f(11));
+        p.remain = c[12];
+        p.rng.s0 = c[13]; p.rng.s1 = c[14];
+        Counters<false> ctr;
+        ShadeInfo info;
+        info.hide_light = hide_light != 0u;
+        info.kind = kInfoUnset;
+        info.normal = v3(__uint_as_float(kInfoUnset), __uint_as_float(kInfoUnset), __uint_as_float(kInfoUnset));
+        const bool ended = shade_hit_info<MODE, false>(sc, p, c[15], f(16), v3(f(17), f(18), f(19)), ctr, info);
+        uint32_t* o = out + (size_t)kOutWords * idx;
+        o[0] = __float_as_uint(p.ray.o.x); o[1] = __float_as_uint(p.ray.o.y); o[2] = __float_as_uint(p.ray.o.z);
+        o[3] = __float_as_uint(p.ray.d.x); o[4] = __float_as_uint(p.ray.d.y); o[5] = __float_as_uint(p.ray.d.z);
+        o[6] = __float_as_uint(p.color.x); o[7] = __float_as_uint(p.color.y); o[8] = __float_as_uint(p.color.z);
+        o[9] = __float_as_uint(p.atten.x); o[10] = __float_as_uint(p.atten.y); o[11] = __float_as_uint(p.atten.z);
+        o[12] = p.remain; o[13] = p.rng.s0; o[14] = p.rng.s1;
+        o[15] = ended ? 1u : 0u;
+        o[16] = info.kind;
+        o[17] = __float_as_uint(info.normal.x); o[18] = __float_as_uint(info.normal.y); o[19] = __float_as_uint(info.normal.z);
+        o[20] = 0u;
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void vec_kernel(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
@@ -125,6 +169,16 @@ void launch(const SceneDev& scd, const uint32_t* d_cases, const uint2* d_tasks, 
     if (lds > 64u * 1024u) { std::printf("LDS plan of %zu bytes\n", lds); std::exit(3); }
     CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(shade_kernel<MODE, STATS, LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((shade_kernel<MODE, STATS, LAZY>), dim3((n_tasks + 3u) / 4u), dim3(kThreads), lds, 0, scd, d_cases, d_tasks, n_tasks, d_out);
+    CHECK(hipGetLastError());
+    CHECK(hipDeviceSynchronize());
+}
+
+template <int MODE>
+void launch_info(const SceneDev& scd, const uint32_t* d_cases, const uint2* d_tasks, uint32_t n_tasks, uint32_t hide_light, uint32_t* d_out) {
+    const size_t lds = MODE == MODE_LDS ? ((size_t)scd.L.hot_bytes + 15u) & ~(size_t)15u : 0u;
+    if (lds > 64u * 1024u) { std::printf("LDS plan of %zu bytes\n", lds); std::exit(3); }
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(shade_info_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((shade_info_kernel<MODE>), dim3((n_tasks + 3u) / 4u), dim3(kThreads), lds, 0, scd, d_cases, d_tasks, n_tasks, hide_light, d_out);
     CHECK(hipGetLastError());
     CHECK(hipDeviceSynchronize());
 }
@@ -201,15 +255,21 @@ unsigned long long run_scene(const char* scene_path, const char* cases_path, con
     if (!ft) { std::printf("cannot write %s\n", out_txt); std::exit(3); }
     std::fprintf(ft, "layout n_spheres=%u n_quads=%u n_materials=%u hot_bytes=%u lazy_color=%u\n", L.n_spheres, L.n_quads, L.n_materials, L.hot_bytes, L.lazy_color);
     std::vector<uint32_t> h((size_t)kOutWords * n_cases);
-    const char* names[5] = {"lds_carried", "lds_lazy", "lds_stats", "global_carried", "global_lazy"};
-    for (int v = 0; v < 5; v++) {
+    constexpr int kVariants = 9;
+    const char* names[kVariants] = {"lds_carried", "lds_lazy", "lds_stats", "global_carried", "global_lazy",
+                                    "lds_info", "lds_info_hidden", "global_info", "global_info_hidden"};
+    for (int v = 0; v < kVariants; v++) {
         CHECK(hipMemset(d_out, 0xCD, out_bytes));
         switch (v) {
             case 0: launch<MODE_LDS, false, false>(scd, d_cases, d_tasks, n_tasks, d_out); break;
             case 1: launch<MODE_LDS, false, true>(scd, d_cases, d_tasks, n_tasks, d_out); break;
             case 2: launch<MODE_LDS, true, false>(scd, d_cases, d_tasks, n_tasks, d_out); break;
             case 3: launch<MODE_GLOBAL, false, false>(scd, d_cases, d_tasks, n_tasks, d_out); break;
-            default: launch<MODE_GLOBAL, false, true>(scd, d_cases, d_tasks, n_tasks, d_out); break;
+            case 4: launch<MODE_GLOBAL, false, true>(scd, d_cases, d_tasks, n_tasks, d_out); break;
+            case 5: launch_info<MODE_LDS>(scd, d_cases, d_tasks, n_tasks, 0u, d_out); break;
+            case 6: launch_info<MODE_LDS>(scd, d_cases, d_tasks, n_tasks, 1u, d_out); break;
+            case 7: launch_info<MODE_GLOBAL>(scd, d_cases, d_tasks, n_tasks, 0u, d_out); break;
+            default: launch_info<MODE_GLOBAL>(scd, d_cases, d_tasks, n_tasks, 1u, d_out); break;
         }
         CHECK(hipMemcpy(h.data(), d_out, out_bytes, hipMemcpyDeviceToHost));
         write_words(out_bin, h, v == 0 ? "wb" : "ab");
@@ -220,7 +280,7 @@ unsigned long long run_scene(const char* scene_path, const char* cases_path, con
     CHECK(hipFree(d_tasks));
     CHECK(hipFree(d_cases));
     CHECK(hipFree(d_blob));
-    return 5ull * n_cases;
+    return (unsigned long long)kVariants * n_cases;
 }
 
 unsigned long long run_vectors(const char* in_path, const char* out_path) {

@@ -837,6 +837,29 @@ def expectations(orc, sc, cases):
     return np.stack([expectation(orc, sc, c) for c in cases])
 
 
+SHADE_KIND_MISS = 0xFFFFFFFF
+INFO_UNSET = 0x5EEDC0DE                  # what the harness puts into ShadeInfo::kind and ::normal before the call
+
+
+def info_expectation(orc, sc, case, hide_light):
+    """shade_hit_info (rt_path.h, the next-event queries' forwarder): the 16 words of expectation(), then info.kind and info.normal -
+    the material kind and the oracle's hit-record normal, or SHADE_KIND_MISS and the untouched normal on a miss.  With hide_light a
+    light's emission is Vec3::zero(): colour = colour + attenuation * 0 in the body's operation order; nothing else moves."""
+    w = expectation(orc, sc, case)
+    if case["geo"] < 0:
+        return np.concatenate([w, np.array([SHADE_KIND_MISS] + [INFO_UNSET] * 3, np.uint32)])
+    kind = sc.material(case["geo"])[0]
+    if hide_light and kind == LIGHT:
+        with np.errstate(all="ignore"):
+            w[6:9] = bits(case["color"] + case["atten"] * np.zeros(3, F))
+    rec = sc.hit(orc, case["geo"], case["o"], case["d"])
+    return np.concatenate([w, np.array([kind], np.uint32), bits(_vec(rec.normal))])
+
+
+def info_expectations(orc, sc, cases, hide_light):
+    return np.stack([info_expectation(orc, sc, c, hide_light) for c in cases])
+
+
 def kind_of_case(sc, c):
     """Material kind of the case's primitive (-1: miss)."""
     return -1 if c["geo"] < 0 else int(sc.material(c["geo"])[0])

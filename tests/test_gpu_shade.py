@@ -6,7 +6,9 @@ back the 15 words of the Path, `ended` and, with STATS, the five shade counters;
 refract, near_zero and ray_at on a list of vectors.  Instantiations: <LDS, false, false>, <LDS, false, true>, <LDS, true, false>,
 <GLOBAL, false, false>, <GLOBAL, false, true>; the GLOBAL forms read the same 32-primitive scene through SceneAcc<MODE_GLOBAL> (the
 accessor allows it: same element offsets), so "the zoo from global memory" needs no padding spheres.  The LAZY forms run only the
-cases whose incoming colour is +0 on the scene with lazy_color set (the harness refuses anything else).  Each scene's list goes in
+cases whose incoming colour is +0 on the scene with lazy_color set (the harness refuses anything else).  shade_hit is a forwarder
+to rt_path.h's one shade body; the other forwarder, shade_hit_info<LDS | GLOBAL, false> of the next-event queries, runs on the same
+lists with hide_light = 0 and = 1 and also writes back info.kind and info.normal (INFO_VARIANTS).  Each scene's list goes in
 twice: one wave takes the whole shuffled list 64 cases at a time (its lanes hold different material kinds), then waves with lists
 of 1, 63, 64 and 65 cases from a second shuffle; every copy must equal the expectation.
 
@@ -50,6 +52,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tiny-raytracer_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 VARIANTS = ["lds_carried", "lds_lazy", "lds_stats", "global_carried", "global_lazy"]
+# shade_hit_info<LDS | GLOBAL, false>, the forwarder of the next-event queries, with hide_light = 0 and = 1: the harness runs them behind VARIANTS
+INFO_VARIANTS = ["lds_info", "lds_info_hidden", "global_info", "global_info_hidden"]
 RUNS = ["zoo", "hot", "control"]
 
 
@@ -105,10 +109,10 @@ def results(orc, harness, tmp_path_factory):
         with open(d / f"{run}.txt") as f:
             lines = f.read().split("\n")
         layout = dict(kv.split("=") for kv in lines[0].split()[1:])
-        assert [l.split()[1] for l in lines[1:] if l.startswith("variant ")] == VARIANTS
+        assert [l.split()[1] for l in lines[1:] if l.startswith("variant ")] == VARIANTS + INFO_VARIANTS
         assert int(layout["lazy_color"]) == (0 if run == "hot" else 1) and int(layout["n_spheres"]) + int(layout["n_quads"]) == 32
-        words = np.fromfile(d / f"{run}.bin", np.uint32).reshape(len(VARIANTS), len(res[run]["order"]), S.OUT_WORDS)
-        res[run]["out"] = dict(zip(VARIANTS, words))
+        words = np.fromfile(d / f"{run}.bin", np.uint32).reshape(len(VARIANTS + INFO_VARIANTS), len(res[run]["order"]), S.OUT_WORDS)
+        res[run]["out"] = dict(zip(VARIANTS + INFO_VARIANTS, words))
         res[run]["lazy_ok"] = np.array([c["lazy_ok"] for c in res[run]["cases"]])[res[run]["order"]]
     res["vec"] = (vc, S.vector_expectation(orc, vc), np.fromfile(d / "vec.bin", np.uint32).reshape(len(vc), S.VEC_OUT_WORDS))
     return res
@@ -161,6 +165,38 @@ def test_shade_counters_equal_the_case_counts(results, run):
     print(f"\n{run}: shade counters {ctr.sum(axis=0).tolist()} (shade, lambertian, metal, dielectric, light)")
     assert np.array_equal(ctr, want)
     assert (res["out"]["lds_carried"][:, 16:21] == 0).all()
+
+
+@pytest.mark.parametrize("variant", INFO_VARIANTS)
+@pytest.mark.parametrize("run", ["zoo", "hot"])
+def test_shade_hit_info_equals_the_oracle_and_the_carried_form(results, orc, run, variant):
+    """shade_hit_info is the body of shade_hit behind a second forwarder.  hide_light = 0: the 15 Path words and `ended` are the
+    *_carried variant's bit for bit (hence the oracle's), info.kind is the oracle's material kind or SHADE_KIND_MISS, info.normal has the
+    bits of the oracle's hit-record normal (a miss leaves it alone).  hide_light = 1: the same, except that at a light the colour is
+    colour + attenuation * 0.  By the bits, NaN words included."""
+    res = results[run]
+    hidden = variant.endswith("_hidden")
+    got = res["out"][variant]
+    exp = S.info_expectations(orc, res["sc"], res["cases"], hidden)[res["order"]]
+    kinds = np.array([S.kind_of_case(res["sc"], c) for c in res["cases"]])[res["order"]]
+    carried = res["out"][variant.split("_")[0] + "_carried"]
+    moved = (got[:, :16] != carried[:, :16]).any(axis=1)
+    bad = got[:, :20] != exp
+    print(f"\n{run} {variant}: {len(exp)} answers, {int(bad.sum())} differing words ({int(bad[:, :16].sum())} path, {int(bad[:, 16].sum())} kind, "
+          f"{int(bad[:, 17:20].sum())} normal); {int(moved.sum())} answers differ from the carried form, {int((kinds == S.LIGHT).sum())} lights, "
+          f"{int((kinds < 0).sum())} misses")
+    where = np.flatnonzero(bad.any(axis=1))
+    assert len(where) == 0, (run, variant, f"{len(where)} answers differ", [describe(res, p) for p in where[:8]], got[where[:3]], exp[where[:3]])
+    assert (got[:, 20] == 0).all()
+    assert (got[kinds < 0, 16] == S.SHADE_KIND_MISS).all() and (got[kinds >= 0, 16] == kinds[kinds >= 0]).all()
+    assert (kinds < 0).any() and (kinds == S.LIGHT).any()
+    if hidden:
+        # only a light's colour can move, and one whose emission is seen does: the path words of every other hit stay the carried form's
+        assert not moved[kinds != S.LIGHT].any()
+        assert np.array_equal(np.delete(got[:, :16], [6, 7, 8], axis=1), np.delete(carried[:, :16], [6, 7, 8], axis=1))
+        assert moved[kinds == S.LIGHT].any()
+    else:
+        assert not moved.any()
 
 
 def test_vector_helpers_equal_the_oracle(results):

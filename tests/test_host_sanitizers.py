@@ -101,7 +101,10 @@ def test_host_stage_under_asan_ubsan(tmp_path):
     """The staging helper of the host-buffer forms (csrc/host_stage.h: trt_intersect, trt_radiance, trt_render_aov, ... go through it) and
     their exception guard, on the simulated runtime: the layout against the forms' formulas, a form whose "kernel" is a task on the
     default stream, every HIP call of the helper failing once at every position (status, message, no later step, no leak, the next
-    call works), and std::bad_alloc thrown with the allocation and the events alive."""
+    call works), and std::bad_alloc thrown with the allocation and the events alive.  Then the scaffold the sample queries' forms share
+    (sample_query_on_host / _on_device) with a fake launcher on a scene handle: the optional table and second sums wanted or not, the
+    sums up only under accumulate and down unless it accumulates nothing, every copy of every configuration failing once, a failing
+    launch (its label, the allocation freed), a failing allocation (TRT_ERR_OOM under the buffers' label), n == 0."""
     exe = str(tmp_path / "host_stage_check")
     n = os.path.join(ROOT, "tests", "native")
     c = os.path.join(ROOT, "tiny-raytracer_amd", "csrc")

@@ -305,3 +305,22 @@ def test_the_case_list_kills_the_mutants(lists, orc):
         assert diff == 0 and n >= 10 ** 6 and "\n  10  " in S.__doc__
     if 11 in not_distinguished:
         assert "\n  11  " in S.__doc__
+
+
+def test_info_expectation_of_shade_hit_info(lists, orc):
+    """What tests/test_gpu_shade.py expects of shade_hit_info: the record of expectation() plus (kind, normal).  The normal is the
+    oracle's hit-record normal and has the bits of the restatement's; hide_light moves nothing but the colour words of a light, to
+    colour + attenuation * 0; a miss reports SHADE_KIND_MISS and leaves the normal alone."""
+    for name, (sc, cases, traces) in lists.items():
+        seen, hidden = S.info_expectations(orc, sc, cases, False), S.info_expectations(orc, sc, cases, True)
+        assert seen.shape == (len(cases), 20) and np.array_equal(seen[:, :16], S.expectations(orc, sc, cases))
+        kinds = np.array([S.kind_of_case(sc, c) for c in cases])
+        assert np.array_equal(seen[kinds >= 0, 16], kinds[kinds >= 0].astype(np.uint32)) and (seen[kinds < 0, 16:] == [S.SHADE_KIND_MISS] + [S.INFO_UNSET] * 3).all()
+        for i in np.flatnonzero(kinds >= 0):
+            assert np.array_equal(seen[i, 17:20], S.bits(traces[i]["normal"])), (name, i, cases[i]["cls"])
+        differs = (seen != hidden).any(axis=1)
+        assert not differs[kinds != S.LIGHT].any() and differs[kinds == S.LIGHT].any()
+        assert np.array_equal(np.delete(seen, [6, 7, 8], axis=1), np.delete(hidden, [6, 7, 8], axis=1))
+        with np.errstate(all="ignore"):
+            for i in np.flatnonzero(kinds == S.LIGHT):
+                assert np.array_equal(hidden[i, 6:9], S.bits(cases[i]["color"] + cases[i]["atten"] * np.zeros(3, F)))

@@ -42,7 +42,7 @@ struct AmbientArgs {
     uint32_t samples_per_item;       // K
     uint32_t first_stream;           // first_stream + n * K <= 2^32 (gather_check): the stream index never wraps
     uint32_t seed_key;               // kernels.h rng_seed_key
-    uint32_t sample_begin, sample_end;      // begin < end (launch_ambient: an empty range launches ambient_zero_kernel or nothing)
+    uint32_t sample_begin, sample_end;      // begin < end (launch_ambient: an empty range launches query_plan.h batch_zero or nothing)
     uint32_t accumulate;
     uint32_t lobe;                   // TRT_LOBE_COSINE or TRT_LOBE_CONE: the same for every lane of the launch
     float spread;
@@ -169,13 +169,6 @@ __global__ __launch_bounds__(THREADS, MINW) void ambient_kernel(SceneDev scd, Am
     flush_counters<false>(aa.counters, n_samples, n_rays, ctr);
 }
 
-// An empty sample range without accumulate: the n entries become 0 (radiance_zero_kernel's idea with this unit's sizes).
-__global__ __launch_bounds__(256) void ambient_zero_kernel(unsigned long long n, float* __restrict__ visibility, float* __restrict__ bent) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;         // [0, n): the floats of visibility; [0, 3 n): those of bent
-    if (i < n) visibility[i] = 0.0f;
-    if (bent && i < 3ull * n) bent[i] = 0.0f;
-}
-
 namespace {
 
 #define TRT_AMBIENT(MODE, WALK, THREADS, MINW) \
@@ -210,9 +203,7 @@ hipError_t launch_ambient(const QueryScene& qs, const AmbientCall& c, const floa
     if (c.nothing()) {
         // the sums start at 0, or stay
         if (c.ra.accumulate) return hipSuccess;
-        const unsigned long long floats = d_bent ? 3ull * n : (unsigned long long)n;
-        hipLaunchKernelGGL(ambient_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, (unsigned long long)n, d_visibility, d_bent);
-        return hipGetLastError();
+        return batch_zero(d_visibility, n, d_bent, 3ull * n, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -223,11 +214,7 @@ hipError_t launch_ambient(const QueryScene& qs, const AmbientCall& c, const floa
                    c.ra.seed_key, c.ra.sample_begin, c.ra.sample_end, c.ra.accumulate, c.lobe.lobe, c.lobe.spread, c.ra.inv_spp, c.max_distance,
                    qs.flat_reuse};
     void* args[] = {&scd, &aa, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
 
 // What both forms check before any device work: trt_gather's rules on p->gather (its max_bounces and background are carried along
@@ -260,54 +247,26 @@ void trt_ambient_params_default(trt_ambient_params* out) {
 int trt_ambient_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_ambient_params* p, float* d_visibility, float* d_bent,
                        uint64_t* d_counters, void* stream) {
     trt::AmbientCall c;
-    int rc = trt::ambient_check(s, d_items, n, p, d_visibility, c);
-    if (rc != TRT_OK || n == 0u) return rc;
-    rc = trt::query_require_device();
+    const int rc = trt::ambient_check(s, d_items, n, p, d_visibility, c);
     if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_ambient(qs, c, reinterpret_cast<const float*>(d_items), n, d_visibility, d_bent,
-                                             reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "ambient query launch");
-    return TRT_OK;
+    return trt::sample_query_on_device(s, n, "ambient query launch", [&](const trt::QueryScene& qs) {
+        return trt::launch_ambient(qs, c, reinterpret_cast<const float*>(d_items), n, d_visibility, d_bent,
+                                   reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    });
 }
 
-// Host buffers: device copies of the items and of the sums are the call's own (one allocation), one stream-ordered sequence on the
-// default stream, complete when the call returns.  The running sums go up only when the call continues them.
+// Host buffers: staged by host_stage.h sample_query_on_host (items | visibility | bent, if wanted | counters).
 int trt_ambient(trt_scene* s, const trt_ray* items, uint32_t n, const trt_ambient_params* p, float* visibility, float* bent, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::AmbientCall c;
-        int rc = trt::ambient_check(s, items, n, p, visibility, c);
+        const int rc = trt::ambient_check(s, items, n, p, visibility, c);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t items_b = (size_t)n * sizeof(trt_ray), vis_b = (size_t)n * 4u, bent_b = (size_t)n * 12u;
-        trt::HostStage st("ambient query buffers");
-        const size_t r_items = st.reserve(items_b), r_vis = st.reserve(vis_b), r_bent = st.reserve(bent_b, bent != nullptr);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_items, items, items_b, "hipMemcpy of the items");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (c.ra.accumulate) st.up(r_vis, visibility, vis_b, "hipMemcpy of the sums");
-        if (c.ra.accumulate) st.up(r_bent, bent, bent_b, "hipMemcpy of the bent sums");
-        st.time_begin();
-        if (st.ok())
-            st.run(trt::launch_ambient(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_vis), st.ptr<float>(r_bent), st.counters(), nullptr),
-                   "ambient query launch");
-        const bool wrote = !(c.ra.accumulate && c.nothing());
-        if (wrote) st.down(visibility, r_vis, vis_b, "hipMemcpy of the results");
-        if (wrote) st.down(bent, r_bent, bent_b, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", nullptr, 0u, "", visibility, (size_t)n * 4u, bent,
+                                (size_t)n * 12u, "hipMemcpy of the bent sums"};
+        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "ambient query buffers", "ambient query launch", stats,
+                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+                                             return trt::launch_ambient(qs, c, d.items, n, d.sums, d.sums2, d.counters, nullptr);
+                                         });
     });
 }
 

@@ -39,7 +39,7 @@ struct DirectArgs {
     uint32_t samples_per_item;       // K
     uint32_t first_stream;           // first_stream + n * K <= 2^32 (radiance_check): the stream index never wraps
     uint32_t seed_key;               // kernels.h rng_seed_key
-    uint32_t sample_begin, sample_end;      // begin < end (launch_direct: an empty range launches direct_zero_kernel or nothing)
+    uint32_t sample_begin, sample_end;      // begin < end (launch_direct: an empty range launches query_plan.h batch_zero or nothing)
     uint32_t accumulate;
     uint32_t n_emitters;             // E: 1 .. 2^20
     float inv_k;                     // 1.0f / float(K)
@@ -171,15 +171,6 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, Dir
     flush_counters<false>(da.counters, n_samples, n_rays, ctr);
 }
 
-// An empty sample range without accumulate: the 3 n floats of each buffer become 0 (radiance_zero_kernel's idea).
-__global__ __launch_bounds__(256) void direct_zero_kernel(unsigned long long floats, float* __restrict__ radiance, float* __restrict__ moment2) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    if (i < floats) {
-        radiance[i] = 0.0f;
-        if (moment2) moment2[i] = 0.0f;
-    }
-}
-
 namespace {
 
 #define TRT_DIRECT(MODE, WALK, THREADS, MINW) \
@@ -214,9 +205,7 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
     if (c.nothing()) {
         // the sums start at 0, or stay
         if (c.ra.accumulate) return hipSuccess;
-        const unsigned long long floats = 3ull * n;
-        hipLaunchKernelGGL(direct_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, floats, d_radiance, d_moment2);
-        return hipGetLastError();
+        return batch_zero(d_radiance, 3ull * n, d_moment2, 3ull * n, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -227,25 +216,18 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
                   c.first_stream, c.ra.seed_key, c.ra.sample_begin, c.ra.sample_end, c.ra.accumulate, c.n_emitters, c.ra.inv_spp, c.shadow_end,
                   qs.flat_reuse};
     void* args[] = {&scd, &da, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
-
-constexpr uint32_t kMaxEmitters = 1u << 20;
 
 // What both forms check before any device work: trt_radiance's rules on p->path (its max_bounces and background are carried along unread),
 // then the table's size and this struct's own fields.  The table's entries are the host form's to check: the device form cannot read them.
 int direct_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_params* p,
                  const float* radiance, DirectCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
-    const int rc = radiance_check(s, items, n, &p->path, radiance, c.ra);
+    int rc = radiance_check(s, items, n, &p->path, radiance, c.ra);
     if (rc != TRT_OK) return rc;
-    if (n > 0u && !emitters) return query_fail(TRT_ERR_INVALID_ARG, "null emitter table");
-    if (n > 0u && (n_emitters < 1u || n_emitters > kMaxEmitters)) return query_fail(TRT_ERR_INVALID_ARG, "n_emitters must be in 1 .. 2^20");
-    if (!(p->shadow_end > 0.0f && p->shadow_end <= 1.0f)) return query_fail(TRT_ERR_INVALID_ARG, "shadow_end must be in (0, 1]");
+    rc = emitter_table_check(n, emitters, n_emitters, p->shadow_end);
+    if (rc != TRT_OK) return rc;
     for (uint32_t r : p->reserved)
         if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
     c.samples_per_item = p->path.samples_per_ray;
@@ -270,62 +252,31 @@ void trt_direct_params_default(trt_direct_params* out) {
 int trt_direct_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters, const trt_direct_params* p,
                       float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
     trt::DirectCall c;
-    int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK || n == 0u) return rc;
-    rc = trt::query_require_device();
+    const int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance,
-                                            d_moment2, reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "direct-light query launch");
-    return TRT_OK;
+    return trt::sample_query_on_device(s, n, "direct-light query launch", [&](const trt::QueryScene& qs) {
+        return trt::launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
+                                  reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    });
 }
 
-// Host buffers: device copies of the items, of the table and of the sums are the call's own (one allocation), one stream-ordered sequence
-// on the default stream, complete when the call returns.  The running sums go up only when the call continues them.
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).  The table's
+// entries are checked where n > 0, ahead of any device work.
 int trt_direct(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_params* p,
                float* radiance, float* moment2, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::DirectCall c;
         int rc = trt::direct_check(s, items, n, emitters, n_emitters, p, radiance, c);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        for (uint32_t k = 0; k < n_emitters; k++) {
-            if (emitters[k].kind > 1u) return trt::query_fail(TRT_ERR_INVALID_ARG, "emitter kind must be 0 (sphere) or 1 (quad)");
-            if (emitters[k].reserved[0] != 0u || emitters[k].reserved[1] != 0u)
-                return trt::query_fail(TRT_ERR_INVALID_ARG, "reserved words of an emitter must be zero");
-        }
-        rc = trt::query_require_device();
+        rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t items_b = (size_t)n * sizeof(trt_ray), table_b = (size_t)n_emitters * sizeof(trt_emitter), sums = (size_t)n * 12u;
-        trt::HostStage st("direct-light query buffers");
-        const size_t r_items = st.reserve(items_b), r_table = st.reserve(table_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_items, items, items_b, "hipMemcpy of the items");
-        st.up(r_table, emitters, table_b, "hipMemcpy of the emitters");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (c.ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
-        if (c.ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
-        st.time_begin();
-        if (st.ok())
-            st.run(trt::launch_direct(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_table), st.ptr<float>(r_rad), st.ptr<float>(r_m2), st.counters(),
-                                      nullptr),
-                   "direct-light query launch");
-        const bool wrote = !(c.ra.accumulate && c.nothing());
-        if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
-        if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        const size_t sums = (size_t)n * 12u;
+        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                                "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "direct-light query buffers", "direct-light query launch", stats,
+                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+                                             return trt::launch_direct(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                         });
     });
 }
 

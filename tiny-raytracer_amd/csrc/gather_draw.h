@@ -1,9 +1,11 @@
 // gather_draw.h - what the units that draw a sample's first ray about a caller-supplied surfel share: the gather queries (radiance.hip:
 // the drawn ray starts a path), the ambient queries (ambient.hip: the drawn ray is an occlusion query), the probe queries (probe.hip) and the
 // direct-light queries (direct.hip: the drawn ray is a shadow ray towards a drawn point on an emitter; nee.hip draws the same from a path's
-// vertices).  ONE copy of the item load and
-// of the draw on the device, and of the argument checks of trt_gather_params on the host.  The two device functions are pure functions
-// of values (wave_run.h says why): moved here from radiance.hip as they stood, radiance_kernel compiles to the registers it had.
+// vertices: ONE body, direct_draw_from, behind both).  ONE copy of the item load and of the draws on the device, and on the host of the
+// argument checks that more than one unit applies: trt_gather_params as a gather takes it (gather_check) and as passes.hip and nee.hip
+// take it (gather_source_check), trt_radiance_params (radiance_check), the emitter table of direct.hip and nee.hip.  The device
+// functions are pure functions of values (wave_run.h says why): moved here from radiance.hip as they stood, radiance_kernel compiles to
+// the registers it had.
 #pragma once
 
 #include "kernels.h"
@@ -65,8 +67,10 @@ struct DirectSample {
     float t_max;                     // sqrt(d2) * shadow_end: the walk covers [0.001, t_max)
     bool live;
 };
-TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters, uint32_t n_emitters,
-                                 float shadow_end, Rng& g) {
+// ONE body for the surfel of an item (direct.hip) and for a surfel held in registers (nee.hip): `surfel()` returns (point, normal) as
+// a Ray and is called after the draws, where an item is loaded so that its six registers are free while the draws run.
+template <class Surfel>
+TRT_DEV DirectSample direct_draw_from(Surfel surfel, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
     const float fe = (float)n_emitters;
     const uint32_t pick = (uint32_t)(rng_random(g) * fe);
     const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
@@ -81,7 +85,7 @@ TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, 
         nl = normalized(random_in_unit_sphere_unit(g));
         y = a + nl * em[5];
     }
-    const Ray item = rad_load_ray(items, idx);                              // after the draws, as in gather_ray
+    const Ray item = surfel();
     const V3 w = y - item.o;
     const float d2 = dot(w, w);
     const float cs = dot(item.d, w);
@@ -95,37 +99,13 @@ TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, 
     smp.c = v3(em[14], em[15], em[16]) * wgt;
     return smp;
 }
-
-// The same sample for a surfel held in registers (nee.hip: a vertex of a path): x the point, n the unit normal on the side the light is
-// gathered on.  A copy of direct_draw's body less the item load, beside it and not under it: as a helper that direct_draw calls, the
-// compiler's output for direct.hip differs from what it was in its block labels.
+TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters, uint32_t n_emitters,
+                                 float shadow_end, Rng& g) {
+    return direct_draw_from([&] { return rad_load_ray(items, idx); }, emitters, n_emitters, shadow_end, g);
+}
+// The same sample for a vertex of a path (nee.hip): x the point, n the unit normal on the side the light is gathered on.
 TRT_DEV DirectSample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
-    const float fe = (float)n_emitters;
-    const uint32_t pick = (uint32_t)(rng_random(g) * fe);
-    const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
-    const V3 a = v3(em[2], em[3], em[4]);
-    V3 y, nl;
-    if (__float_as_uint(em[0]) == 1u) {
-        const float ra = rng_random(g);
-        const float rb = rng_random(g);
-        y = (a + v3(em[5], em[6], em[7]) * ra) + v3(em[8], em[9], em[10]) * rb;
-        nl = v3(em[11], em[12], em[13]);
-    } else {
-        nl = normalized(random_in_unit_sphere_unit(g));
-        y = a + nl * em[5];
-    }
-    const V3 w = y - x;
-    const float d2 = dot(w, w);
-    const float cs = dot(n, w);
-    const float cl = __builtin_fabsf(dot(nl, w));
-    const float scale = (em[17] * fe) * 0.318309886f;
-    const float wgt = ((cs * cl) / (d2 * d2)) * scale;
-    DirectSample smp;
-    smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
-    smp.ray = ray_new(x, w);
-    smp.t_max = __builtin_sqrtf(d2) * shadow_end;
-    smp.c = v3(em[14], em[15], em[16]) * wgt;
-    return smp;
+    return direct_draw_from([&] { Ray r; r.o = x; r.d = n; return r; }, emitters, n_emitters, shadow_end, g);
 }
 
 // The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.
@@ -134,11 +114,18 @@ struct Lobe {
     float spread;
 };
 
-// Host side, declared here because the same two units need it and nothing else does: a header for one declaration would be a file more.
+// Host side (defined in radiance.hip), declared here because only the units that include this header need it: a header for a handful of
+// declarations would be a file more.
 // What the forms that take a trt_gather_params check before any device work: trt_radiance's rules on p->path, then the lobe; and the
 // kernel arguments of the parameters (radiance.hip).  `sums`: the required output buffer.
 int gather_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_gather_params* p, const float* sums, RenderArgs& ra, Lobe& lobe);
 // trt_radiance's own rules on a trt_radiance_params, which gather_check applies to p->path and the probe queries (probe.hip) to theirs.
 int radiance_check(const trt_scene* s, const trt_ray* rays, uint32_t n, const trt_radiance_params* p, const float* sums, RenderArgs& ra);
+// The source, spread and reserved words of a trt_gather_params whose lobe word is an enum trt_passes_source (passes.hip, nee.hip).
+int gather_source_check(const trt_gather_params& g);
+// The emitter table's pointer and size (1 .. 2^20 where n > 0) and shadow_end, for both forms of direct.hip and nee.hip; and the table's
+// entries, which only a host form can read.
+int emitter_table_check(uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, float shadow_end);
+int emitter_entries_check(const trt_emitter* emitters, uint32_t n_emitters);
 
 }  // namespace trt

@@ -1,7 +1,10 @@
 // host_stage.h - what the host-buffer forms of the C ABI (trt_intersect, trt_radiance, trt_render_aov, ...) share: host code only, no kernel.
 // Such a form stages the caller's buffers through ONE device allocation of its own on the default stream and returns when the answer is
-// back.  HostStage is that allocation for the length of one call; host_form is the guard the form runs in.  Needs scene_query.h
-// (query_fail, query_fail_hip) and nothing of the kernel units: tests/native/host_stage_check.cpp drives it on the simulated runtime.
+// back.  HostStage is that allocation for the length of one call; host_form is the guard the form runs in.  The sample queries
+// (radiance, gather, ambient, probe, passes, direct, nee) stage the same buffers in the same order, so the body of their host form and
+// of their device form is here too, with the unit's launcher as a callable: sample_query_on_host, sample_query_on_device.  Needs
+// scene_query.h (query_fail, query_fail_hip, the scene on the device) and nothing of the kernel units: tests/native/host_stage_check.cpp
+// drives all of it on the simulated runtime.
 #pragma once
 
 #include <new>
@@ -83,5 +86,70 @@ class HostStage {
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     unsigned long long h_ctr_[CTR_COUNT] = {0};
 };
+
+// ---- the sample queries (radiance, gather, ambient, direct, nee, probe, passes): ONE copy of what their two forms do around the launch ----
+
+// The device form after the unit's checks: buffers in HBM, asynchronous on the caller's stream.  launch(qs) is the unit's launcher.
+template <class Launch>
+int sample_query_on_device(trt_scene* s, uint32_t n, const char* what, Launch&& launch) {
+    if (n == 0u) return TRT_OK;
+    int rc = query_require_device();
+    if (rc != TRT_OK) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    const hipError_t e = launch(qs);
+    if (e != hipSuccess) return query_fail_hip(e, what);
+    return TRT_OK;
+}
+
+// The caller's buffers of a host form, and the device copies its launcher is given.
+struct SampleHost {
+    const void* items; size_t items_b; const char* items_what;      // the rays or surfels, and what their copy is called
+    const void* table; size_t table_b; const char* table_what;      // a second input (the emitter table), or nullptr
+    float* sums; size_t sums_b;                                      // the required output
+    float* sums2; size_t sums2_b; const char* sums2_what;            // the optional output (nullptr: not wanted), and what its upload is called
+};
+struct SampleDev {
+    const float *items, *table;
+    float *sums, *sums2;             // sums2: nullptr where the caller's is
+    unsigned long long* counters;
+};
+// The host form after the unit's checks (inside host_form).  Device copies of the inputs and of the sums are the call's own (one
+// allocation), one stream-ordered sequence on the default stream, complete when the call returns.  The running sums go up only when
+// the call continues them (accumulate), and come down unless it continues them with nothing to trace.  launch(qs, dev) is the unit's
+// launcher on the default stream.
+template <class Launch>
+int sample_query_on_host(trt_scene* s, uint32_t n, const SampleHost& h, bool accumulate, bool nothing, const char* buffers, const char* what,
+                         trt_stats* stats, Launch&& launch) {
+    if (n == 0u) {
+        if (stats) *stats = trt_stats{};
+        return TRT_OK;
+    }
+    int rc = query_require_device();
+    if (rc != TRT_OK) return rc;
+    QueryScene qs;
+    rc = query_scene_on_device(s, qs);
+    if (rc != TRT_OK) return rc;
+    HostStage st(buffers);
+    const size_t r_items = st.reserve(h.items_b), r_table = st.reserve(h.table_b, h.table != nullptr), r_sums = st.reserve(h.sums_b),
+                 r_sums2 = st.reserve(h.sums2_b, h.sums2 != nullptr);
+    st.reserve_counters();
+    st.alloc();
+    st.up(r_items, h.items, h.items_b, h.items_what);
+    st.up(r_table, h.table, h.table_b, h.table_what);
+    st.zero_counters();
+    // the running sums a pass continues go up; a pass that starts them reads nothing
+    if (accumulate) st.up(r_sums, h.sums, h.sums_b, "hipMemcpy of the sums");
+    if (accumulate) st.up(r_sums2, h.sums2, h.sums2_b, h.sums2_what);
+    st.time_begin();
+    if (st.ok())
+        st.run(launch(qs, SampleDev{st.ptr<float>(r_items), st.ptr<float>(r_table), st.ptr<float>(r_sums), st.ptr<float>(r_sums2), st.counters()}), what);
+    const bool wrote = !(accumulate && nothing);
+    if (wrote) st.down(h.sums, r_sums, h.sums_b, "hipMemcpy of the results");
+    if (wrote) st.down(h.sums2, r_sums2, h.sums2_b, "hipMemcpy of the results");
+    st.read_stats(stats);
+    return st.finish();
+}
 
 }  // namespace trt

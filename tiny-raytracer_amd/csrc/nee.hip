@@ -6,7 +6,8 @@
 // (cpu.rs:39-65) on RNG stream (seed, j, 0) with exactly the reference's draws, so its vertices are trt_radiance's / trt_gather's bit for
 // bit, and changes the loop body in two places:
 //   * at a hit a light's emission is Vec3::zero() when the path came there by a Lambertian scatter (after_diffuse);
-//   * after a Lambertian scatter that leaves bounce budget, gather_draw.h direct_draw_at on stream (seed, j, 2 + d) - d scatters before
+//   * after a Lambertian scatter that leaves bounce budget, gather_draw.h direct_draw_at (direct_draw's body, given the vertex in place
+//     of an item) on stream (seed, j, 2 + d) - d scatters before
 //     this vertex - draws an emitter point for the surfel (rec.p, rec.normal); a live sample whose shadow ray finds nothing in
 //     [0.001, t_max) adds  color = color + atten * c,  atten being the attenuation after the vertex's albedo.
 // The shadow ray stands for the emission the reference would find one hit later, which is why a light reached diffusely is hidden and why
@@ -20,6 +21,9 @@
 // closest-hit walk that starts at t_max (rt_path.h: up to the first acceptance t_best is the caller's t_max).  A lane with a shadow ray
 // walks its continuation ray in the next round.  Every sample walks its own first segment (no kShareFirst): the two registers are
 // needed elsewhere.  There is no walk code in this file; the dynamic LDS is the queries' (wave_run.h), the launch rule too (query_plan.h).
+// Nor is there shading code: shade_hit_info is rt_path.h's one shade body with the lines that read and fill ShadeInfo switched on.  The
+// two forms' scaffold is host_stage.h's, the checks of the source and of the emitter table are gather_draw.h's, shared with passes.hip
+// and direct.hip.
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -51,7 +55,7 @@ struct NeeArgs {
 };
 constexpr int NEE_RAYS = 0, NEE_LOBE = 1;      // nee_kernel's SOURCE: the items are rays | surfels whose lobe is NeeArgs::source
 
-// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches nee_zero_kernel or nothing)
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches query_plan.h batch_zero or nothing)
 template <int MODE, int WALK, int THREADS, int MINW, int SOURCE>
 __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, RenderArgs ra, NeeArgs ga, const float4* __restrict__ leaf_list,
                                                                  const uint4* __restrict__ nodes16) {
@@ -201,15 +205,6 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
     flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
 }
 
-// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the 3 n floats of each buffer become 0.
-__global__ __launch_bounds__(256) void nee_zero_kernel(unsigned long long floats, float* __restrict__ radiance, float* __restrict__ moment2) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    if (i < floats) {
-        radiance[i] = 0.0f;
-        if (moment2) moment2[i] = 0.0f;
-    }
-}
-
 namespace {
 
 #define TRT_NEE(MODE, WALK, THREADS, MINW, SOURCE) \
@@ -257,9 +252,7 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     if (c.nothing()) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
         if (c.ra.accumulate) return hipSuccess;
-        const unsigned long long floats = 3ull * n;
-        hipLaunchKernelGGL(nee_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, floats, d_radiance, d_moment2);
-        return hipGetLastError();
+        return batch_zero(d_radiance, 3ull * n, d_moment2, 3ull * n, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -271,14 +264,8 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     NeeArgs ga{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
                c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
-
-constexpr uint32_t kMaxEmitters = 1u << 20;
 
 // What both forms check before any device work: trt_passes' rules on p->gather (radiance_check on the path, the source, the cone's spread,
 // the reserved words), trt_direct's on the table's size and on shadow_end, then this struct's own fields.  The table's entries are the
@@ -287,17 +274,12 @@ int nee_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_em
               const float* radiance, NeeCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     const trt_gather_params& g = p->gather;
-    const int rc = radiance_check(s, items, n, &g.path, radiance, c.ra);
+    int rc = radiance_check(s, items, n, &g.path, radiance, c.ra);
     if (rc != TRT_OK) return rc;
-    if (g.lobe != TRT_PASSES_RAYS && g.lobe != TRT_PASSES_COSINE && g.lobe != TRT_PASSES_CONE)
-        return query_fail(TRT_ERR_INVALID_ARG, "source must be TRT_PASSES_RAYS, TRT_PASSES_COSINE or TRT_PASSES_CONE");
-    if (g.lobe == TRT_PASSES_CONE && !(g.spread >= 0.0f && g.spread < __builtin_inff()))
-        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
-    for (uint32_t r : g.reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
-    if (n > 0u && !emitters) return query_fail(TRT_ERR_INVALID_ARG, "null emitter table");
-    if (n > 0u && (n_emitters < 1u || n_emitters > kMaxEmitters)) return query_fail(TRT_ERR_INVALID_ARG, "n_emitters must be in 1 .. 2^20");
-    if (!(p->shadow_end > 0.0f && p->shadow_end <= 1.0f)) return query_fail(TRT_ERR_INVALID_ARG, "shadow_end must be in (0, 1]");
+    rc = gather_source_check(g);
+    if (rc != TRT_OK) return rc;
+    rc = emitter_table_check(n, emitters, n_emitters, p->shadow_end);
+    if (rc != TRT_OK) return rc;
     if (p->source_is_diffuse > 1u) return query_fail(TRT_ERR_INVALID_ARG, "source_is_diffuse must be 0 or 1");
     for (uint32_t r : p->reserved)
         if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
@@ -327,62 +309,31 @@ void trt_nee_params_default(trt_nee_params* out) {
 int trt_nee_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters, const trt_nee_params* p,
                    float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
     trt::NeeCall c;
-    int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK || n == 0u) return rc;
-    rc = trt::query_require_device();
+    const int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance,
-                                         d_moment2, reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "next-event query launch");
-    return TRT_OK;
+    return trt::sample_query_on_device(s, n, "next-event query launch", [&](const trt::QueryScene& qs) {
+        return trt::launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
+                               reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    });
 }
 
-// Host buffers: device copies of the items, of the table and of the sums are the call's own (one allocation), one stream-ordered sequence
-// on the default stream, complete when the call returns.  The running sums go up only when the call continues them.
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).  The table's
+// entries are checked where n > 0, ahead of any device work.
 int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_params* p, float* radiance,
             float* moment2, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::NeeCall c;
         int rc = trt::nee_check(s, items, n, emitters, n_emitters, p, radiance, c);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        for (uint32_t k = 0; k < n_emitters; k++) {
-            if (emitters[k].kind > 1u) return trt::query_fail(TRT_ERR_INVALID_ARG, "emitter kind must be 0 (sphere) or 1 (quad)");
-            if (emitters[k].reserved[0] != 0u || emitters[k].reserved[1] != 0u)
-                return trt::query_fail(TRT_ERR_INVALID_ARG, "reserved words of an emitter must be zero");
-        }
-        rc = trt::query_require_device();
+        rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t items_b = (size_t)n * sizeof(trt_ray), table_b = (size_t)n_emitters * sizeof(trt_emitter), sums = (size_t)n * 12u;
-        trt::HostStage st("next-event query buffers");
-        const size_t r_items = st.reserve(items_b), r_table = st.reserve(table_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_items, items, items_b, "hipMemcpy of the items");
-        st.up(r_table, emitters, table_b, "hipMemcpy of the emitters");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (c.ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
-        if (c.ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
-        st.time_begin();
-        if (st.ok())
-            st.run(trt::launch_nee(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_table), st.ptr<float>(r_rad), st.ptr<float>(r_m2), st.counters(),
-                                   nullptr),
-                   "next-event query launch");
-        const bool wrote = !(c.ra.accumulate && c.nothing());
-        if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
-        if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        const size_t sums = (size_t)n * 12u;
+        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                                "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "next-event query buffers", "next-event query launch", stats,
+                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+                                             return trt::launch_nee(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                         });
     });
 }
 

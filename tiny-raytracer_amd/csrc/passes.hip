@@ -59,7 +59,7 @@ TRT_DEV void passes_fold(float (&acc)[6 * NB], uint32_t slot, const V3& c, float
     }
 }
 
-// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_passes: nothing to trace launches passes_zero_kernel or nothing)
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_passes: nothing to trace launches query_plan.h batch_zero or nothing)
 template <int MODE, int WALK, int THREADS, int MINW, int NB>
 __global__ __launch_bounds__(THREADS, MINW) void passes_kernel(SceneDev scd, RenderArgs ra, PassesArgs ga, const float4* __restrict__ leaf_list,
                                                                     const uint4* __restrict__ nodes16) {
@@ -188,14 +188,6 @@ __global__ __launch_bounds__(THREADS, MINW) void passes_kernel(SceneDev scd, Ren
     flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
 }
 
-// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the 6 B n floats of `passes` and the n of `spent` become 0.
-__global__ __launch_bounds__(256) void passes_zero_kernel(unsigned long long floats, float* __restrict__ passes, unsigned long long n,
-                                                         float* __restrict__ spent) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    if (i < floats) passes[i] = 0.0f;
-    if (spent && i < n) spent[i] = 0.0f;                                    // n <= floats
-}
-
 namespace {
 
 #define TRT_PASSES(MODE, WALK, THREADS, MINW, NB) \
@@ -240,10 +232,7 @@ hipError_t launch_passes(const QueryScene& qs, const PassesCall& c, const float*
     if (c.nothing()) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64) and is no sample of the call; the sums start at 0, or stay
         if (c.ra.accumulate) return hipSuccess;
-        const unsigned long long floats = 6ull * c.bins * n;
-        hipLaunchKernelGGL(passes_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, floats, d_passes,
-                           (unsigned long long)n, d_spent);
-        return hipGetLastError();
+        return batch_zero(d_passes, 6ull * c.bins * n, d_spent, n, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -255,11 +244,7 @@ hipError_t launch_passes(const QueryScene& qs, const PassesCall& c, const float*
     PassesArgs ga{d_items, d_passes, d_spent, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item, c.first_stream,
                   c.source, c.spread, c.bins};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
 
 // What both forms check before any device work: trt_radiance's rules on p->gather.path (radiance_check), trt_gather's on the source where
@@ -267,14 +252,10 @@ hipError_t launch_passes(const QueryScene& qs, const PassesCall& c, const float*
 int passes_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_passes_params* p, const float* passes, PassesCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     const trt_gather_params& g = p->gather;
-    const int rc = radiance_check(s, items, n, &g.path, passes, c.ra);
+    int rc = radiance_check(s, items, n, &g.path, passes, c.ra);
     if (rc != TRT_OK) return rc;
-    if (g.lobe != TRT_PASSES_RAYS && g.lobe != TRT_PASSES_COSINE && g.lobe != TRT_PASSES_CONE)
-        return query_fail(TRT_ERR_INVALID_ARG, "source must be TRT_PASSES_RAYS, TRT_PASSES_COSINE or TRT_PASSES_CONE");
-    if (g.lobe == TRT_PASSES_CONE && !(g.spread >= 0.0f && g.spread < __builtin_inff()))
-        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
-    for (uint32_t r : g.reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    rc = gather_source_check(g);
+    if (rc != TRT_OK) return rc;
     if (p->depth_bins < 1u || p->depth_bins > 4u) return query_fail(TRT_ERR_INVALID_ARG, "depth_bins must be 1, 2, 3 or 4");
     for (uint32_t r : p->reserved)
         if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
@@ -302,54 +283,26 @@ void trt_passes_params_default(trt_passes_params* out) {
 int trt_passes_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_passes_params* p, float* d_passes, float* d_spent,
                       uint64_t* d_counters, void* stream) {
     trt::PassesCall c;
-    int rc = trt::passes_check(s, d_items, n, p, d_passes, c);
-    if (rc != TRT_OK || n == 0u) return rc;
-    rc = trt::query_require_device();
+    const int rc = trt::passes_check(s, d_items, n, p, d_passes, c);
     if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_passes(qs, c, reinterpret_cast<const float*>(d_items), n, d_passes, d_spent,
-                                            reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "passes query launch");
-    return TRT_OK;
+    return trt::sample_query_on_device(s, n, "passes query launch", [&](const trt::QueryScene& qs) {
+        return trt::launch_passes(qs, c, reinterpret_cast<const float*>(d_items), n, d_passes, d_spent, reinterpret_cast<unsigned long long*>(d_counters),
+                                  static_cast<hipStream_t>(stream));
+    });
 }
 
-// Host buffers: device copies of the items and of the sums are the call's own (one allocation), one stream-ordered sequence on the
-// default stream, complete when the call returns.  The running sums go up only when the call continues them.
+// Host buffers: staged by host_stage.h sample_query_on_host (items | passes | spent, if wanted | counters).
 int trt_passes(trt_scene* s, const trt_ray* items, uint32_t n, const trt_passes_params* p, float* passes, float* spent, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::PassesCall c;
-        int rc = trt::passes_check(s, items, n, p, passes, c);
+        const int rc = trt::passes_check(s, items, n, p, passes, c);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t items_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 24u * c.bins, spent_b = (size_t)n * 4u;
-        trt::HostStage st("passes query buffers");
-        const size_t r_items = st.reserve(items_b), r_passes = st.reserve(sums), r_spent = st.reserve(spent_b, spent != nullptr);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_items, items, items_b, "hipMemcpy of the items");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (c.ra.accumulate) st.up(r_passes, passes, sums, "hipMemcpy of the sums");
-        if (c.ra.accumulate) st.up(r_spent, spent, spent_b, "hipMemcpy of the spent shares");
-        st.time_begin();
-        if (st.ok())
-            st.run(trt::launch_passes(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_passes), st.ptr<float>(r_spent), st.counters(), nullptr),
-                   "passes query launch");
-        const bool wrote = !(c.ra.accumulate && c.nothing());
-        if (wrote) st.down(passes, r_passes, sums, "hipMemcpy of the results");
-        if (wrote) st.down(spent, r_spent, spent_b, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", nullptr, 0u, "", passes, (size_t)n * 24u * c.bins, spent,
+                                (size_t)n * 4u, "hipMemcpy of the spent shares"};
+        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "passes query buffers", "passes query launch", stats,
+                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+                                             return trt::launch_passes(qs, c, d.items, n, d.sums, d.sums2, d.counters, nullptr);
+                                         });
     });
 }
 

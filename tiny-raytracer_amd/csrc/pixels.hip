@@ -286,11 +286,7 @@ hipError_t launch_pixels(const QueryScene& qs, const CameraDev& cd, RenderArgs r
     ra.flat_reuse = qs.flat_reuse;
     PixelsArgs pa{d_pixels, d_count, d_accum, d_moment2, d_counters, n, npixels, q.rays_per_wave, q.leaf_slots, q.stragglers};
     void* args[] = {&scd, &cam, &ra, &pa, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
 
 // What both forms check before any device work.  npixels = pixels of the local image.

@@ -68,7 +68,7 @@ TRT_DEV void probe_fold(float (&acc)[3 * NC], const V3& d, const V3& c, float in
     }
 }
 
-// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_probe: nothing to trace launches probe_zero_kernel or nothing)
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_probe: nothing to trace launches query_plan.h batch_zero or nothing)
 template <int MODE, int WALK, int THREADS, int MINW, int NC>
 __global__ __launch_bounds__(THREADS, MINW) void probe_kernel(SceneDev scd, RenderArgs ra, ProbeArgs ga, const float4* __restrict__ leaf_list,
                                                                    const uint4* __restrict__ nodes16) {
@@ -180,12 +180,6 @@ __global__ __launch_bounds__(THREADS, MINW) void probe_kernel(SceneDev scd, Rend
     flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
 }
 
-// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the 3 C n floats become 0 (radiance_zero_kernel's idea).
-__global__ __launch_bounds__(256) void probe_zero_kernel(unsigned long long floats, float* __restrict__ sh) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
-    if (i < floats) sh[i] = 0.0f;
-}
-
 namespace {
 
 #define TRT_PROBE(MODE, WALK, THREADS, MINW, NC) \
@@ -230,9 +224,7 @@ hipError_t launch_probe(const QueryScene& qs, const ProbeCall& c, const float* d
     if (c.nothing()) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
         if (c.ra.accumulate) return hipSuccess;
-        const unsigned long long floats = 3ull * c.coeffs() * n;
-        hipLaunchKernelGGL(probe_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, floats, d_sh);
-        return hipGetLastError();
+        return batch_zero(d_sh, 3ull * c.coeffs() * n, nullptr, 0ull, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -243,11 +235,7 @@ hipError_t launch_probe(const QueryScene& qs, const ProbeCall& c, const float* d
     ra.flat_reuse = qs.flat_reuse;
     ProbeArgs ga{d_items, d_sh, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item, c.first_stream, c.hemisphere, c.coeffs()};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
 
 // What both forms check before any device work: trt_radiance's rules on p->path (radiance.hip radiance_check), then this struct's fields.
@@ -282,50 +270,25 @@ void trt_probe_params_default(trt_probe_params* out) {
 
 int trt_probe_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_probe_params* p, float* d_sh, uint64_t* d_counters, void* stream) {
     trt::ProbeCall c;
-    int rc = trt::probe_check(s, d_items, n, p, d_sh, c);
-    if (rc != TRT_OK || n == 0u) return rc;
-    rc = trt::query_require_device();
+    const int rc = trt::probe_check(s, d_items, n, p, d_sh, c);
     if (rc != TRT_OK) return rc;
-    trt::QueryScene qs;
-    rc = trt::query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = trt::launch_probe(qs, c, reinterpret_cast<const float*>(d_items), n, d_sh, reinterpret_cast<unsigned long long*>(d_counters),
-                                           static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return trt::query_fail_hip(e, "probe query launch");
-    return TRT_OK;
+    return trt::sample_query_on_device(s, n, "probe query launch", [&](const trt::QueryScene& qs) {
+        return trt::launch_probe(qs, c, reinterpret_cast<const float*>(d_items), n, d_sh, reinterpret_cast<unsigned long long*>(d_counters),
+                                 static_cast<hipStream_t>(stream));
+    });
 }
 
-// Host buffers: device copies of the items and of the sums are the call's own (one allocation), one stream-ordered sequence on the
-// default stream, complete when the call returns.  The running sums go up only when the call continues them.
+// Host buffers: staged by host_stage.h sample_query_on_host (items | sums | counters; there is no second output).
 int trt_probe(trt_scene* s, const trt_ray* items, uint32_t n, const trt_probe_params* p, float* sh, trt_stats* stats) {
     return trt::host_form([&]() -> int {
         trt::ProbeCall c;
-        int rc = trt::probe_check(s, items, n, p, sh, c);
+        const int rc = trt::probe_check(s, items, n, p, sh, c);
         if (rc != TRT_OK) return rc;
-        if (n == 0u) {
-            if (stats) *stats = trt_stats{};
-            return TRT_OK;
-        }
-        rc = trt::query_require_device();
-        if (rc != TRT_OK) return rc;
-        trt::QueryScene qs;
-        rc = trt::query_scene_on_device(s, qs);
-        if (rc != TRT_OK) return rc;
-        const size_t items_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u * c.coeffs();
-        trt::HostStage st("probe query buffers");
-        const size_t r_items = st.reserve(items_b), r_sh = st.reserve(sums);
-        st.reserve_counters();
-        st.alloc();
-        st.up(r_items, items, items_b, "hipMemcpy of the items");
-        st.zero_counters();
-        // the running sums a pass continues go up; a pass that starts them reads nothing
-        if (c.ra.accumulate) st.up(r_sh, sh, sums, "hipMemcpy of the sums");
-        st.time_begin();
-        if (st.ok()) st.run(trt::launch_probe(qs, c, st.ptr<float>(r_items), n, st.ptr<float>(r_sh), st.counters(), nullptr), "probe query launch");
-        const bool wrote = !(c.ra.accumulate && c.nothing());
-        if (wrote) st.down(sh, r_sh, sums, "hipMemcpy of the results");
-        st.read_stats(stats);
-        return st.finish();
+        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", nullptr, 0u, "", sh, (size_t)n * 12u * c.coeffs(), nullptr, 0u, ""};
+        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "probe query buffers", "probe query launch", stats,
+                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
+                                             return trt::launch_probe(qs, c, d.items, n, d.sums, d.counters, nullptr);
+                                         });
     });
 }
 

@@ -4,9 +4,11 @@
 // the argument checks of the units that trace camera rays (batch_render_args).  The kernel table's entry (BatchKernel) and the launch rule
 // over the unit's own table (plan_batch) are host arithmetic only and live in stream_plan.h, beside the streamed rule they follow.  The
 // device side of the same units is wave_run.h; their host-buffer forms stage through host_stage.h.
-// The radiance and gather queries (radiance.hip: a run of the caller's rays or surfels) and the ambient queries (ambient.hip: a run of
-// surfels) use the same table entry, rule, preamble and plan entry point with tables of their own.
-// For those three units only: batch_prepare and batch_launch_plan call the HIP runtime and scene_query.h's helpers, so capi.hip, whose
+// The sample queries (radiance.hip: radiance and gather, a run of the caller's rays or surfels; ambient.hip, probe.hip, passes.hip,
+// direct.hip, nee.hip: a run of surfels or rays) use the same table entry, rule, preamble and plan entry point with tables of their own,
+// and with pixels.hip the ONE launch tail (batch_launch); "nothing to trace" is ONE zero kernel for all of them (batch_zero).  What
+// their two forms do around the launch is host_stage.h's sample_query_on_device / sample_query_on_host.
+// For the units only: batch_prepare and batch_launch_plan call the HIP runtime and scene_query.h's helpers, so capi.hip, whose
 // host-only build links without the units, must not include this header.
 #pragma once
 
@@ -51,6 +53,19 @@ inline hipError_t batch_prepare(const SceneDev& scd, uint32_t n, const BatchKern
     b.nodes16 = compact ? reinterpret_cast<const uint4*>(scd.blob + L.off_compact) : nullptr;
     return hipSuccess;
 }
+
+// The launch itself, for the units whose kernel trt_kernel_timing_* measures: the launch pattern of kernels.hip, timing_mark brackets it.
+inline hipError_t batch_launch(const BatchLaunch& b, void** args, hipStream_t stream) {
+    const trt_query_plan& q = b.q;
+    timing_mark(stream, true);
+    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
+    timing_mark(stream, false);
+    return le;
+}
+
+// Nothing to trace without accumulate, for the sample queries: n_a floats of d_a and, where d_b is not null, n_b floats of d_b become 0
+// (one kernel for all of them, radiance.hip sums_zero_kernel).
+hipError_t batch_zero(float* d_a, unsigned long long n_a, float* d_b, unsigned long long n_b, hipStream_t stream);
 
 // The trt_*_launch_plan entry points: how batch_prepare would launch n items on this scene (host arithmetic only: works without a GPU
 // when the CU count is given).

@@ -63,7 +63,7 @@ template <> struct RadianceArgsOf<LOBE_GATHER> { using type = GatherArgs; };
 
 // (rad_load_ray and gather_ray, the item load and the draw of a gather sample: gather_draw.h, shared with ambient.hip)
 
-// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_radiance: nothing to trace launches radiance_zero_kernel or nothing)
+// ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_radiance: nothing to trace launches the zero kernel or nothing)
 template <int MODE, int WALK, int THREADS, int MINW, int LOBE>
 __global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, RenderArgs ra, typename RadianceArgsOf<LOBE>::type ga,
                                                                       const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16) {
@@ -189,12 +189,18 @@ __global__ __launch_bounds__(THREADS, MINW) void radiance_kernel(SceneDev scd, R
     flush_counters<false>(ga.counters, n_samples, n_rays, ctr);
 }
 
-// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the n entries become 0.
-__global__ __launch_bounds__(256) void radiance_zero_kernel(unsigned long long n3, float* __restrict__ radiance, float* __restrict__ moment2) {
-    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;         // n3 = 3 n: the floats of [0, 12 n)
-    if (i >= n3) return;
-    radiance[i] = 0.0f;
-    if (moment2) moment2[i] = 0.0f;
+// Nothing to trace (an empty sample range, max_bounces == 0) without accumulate: the sums become 0.  The ONE zero kernel of the sample
+// queries (query_plan.h batch_zero): n_a floats of a, and n_b floats of b where b is wanted.
+__global__ __launch_bounds__(256) void sums_zero_kernel(float* __restrict__ a, unsigned long long n_a, float* __restrict__ b, unsigned long long n_b) {
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    if (i < n_a) a[i] = 0.0f;
+    if (b && i < n_b) b[i] = 0.0f;
+}
+hipError_t batch_zero(float* d_a, unsigned long long n_a, float* d_b, unsigned long long n_b, hipStream_t stream) {
+    const unsigned long long floats = d_b && n_b > n_a ? n_b : n_a;
+    if (floats == 0ull) return hipSuccess;
+    hipLaunchKernelGGL(sums_zero_kernel, dim3((uint32_t)((floats + 255ull) / 256ull)), dim3(256), 0, stream, d_a, n_a, d_b, n_b);
+    return hipGetLastError();
 }
 
 namespace {
@@ -240,9 +246,7 @@ hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_r
     if (ra.sample_begin == ra.sample_end || ra.max_bounces == 0) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
         if (ra.accumulate) return hipSuccess;
-        const unsigned long long n3 = 3ull * n;
-        hipLaunchKernelGGL(radiance_zero_kernel, dim3((uint32_t)((n3 + 255ull) / 256ull)), dim3(256), 0, stream, n3, d_radiance, d_moment2);
-        return hipGetLastError();
+        return batch_zero(d_radiance, 3ull * n, d_moment2, 3ull * n, stream);
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
@@ -254,64 +258,60 @@ hipError_t launch_radiance(const QueryScene& qs, RenderArgs ra, const float* d_r
     GatherArgs ga{{d_rays, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, samples_per_ray, first_stream},
                   lobe.lobe, lobe.spread};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
-    // the launch pattern of kernels.hip: trt_kernel_timing_* brackets the launch
-    timing_mark(stream, true);
-    const hipError_t le = hipLaunchKernel(b.fn, dim3(q.workgroups), dim3(q.threads_per_workgroup), args, q.lds_bytes, stream);
-    timing_mark(stream, false);
-    return le;
+    return batch_launch(b, args, stream);
 }
 
-// The device form of both queries, after the checks: buffers in HBM, asynchronous on `stream`.
+// The device form of both queries, after the checks (host_stage.h sample_query_on_device).
 int radiance_on_device(trt_scene* s, const RenderArgs& ra, const trt_radiance_params& p, Lobe lobe, const trt_ray* d_rays, uint32_t n, float* d_radiance,
                        float* d_moment2, uint64_t* d_counters, void* stream, const char* what) {
-    if (n == 0u) return TRT_OK;
-    int rc = query_require_device();
-    if (rc != TRT_OK) return rc;
-    QueryScene qs;
-    rc = query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const hipError_t e = launch_radiance(qs, ra, reinterpret_cast<const float*>(d_rays), n, p.samples_per_ray, p.first_stream, d_radiance, d_moment2,
-                                         reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream), lobe);
-    if (e != hipSuccess) return query_fail_hip(e, what);
-    return TRT_OK;
+    return sample_query_on_device(s, n, what, [&](const QueryScene& qs) {
+        return launch_radiance(qs, ra, reinterpret_cast<const float*>(d_rays), n, p.samples_per_ray, p.first_stream, d_radiance, d_moment2,
+                               reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream), lobe);
+    });
 }
 
-// The host form of both queries, after the checks (inside host_form).  Host buffers: device copies of the rays and of the two sums are
-// the call's own (one allocation), one stream-ordered sequence on the default stream, complete when the call returns.  The running sums
-// go up only when the call continues them.
+// The host form of both queries, after the checks (inside host_form; host_stage.h sample_query_on_host).
 int radiance_on_host(trt_scene* s, const RenderArgs& ra, const trt_radiance_params& p, Lobe lobe, const trt_ray* rays, uint32_t n, float* radiance,
                      float* moment2, trt_stats* stats, const char* buffers, const char* launch) {
-    if (n == 0u) {
-        if (stats) *stats = trt_stats{};
-        return TRT_OK;
-    }
-    int rc = query_require_device();
-    if (rc != TRT_OK) return rc;
-    QueryScene qs;
-    rc = query_scene_on_device(s, qs);
-    if (rc != TRT_OK) return rc;
-    const size_t rays_b = (size_t)n * sizeof(trt_ray), sums = (size_t)n * 12u;
-    HostStage st(buffers);
-    const size_t r_rays = st.reserve(rays_b), r_rad = st.reserve(sums), r_m2 = st.reserve(sums, moment2 != nullptr);
-    st.reserve_counters();
-    st.alloc();
-    st.up(r_rays, rays, rays_b, "hipMemcpy of the rays");
-    st.zero_counters();
-    // the running sums a pass continues go up; a pass that starts them reads nothing
-    if (ra.accumulate) st.up(r_rad, radiance, sums, "hipMemcpy of the sums");
-    if (ra.accumulate) st.up(r_m2, moment2, sums, "hipMemcpy of the second moments");
-    st.time_begin();
-    if (st.ok())
-        st.run(launch_radiance(qs, ra, st.ptr<float>(r_rays), n, p.samples_per_ray, p.first_stream, st.ptr<float>(r_rad), st.ptr<float>(r_m2),
-                               st.counters(), nullptr, lobe), launch);
-    const bool wrote = !(ra.accumulate && (ra.sample_begin == ra.sample_end || ra.max_bounces == 0u));
-    if (wrote) st.down(radiance, r_rad, sums, "hipMemcpy of the results");
-    if (wrote) st.down(moment2, r_m2, sums, "hipMemcpy of the results");
-    st.read_stats(stats);
-    return st.finish();
+    const size_t sums = (size_t)n * 12u;
+    const SampleHost h{rays, (size_t)n * sizeof(trt_ray), "hipMemcpy of the rays", nullptr, 0u, "", radiance, sums, moment2, sums,
+                       "hipMemcpy of the second moments"};
+    const bool nothing = ra.sample_begin == ra.sample_end || ra.max_bounces == 0u;
+    return sample_query_on_host(s, n, h, ra.accumulate != 0u, nothing, buffers, launch, stats, [&](const QueryScene& qs, const SampleDev& d) {
+        return launch_radiance(qs, ra, d.items, n, p.samples_per_ray, p.first_stream, d.sums, d.sums2, d.counters, nullptr, lobe);
+    });
 }
 
 }  // namespace
+
+// The rules that more than one unit applies to its parameters (declared in gather_draw.h).  The source, spread and reserved words of a
+// trt_gather_params whose lobe word is an enum trt_passes_source (passes.hip, nee.hip):
+int gather_source_check(const trt_gather_params& g) {
+    if (g.lobe != TRT_PASSES_RAYS && g.lobe != TRT_PASSES_COSINE && g.lobe != TRT_PASSES_CONE)
+        return query_fail(TRT_ERR_INVALID_ARG, "source must be TRT_PASSES_RAYS, TRT_PASSES_COSINE or TRT_PASSES_CONE");
+    if (g.lobe == TRT_PASSES_CONE && !(g.spread >= 0.0f && g.spread < __builtin_inff()))
+        return query_fail(TRT_ERR_INVALID_ARG, "spread of the cone lobe must be finite and not negative");
+    for (uint32_t r : g.reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    return TRT_OK;
+}
+// the emitter table's pointer and size and the shadow ray's end (direct.hip, nee.hip), for both forms
+int emitter_table_check(uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, float shadow_end) {
+    constexpr uint32_t kMaxEmitters = 1u << 20;
+    if (n > 0u && !emitters) return query_fail(TRT_ERR_INVALID_ARG, "null emitter table");
+    if (n > 0u && (n_emitters < 1u || n_emitters > kMaxEmitters)) return query_fail(TRT_ERR_INVALID_ARG, "n_emitters must be in 1 .. 2^20");
+    if (!(shadow_end > 0.0f && shadow_end <= 1.0f)) return query_fail(TRT_ERR_INVALID_ARG, "shadow_end must be in (0, 1]");
+    return TRT_OK;
+}
+// and the table's entries, which are the host form's to check: the device form cannot read them
+int emitter_entries_check(const trt_emitter* emitters, uint32_t n_emitters) {
+    for (uint32_t k = 0; k < n_emitters; k++) {
+        if (emitters[k].kind > 1u) return query_fail(TRT_ERR_INVALID_ARG, "emitter kind must be 0 (sphere) or 1 (quad)");
+        if (emitters[k].reserved[0] != 0u || emitters[k].reserved[1] != 0u)
+            return query_fail(TRT_ERR_INVALID_ARG, "reserved words of an emitter must be zero");
+    }
+    return TRT_OK;
+}
 
 // What both forms check before any device work, and the kernel arguments of the parameters (declared in gather_draw.h: the probe queries
 // apply the same rules to their path).

@@ -1145,10 +1145,24 @@ struct Path {
 // LAZY (SceneLayout::lazy_color): the colour is known to be +0 until the path ends - `color += attenuation * emission`
 // (cpu.rs:49-50) adds +-0 at every hit that is not a light, and the attenuation cannot overflow - so it is written once,
 // as 0 + attenuation * (light colour | background), and need not be carried from bounce to bounce.
-template <int MODE, bool STATS, bool LAZY = false>
-TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background, Counters<STATS>& ctr) {
+// INFO (the next-event queries, nee.hip): the body also reads and fills `info`.  In: hide_light - a light's emission counts as
+// Vec3::zero() at this hit (the path came here by a diffuse scatter, and a shadow ray has already stood for the light).  Out: the
+// material kind of the hit (SHADE_KIND_MISS on a miss) and the record's normal, unit and facing against the incoming ray.
+// ONE body behind two forwarders, shade_hit and shade_hit_info, which keep their names and template parameter lists: the callers'
+// mangled names stay, and with the emission condition formed as `emits` below every unit that shades (direct, nee, pixels, streamed,
+// radiance, passes) compiles to the assembly the two separate bodies gave, block labels included; only the translation unit's
+// __hip_cuid_ symbol differs.  tests/native/shade_cases.hip checks both forwarders case by case, every word of the result.
+constexpr uint32_t SHADE_KIND_MISS = 0xFFFFFFFFu;
+struct ShadeInfo {
+    bool hide_light;
+    uint32_t kind;
+    V3 normal;
+};
+template <int MODE, bool STATS, bool LAZY, bool INFO>
+TRT_DEV bool shade_body(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background, Counters<STATS>& ctr, ShadeInfo* info) {
     if (prim == PRIM_NONE) {                                           // cpu.rs:58-61
         p.color = (LAZY ? v3(0.0f, 0.0f, 0.0f) : p.color) + p.atten * background;
+        if constexpr (INFO) info->kind = SHADE_KIND_MISS;
         return true;
     }
     if constexpr (STATS) ctr.shade++;
@@ -1180,11 +1194,17 @@ TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t
         ctr.shade_dielectric += kind == TRT_DIELECTRIC; ctr.shade_light += kind == TRT_LIGHT;
     }
     // cpu.rs:49-50: emitted() is the light's colour, None -> 0 for everything else (material/mod.rs:8-10)
+    bool emits = kind == TRT_LIGHT;
+    if constexpr (INFO) {
+        info->kind = kind;
+        info->normal = normal;
+        emits = emits && !info->hide_light;
+    }
     if constexpr (LAZY) {
         p.color = v3(0.0f, 0.0f, 0.0f);                                // what the sum is after any hit that is not a light
-        if (kind == TRT_LIGHT) p.color = v3(0.0f, 0.0f, 0.0f) + p.atten * albedo;
+        if (emits) p.color = v3(0.0f, 0.0f, 0.0f) + p.atten * albedo;
     } else {
-        V3 emission = (kind == TRT_LIGHT) ? albedo : v3(0.0f, 0.0f, 0.0f);
+        V3 emission = emits ? albedo : v3(0.0f, 0.0f, 0.0f);
         p.color = p.color + p.atten * emission;
     }
     V3 dir;
@@ -1221,93 +1241,13 @@ TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t
     p.remain -= 1u;                                                    // cpu.rs:54
     return p.remain == 0u;
 }
-
-// shade_hit for the next-event queries (nee.hip): the same loop body, which also reads and fills `info`.  In: hide_light - a light's
-// emission counts as Vec3::zero() at this hit (the path came here by a diffuse scatter, and a shadow ray has already stood for the
-// light).  Out: the material kind of the hit (SHADE_KIND_MISS on a miss) and the record's normal, unit and facing against the incoming
-// ray.  A copy beside shade_hit and not one body behind a defaulted template parameter: a fourth parameter changes shade_hit's mangled
-// name, which the compiler writes into the block labels of streamed.hip's and pixels.hip's assembly, and those files are to stay what
-// they were byte for byte.  Every line that does not name `info` is shade_hit's without LAZY; tests/test_gpu_nee.py holds the two together
-// (B == 1 and scenes without a Lambertian give trt_gather's bits).
-constexpr uint32_t SHADE_KIND_MISS = 0xFFFFFFFFu;
-struct ShadeInfo {
-    bool hide_light;
-    uint32_t kind;
-    V3 normal;
-};
+template <int MODE, bool STATS, bool LAZY = false>
+TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background, Counters<STATS>& ctr) {
+    return shade_body<MODE, STATS, LAZY, false>(sc, p, prim, t, background, ctr, nullptr);
+}
 template <int MODE, bool STATS>
 TRT_DEV bool shade_hit_info(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background, Counters<STATS>& ctr, ShadeInfo& info) {
-    if (prim == PRIM_NONE) {                                           // cpu.rs:58-61
-        p.color = p.color + p.atten * background;
-        info.kind = SHADE_KIND_MISS;
-        return true;
-    }
-    if constexpr (STATS) ctr.shade++;
-    // HitRecord::new (hittable/mod.rs:28-48), built once for the winning primitive
-    const uint32_t idx = prim & PRIM_INDEX_MASK;
-    V3 point = ray_at(p.ray, t);
-    V3 normal;
-    bool front_face;
-    uint32_t mat;
-    if (prim & PRIM_QUAD_BIT) {
-        float4 q0 = sc.quad(0, idx), q1 = sc.quad(1, idx), q4 = sc.quad(4, idx);
-        front_face = dot(p.ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;        // outward normal = n, un-normalised (quad.rs:45)
-        V3 nu = v3(q4.y, q4.z, q4.w);                                  // n.normalized(), precomputed on the host
-        normal = front_face ? nu : -nu;
-        mat = __float_as_uint(q1.w);
-    } else {
-        float4 sp = sc.sphere(idx);
-        V3 outward = point - v3(sp.x, sp.y, sp.z);                     // sphere.rs:47-51 (p = ray.at(t))
-        front_face = dot(p.ray.d, outward) < 0.0f;
-        V3 nu = normalized(outward);
-        normal = front_face ? nu : -nu;
-        mat = sc.sphere_material(idx);
-    }
-    const float4 m = sc.material(mat);
-    const uint32_t kind = sc.material_kind(mat);
-    const V3 albedo = v3(m.x, m.y, m.z);
-    if constexpr (STATS) {
-        ctr.shade_lambertian += kind == TRT_LAMBERTIAN; ctr.shade_metal += kind == TRT_METAL;
-        ctr.shade_dielectric += kind == TRT_DIELECTRIC; ctr.shade_light += kind == TRT_LIGHT;
-    }
-    // cpu.rs:49-50: emitted() is the light's colour, None -> 0 for everything else (material/mod.rs:8-10)
-    info.kind = kind;
-    info.normal = normal;
-    V3 emission = (kind == TRT_LIGHT && !info.hide_light) ? albedo : v3(0.0f, 0.0f, 0.0f);
-    p.color = p.color + p.atten * emission;
-    V3 dir;
-    if (kind == TRT_LAMBERTIAN || kind == TRT_METAL) {
-        // Both draw ONE point in the unit sphere (three random numbers, acos, cbrt, two sincos: the expensive part of a shade) and use
-        // it differently: evaluated once for the lanes of either kind - as two branches a wave that holds both kinds (nearly every wave
-        // of the random-spheres scene) ran that code twice, the second time for a handful of metal lanes.  Same draws, same operations.
-        const V3 in_sphere = random_in_unit_sphere_unit(p.rng);               // rt_device.h: the general one, less its identities
-        if (kind == TRT_LAMBERTIAN) {                                  // lambertian.rs:16-22: normal + random_unit_vector (vec3extend.rs:32-34)
-            dir = normal + normalized(in_sphere);
-            if (near_zero(dir)) dir = normal;
-        } else {                                                       // metal.rs:18-25 (fuzz clamped at creation)
-            V3 reflected = reflect(p.ray.d, normal);
-            dir = reflected + m.w * in_sphere;
-        }
-    } else if (kind == TRT_DIELECTRIC) {                               // dielectric.rs:26-46
-        float ri = front_face ? 1.0f / m.w : m.w;
-        float cosv = __builtin_fminf(-dot(normal, p.ray.d), 1.0f);
-        float sinv = __builtin_sqrtf(1.0f - cosv * cosv);
-        bool total_reflection = ri * sinv > 1.0f;
-        float sqrt_r0 = (1.0f - ri) / (1.0f + ri);                     // reflectance(), dielectric.rs:16-22
-        float r0 = sqrt_r0 * sqrt_r0;
-        float x = 1.0f - cosv;
-        float x2 = x * x;
-        float reflectance = r0 + (1.0f - r0) * (x * (x2 * x2));        // powi(5): x * ((x*x)*(x*x))
-        bool do_reflect = total_reflection;
-        if (!do_reflect) do_reflect = reflectance > rng_random(p.rng); // `||` short-circuit: no draw on TIR
-        dir = do_reflect ? reflect(p.ray.d, normal) : refract(p.ray.d, normal, ri);
-    } else {                                                           // Light::scatter -> None (light.rs:17-19)
-        return true;
-    }
-    p.atten = p.atten * albedo;                                        // cpu.rs:52
-    p.ray = ray_new(point, dir);                                       // Ray::new normalises (ray.rs:12-14)
-    p.remain -= 1u;                                                    // cpu.rs:54
-    return p.remain == 0u;
+    return shade_body<MODE, STATS, false, true>(sc, p, prim, t, background, ctr, &info);
 }
 
 // SamplePointGenerator::generate body (pointgen.rs:41-43) + Camera::get_ray (camera.rs:58-66)

@@ -3,8 +3,11 @@
 // pixel list).  ONE copy of the lane rank, the run of a wave, the place of the leaf stacks, the cursor step of the round loop's refill
 // and the surface record of a closest hit; each kernel keeps its own loop body, because what a lane carries and does with a finished
 // walk differs.  The host side of the same units is stream_plan.h (kernel table entry, launch rule) and query_plan.h (launch preamble).
-// radiance.hip (radiance and gather queries: a run of the caller's rays or surfels) and ambient.hip (ambient queries: a run of surfels)
-// take the run, the leaf stacks and the refill step from here too.
+// The sample queries - radiance.hip (radiance and gather: a run of the caller's rays or surfels), ambient.hip, probe.hip, passes.hip,
+// direct.hip and nee.hip - take the run, the leaf stacks and the refill step from here too, and keep their own round loops for the same
+// reason: the walk block of those loops (trav_begin / trav_unpark / closest_hit_resume | closest_hit) as a helper that takes walking,
+// n_rays, prim and t by reference changes 3 000 to 19 000 lines of their assembly.  What surrounds the loops is shared: the shade body
+// (rt_path.h shade_body), the draws (gather_draw.h), the launch (query_plan.h) and the two forms' scaffold (host_stage.h).
 //
 // Every function here is a pure function of values, and that is deliberate: with these the device assembly of all kernels that use them
 // is, instruction for instruction, what their own copies gave.  Forms that did more were built and dropped because the compiler then
