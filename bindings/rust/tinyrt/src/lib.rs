@@ -136,6 +136,36 @@ pub enum PassesSource {
     Lobe(Lobe),
 }
 
+/// How `World::nee_mis` weights a shadow ray against the hit the path makes anyway (`enum trt_mis_heuristic`).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum MisHeuristic {
+    Balance,
+    Power,
+}
+
+/// The `trt_nee_params` of `World::nee` and `World::nee_mis`.
+fn nee_params(samples_per_item: u32, source: PassesSource, source_is_diffuse: bool, shadow_end: Float, max_bounces: u32, background: Vec3,
+              seed: u32, first_stream: u32) -> sys::trt_nee_params {
+    let mut params = sys::trt_nee_params::default();
+    unsafe { sys::trt_nee_params_default(&mut params) };
+    params.gather.path.samples_per_ray = samples_per_item;
+    params.gather.path.max_bounces = max_bounces;
+    params.gather.path.background = background.raw();
+    params.gather.path.seed = seed;
+    params.gather.path.first_stream = first_stream;
+    params.shadow_end = shadow_end;
+    params.source_is_diffuse = source_is_diffuse as u32;
+    match source {
+        PassesSource::Rays => params.gather.lobe = sys::TRT_PASSES_RAYS,
+        PassesSource::Lobe(Lobe::Cosine) => params.gather.lobe = sys::TRT_PASSES_COSINE,
+        PassesSource::Lobe(Lobe::Cone(spread)) => {
+            params.gather.lobe = sys::TRT_PASSES_CONE;
+            params.gather.spread = spread;
+        }
+    }
+    params
+}
+
 pub enum Geometry {
     Sphere { center: Vec3, radius: Float, material: MaterialHandle },
     Quad { corner: Vec3, u: Vec3, v: Vec3, material: MaterialHandle },
@@ -438,28 +468,40 @@ impl World {
             return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
         }
         let scene = self.get_bvh()?;
-        let mut params = sys::trt_nee_params::default();
-        unsafe { sys::trt_nee_params_default(&mut params) };
-        params.gather.path.samples_per_ray = samples_per_item;
-        params.gather.path.max_bounces = max_bounces;
-        params.gather.path.background = background.raw();
-        params.gather.path.seed = seed;
-        params.gather.path.first_stream = first_stream;
-        params.shadow_end = shadow_end;
-        params.source_is_diffuse = source_is_diffuse as u32;
-        match source {
-            PassesSource::Rays => params.gather.lobe = sys::TRT_PASSES_RAYS,
-            PassesSource::Lobe(Lobe::Cosine) => params.gather.lobe = sys::TRT_PASSES_COSINE,
-            PassesSource::Lobe(Lobe::Cone(spread)) => {
-                params.gather.lobe = sys::TRT_PASSES_CONE;
-                params.gather.spread = spread;
-            }
-        }
+        let params = nee_params(samples_per_item, source, source_is_diffuse, shadow_end, max_bounces, background, seed, first_stream);
         let mut radiance = vec![0.0 as Float; items.len() * 3];
         let mut moment2 = vec![0.0 as Float; items.len() * 3];
         check(unsafe {
             sys::trt_nee(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32, &params,
                          radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
+    /// `nee` with multiple importance sampling (`trt_nee_mis`): the same paths and shadow rays, but a light reached after a diffuse
+    /// scatter (from the second hit on) counts both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the hit by the
+    /// complement, q(x) = x (`MisHeuristic::Balance`) or x * x (`Power`): the same expectation without the 1/d2 tail of shadow samples
+    /// beside a lamp.  `emitters` must hold exactly the scene's own lights (`emitters()`), each once, plus any virtual ones; anything else
+    /// is an error.  Returns `(radiance, moment2)` as `nee` does.
+    pub fn nee_mis(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], samples_per_item: u32, source: PassesSource,
+                   source_is_diffuse: bool, heuristic: MisHeuristic, shadow_end: Float, max_bounces: u32, background: Vec3, seed: u32,
+                   first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_nee_mis_params::default();
+        unsafe { sys::trt_nee_mis_params_default(&mut params) };
+        params.nee = nee_params(samples_per_item, source, source_is_diffuse, shadow_end, max_bounces, background, seed, first_stream);
+        params.heuristic = match heuristic {
+            MisHeuristic::Balance => sys::TRT_MIS_BALANCE,
+            MisHeuristic::Power => sys::TRT_MIS_POWER,
+        };
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_nee_mis(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32, &params,
+                             radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((radiance, moment2))
     }

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """A frame of the Cornell box through the queries, with the lamp aimed at at every diffuse hit -> nee_frame.png.
-   python examples/render_nee.py [W H SPP]
+   python examples/render_nee.py [W H SPP] [--mis balance|power]
 Everything stays in HBM.  For sample s of SPP the camera writes the frame's primary rays (trt_primary_rays_device: the rays the render
 traces for that sample) and Scene.nee_device (trt_nee_device, source "rays") folds one sample per pixel into the running sums: K = SPP,
 the sample range [s, s + 1), accumulate from the second pass on - the frame in passes that tinyrt.h describes for trt_passes.  The first
 hit of a camera ray is no diffuse vertex (source_is_diffuse = 0): the lamp is seen where the camera looks at it, and hidden where a path
-reaches it by a diffuse bounce, because the shadow ray from that bounce has already counted it."""
+reaches it by a diffuse bounce, because the shadow ray from that bounce has already counted it.  With --mis (trt_nee_mis_device) the
+shadow ray and that hit are both counted, weighted by their densities.  (The stock box's lamp is coplanar with the ceiling, where the two
+disagree about visibility: tinyrt.h, limits.)"""
 import os
 import sys
 import time
@@ -14,6 +16,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tinyrt_amd as trt
 
 argv = sys.argv[1:]
+mis = None
+if "--mis" in argv:
+    at = argv.index("--mis")
+    mis = argv[at + 1]
+    del argv[at:at + 2]
 w, h, spp = (int(a) for a in argv[:3]) if len(argv) >= 3 else (300, 300, 64)
 import torch
 
@@ -32,7 +39,7 @@ for s in range(spp):
     camera.primary_rays_device(s, spp, d_rays.data_ptr(), seed=1)
     scene.nee_device(d_rays.data_ptr(), n, d_table.data_ptr(), len(table), d_sum.data_ptr(), d_m2.data_ptr(), d_counters_ptr=ctr.data_ptr(),
                      samples_per_item=spp, source="rays", max_bounces=20, background=(0.001, 0.001, 0.001), seed=1, sample_begin=s,
-                     sample_end=s + 1, accumulate=s > 0)
+                     sample_end=s + 1, accumulate=s > 0, mis=mis)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 frame = d_sum.view(h, w, 3).cpu().numpy()

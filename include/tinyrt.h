@@ -51,7 +51,8 @@ extern "C" {
  *              trt_probe_launch_plan; trt_passes_source, trt_passes_params, trt_passes_params_default, trt_passes, trt_passes_device,
  *              trt_passes_launch_plan; trt_emitter, trt_scene_emitters, trt_emitter_init_quad, trt_emitter_init_sphere, trt_direct_params,
  *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan; trt_nee_params, trt_nee_params_default,
- *              trt_nee, trt_nee_device, trt_nee_launch_plan. */
+ *              trt_nee, trt_nee_device, trt_nee_launch_plan; trt_mis_heuristic, trt_nee_mis_params, trt_nee_mis_params_default,
+ *              trt_nee_mis, trt_nee_mis_device, trt_nee_mis_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -894,6 +895,64 @@ int trt_nee_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_e
 /* How trt_nee[_device] launches n items on this scene: trt_passes_launch_plan's rule and fields over the next-event kernels' own table
  * (the same shapes; kernel_waves_per_simd is that table's bound, the same for every source). */
 int trt_nee_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Next-event queries with multiple importance sampling: the shadow ray and the hit the path makes anyway, weighted by their densities ----
+ * trt_nee counts a light after a diffuse scatter through the shadow ray alone.  For a vertex beside a lamp the shadow sample's 1/d2 weight
+ * is hundreds of times the mean, and that tail carries the variance above the plain gather's.  A light after a diffuse
+ * scatter can be found two ways - by the shadow ray of the vertex before (density p_light) and by the scattered ray itself (density
+ * p_bsdf) - and this query counts BOTH, each weighted so that the two weights of one point sum to 1.  Near the lamp p_bsdf / p_light is
+ * large, the shadow sample's weight small: the tail is gone, the expectation stays.
+ *
+ * Contract of a sample.  trt_nee's, with params->nee in the place of its params, except for what a sample ADDS in steps 3 and 5.
+ * Unchanged: streams, vertices, the draws of steps 1-2 and 4-6, the fold, sample ranges, accumulate, both split invariances, "nothing
+ * to trace", the NaN-first-ray rule, output bounds and counters; the paths and the shadow rays walked are trt_nee's.  All f32, one IEEE
+ * operation per operator, nothing fused.  E = n_emitters;  sc(a) = (a * float(E)) * 0.318309886f;  q(x) = x for TRT_MIS_BALANCE and
+ * x * x for TRT_MIS_POWER.
+ *  - Lambertian scatter (step 4).  After every Lambertian scatter csh = dot(rec.normal, new_ray.direction): the facing unit normal with
+ *    the direction as Ray::new normalised it.  It is kept until the next hit.
+ *  - Next event (step 5).  With wgt from trt_direct's step 5 for the drawn record:  wl = 1.0f / (1.0f + q(wgt));  if the record's
+ *    `geometry` word is 0xFFFFFFFF, wl = 1.0f (a virtual emitter cannot be hit: its shadow ray counts in full).  A live, unoccluded
+ *    sample has c.ch = (colour.ch * wgt) * wl and adds color = color + atten * c.  Liveness, t_max, which samples walk and the condition on
+ *    remain are unchanged.
+ *  - Light hit (step 3).  When the material is a light and after_diffuse is set, color = color + atten * Vec3::zero() happens as in
+ *    trt_nee.  At hit number 1 (which has after_diffuse only through source_is_diffuse) nothing more is added: it is hidden in full, as
+ *    trt_direct, which that mode pairs with, has no weights.  At any later hit, with t = rec.t and the incoming ray:
+ *      clh = |dot(rec.normal, ray.direction)|
+ *      area = the hit primitive's own: quad sqrt((n.x*n.x + n.y*n.y) + n.z*n.z) of the un-normalised normal the packed scene holds,
+ *             sphere 12.566371f * (r * r) - the bits trt_scene_emitters writes for that geometry
+ *      g = ((csh * clh) / (t * t)) * sc(area)
+ *      wb = q(g) / (1.0f + q(g)) if csh > 0 and q(g) is finite, else 1.0f (the matching shadow sample would have been dead)
+ *      color = color + atten * (emission * wb)
+ *    A light reached without after_diffuse counts in full, as in trt_nee.
+ *  - Why the weights sum to 1: wgt is f cos / p_light = p_bsdf / p_light for the cosine lobe, g is the same ratio seen from the hit, so
+ *    1 / (1 + wgt) and g / (1 + g) are the balance weights of the two strategies at one point; the power form squares the ratio.
+ *  - Bound.  With the scene's own table, BALANCE and albedos <= 1 every term is at most the emitter's colour up to rounding: a sample is
+ *    at most B x the largest colour channel.
+ *  - Table rule.  The entries whose `geometry` is not 0xFFFFFFFF must be exactly the scene's TRT_LIGHT geometries, each once, as
+ *    trt_scene_emitters wrote them; any order, with any virtual entries among them.  The device does not look the hit up in the table:
+ *    it takes E from the table and the area from the hit.  The host form checks the set of `geometry` words against the scene; THE
+ *    DEVICE FORM CANNOT CHECK: with another table its weights do not sum to 1 and the result is biased.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_nee's on `nee`; heuristic above 1; a non-zero reserved word;
+ *    the table rule (host form, n > 0).  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM.  n == 0 succeeds and touches nothing.
+ *  - Identities.  (1) With B == 1 and source_is_diffuse == 0 the result is trt_radiance's / trt_gather's, byte for byte.  (2) On a scene
+ *    without a Lambertian the result is theirs for any B.  (3) With a table of virtual emitters only, on a scene without a TRT_LIGHT
+ *    geometry, the result is trt_nee's bytes for both heuristics.  (4) stats.rays and stats.samples equal trt_nee's for the same call.
+ *  - Limits.  The uniform choice among emitters and shadow_end are inherited.  On the stock Cornell box, whose lamp is coplanar with the
+ *    ceiling, the two strategies disagree about visibility and the weights do not sum to 1 there: compare on the lowered lamp. */
+enum trt_mis_heuristic { TRT_MIS_BALANCE = 0, TRT_MIS_POWER = 1 };
+typedef struct {
+    trt_nee_params nee;           /* trt_nee's rules and errors, unchanged */
+    uint32_t heuristic;           /* enum trt_mis_heuristic */
+    uint32_t reserved[7];         /* zero */
+} trt_nee_mis_params;             /* 160 B: offsets 0, 128, 132 */
+void trt_nee_mis_params_default(trt_nee_mis_params *out);   /* nee = trt_nee_params_default's, heuristic TRT_MIS_BALANCE; NULL tolerated */
+int trt_nee_mis(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, uint32_t n_emitters,
+                const trt_nee_mis_params *p, float *radiance, float *moment2, trt_stats *stats);
+int trt_nee_mis_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, uint32_t n_emitters,
+                       const trt_nee_mis_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_nee_mis[_device] launches n items on this scene: trt_nee_launch_plan's rule and fields over the weighted kernels' own table
+ * (the same shapes; kernel_waves_per_simd is that table's bound, the same for every source and heuristic). */
+int trt_nee_mis_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

@@ -165,6 +165,18 @@ public:
         check(trt_nee(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
                       moment2 ? moment2->data() : nullptr, stats));
     }
+    // nee() with multiple importance sampling (trt_nee_mis): the same paths and shadow rays, but a light reached after a diffuse scatter
+    // (from the second hit on) counts both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the hit by the complement,
+    // q(x) = x (TRT_MIS_BALANCE) or x * x (TRT_MIS_POWER): the same expectation without the 1/d2 tail of shadow samples beside a lamp.
+    // `table` must hold exactly the scene's own lights (emitters()), each once, plus any virtual ones; anything else is an error.  Start
+    // `p` from trt_nee_mis_params_default.
+    void nee_mis(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_nee_mis_params& p, std::vector<float>& radiance,
+                 std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_nee_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
+                          moment2 ? moment2->data() : nullptr, stats));
+    }
     // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
     // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
     // gather() does and adds colour * Y_k(direction) / K to coefficient k of the item.  `sh` becomes p.bands^2 x 3 floats per item - real

@@ -177,6 +177,14 @@ class NeeParams(C.Structure):
     _fields_ = [("gather", GatherParams), ("shadow_end", C.c_float), ("source_is_diffuse", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
+MIS_BALANCE, MIS_POWER = 0, 1                                               # tinyrt.h enum trt_mis_heuristic
+
+
+class NeeMisParams(C.Structure):
+    """tinyrt.h trt_nee_mis_params: trt_nee_params and the heuristic that weights a shadow ray against the path's own hit (160 bytes)."""
+    _fields_ = [("nee", NeeParams), ("heuristic", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -295,6 +303,12 @@ SIGNATURES = {
     "trt_nee_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeParams), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "trt_nee_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_nee_mis_params_default": (None, [C.POINTER(NeeMisParams)]),
+    "trt_nee_mis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeMisParams), C.c_void_p, C.c_void_p,
+                              C.POINTER(Stats)]),
+    "trt_nee_mis_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeMisParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "trt_nee_mis_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

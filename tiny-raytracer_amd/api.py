@@ -521,21 +521,31 @@ class Scene:
         return plan.as_dict()
 
     # ---- next-event queries (tinyrt.h trt_nee): the paths of radiance() / gather() with a shadow ray to the table at every diffuse hit ----
+    MIS = {"balance": _lib.MIS_BALANCE, "power": _lib.MIS_POWER}
+
     @classmethod
-    def _nee_params(cls, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, **path):
-        """shadow_end = None: the library's default (0.999)."""
+    def _nee_params(cls, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, mis=None, **path):
+        """shadow_end = None: the library's default (0.999).  mis = None: a trt_nee_params; "balance" or "power": a trt_nee_mis_params."""
         if source not in cls.SOURCES:
             raise ValueError("source must be 'rays', 'cosine' or 'cone'")
+        if mis is not None and mis not in cls.MIS:
+            raise ValueError("mis must be None, 'balance' or 'power'")
         p = _lib.NeeParams()
         lib.trt_nee_params_default(C.byref(p))
         p.gather.path = cls._radiance_params(samples_per_item, **path)
         p.gather.lobe, p.gather.spread, p.source_is_diffuse = cls.SOURCES[source], float(spread), int(source_is_diffuse)
         if shadow_end is not None:
             p.shadow_end = float(shadow_end)
-        return p
+        if mis is None:
+            return p
+        m = _lib.NeeMisParams()
+        lib.trt_nee_mis_params_default(C.byref(m))
+        m.nee, m.heuristic = p, cls.MIS[mis]
+        return m
 
     def nee(self, items, emitters, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, max_bounces=50,
-            background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None, accumulate=False, radiance=None, moment2=None):
+            background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None, accumulate=False, radiance=None, moment2=None,
+            mis=None):
         """trt_nee: what radiance() (source "rays": items float32 [n, 6] are rays, used as given) or gather() (source "cosine" or "cone":
         items are surfels) estimates, with the lights aimed at: the path of every sample is gather()'s bit for bit, at every Lambertian
         hit that leaves bounce budget one shadow ray goes to the emitter table as in direct() (stream (seed, j, 2 + scatters before)), and
@@ -543,11 +553,15 @@ class Scene:
         emitters(): a light left out is still hidden.  source_is_diffuse=True treats the first hit as diffusely reached too: with the
         cosine source the result is the surfel's indirect light only, and direct() + nee(source_is_diffuse=True) is a full bake.
         Sample range, accumulate, `radiance`, `moment2` and the returns as in radiance(); stats carry samples and rays = path segments
-        plus shadow walks."""
+        plus shadow walks.
+        mis = "balance" | "power" (trt_nee_mis): the same paths and shadow rays, but a light reached after a diffuse scatter (from the
+        second hit on) is counted both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the hit by its complement,
+        q(x) = x or x * x: the same expectation without the 1/d2 tail of shadow samples beside a lamp.  `emitters` must then hold
+        exactly the scene's own lights (emitters()), each once, plus any virtual ones; anything else is an error."""
         r, _ = _rays_and_t_max(items, None)
         n = len(r)
         e = self._emitter_table(emitters)
-        p = self._nee_params(samples_per_item, source, spread, shadow_end, source_is_diffuse, max_bounces=max_bounces, background=background,
+        p = self._nee_params(samples_per_item, source, spread, shadow_end, source_is_diffuse, mis, max_bounces=max_bounces, background=background,
                              seed=seed, first_stream=first_stream, sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
         if radiance is None:
             radiance = np.zeros((n, 3), np.float32)
@@ -556,22 +570,27 @@ class Scene:
         for a in (radiance, moment2):
             assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
         st = Stats()
-        check(lib.trt_nee(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
-                          radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        fn = lib.trt_nee if mis is None else lib.trt_nee_mis
+        check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
+                 radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
         return radiance, moment2, st.as_dict()
 
     def nee_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
         """Enqueue nee() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n_emitters x 80 bytes of
         trt_emitter records, n x 12 bytes of sums each) on the current device; asynchronous on the stream, allocates nothing.  `params`:
-        nee()'s keywords, samples_per_item included."""
+        nee()'s keywords, samples_per_item and mis included (trt_nee_mis_device where mis is given: the device form cannot check the
+        table rule)."""
         p = self._nee_params(**params)
-        check(lib.trt_nee_device(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
-                                 C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+        fn = lib.trt_nee_mis_device if isinstance(p, _lib.NeeMisParams) else lib.trt_nee_device
+        check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
+                 C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
 
-    def nee_plan(self, n, compute_units=0):
-        """trt_nee_launch_plan: how nee() launches n items on this scene, as a dict with gather_plan()'s fields."""
+    def nee_plan(self, n, compute_units=0, mis=None):
+        """trt_nee_launch_plan (mis given: trt_nee_mis_launch_plan): how nee() launches n items on this scene, as a dict with
+        gather_plan()'s fields."""
         plan = _lib.QueryPlan()
-        check(lib.trt_nee_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        fn = lib.trt_nee_launch_plan if mis is None else lib.trt_nee_mis_launch_plan
+        check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
     def compact_nodes(self):

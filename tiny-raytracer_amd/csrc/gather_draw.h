@@ -8,6 +8,8 @@
 // the registers it had.
 #pragma once
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "rt_path.h"
 
@@ -67,10 +69,16 @@ struct DirectSample {
     float t_max;                     // sqrt(d2) * shadow_end: the walk covers [0.001, t_max)
     bool live;
 };
+// ... with step 5's weight and the record's `geometry` word besides, which the weighted next-event kernels (nee.hip, MIS) weigh the
+// sample by.  A type of its own, filled under `if constexpr`: the other callers' code is the code they had.
+struct WeightedDirectSample : DirectSample {
+    float wgt;
+    uint32_t geometry;
+};
 // ONE body for the surfel of an item (direct.hip) and for a surfel held in registers (nee.hip): `surfel()` returns (point, normal) as
 // a Ray and is called after the draws, where an item is loaded so that its six registers are free while the draws run.
-template <class Surfel>
-TRT_DEV DirectSample direct_draw_from(Surfel surfel, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
+template <class Surfel, class Sample = DirectSample>
+TRT_DEV Sample direct_draw_from(Surfel surfel, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
     const float fe = (float)n_emitters;
     const uint32_t pick = (uint32_t)(rng_random(g) * fe);
     const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
@@ -92,11 +100,15 @@ TRT_DEV DirectSample direct_draw_from(Surfel surfel, const float* __restrict__ e
     const float cl = __builtin_fabsf(dot(nl, w));
     const float scale = (em[17] * fe) * 0.318309886f;
     const float wgt = ((cs * cl) / (d2 * d2)) * scale;
-    DirectSample smp;
+    Sample smp;
     smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
     smp.ray = ray_new(item.o, w);
     smp.t_max = __builtin_sqrtf(d2) * shadow_end;
     smp.c = v3(em[14], em[15], em[16]) * wgt;
+    if constexpr (std::is_same_v<Sample, WeightedDirectSample>) {
+        smp.wgt = wgt;
+        smp.geometry = __float_as_uint(em[1]);
+    }
     return smp;
 }
 TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters, uint32_t n_emitters,
@@ -106,6 +118,11 @@ TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, 
 // The same sample for a vertex of a path (nee.hip): x the point, n the unit normal on the side the light is gathered on.
 TRT_DEV DirectSample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
     return direct_draw_from([&] { Ray r; r.o = x; r.d = n; return r; }, emitters, n_emitters, shadow_end, g);
+}
+TRT_DEV WeightedDirectSample direct_draw_at_weighted(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters,
+                                                     float shadow_end, Rng& g) {
+    auto surfel = [&] { Ray r; r.o = x; r.d = n; return r; };
+    return direct_draw_from<decltype(surfel), WeightedDirectSample>(surfel, emitters, n_emitters, shadow_end, g);
 }
 
 // The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.

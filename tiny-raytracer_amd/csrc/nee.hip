@@ -24,6 +24,13 @@
 // Nor is there shading code: shade_hit_info is rt_path.h's one shade body with the lines that read and fill ShadeInfo switched on.  The
 // two forms' scaffold is host_stage.h's, the checks of the source and of the emitter table are gather_draw.h's, shared with passes.hip
 // and direct.hip.
+//
+// trt_nee_mis / trt_nee_mis_device (tinyrt.h) are the same kernel with MIS = true: the same rounds, walks and draws, and two weights on
+// what a sample adds.  The shadow term is scaled by wl = 1 / (1 + q(wgt)) where the draw's result becomes sh_c (1 for a virtual
+// emitter), and a light the path reaches after a diffuse scatter at hit >= 2, which the plain kernel hides, adds its emission scaled by
+// wb = q(g) / (1 + q(g)) (mis_hit_weight) in the branch where shade has ended the path: cold, since a light always ends it.  A lane
+// carries csh, the cosine of its last Lambertian scatter, besides.  The MIS = false instantiations are instruction for instruction what
+// they were without the parameter; the two entry points share their checks, launcher and both forms' bodies with trt_nee.
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -32,10 +39,15 @@
 #include "scene_query.h"
 #include "wave_run.h"
 
+#include <algorithm>
+#include <vector>
+
 namespace trt {
 
 static_assert(sizeof(trt_nee_params) == 128 && offsetof(trt_nee_params, gather) == 0 && offsetof(trt_nee_params, shadow_end) == 96 &&
               offsetof(trt_nee_params, source_is_diffuse) == 100 && offsetof(trt_nee_params, reserved) == 104, "trt_nee_params layout (tinyrt.h)");
+static_assert(sizeof(trt_nee_mis_params) == 160 && offsetof(trt_nee_mis_params, nee) == 0 && offsetof(trt_nee_mis_params, heuristic) == 128 &&
+              offsetof(trt_nee_mis_params, reserved) == 132, "trt_nee_mis_params layout (tinyrt.h)");
 
 struct NeeArgs {
     const float* items;              // n x (origin, direction) or n x (point, axis), used as given
@@ -52,11 +64,35 @@ struct NeeArgs {
     uint32_t n_emitters;             // E: 1 .. 2^20
     float shadow_end;                // in (0, 1]
     uint32_t source_is_diffuse;      // after_diffuse at the first hit
+    uint32_t heuristic;              // enum trt_mis_heuristic, wave-uniform (the MIS kernels; the others do not read it)
 };
 constexpr int NEE_RAYS = 0, NEE_LOBE = 1;      // nee_kernel's SOURCE: the items are rays | surfels whose lobe is NeeArgs::source
 
+// The weight of the path's own hit on a light (tinyrt.h trt_nee_mis, "light hit"): wb for the hit primitive, reached at parameter t of `ray`
+// after a Lambertian scatter whose cosine was csh.  `normal` is the record's (unit, facing).  The area is the primitive's own, in the
+// bits trt_scene_emitters writes: |n| of the packed un-normalised quad normal, 4 pi r^2 with the header's constant for a sphere.
+template <int MODE>
+TRT_DEV float mis_hit_weight(const SceneAcc<MODE>& sc, uint32_t prim, const Ray& ray, const V3& normal, float t, float csh, uint32_t n_emitters,
+                             uint32_t heuristic) {
+    const uint32_t pidx = prim & PRIM_INDEX_MASK;
+    float area;
+    if (prim & PRIM_QUAD_BIT) {
+        const float4 q0 = sc.quad(0, pidx);
+        area = __builtin_sqrtf((q0.x * q0.x + q0.y * q0.y) + q0.z * q0.z);
+    } else {
+        const float r = sc.sphere(pidx).w;
+        area = 12.566371f * (r * r);
+    }
+    const float clh = __builtin_fabsf(dot(normal, ray.d));
+    const float g = ((csh * clh) / (t * t)) * ((area * (float)n_emitters) * 0.318309886f);
+    const float qg = heuristic == TRT_MIS_POWER ? g * g : g;
+    return csh > 0.0f && __builtin_fabsf(qg) < __builtin_inff() ? qg / (1.0f + qg) : 1.0f;
+}
+
 // ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches query_plan.h batch_zero or nothing)
-template <int MODE, int WALK, int THREADS, int MINW, int SOURCE>
+// MIS (tinyrt.h trt_nee_mis): the same rounds, walks and draws; a shadow sample is scaled by wl, and a light the path reaches after a
+// diffuse scatter at hit >= 2 adds its emission scaled by wb where the plain kernel adds nothing.  A lane carries csh, one register more.
+template <int MODE, int WALK, int THREADS, int MINW, int SOURCE, bool MIS>
 __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, RenderArgs ra, NeeArgs ga, const float4* __restrict__ leaf_list,
                                                                  const uint4* __restrict__ nodes16) {
     stage_scene_to_lds<MODE>(scd);
@@ -86,6 +122,7 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
     V3 acc = v3(0.0f, 0.0f, 0.0f), m2 = v3(0.0f, 0.0f, 0.0f);
     V3 sh_d = v3(0.0f, 0.0f, 0.0f), sh_c = v3(0.0f, 0.0f, 0.0f);            // of the outstanding shadow ray: direction, atten * c
     float sh_t = 0.0f;                                                      // and its t_max
+    [[maybe_unused]] float csh = 0.0f;                                      // MIS: the cosine of the last Lambertian scatter, kept until the next hit
     Path p;
     p.ray.o = v3(0.0f, 0.0f, 0.0f); p.ray.d = v3(0.0f, 0.0f, 0.0f);
     p.color = v3(0.0f, 0.0f, 0.0f); p.atten = v3(0.0f, 0.0f, 0.0f);
@@ -138,6 +175,15 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
                 info.kind = SHADE_KIND_MISS;
                 info.normal = v3(0.0f, 0.0f, 0.0f);
                 if (shade_hit_info<MODE, false>(sc, p, hit_prim, hit_t, background, ctr, info)) {
+                    if constexpr (MIS) {
+                        // a light reached by a diffuse scatter at hit >= 2 (a light leaves remain and the ray as they were): the shadow ray of
+                        // the vertex before has counted it with wl, the hit counts with wb.  Cold: the path has ended.
+                        if (info.kind == TRT_LIGHT && after_diffuse && p.remain != ra.max_bounces) {
+                            const float wb = mis_hit_weight<MODE>(sc, hit_prim, p.ray, info.normal, hit_t, csh, ga.n_emitters, ga.heuristic);
+                            const float4 m = sc.material(prim_material<MODE>(sc, hit_prim));
+                            p.color = p.color + p.atten * (v3(m.x, m.y, m.z) * wb);
+                        }
+                    }
                     // imager.rs:35,50 and the second moment beside it, in the operation order of pixels_kernel
                     acc = acc + p.color * ra.inv_spp;
                     m2.x = m2.x + (p.color.x * p.color.x) * ra.inv_spp;
@@ -158,8 +204,21 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
                         // ---- next event: the surfel is (the new ray's origin, the record's normal); d = max_bounces - remain - 1 scatters before ----
                         const uint32_t stream = ga.first_stream + idx * ga.samples_per_item + s;
                         Rng g = rng_seed(ra.seed_key, stream, 1u + (ra.max_bounces - p.remain));
-                        const DirectSample smp = direct_draw_at(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
-                        const V3 term = p.atten * smp.c;
+                        DirectSample smp;
+                        [[maybe_unused]] float wl = 1.0f;
+                        if constexpr (MIS) {
+                            const WeightedDirectSample w = direct_draw_at_weighted(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
+                            smp = w;
+                            csh = dot(info.normal, p.ray.d);
+                            // the shadow sample's share: 1 / (1 + q(p_bsdf / p_light)); a virtual emitter cannot be hit and counts in full
+                            const float qw = ga.heuristic == TRT_MIS_POWER ? w.wgt * w.wgt : w.wgt;
+                            if (w.geometry != 0xFFFFFFFFu) wl = 1.0f / (1.0f + qw);
+                        } else {
+                            smp = direct_draw_at(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
+                        }
+                        V3 c = smp.c;
+                        if constexpr (MIS) c = c * wl;
+                        const V3 term = p.atten * c;
                         if (smp.live) {
                             if (smp.t_max > kTMin) {
                                 shadow = true;
@@ -208,7 +267,9 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
 namespace {
 
 #define TRT_NEE(MODE, WALK, THREADS, MINW, SOURCE) \
-    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE>), MODE, WALK, THREADS, MINW}
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, false>), MODE, WALK, THREADS, MINW}
+#define TRT_NEE_MIS(MODE, WALK, THREADS, MINW, SOURCE) \
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, true>), MODE, WALK, THREADS, MINW}
 // The (scene mode, walk, workgroup shape) set of the other batch units, with the register-slot fallback (query_plan.h), so that every
 // scene has a kernel; one set for rays as given, one for the drawn lobes, as radiance.hip has.  A lane carries what a lane of the gather
 // kernel carries plus the outstanding shadow ray (direction, t_max, colour) and two flags: the launch bounds are the highest at which
@@ -230,9 +291,29 @@ const BatchKernel kNeeLobeKernels[] = {
     TRT_NEE(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
     TRT_NEE(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
 };
+// The weighted kernels (trt_nee_mis): the same shapes; a lane carries csh besides.  Bounds by the same rule, read per shape off both
+// sources (profiles/nee_mis_resource_usage.txt).
+const BatchKernel kNeeMisRayKernels[] = {
+    TRT_NEE_MIS(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_RAYS),
+    TRT_NEE_MIS(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
+    TRT_NEE_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
+};
+const BatchKernel kNeeMisLobeKernels[] = {
+    TRT_NEE_MIS(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_LOBE),
+    TRT_NEE_MIS(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
+    TRT_NEE_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
+};
 #undef TRT_NEE
+#undef TRT_NEE_MIS
 constexpr size_t kNeeShapes = sizeof(kNeeRayKernels) / sizeof(kNeeRayKernels[0]);
 static_assert(sizeof(kNeeLobeKernels) == sizeof(kNeeRayKernels), "one lobe instantiation per shape");
+static_assert(sizeof(kNeeMisRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeeMisLobeKernels) == sizeof(kNeeRayKernels), "one weighted instantiation per shape and source");
 
 // What a call asks of the device, after the checks.
 struct NeeCall {
@@ -243,6 +324,8 @@ struct NeeCall {
     uint32_t n_emitters;
     float shadow_end;
     uint32_t source_is_diffuse;
+    bool mis = false;                // trt_nee_mis: the weighted kernels, with `heuristic`
+    uint32_t heuristic = 0u;
     bool nothing() const { return ra.sample_begin == ra.sample_end || ra.max_bounces == 0u; }
 };
 
@@ -256,13 +339,15 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, c.source == TRT_PASSES_RAYS ? kNeeRayKernels : kNeeLobeKernels, kNeeShapes, b);
+    const bool rays = c.source == TRT_PASSES_RAYS;
+    const BatchKernel* const table = c.mis ? (rays ? kNeeMisRayKernels : kNeeMisLobeKernels) : (rays ? kNeeRayKernels : kNeeLobeKernels);
+    const hipError_t e = batch_prepare(scd, n, table, kNeeShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     RenderArgs ra = c.ra;
     ra.flat_reuse = qs.flat_reuse;
     NeeArgs ga{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
-               c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse};
+               c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse, c.heuristic};
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
     return batch_launch(b, args, stream);
 }
@@ -293,6 +378,60 @@ int nee_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_em
     return TRT_OK;
 }
 
+// trt_nee_mis' checks before any device work: trt_nee's on p->nee, then the heuristic and this struct's reserved words.
+int nee_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
+                  const float* radiance, NeeCall& c) {
+    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    const int rc = nee_check(s, items, n, emitters, n_emitters, &p->nee, radiance, c);
+    if (rc != TRT_OK) return rc;
+    if (p->heuristic > TRT_MIS_POWER) return query_fail(TRT_ERR_INVALID_ARG, "heuristic must be TRT_MIS_BALANCE or TRT_MIS_POWER");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    c.mis = true;
+    c.heuristic = p->heuristic;
+    return TRT_OK;
+}
+
+// The table rule of trt_nee_mis, which only a host form can check: the entries that name a geometry are exactly the scene's TRT_LIGHT
+// geometries (trt_scene_emitters), each once, in any order.  The weights of a light's two strategies sum to 1 only then.
+int nee_mis_table_check(const trt_scene* s, const trt_emitter* emitters, uint32_t n_emitters) {
+    uint32_t count = 0;
+    int rc = trt_scene_emitters(s, nullptr, 0u, &count);
+    if (rc != TRT_OK) return rc;
+    std::vector<trt_emitter> own(count);
+    rc = trt_scene_emitters(s, own.data(), count, &count);
+    if (rc != TRT_OK) return rc;
+    std::vector<uint32_t> want, have;
+    for (const trt_emitter& e : own) want.push_back(e.geometry);
+    for (uint32_t i = 0; i < n_emitters; i++)
+        if (emitters[i].geometry != 0xFFFFFFFFu) have.push_back(emitters[i].geometry);
+    std::sort(want.begin(), want.end());
+    std::sort(have.begin(), have.end());
+    if (want != have)
+        return query_fail(TRT_ERR_INVALID_ARG, "the table's entries with a geometry must be the scene's lights, each once (trt_scene_emitters)");
+    return TRT_OK;
+}
+
+// The two forms after their checks, for trt_nee and trt_nee_mis alike: `c` says which kernels.
+int nee_on_device(trt_scene* s, const NeeCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, float* d_radiance, float* d_moment2,
+                  uint64_t* d_counters, void* stream) {
+    return sample_query_on_device(s, n, "next-event query launch", [&](const QueryScene& qs) {
+        return launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
+                          reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    });
+}
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).
+int nee_on_host(trt_scene* s, const NeeCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, float* radiance,
+                float* moment2, trt_stats* stats) {
+    const size_t sums = (size_t)n * 12u;
+    const SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                       "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "next-event query buffers", "next-event query launch", stats,
+                                [&](const QueryScene& qs, const SampleDev& d) {
+                                    return launch_nee(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                });
+}
+
 }  // namespace
 }  // namespace trt
 
@@ -311,14 +450,10 @@ int trt_nee_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_e
     trt::NeeCall c;
     const int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::sample_query_on_device(s, n, "next-event query launch", [&](const trt::QueryScene& qs) {
-        return trt::launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
-                               reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    });
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
 }
 
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).  The table's
-// entries are checked where n > 0, ahead of any device work.
+// The table's entries are checked where n > 0, ahead of any device work.
 int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_params* p, float* radiance,
             float* moment2, trt_stats* stats) {
     return trt::host_form([&]() -> int {
@@ -327,19 +462,50 @@ int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* e
         if (rc != TRT_OK) return rc;
         rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        const size_t sums = (size_t)n * 12u;
-        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                                "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
-        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "next-event query buffers", "next-event query launch", stats,
-                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
-                                             return trt::launch_nee(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
-                                         });
+        return trt::nee_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
     });
 }
 
 // How launch_nee would launch n items on this scene: the two tables share their shapes and bounds, so the source does not enter.
 int trt_nee_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
     return trt::batch_launch_plan(s, n, compute_units, trt::kNeeLobeKernels, trt::kNeeShapes, out);
+}
+
+void trt_nee_mis_params_default(trt_nee_mis_params* out) {
+    if (!out) return;
+    *out = trt_nee_mis_params{};
+    trt_nee_params_default(&out->nee);
+    out->heuristic = TRT_MIS_BALANCE;
+}
+
+// The device form cannot read the table: the table rule is the caller's to keep.
+int trt_nee_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters,
+                       const trt_nee_mis_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::NeeCall c;
+    const int rc = trt::nee_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_nee_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
+                float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::NeeCall c;
+        int rc = trt::nee_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+        }
+        return trt::nee_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+    });
+}
+
+// The weighted kernels' table: the same shapes, its own bounds.
+int trt_nee_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeMisLobeKernels, trt::kNeeShapes, out);
 }
 
 }  // extern "C"
