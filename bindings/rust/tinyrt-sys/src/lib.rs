@@ -348,6 +348,16 @@ pub struct trt_nee_mis_params {
     pub reserved: [u32; 7],
 }
 
+/// `trt_direct_params` and the heuristic (`enum trt_mis_heuristic`) that weights a shadow ray against a cosine-lobe ray from the surfel,
+/// for `trt_direct_mis` (128 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_direct_mis_params {
+    pub direct: trt_direct_params,
+    pub heuristic: u32,
+    pub reserved: [u32; 7],
+}
+
 /// The six feature buffers of `trt_render_aov`; a null pointer = not wanted.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -536,6 +546,13 @@ extern "C" {
                               p: *const trt_nee_mis_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
                               stream: *mut c_void) -> c_int;
     pub fn trt_nee_mis_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_direct_mis_params_default(out: *mut trt_direct_mis_params);
+    pub fn trt_direct_mis(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, n_emitters: u32,
+                          p: *const trt_direct_mis_params, radiance: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_direct_mis_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter, n_emitters: u32,
+                                 p: *const trt_direct_mis_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
+                                 stream: *mut c_void) -> c_int;
+    pub fn trt_direct_mis_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_probe_params_default(out: *mut trt_probe_params);
     pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
                      stats: *mut trt_stats) -> c_int;

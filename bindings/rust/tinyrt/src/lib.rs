@@ -136,7 +136,7 @@ pub enum PassesSource {
     Lobe(Lobe),
 }
 
-/// How `World::nee_mis` weights a shadow ray against the hit the path makes anyway (`enum trt_mis_heuristic`).
+/// How `World::nee_mis` and `World::direct_mis` weight a shadow ray against the hit a scattered ray makes (`enum trt_mis_heuristic`).
 #[derive(Clone, Copy, Debug, PartialEq)]
 pub enum MisHeuristic {
     Balance,
@@ -378,6 +378,37 @@ impl World {
         check(unsafe {
             sys::trt_direct(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32,
                             &params, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
+    /// `direct` with multiple importance sampling (`trt_direct_mis`): every sample also sends one cosine-lobe ray from the surfel (RNG
+    /// stream `(seed, j, 0xFFFFFFFF)`), and a light of the scene counts both ways, the shadow sample scaled by
+    /// 1 / (1 + q(p_bsdf / p_light)) and the lobe ray's hit on a light by the complement, q(x) = x (`MisHeuristic::Balance`) or x * x
+    /// (`Power`): the same expectation without the 1/d2 tail of surfels beside a lamp, for one closest-hit walk more per sample.
+    /// `emitters` must hold exactly the scene's own lights (`emitters()`), each once, plus any virtual ones; anything else is an error.
+    /// Returns `(radiance, moment2)` as `direct` does.
+    pub fn direct_mis(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], samples_per_item: u32, heuristic: MisHeuristic,
+                      shadow_end: Float, seed: u32, first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_direct_mis_params::default();
+        unsafe { sys::trt_direct_mis_params_default(&mut params) };
+        params.direct.path.samples_per_ray = samples_per_item;
+        params.direct.path.seed = seed;
+        params.direct.path.first_stream = first_stream;
+        params.direct.shadow_end = shadow_end;
+        params.heuristic = match heuristic {
+            MisHeuristic::Balance => sys::TRT_MIS_BALANCE,
+            MisHeuristic::Power => sys::TRT_MIS_POWER,
+        };
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_direct_mis(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), emitters.len() as u32,
+                                &params, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((radiance, moment2))
     }

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Bake the direct light of the Cornell box's floor with shadow rays -> direct_nee.png, beside the same light found by chance.
-   python examples/bake_direct.py [texels samples]
+   python examples/bake_direct.py [texels samples] [--mis balance|power]
 bake.quad_texels lays texels x texels surfels over the floor quad (as examples/bake_passes.py does).  Scene.direct (trt_direct) aims every
 sample at a point on the lamp - the table is Scene.emitters(), the scene's own lights - and asks whether the segment is blocked;
 Scene.passes (trt_passes) draws cosine-distributed first rays, of which about one in 200 reaches the lamp, and keeps those in its depth-0
 slot.  Both estimate the same integral, so the two means agree to sampling noise, and the standard error of a texel (trt_variance's
 square root) says at what price: at the same number of samples the shadow rays are about two orders of magnitude quieter.
+
+--mis sends one cosine-lobe ray from every texel besides and weights the two against each other (trt_direct_mis): the same mean; on the
+floor, far from the lamp, it buys nothing and costs a walk, beside the lamp (a ceiling, the top of a wall) it removes the 1/d2 tail.
 
 The lamp is lowered from y = 100 to y = 99 here.  In the stock box it lies in the ceiling's plane, and the reference's own paths - hence
 trt_gather and trt_passes - see it only where rounding lets the lamp win the tie with the ceiling, about a quarter of the time; a shadow
@@ -20,6 +23,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tinyrt_amd as trt
 
 argv = sys.argv[1:]
+mis = None
+if "--mis" in argv:
+    at = argv.index("--mis")
+    mis = argv[at + 1]
+    del argv[at:at + 2]
 texels, spp = (int(a) for a in argv[:2]) if len(argv) >= 2 else (256, 64)
 desc = trt.scenes.cornell(2, 2)                                              # the camera of the description is not used
 geos = list(desc["geometries"])
@@ -34,14 +42,15 @@ assert kind == "quad"
 items = trt.bake.quad_texels(corner, u, v, texels, texels, flip=True)        # the axis points up, into the box
 table = scene.emitters()
 t0 = time.perf_counter()
-direct, moment2, st = scene.direct(items, table, spp, moment2=True)
+direct, moment2, st = scene.direct(items, table, spp, moment2=True, mis=mis)
 dt = time.perf_counter() - t0
 passes, _, pst = scene.passes(items, spp, depth_bins=2, source="cosine", max_bounces=1, background=(0.0, 0.0, 0.0), spent=False)
 by_chance = trt.passes.direct(passes)
 trt.Image(direct.reshape(texels, texels, 3)).save("direct_nee.png")
 with np.errstate(invalid="ignore"):
     err = np.sqrt(np.maximum(moment2 - direct * direct, 0.0) / max(spp - 1, 1))[:, 0]
-print(f"{texels}x{texels} texels of the floor, {spp} samples each, {len(table)} emitter: {st['rays']} shadow rays of {st['samples']} samples, "
+print(f"{texels}x{texels} texels of the floor, {spp} samples each, {len(table)} emitter: {st['rays']} {'shadow' if mis is None else 'shadow and lobe'} rays of "
+      f"{st['samples']} samples, "
       f"kernel {st['kernel_ms']:.1f} ms, call {dt * 1e3:.1f} ms; mean direct light {float(direct[:, 0].mean()):.4f} "
       f"(standard error of a texel {float(err.mean()):.4f}) beside passes.direct {float(by_chance[:, 0].mean()):.4f} "
       f"from {pst['rays']} rays found by chance -> direct_nee.png")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bake the full light of the Cornell box's floor with the lights aimed at at every bounce -> nee.png, beside the same light found by
 chance -> gather.png.
-   python examples/bake_nee.py [SIZE K] [--mis balance|power]
+   python examples/bake_nee.py [SIZE K] [--mis balance|power] [--direct-mis balance|power]
 bake.quad_texels lays SIZE x SIZE surfels over the floor quad.  Scene.direct (trt_direct) aims every sample at the lamp from the texel
 itself; Scene.nee (trt_nee) with source_is_diffuse=True traces the cosine-distributed paths Scene.gather traces, hides the lamp where a
 path reaches it by a diffuse bounce and sends one shadow ray to it from every diffuse vertex instead: the texel's indirect light.  Their sum
@@ -9,6 +9,9 @@ and Scene.gather at the same K estimate the same integral; the standard error of
 
 --mis weights every shadow ray against the hit the path makes anyway (trt_nee_mis): the same mean, without the 1/d2 tail of the shadow
 rays sent from vertices beside the lamp.
+
+--direct-mis takes the direct part from trt_direct_mis, which weights the texel's own shadow ray against a cosine-lobe ray from the texel:
+with both flags no term of the bake is unbounded, which matters for texels beside the lamp (not the floor's).
 
 The lamp is lowered from y = 100 to y = 99 here, as in examples/bake_direct.py: in the stock box it lies in the ceiling's plane."""
 import os
@@ -26,6 +29,11 @@ if "--mis" in argv:
     at = argv.index("--mis")
     mis = argv[at + 1]
     del argv[at:at + 2]
+direct_mis = None
+if "--direct-mis" in argv:
+    at = argv.index("--direct-mis")
+    direct_mis = argv[at + 1]
+    del argv[at:at + 2]
 size, spp = (int(a) for a in argv[:2]) if len(argv) >= 2 else (256, 64)
 desc = trt.scenes.cornell(2, 2)                                              # the camera of the description is not used
 geos = list(desc["geometries"])
@@ -40,7 +48,7 @@ items = trt.bake.quad_texels(corner, u, v, size, size, flip=True)            # t
 table = scene.emitters()
 path = dict(max_bounces=5, background=(0.0, 0.0, 0.0))
 t0 = time.perf_counter()
-direct, d_m2, dst = scene.direct(items, table, spp, moment2=True)
+direct, d_m2, dst = scene.direct(items, table, spp, moment2=True, mis=direct_mis)
 indirect, i_m2, ist = scene.nee(items, table, spp, source="cosine", source_is_diffuse=True, moment2=True, mis=mis, **path)
 t1 = time.perf_counter()
 gather, g_m2, gst = scene.gather(items, spp, lobe="cosine", moment2=True, **path)

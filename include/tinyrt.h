@@ -52,7 +52,8 @@ extern "C" {
  *              trt_passes_launch_plan; trt_emitter, trt_scene_emitters, trt_emitter_init_quad, trt_emitter_init_sphere, trt_direct_params,
  *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan; trt_nee_params, trt_nee_params_default,
  *              trt_nee, trt_nee_device, trt_nee_launch_plan; trt_mis_heuristic, trt_nee_mis_params, trt_nee_mis_params_default,
- *              trt_nee_mis, trt_nee_mis_device, trt_nee_mis_launch_plan. */
+ *              trt_nee_mis, trt_nee_mis_device, trt_nee_mis_launch_plan; trt_direct_mis_params, trt_direct_mis_params_default,
+ *              trt_direct_mis, trt_direct_mis_device, trt_direct_mis_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -953,6 +954,68 @@ int trt_nee_mis_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const t
 /* How trt_nee_mis[_device] launches n items on this scene: trt_nee_launch_plan's rule and fields over the weighted kernels' own table
  * (the same shapes; kernel_waves_per_simd is that table's bound, the same for every source and heuristic). */
 int trt_nee_mis_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Direct-light queries with multiple importance sampling: the shadow ray and a cosine-lobe ray from the surfel, weighted by their densities ----
+ * trt_direct finds a surfel's direct light by the shadow ray alone.  For a surfel beside a lamp - the ceiling, the top rows of the walls - the
+ * shadow sample's 1/d2 weight is a thousand times the mean, and trt_nee_mis hides hit 1 in full under source_is_diffuse = 1 because
+ * trt_direct has no weights.  The surfel's direct light can be found two ways - by the shadow ray (density p_light) and by a cosine-lobe
+ * ray from the surfel (density p_bsdf) - and this query counts BOTH in one sample, each weighted so that the two weights of one point sum
+ * to 1.  It costs one closest-hit walk more per sample: where no surfel is near a light trt_direct stays the cheaper choice.
+ *
+ * Contract of a sample.  Unchanged from trt_direct, with params->direct in the place of its params: the items, used as given; K, E and
+ * j = first_stream + i * K + s; sample ranges and accumulate; both split invariances; the output bounds; max_bounces and background are
+ * not read.  All f32, one IEEE operation per operator, nothing fused.  q(x) = x for TRT_MIS_BALANCE and x * x for TRT_MIS_POWER;
+ * sc(a) = (a * float(E)) * 0.318309886f.
+ *  1. Shadow sample.  trt_direct's steps 1-7 exactly, on stream (seed, j, 1): the same emitter, point, wgt, liveness, ray, t_max, walk, and
+ *     "an empty range walks nothing".  wl = 1.0f / (1.0f + q(wgt));  if the record's `geometry` word is 0xFFFFFFFF, wl = 1.0f (a virtual
+ *     emitter cannot be hit: its shadow ray counts in full).  A live, unoccluded sample has  T_l.ch = (colour.ch * wgt) * wl.
+ *  2. Lobe sample.  g = RNG(seed, j, 0xFFFFFFFF) - no other query reaches this stream (trt_nee's 2 + d would need 2^32 - 3 scatters); it
+ *     is independent of stream 1, which the shadow draw uses and on which trt_gather / trt_nee draw their first ray, and of the path
+ *     stream 0.  The ray is trt_gather's TRT_LOBE_COSINE draw about the item: three draws, axis + random_unit_vector, the axis itself
+ *     if that is near zero, and Ray::new normalises.  It is walked as the gather walks its first ray: BVH::hit over [0.001, inf), closest
+ *     hit; a ray with a NaN component hits nothing.  A miss, or a hit on anything but a TRT_LIGHT material, adds nothing: the background
+ *     is not light from the table.  At a light, with t = rec.t:
+ *       csh = dot(axis as given, ray.direction)
+ *       clh = |dot(rec.normal, ray.direction)|
+ *       area = the hit primitive's own, as in trt_nee_mis: quad sqrt((n.x*n.x + n.y*n.y) + n.z*n.z) of the un-normalised normal the
+ *              packed scene holds, sphere 12.566371f * (r * r)
+ *       g = ((csh * clh) / (t * t)) * sc(area)
+ *       wb = q(g) / (1.0f + q(g)) if csh > 0 and q(g) is finite, else 1.0f
+ *       T_b.ch = emission.ch * wb
+ *  3. Fold.  A sample with neither term adds nothing, as in trt_direct.  Otherwise c = T_l, or T_b, or T_l + T_b (c.ch = T_l.ch + T_b.ch)
+ *     - ONE sample, so moment2 is the second moment of the sum:
+ *       radiance.ch = radiance.ch + c.ch * inv_K;   moment2.ch = moment2.ch + (c.ch * c.ch) * inv_K
+ *  4. Counters.  stats.samples is trt_direct's.  stats.rays counts the shadow walks made plus one per sample for the lobe ray, counted
+ *     as trt_gather counts its first world.hit call (cpu.rs:48).
+ *  5. Table rule and errors.  The table rule is trt_nee_mis': the entries whose `geometry` is not 0xFFFFFFFF must be exactly the scene's
+ *     TRT_LIGHT geometries, each once, as trt_scene_emitters wrote them; any order, with any virtual entries among them.  The host form
+ *     checks it; THE DEVICE FORM CANNOT CHECK: with another table its weights do not sum to 1 and the result is biased.  Errors, before
+ *     any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_direct's on `direct`; heuristic above 1; a non-zero reserved word; the
+ *     table rule (host form, n > 0).  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM.  n == 0 succeeds and touches nothing.
+ *  6. Meaning and limits.  With a unit axis wgt = p_bsdf / p_light, and g is the same ratio seen from the hit, so 1 / (1 + wgt) and
+ *     g / (1 + g) are the balance weights of the two strategies at one point and sum to 1 (the power form squares the ratio): the mean
+ *     is trt_direct's - irradiance / pi from the scene's lights, plus virtual emitters in full.  With BALANCE and the scene's own table
+ *     every term is at most the emitter's colour up to rounding: a sample is at most 2 x the largest colour channel.
+ *     trt_direct_mis + trt_nee_mis(source_is_diffuse = 1) is the full bake with no unbounded term.  A non-unit axis is used as given in
+ *     both draws and the bits are defined, but the weights no longer sum to 1 and the result does not scale linearly as trt_direct's
+ *     does.  The coplanar lamp of the stock Cornell box (the two strategies disagree about its visibility), shadow_end and the uniform
+ *     choice among emitters are inherited.
+ *  7. Identities.  (1) On a scene without a TRT_LIGHT geometry and with a table of virtual emitters, radiance and moment2 are
+ *     trt_direct's bytes for both heuristics.  (2) stats.samples equals trt_direct's.  (3) stats.rays equals trt_direct's plus
+ *     trt_gather's at max_bounces = 1 for the same items and K. */
+typedef struct {
+    trt_direct_params direct;     /* trt_direct's rules and errors, unchanged */
+    uint32_t heuristic;           /* enum trt_mis_heuristic */
+    uint32_t reserved[7];         /* zero */
+} trt_direct_mis_params;          /* 128 B: offsets 0, 96, 100 */
+void trt_direct_mis_params_default(trt_direct_mis_params *out);   /* direct = trt_direct_params_default's, heuristic TRT_MIS_BALANCE; NULL tolerated */
+int trt_direct_mis(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, uint32_t n_emitters,
+                   const trt_direct_mis_params *p, float *radiance, float *moment2, trt_stats *stats);
+int trt_direct_mis_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, uint32_t n_emitters,
+                          const trt_direct_mis_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+/* How trt_direct_mis[_device] launches n items on this scene: trt_direct_launch_plan's rule and fields over the weighted kernels' own
+ * table (the same shapes; kernel_waves_per_simd is that table's bound, the same for both heuristics). */
+int trt_direct_mis_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

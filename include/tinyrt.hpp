@@ -152,6 +152,18 @@ public:
         check(trt_direct(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
                          moment2 ? moment2->data() : nullptr, stats));
     }
+    // direct() with multiple importance sampling (trt_direct_mis): every sample also sends one cosine-lobe ray from the surfel, and a light
+    // of the scene counts both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the lobe ray's hit on a light by the
+    // complement, q(x) = x (TRT_MIS_BALANCE) or x * x (TRT_MIS_POWER): the same expectation without the 1/d2 tail of surfels beside a
+    // lamp, for one closest-hit walk more per sample.  `table` must hold exactly the scene's own lights (emitters()), each once, plus any
+    // virtual ones; anything else is an error.  Start `p` from trt_direct_mis_params_default.
+    void direct_mis(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_direct_mis_params& p,
+                    std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_direct_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
+                             moment2 ? moment2->data() : nullptr, stats));
+    }
     // What radiance() / gather() estimate, with the lights aimed at (trt_nee): the path of every sample is theirs bit for bit (p.gather:
     // path, source - TRT_PASSES_RAYS, _COSINE, _CONE - and spread), at every Lambertian hit that leaves bounce budget one shadow ray goes
     // to `table` as in direct(), and a light the path then reaches by a diffuse scatter counts as black.  `table` should be emitters():

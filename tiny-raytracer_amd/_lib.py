@@ -185,6 +185,12 @@ class NeeMisParams(C.Structure):
     _fields_ = [("nee", NeeParams), ("heuristic", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class DirectMisParams(C.Structure):
+    """tinyrt.h trt_direct_mis_params: trt_direct_params and the heuristic that weights a shadow ray against a cosine-lobe ray from the
+    surfel (128 bytes)."""
+    _fields_ = [("direct", DirectParams), ("heuristic", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
 class Tuning(C.Structure):
     """tinyrt.h trt_tuning: scheduling / placement knobs of a render; every value renders the same frame."""
     FIELDS = ("stream_waves_per_simd", "stream_big_threads", "stream_batch_spp", "radiance_gb", "leaf_slots", "lds_leaf_stack", "ray_pool",
@@ -309,6 +315,12 @@ SIGNATURES = {
     "trt_nee_mis_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(NeeMisParams), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "trt_nee_mis_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_direct_mis_params_default": (None, [C.POINTER(DirectMisParams)]),
+    "trt_direct_mis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams), C.c_void_p, C.c_void_p,
+                                 C.POINTER(Stats)]),
+    "trt_direct_mis_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_direct_mis_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

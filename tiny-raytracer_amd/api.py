@@ -361,8 +361,11 @@ class Scene:
         return out
 
     @staticmethod
-    def _direct_params(samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0, accumulate=False):
-        """sample_end = 0 means samples_per_item, as at the C boundary; shadow_end = None: the library's default (0.999)."""
+    def _direct_params(samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0, accumulate=False, mis=None):
+        """sample_end = 0 means samples_per_item, as at the C boundary; shadow_end = None: the library's default (0.999).  mis = None: a
+        trt_direct_params; "balance" or "power": a trt_direct_mis_params."""
+        if mis is not None and mis not in Scene.MIS:
+            raise ValueError("mis must be None, 'balance' or 'power'")
         p = _lib.DirectParams()
         lib.trt_direct_params_default(C.byref(p))
         path = p.path
@@ -370,7 +373,12 @@ class Scene:
         path.sample_begin, path.sample_end, path.accumulate = int(sample_begin), int(sample_end), 1 if accumulate else 0
         if shadow_end is not None:
             p.shadow_end = float(shadow_end)
-        return p
+        if mis is None:
+            return p
+        m = _lib.DirectMisParams()
+        lib.trt_direct_mis_params_default(C.byref(m))
+        m.direct, m.heuristic = p, Scene.MIS[mis]
+        return m
 
     @staticmethod
     def _emitter_table(emitters):
@@ -380,18 +388,23 @@ class Scene:
         return e
 
     def direct(self, items, emitters, samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0,
-               accumulate=False, radiance=None, moment2=None):
+               accumulate=False, radiance=None, moment2=None, mis=None):
         """trt_direct: the light that reaches surfels float32 [n, 6] (point, axis; used as given) straight from the emitters of a table
         (emitters(), lights.quad / lights.sphere records, or any mix).  Each of samples_per_item = K samples picks an emitter uniformly and
         a point on it from RNG stream (seed, first_stream + i * K + s, 1), and asks occluded()'s question of the normalised ray towards
         it over [0.001, distance * shadow_end); an unoccluded sample that faces the point adds colour * cos * |cos_l| * area * E /
         (pi * distance^2) / K.  With a unit axis the result is what a white diffuse surface reflects from those emitters alone -
         gather()'s convention, with far less noise.  Sample range, accumulate, `radiance`, `moment2` and the returns as in radiance()
-        (sample_end = 0: K); stats carry samples and rays = the occlusion walks made."""
+        (sample_end = 0: K); stats carry samples and rays = the occlusion walks made.
+        mis = "balance" | "power" (trt_direct_mis): every sample also sends one cosine-lobe ray from the surfel (stream (seed, j,
+        0xFFFFFFFF)), and a light of the scene is counted both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the
+        lobe ray's hit on a light by its complement, q(x) = x or x * x: the same expectation without the 1/d2 tail of surfels beside a
+        lamp, for one closest-hit walk more per sample (rays = occlusion walks + samples).  `emitters` must then hold exactly the scene's
+        own lights (emitters()), each once, plus any virtual ones; anything else is an error."""
         r, _ = _rays_and_t_max(items, None)
         n = len(r)
         e = self._emitter_table(emitters)
-        p = self._direct_params(samples_per_item, shadow_end, seed, first_stream, sample_begin, sample_end, accumulate)
+        p = self._direct_params(samples_per_item, shadow_end, seed, first_stream, sample_begin, sample_end, accumulate, mis)
         if radiance is None:
             radiance = np.zeros((n, 3), np.float32)
         if moment2 is True:
@@ -399,22 +412,27 @@ class Scene:
         for a in (radiance, moment2):
             assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
         st = Stats()
-        check(lib.trt_direct(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
-                             radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        fn = lib.trt_direct if mis is None else lib.trt_direct_mis
+        check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
+                 radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
         return radiance, moment2, st.as_dict()
 
     def direct_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
         """Enqueue direct() on buffers already in HBM (device pointers as integers: n x 24 bytes of surfels, n_emitters x 80 bytes of
         trt_emitter records, n x 12 bytes of sums each) on the current device; asynchronous on the stream, allocates nothing.  `params`:
-        direct()'s keywords, samples_per_item included."""
+        direct()'s keywords, samples_per_item and mis included (trt_direct_mis_device where mis is given: the device form cannot check the
+        table rule)."""
         p = self._direct_params(**params)
-        check(lib.trt_direct_device(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
-                                    C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+        fn = lib.trt_direct_mis_device if isinstance(p, _lib.DirectMisParams) else lib.trt_direct_device
+        check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
+                 C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
 
-    def direct_plan(self, n, compute_units=0):
-        """trt_direct_launch_plan: how direct() launches n surfels on this scene, as a dict with ambient_plan()'s fields."""
+    def direct_plan(self, n, compute_units=0, mis=None):
+        """trt_direct_launch_plan (mis given: trt_direct_mis_launch_plan): how direct() launches n surfels on this scene, as a dict with
+        ambient_plan()'s fields."""
         plan = _lib.QueryPlan()
-        check(lib.trt_direct_launch_plan(self._h, int(n), int(compute_units), C.byref(plan)))
+        fn = lib.trt_direct_launch_plan if mis is None else lib.trt_direct_mis_launch_plan
+        check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
     # ---- probe queries (tinyrt.h trt_probe): spherical-harmonic radiance from first rays the device draws over the sphere ----

@@ -13,9 +13,16 @@
 // this sample" - a dead sample (facing away, on the point, a weight that is no number) and one whose range [0.001, t_max) is empty stay in
 // the wave's rounds and walk nothing.  The dynamic LDS is laid out as the queries lay it out (wave_run.h) and the launch rule is the
 // queries' (query_plan.h): a wave owns a contiguous run of the items.
+//
+// trt_direct_mis / trt_direct_mis_device (tinyrt.h) are a kernel of their own, direct_mis_kernel, in the same six shapes and both forms:
+// the shadow sample scaled by wl = 1 / (1 + q(wgt)) (1 for a virtual emitter) and, on stream (seed, j, 0xFFFFFFFF), the gather's cosine
+// ray from the surfel, whose hit on a light adds emission * wb (mis_weight.h mis_hit_weight, shared with nee.hip).  Up to two walks per
+// sample go through ONE walk call site, nee_kernel's way.  direct_kernel is instruction for instruction what it was; the
+// two queries share their checks, launcher and both forms' bodies.
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
+#include "mis_weight.h"
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
@@ -171,6 +178,184 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, Dir
     flush_counters<false>(da.counters, n_samples, n_rays, ctr);
 }
 
+// ---- trt_direct_mis: the shadow sample AND a cosine-lobe ray from the surfel, weighted by their densities (tinyrt.h) ----
+static_assert(sizeof(trt_direct_mis_params) == 128 && offsetof(trt_direct_mis_params, direct) == 0 && offsetof(trt_direct_mis_params, heuristic) == 96 &&
+              offsetof(trt_direct_mis_params, reserved) == 100, "trt_direct_mis_params layout (tinyrt.h)");
+
+struct DirectMisArgs {
+    DirectArgs d;                    // direct_kernel's, read the same way
+    uint32_t heuristic;              // enum trt_mis_heuristic, wave-uniform
+};
+
+// The shadow sample's share of a drawn sample: 1 / (1 + q(p_bsdf / p_light)); a virtual emitter cannot be hit and counts in full.
+TRT_DEV float mis_shadow_weight(const WeightedDirectSample& w, uint32_t heuristic) {
+    const float qw = heuristic == TRT_MIS_POWER ? w.wgt * w.wgt : w.wgt;
+    return w.geometry != 0xFFFFFFFFu ? 1.0f / (1.0f + qw) : 1.0f;
+}
+// What the lobe ray of a sample adds, T_b: nothing (false) on a miss or a hit on anything but a light, else emission * wb with csh from the
+// item's axis as given (re-read: three registers less per lane while the walks run; a light hit is the rare case).
+template <int MODE>
+TRT_DEV bool mis_lobe_term(const SceneAcc<MODE>& sc, const float* __restrict__ items, uint32_t idx, const Ray& ray, uint32_t prim, float t,
+                           uint32_t n_emitters, uint32_t heuristic, V3& tb) {
+    if (prim == PRIM_NONE) return false;
+    const uint32_t mat = prim_material<MODE>(sc, prim);
+    if (sc.material_kind(mat) != TRT_LIGHT) return false;
+    const float* const it = items + 6ull * idx;
+    const float csh = dot(v3(it[3], it[4], it[5]), ray.d);
+    const V3 normal = hit_unit_normal<MODE>(sc, prim, ray, t);
+    const float wb = mis_hit_weight<MODE>(sc, prim, ray, normal, t, csh, n_emitters, heuristic);
+    const float4 m = sc.material(mat);
+    tb = v3(m.x, m.y, m.z) * wb;
+    return true;
+}
+
+// direct_kernel's two forms with up to two walks per sample through ONE walk call site, as nee_kernel has it: a closest-hit walk whose
+// first t_best is the shadow ray's t_max ("anything in [0.001, t_max)" is prim_best != PRIM_NONE then) or +inf for the lobe ray.  The
+// shadow sample is drawn on stream (seed, j, 1) exactly as direct_kernel draws it, the lobe ray on (seed, j, 0xFFFFFFFF) once the shadow
+// walk is over: a lane keeps one ray.  `c` holds T_l while `lit` says it counts; the lobe ray's term joins it or stands alone.
+constexpr uint32_t kLobeStreamWord = 0xFFFFFFFFu;
+template <int MODE, int WALK, int THREADS, int MINW>
+__global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd, DirectMisArgs ma, const float4* __restrict__ leaf_list,
+                                                                        const uint4* __restrict__ nodes16) {
+    const DirectArgs& da = ma.d;
+    stage_scene_to_lds<MODE>(scd);
+    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, da.flat_reuse);
+    const SceneAcc<MODE> sc{scd.blob, scd.L};
+    const float* __restrict__ const items = da.items;
+    const float* __restrict__ const emitters = da.emitters;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long begin64 = wave_begin<THREADS>(da.rays_per_wave);
+    if (begin64 >= da.n) return;                                            // (after the barriers above)
+    const uint32_t begin = (uint32_t)begin64;
+    const uint32_t count = wave_count(da.n, da.rays_per_wave, begin);
+    // this lane's postponed-leaf stack: behind the scene copy, slots x 64 x 8 bytes per wave
+    float2* const stack = WALK != WALK_REGS ? reinterpret_cast<float2*>(lds_behind_scene(sc)) + (threadIdx.x >> 6) * (64u * da.slots) + lane : nullptr;
+    Counters<false> ctr;
+    constexpr bool kResumable = WALK == WALK_COMPACT || WALK == WALK_LDS_STACK;
+    uint32_t n_samples = 0, n_rays = 0;
+
+    if constexpr (kResumable) {
+        constexpr uint32_t PH_START = 0u, PH_SHADOW = 1u, PH_LOBE_DRAW = 2u, PH_LOBE = 3u;
+        uint32_t cursor = 0;                                                // wave-uniform
+        bool own = false, walking = false;                                  // the lane owns an item; its walk is parked
+        bool lit = false;                                                   // of the sample under way: c counts
+        uint32_t phase = PH_START;                                          // draw the shadow sample | its walk | draw the lobe ray | its walk
+        uint32_t idx = 0, s = 0;
+        DirectSums acc;
+        acc.rad = v3(0.0f, 0.0f, 0.0f); acc.m2 = v3(0.0f, 0.0f, 0.0f);
+        Ray ray;
+        ray.o = v3(0.0f, 0.0f, 0.0f); ray.d = v3(0.0f, 0.0f, 0.0f);
+        V3 c = v3(0.0f, 0.0f, 0.0f);
+        float t_first = 0.0f;
+        for (;;) {
+            // ---- refill: every lane without an item takes the next one of the run (begin + item < n: item < count <= n - begin) ----
+            const uint64_t need = __builtin_amdgcn_ballot_w64(!own);
+            if (need != 0ull && cursor < count) {
+                const uint32_t item = cursor + wave_rank(need);
+                if (!own && item < count) {
+                    idx = begin + item;
+                    s = da.sample_begin;
+                    acc = dir_begin(da, idx);
+                    phase = PH_START;
+                    own = true;
+                }
+                cursor = wave_advance(cursor, need, count);
+            }
+            if (__builtin_amdgcn_ballot_w64(own) == 0ull) break;            // every lane is free and none could take an item: the run is done
+            if (own) {
+                const uint32_t stream = da.first_stream + idx * da.samples_per_item + s;
+                // ---- start: the item's next sample draws its emitter point and shadow ray (stream (seed, j, 1)) ----
+                if (phase == PH_START) {
+                    Rng g = rng_seed(da.seed_key, stream, 1u);
+                    const WeightedDirectSample w = direct_draw_weighted(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    c = w.c * mis_shadow_weight(w, ma.heuristic);
+                    lit = w.live;                                           // until its walk finds something
+                    n_samples++;
+                    phase = PH_LOBE_DRAW;                                   // dead, or an empty range: nothing is walked
+                    if (w.live && w.t_max > kTMin) { ray = w.ray; t_first = w.t_max; phase = PH_SHADOW; }
+                }
+                // ---- the lobe ray (stream (seed, j, 0xFFFFFFFF)): trt_gather's cosine draw about the item ----
+                if (phase == PH_LOBE_DRAW) {
+                    Rng g = rng_seed(da.seed_key, stream, kLobeStreamWord);
+                    ray = gather_ray(items, idx, TRT_LOBE_COSINE, 0.0f, g);
+                    t_first = __builtin_inff();
+                    phase = PH_LOBE;
+                }
+                // ---- walk; a finished walk is answered at once ----
+                Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, ray, false);          // a new walk, or the frame of a parked one
+                if (walking) trav_unpark(stack, tr); else { tr.t_best = t_first; n_rays++; }
+                const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+                walking = !closest_hit_resume<MODE, false, WALK, false>(sc, ray, tr, ctr, da.slots, stack, leaf_list, nodes16, da.stragglers, entered);
+                if (!walking) {
+                    if (phase == PH_SHADOW) {
+                        if (tr.prim_best != PRIM_NONE) lit = false;
+                        phase = PH_LOBE_DRAW;                               // drawn and walked in the next round
+                    } else {
+                        V3 tb;
+                        if (mis_lobe_term<MODE>(sc, items, idx, ray, tr.prim_best, tr.t_best, da.n_emitters, ma.heuristic, tb)) {
+                            c = lit ? c + tb : tb;
+                            lit = true;
+                        }
+                        if (lit) dir_fold(acc, c, da.inv_k);
+                        phase = PH_START;
+                        s += 1u;
+                        if (s == da.sample_end) {
+                            dir_store(da, idx, acc);
+                            own = false;
+                        }
+                    }
+                }
+            }
+        }
+    } else {
+        for (uint32_t base = 0; base < count; base += 64u) {
+            if (base + lane < count) {
+                const uint32_t idx = begin + base + lane;
+                DirectSums acc = dir_begin(da, idx);
+                for (uint32_t s = da.sample_begin; s != da.sample_end; s++) {
+                    const uint32_t stream = da.first_stream + idx * da.samples_per_item + s;
+                    Rng g = rng_seed(da.seed_key, stream, 1u);
+                    const WeightedDirectSample w = direct_draw_weighted(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    n_samples++;
+                    V3 c = w.c * mis_shadow_weight(w, ma.heuristic);
+                    bool lit = w.live;
+                    Ray ray = w.ray;
+                    float t_first = w.t_max;
+                    bool walks = w.live && w.t_max > kTMin;
+                    // the shadow ray, then the lobe ray, through one walk
+#pragma unroll 1
+                    for (uint32_t lobe = 0; lobe < 2u; lobe++) {
+                        if (lobe != 0u) {
+                            Rng gl = rng_seed(da.seed_key, stream, kLobeStreamWord);
+                            ray = gather_ray(items, idx, TRT_LOBE_COSINE, 0.0f, gl);
+                            t_first = __builtin_inff();
+                            walks = true;
+                        }
+                        uint32_t prim = PRIM_NONE;
+                        float t = 0.0f;
+                        if (walks) {
+                            n_rays++;
+                            prim = closest_hit<MODE, false, WALK, false>(sc, ray, false, t, ctr, da.slots, stack, leaf_list, nodes16, flat_reuse, t_first);
+                        }
+                        if (lobe == 0u) {
+                            if (prim != PRIM_NONE) lit = false;
+                        } else {
+                            V3 tb;
+                            if (mis_lobe_term<MODE>(sc, items, idx, ray, prim, t, da.n_emitters, ma.heuristic, tb)) {
+                                c = lit ? c + tb : tb;
+                                lit = true;
+                            }
+                        }
+                    }
+                    if (lit) dir_fold(acc, c, da.inv_k);
+                }
+                dir_store(da, idx, acc);
+            }
+        }
+    }
+    flush_counters<false>(da.counters, n_samples, n_rays, ctr);
+}
+
 namespace {
 
 #define TRT_DIRECT(MODE, WALK, THREADS, MINW) \
@@ -188,6 +373,20 @@ const BatchKernel kDirectKernels[] = {
     TRT_DIRECT(MODE_GLOBAL, WALK_REGS, 256, 6),
 };
 #undef TRT_DIRECT
+#define TRT_DIRECT_MIS(MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&direct_mis_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
+// The weighted kernels (trt_direct_mis): the same shapes.  A lane carries a whole ray where direct_kernel's any-hit walk carries less, and
+// the light-hit weight besides: bounds by the same rule (profiles/direct_mis_resource_usage.txt).
+const BatchKernel kDirectMisKernels[] = {
+    TRT_DIRECT_MIS(MODE_LDS, WALK_FLAT, 256, 5),
+    TRT_DIRECT_MIS(MODE_LDS, WALK_LDS_STACK, 256, 7),
+    TRT_DIRECT_MIS(MODE_LDS, WALK_LDS_STACK, 768, 7),
+    TRT_DIRECT_MIS(MODE_LDS, WALK_REGS, 512, 5),
+    TRT_DIRECT_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 7),
+    TRT_DIRECT_MIS(MODE_GLOBAL, WALK_REGS, 256, 5),
+};
+#undef TRT_DIRECT_MIS
+static_assert(sizeof(kDirectMisKernels) == sizeof(kDirectKernels), "one weighted instantiation per shape");
 constexpr size_t kDirectShapes = sizeof(kDirectKernels) / sizeof(kDirectKernels[0]);
 
 // What a call asks of the device, after the checks.
@@ -196,6 +395,8 @@ struct DirectCall {
     uint32_t samples_per_item, first_stream;
     uint32_t n_emitters;
     float shadow_end;
+    bool mis = false;                // trt_direct_mis: the weighted kernels, with `heuristic`
+    uint32_t heuristic = 0u;
     bool nothing() const { return ra.sample_begin == ra.sample_end; }       // an empty sample range: no sample is drawn
 };
 
@@ -209,13 +410,14 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, kDirectKernels, kDirectShapes, b);
+    const hipError_t e = batch_prepare(scd, n, c.mis ? kDirectMisKernels : kDirectKernels, kDirectShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     DirectArgs da{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
                   c.first_stream, c.ra.seed_key, c.ra.sample_begin, c.ra.sample_end, c.ra.accumulate, c.n_emitters, c.ra.inv_spp, c.shadow_end,
                   qs.flat_reuse};
-    void* args[] = {&scd, &da, &b.leaf_list, &b.nodes16};
+    DirectMisArgs ma{da, c.heuristic};
+    void* args[] = {&scd, c.mis ? static_cast<void*>(&ma) : static_cast<void*>(&da), &b.leaf_list, &b.nodes16};
     return batch_launch(b, args, stream);
 }
 
@@ -237,6 +439,40 @@ int direct_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt
     return TRT_OK;
 }
 
+// trt_direct_mis' checks before any device work: trt_direct's on p->direct, then the heuristic and this struct's reserved words.
+int direct_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters,
+                     const trt_direct_mis_params* p, const float* radiance, DirectCall& c) {
+    if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
+    const int rc = direct_check(s, items, n, emitters, n_emitters, &p->direct, radiance, c);
+    if (rc != TRT_OK) return rc;
+    if (p->heuristic > TRT_MIS_POWER) return query_fail(TRT_ERR_INVALID_ARG, "heuristic must be TRT_MIS_BALANCE or TRT_MIS_POWER");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
+    c.mis = true;
+    c.heuristic = p->heuristic;
+    return TRT_OK;
+}
+
+// The two forms after their checks, for trt_direct and trt_direct_mis alike: `c` says which kernels.
+int direct_on_device(trt_scene* s, const DirectCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, float* d_radiance,
+                     float* d_moment2, uint64_t* d_counters, void* stream) {
+    return sample_query_on_device(s, n, "direct-light query launch", [&](const QueryScene& qs) {
+        return launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
+                             reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+    });
+}
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).
+int direct_on_host(trt_scene* s, const DirectCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters,
+                   float* radiance, float* moment2, trt_stats* stats) {
+    const size_t sums = (size_t)n * 12u;
+    const SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                       "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "direct-light query buffers", "direct-light query launch", stats,
+                                [&](const QueryScene& qs, const SampleDev& d) {
+                                    return launch_direct(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                });
+}
+
 }  // namespace
 }  // namespace trt
 
@@ -254,14 +490,10 @@ int trt_direct_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const tr
     trt::DirectCall c;
     const int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::sample_query_on_device(s, n, "direct-light query launch", [&](const trt::QueryScene& qs) {
-        return trt::launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
-                                  reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
-    });
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
 }
 
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).  The table's
-// entries are checked where n > 0, ahead of any device work.
+// The table's entries are checked where n > 0, ahead of any device work.
 int trt_direct(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_params* p,
                float* radiance, float* moment2, trt_stats* stats) {
     return trt::host_form([&]() -> int {
@@ -270,19 +502,50 @@ int trt_direct(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter
         if (rc != TRT_OK) return rc;
         rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        const size_t sums = (size_t)n * 12u;
-        const trt::SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                                "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
-        return trt::sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "direct-light query buffers", "direct-light query launch", stats,
-                                         [&](const trt::QueryScene& qs, const trt::SampleDev& d) {
-                                             return trt::launch_direct(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
-                                         });
+        return trt::direct_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
     });
 }
 
 // How launch_direct would launch n items on this scene.
 int trt_direct_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
     return trt::batch_launch_plan(s, n, compute_units, trt::kDirectKernels, trt::kDirectShapes, out);
+}
+
+void trt_direct_mis_params_default(trt_direct_mis_params* out) {
+    if (!out) return;
+    *out = trt_direct_mis_params{};
+    trt_direct_params_default(&out->direct);
+    out->heuristic = TRT_MIS_BALANCE;
+}
+
+// The device form cannot read the table: the table rule is the caller's to keep.
+int trt_direct_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters,
+                          const trt_direct_mis_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::DirectCall c;
+    const int rc = trt::direct_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_direct_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_mis_params* p,
+                   float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::DirectCall c;
+        int rc = trt::direct_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+        }
+        return trt::direct_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+    });
+}
+
+// The weighted kernels' table: the same shapes, its own bounds.
+int trt_direct_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectMisKernels, trt::kDirectShapes, out);
 }
 
 }  // extern "C"

@@ -115,6 +115,12 @@ TRT_DEV DirectSample direct_draw(const float* __restrict__ items, uint32_t idx, 
                                  float shadow_end, Rng& g) {
     return direct_draw_from([&] { return rad_load_ray(items, idx); }, emitters, n_emitters, shadow_end, g);
 }
+// ... with the weight and the `geometry` word, for the weighted direct-light kernel (direct.hip, direct_mis_kernel).
+TRT_DEV WeightedDirectSample direct_draw_weighted(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters,
+                                                  uint32_t n_emitters, float shadow_end, Rng& g) {
+    auto surfel = [&] { return rad_load_ray(items, idx); };
+    return direct_draw_from<decltype(surfel), WeightedDirectSample>(surfel, emitters, n_emitters, shadow_end, g);
+}
 // The same sample for a vertex of a path (nee.hip): x the point, n the unit normal on the side the light is gathered on.
 TRT_DEV DirectSample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
     return direct_draw_from([&] { Ray r; r.o = x; r.d = n; return r; }, emitters, n_emitters, shadow_end, g);

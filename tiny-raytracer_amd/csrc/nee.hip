@@ -28,19 +28,17 @@
 // trt_nee_mis / trt_nee_mis_device (tinyrt.h) are the same kernel with MIS = true: the same rounds, walks and draws, and two weights on
 // what a sample adds.  The shadow term is scaled by wl = 1 / (1 + q(wgt)) where the draw's result becomes sh_c (1 for a virtual
 // emitter), and a light the path reaches after a diffuse scatter at hit >= 2, which the plain kernel hides, adds its emission scaled by
-// wb = q(g) / (1 + q(g)) (mis_hit_weight) in the branch where shade has ended the path: cold, since a light always ends it.  A lane
+// wb = q(g) / (1 + q(g)) (mis_weight.h mis_hit_weight) in the branch where shade has ended the path: cold, since a light always ends it.  A lane
 // carries csh, the cosine of its last Lambertian scatter, besides.  The MIS = false instantiations are instruction for instruction what
 // they were without the parameter; the two entry points share their checks, launcher and both forms' bodies with trt_nee.
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
+#include "mis_weight.h"
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
 #include "wave_run.h"
-
-#include <algorithm>
-#include <vector>
 
 namespace trt {
 
@@ -67,27 +65,6 @@ struct NeeArgs {
     uint32_t heuristic;              // enum trt_mis_heuristic, wave-uniform (the MIS kernels; the others do not read it)
 };
 constexpr int NEE_RAYS = 0, NEE_LOBE = 1;      // nee_kernel's SOURCE: the items are rays | surfels whose lobe is NeeArgs::source
-
-// The weight of the path's own hit on a light (tinyrt.h trt_nee_mis, "light hit"): wb for the hit primitive, reached at parameter t of `ray`
-// after a Lambertian scatter whose cosine was csh.  `normal` is the record's (unit, facing).  The area is the primitive's own, in the
-// bits trt_scene_emitters writes: |n| of the packed un-normalised quad normal, 4 pi r^2 with the header's constant for a sphere.
-template <int MODE>
-TRT_DEV float mis_hit_weight(const SceneAcc<MODE>& sc, uint32_t prim, const Ray& ray, const V3& normal, float t, float csh, uint32_t n_emitters,
-                             uint32_t heuristic) {
-    const uint32_t pidx = prim & PRIM_INDEX_MASK;
-    float area;
-    if (prim & PRIM_QUAD_BIT) {
-        const float4 q0 = sc.quad(0, pidx);
-        area = __builtin_sqrtf((q0.x * q0.x + q0.y * q0.y) + q0.z * q0.z);
-    } else {
-        const float r = sc.sphere(pidx).w;
-        area = 12.566371f * (r * r);
-    }
-    const float clh = __builtin_fabsf(dot(normal, ray.d));
-    const float g = ((csh * clh) / (t * t)) * ((area * (float)n_emitters) * 0.318309886f);
-    const float qg = heuristic == TRT_MIS_POWER ? g * g : g;
-    return csh > 0.0f && __builtin_fabsf(qg) < __builtin_inff() ? qg / (1.0f + qg) : 1.0f;
-}
 
 // ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches query_plan.h batch_zero or nothing)
 // MIS (tinyrt.h trt_nee_mis): the same rounds, walks and draws; a shadow sample is scaled by wl, and a light the path reaches after a
@@ -389,26 +366,6 @@ int nee_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const tr
         if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
     c.mis = true;
     c.heuristic = p->heuristic;
-    return TRT_OK;
-}
-
-// The table rule of trt_nee_mis, which only a host form can check: the entries that name a geometry are exactly the scene's TRT_LIGHT
-// geometries (trt_scene_emitters), each once, in any order.  The weights of a light's two strategies sum to 1 only then.
-int nee_mis_table_check(const trt_scene* s, const trt_emitter* emitters, uint32_t n_emitters) {
-    uint32_t count = 0;
-    int rc = trt_scene_emitters(s, nullptr, 0u, &count);
-    if (rc != TRT_OK) return rc;
-    std::vector<trt_emitter> own(count);
-    rc = trt_scene_emitters(s, own.data(), count, &count);
-    if (rc != TRT_OK) return rc;
-    std::vector<uint32_t> want, have;
-    for (const trt_emitter& e : own) want.push_back(e.geometry);
-    for (uint32_t i = 0; i < n_emitters; i++)
-        if (emitters[i].geometry != 0xFFFFFFFFu) have.push_back(emitters[i].geometry);
-    std::sort(want.begin(), want.end());
-    std::sort(have.begin(), have.end());
-    if (want != have)
-        return query_fail(TRT_ERR_INVALID_ARG, "the table's entries with a geometry must be the scene's lights, each once (trt_scene_emitters)");
     return TRT_OK;
 }
 
