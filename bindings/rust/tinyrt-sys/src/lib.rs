@@ -348,6 +348,17 @@ pub struct trt_nee_mis_params {
     pub reserved: [u32; 7],
 }
 
+/// One record of the alias table `trt_direct_pick` / `trt_direct_mis_pick` choose their emitter through (16 bytes): slot k keeps
+/// emitter k where the second draw is below `q`, else takes `alias`; `prob` is the probability with which emitter k is chosen.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_emitter_pick {
+    pub q: f32,
+    pub alias: u32,
+    pub prob: f32,
+    pub reserved: u32,
+}
+
 /// `trt_direct_params` and the heuristic (`enum trt_mis_heuristic`) that weights a shadow ray against a cosine-lobe ray from the surfel,
 /// for `trt_direct_mis` (128 bytes); `reserved` stays zero.
 #[repr(C)]
@@ -553,6 +564,21 @@ extern "C" {
                                  p: *const trt_direct_mis_params, d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64,
                                  stream: *mut c_void) -> c_int;
     pub fn trt_direct_mis_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_emitter_pick_build(emitters: *const trt_emitter, n_emitters: u32, weights: *const f32, out: *mut trt_emitter_pick,
+                                  total: *mut f32) -> c_int;
+    pub fn trt_direct_pick(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
+                           n_emitters: u32, p: *const trt_direct_params, radiance: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_direct_pick_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter,
+                                  d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_direct_params, d_radiance: *mut f32,
+                                  d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_direct_pick_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_direct_mis_pick(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
+                               n_emitters: u32, p: *const trt_direct_mis_params, total_power: f32, radiance: *mut f32, moment2: *mut f32,
+                               stats: *mut trt_stats) -> c_int;
+    pub fn trt_direct_mis_pick_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter,
+                                      d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_direct_mis_params, total_power: f32,
+                                      d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_direct_mis_pick_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_probe_params_default(out: *mut trt_probe_params);
     pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
                      stats: *mut trt_stats) -> c_int;

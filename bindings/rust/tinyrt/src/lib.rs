@@ -413,6 +413,73 @@ impl World {
         Ok((radiance, moment2))
     }
 
+    /// The alias table over `emitters` (`trt_emitter_pick_build`) through which `direct_pick` and `direct_mis_pick` choose their
+    /// emitter, and the weights' total: by power (`weights` = `None`; the table `direct_mis_pick` needs) or by the caller's weights,
+    /// one finite non-negative value per emitter.  Host only.
+    pub fn pick_table(emitters: &[sys::trt_emitter], weights: Option<&[Float]>) -> Result<(Vec<sys::trt_emitter_pick>, Float), Error> {
+        if emitters.len() > u32::MAX as usize || weights.map_or(false, |w| w.len() != emitters.len()) {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "one weight per emitter, at most 2^32 - 1 emitters".to_string() });
+        }
+        let mut pick = vec![sys::trt_emitter_pick::default(); emitters.len()];
+        let mut total: Float = 0.0;
+        check(unsafe {
+            sys::trt_emitter_pick_build(emitters.as_ptr(), emitters.len() as u32, weights.map_or(ptr::null(), |w| w.as_ptr()), pick.as_mut_ptr(),
+                                        &mut total)
+        })?;
+        Ok((pick, total))
+    }
+
+    /// `direct` with the emitter of a sample chosen through `pick` (`trt_direct_pick`) - by power or by the weights the table was built
+    /// from, not uniformly: one draw more per sample, far less noise where the emitters' powers differ much.
+    pub fn direct_pick(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], pick: &[sys::trt_emitter_pick], samples_per_item: u32,
+                       shadow_end: Float, seed: u32, first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize || pick.len() != emitters.len() {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "one pick record per emitter, at most 2^32 - 1 items or emitters".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_direct_params::default();
+        unsafe { sys::trt_direct_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        params.shadow_end = shadow_end;
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_direct_pick(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), pick.as_ptr(),
+                                 emitters.len() as u32, &params, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
+    /// `direct_mis` with the emitter chosen through `pick` (`trt_direct_mis_pick`): `pick` must be `pick_table(emitters, None)` - the
+    /// power table - and `total_power` the total it returned; the lobe ray's hit on a light is weighted by the same probability.
+    pub fn direct_mis_pick(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], pick: &[sys::trt_emitter_pick], total_power: Float,
+                           samples_per_item: u32, heuristic: MisHeuristic, shadow_end: Float, seed: u32, first_stream: u32)
+                           -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize || pick.len() != emitters.len() {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "one pick record per emitter, at most 2^32 - 1 items or emitters".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_direct_mis_params::default();
+        unsafe { sys::trt_direct_mis_params_default(&mut params) };
+        params.direct.path.samples_per_ray = samples_per_item;
+        params.direct.path.seed = seed;
+        params.direct.path.first_stream = first_stream;
+        params.direct.shadow_end = shadow_end;
+        params.heuristic = match heuristic {
+            MisHeuristic::Balance => sys::TRT_MIS_BALANCE,
+            MisHeuristic::Power => sys::TRT_MIS_POWER,
+        };
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_direct_mis_pick(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), pick.as_ptr(),
+                                     emitters.len() as u32, &params, total_power, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
     /// The radiance arriving at caller-supplied points as a function of direction (`trt_probe`): each `(point, axis)` as six floats, used
     /// as given.  For every one of `samples_per_item` samples the device draws a first ray uniformly over the sphere
     /// (`ProbeDomain::Sphere`) or over the hemisphere about the axis (`ProbeDomain::Hemisphere`) from RNG stream

@@ -53,7 +53,9 @@ extern "C" {
  *              trt_direct_params_default, trt_direct, trt_direct_device, trt_direct_launch_plan; trt_nee_params, trt_nee_params_default,
  *              trt_nee, trt_nee_device, trt_nee_launch_plan; trt_mis_heuristic, trt_nee_mis_params, trt_nee_mis_params_default,
  *              trt_nee_mis, trt_nee_mis_device, trt_nee_mis_launch_plan; trt_direct_mis_params, trt_direct_mis_params_default,
- *              trt_direct_mis, trt_direct_mis_device, trt_direct_mis_launch_plan. */
+ *              trt_direct_mis, trt_direct_mis_device, trt_direct_mis_launch_plan; trt_emitter_pick, trt_emitter_pick_build,
+ *              trt_direct_pick, trt_direct_pick_device, trt_direct_pick_launch_plan, trt_direct_mis_pick, trt_direct_mis_pick_device,
+ *              trt_direct_mis_pick_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -1016,6 +1018,90 @@ int trt_direct_mis_device(trt_scene *s, const trt_ray *d_items, uint32_t n, cons
 /* How trt_direct_mis[_device] launches n items on this scene: trt_direct_launch_plan's rule and fields over the weighted kernels' own
  * table (the same shapes; kernel_waves_per_simd is that table's bound, the same for both heuristics). */
 int trt_direct_mis_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Direct-light queries that choose the emitter by power: an alias table over the emitter table ----
+ * trt_direct and trt_direct_mis choose an emitter with probability 1 / E whatever its power (limit (1) of trt_direct).  In a room with one
+ * lamp and sixty dim lights sixty of sixty-one shadow rays go to a few percent of the light, and the one that reaches the lamp is scaled
+ * by E.  trt_direct_pick and trt_direct_mis_pick are the same two queries with the emitter chosen through a Walker/Vose alias table the
+ * caller builds once per emitter table: probability prob[e], one draw and two loads more per sample.  trt_direct,
+ * trt_direct_mis and the next-event queries are unchanged and still choose uniformly.
+ *
+ * The pick table: E records, record k for slot k AND for emitter k.  trt_emitter_pick_build is host only, needs no device and is
+ * deterministic - the same input gives the same bytes:
+ *  - Weights.  weights == NULL: w_e is the emitter's power, f32, one IEEE operation per operator, nothing fused:
+ *      power_e = ((0.2126f * color.x + 0.7152f * color.y) + 0.0722f * color.z) * area
+ *    Else w_e = weights[e], taken as given: any finite, non-negative values with a positive sum (distance, importance; trt_direct_pick
+ *    only - trt_direct_mis_pick needs the power rule).
+ *  - Total.  *total = the sum of the w_e accumulated in double in table order, rounded once to f32.  `total` may be NULL.
+ *  - Probability.  prob[e] = w_e / *total: one f32 division.  These three rules are contract: the weighted kernel recomputes prob from a
+ *    hit (trt_direct_mis_pick below).
+ *  - Construction (Vose), in double, every step in this order so that the bytes are reproducible:
+ *      (a) c_e = w_e where prob[e] > 0, else 0: a weight so small that the division underflows is built as weight 0.
+ *      (b) S = the sum of the c_e in table order, compensated (Neumaier):  t = s + c;  lost += s >= c ? (s - t) + c : (c - t) + s;
+ *          s = t;  at the end S = s + lost.  (A plain sum's rounding, times E, would land whole on the slot step (d) ends with.)
+ *      (c) scaled_e = (c_e * double(E)) / S.  Two work lists, small (scaled_e < 1) and large (the others), are filled in increasing
+ *          index order and emptied FROM THE BACK.
+ *      (d) While neither is empty: take s off small and l off large;  q[s] = scaled_s, alias[s] = l;
+ *          scaled_l = (scaled_l + scaled_s) - 1;  l goes to the back of small if scaled_l < 1, else to the back of large.
+ *      (e) Every slot left on either list gets q = 1 and alias = its own index - except a slot left on small with scaled = 0, which gets
+ *          q = 0 and the first emitter of largest c as its alias.
+ *      (f) q is rounded to f32 and clamped to [0, 1]; reserved = 0.
+ *    An emitter of weight 0 has q = 0 and is nobody's alias: it is never chosen.
+ *  - Errors, all TRT_ERR_INVALID_ARG, in this order: a NULL `emitters` or `out`; E outside 1 .. 2^20; a weight that is negative or not
+ *    finite; a total that is not positive and finite.  `out` is not written then.
+ *
+ * trt_direct_pick.  The contract of a sample is trt_direct's, word for word, except steps 2 and 5:
+ *  2. u0 = random(g);  k = min(uint32(u0 * float(E)), E - 1);  u1 = random(g);  e = (u1 < pick[k].q) ? k : min(pick[k].alias, E - 1).
+ *     One draw more than trt_direct: four for a quad, five for a sphere.  The min on the alias is contract: no table the device form is
+ *     handed, however wrong, makes the kernel read outside the E records of either table.  A NaN q takes the alias.
+ *  5. p = pick[e].prob;  scale = (area / p) * 0.318309886f;  geom = (cs * cl) / (d2 * d2);  wgt = geom * scale.  p == 0, or any p that
+ *     makes wgt no finite number, is a dead sample under step 6.
+ * Liveness, the shadow ray, t_max and the walk, the fold, sample ranges and accumulate, both split invariances, the output bounds and the
+ * counters are trt_direct's.  With the table trt_emitter_pick_build makes of all-equal weights the choice is uniform but the bits are
+ * not trt_direct's: one draw more is taken, and area / (1 / E) is not always area * E.
+ *  - Errors: trt_direct's, in trt_direct's order, as far as its table size and reserved words; then with n > 0 a NULL `pick`; then, HOST
+ *    FORM ONLY, trt_direct's check of the emitter records; then for each pick record in table order: q NaN or outside [0, 1], alias >= E,
+ *    prob NaN, negative or above 1, a non-zero reserved word; then an emitter that can be chosen (q[k] > 0, or the alias of a slot with
+ *    q < 1) whose prob is 0.  THE DEVICE FORM CHECKS ONLY THE POINTER: with a table whose prob is not the probability its q and alias
+ *    imply the result is biased; the reads stay in bounds regardless.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM.  n == 0 succeeds and
+ *    touches nothing.
+ *  - trt_direct_pick: host buffers, the pick table in the call's one device allocation.  trt_direct_pick_device: `d_pick` in HBM,
+ *    n_emitters x 16 bytes, 4-byte aligned; allocates nothing.
+ *
+ * trt_direct_mis_pick.  The contract is trt_direct_mis', with `total_power` = the builder's *total, and these changes:
+ *  - The shadow sample uses steps 2 and 5 above;  wl = 1 / (1 + q(wgt)), 1 for a virtual emitter, as before.
+ *  - At a light the lobe ray hits, sc(area) is replaced by the same ratio seen from the hit:
+ *      pw = ((0.2126f * em.x + 0.7152f * em.y) + 0.0722f * em.z) * area      (em the hit material's emitted colour, area the hit primitive's own)
+ *      ph = pw / total_power
+ *      g = ((csh * clh) / (t * t)) * ((area / ph) * 0.318309886f)
+ *    wb is unchanged: 1 when csh <= 0 or q(g) is not finite, which covers a black light (ph = 0).
+ *  - ph repeats the builder's operations on the bits trt_scene_emitters writes, so it has the bits of prob[e] of that light: the two
+ *    weights of one point sum to 1 as in trt_direct_mis, and with BALANCE a sample is at most 2 x the largest colour channel.
+ *  - Table rule: trt_nee_mis' AND the pick table is the power-rule table (weights == NULL) of that emitter table.  The host form checks,
+ *    after trt_direct_pick's checks and the emitter table rule: total_power positive and finite, then pick[e].prob bit for bit against
+ *    power_e / total_power for every e.  THE DEVICE FORM CANNOT CHECK EITHER RULE: with a caller-weighted table or another total the
+ *    weights do not sum to 1 and the result is biased.
+ * The launch plans: trt_direct_launch_plan's rule and fields over the PICK kernels' own tables. */
+typedef struct {
+    float q;                      /* slot k keeps emitter k where u1 < q, else takes `alias`: in [0, 1] */
+    uint32_t alias;               /* below E */
+    float prob;                   /* the probability with which emitter k is chosen: w_k / total */
+    uint32_t reserved;            /* zero */
+} trt_emitter_pick;               /* 16 B: offsets 0, 4, 8, 12 */
+int trt_emitter_pick_build(const trt_emitter *emitters, uint32_t n_emitters, const float *weights, trt_emitter_pick *out, float *total);
+int trt_direct_pick(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, const trt_emitter_pick *pick,
+                    uint32_t n_emitters, const trt_direct_params *p, float *radiance, float *moment2, trt_stats *stats);
+int trt_direct_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, const trt_emitter_pick *d_pick,
+                           uint32_t n_emitters, const trt_direct_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters,
+                           void *stream);
+int trt_direct_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+int trt_direct_mis_pick(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, const trt_emitter_pick *pick,
+                        uint32_t n_emitters, const trt_direct_mis_params *p, float total_power, float *radiance, float *moment2,
+                        trt_stats *stats);
+int trt_direct_mis_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters,
+                               const trt_emitter_pick *d_pick, uint32_t n_emitters, const trt_direct_mis_params *p, float total_power,
+                               float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+int trt_direct_mis_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

@@ -164,6 +164,35 @@ public:
         check(trt_direct_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
                              moment2 ? moment2->data() : nullptr, stats));
     }
+    // The alias table over `table` (trt_emitter_pick_build) through which direct_pick() and direct_mis_pick() choose their emitter: by
+    // power (weights == nullptr; the table direct_mis_pick() needs) or by `weights`, table.size() finite non-negative values.  `total`
+    // receives the weights' sum.  Host only.
+    static std::vector<trt_emitter_pick> pick_table(const std::vector<trt_emitter>& table, const float* weights = nullptr, float* total = nullptr) {
+        std::vector<trt_emitter_pick> pick(table.size());
+        check(trt_emitter_pick_build(table.data(), (uint32_t)table.size(), weights, pick.data(), total));
+        return pick;
+    }
+    // direct() with the emitter of a sample chosen through `pick` (trt_direct_pick) - by power, not uniformly: one draw more per sample,
+    // far less noise where the emitters' powers differ much.
+    void direct_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
+                     const trt_direct_params& p, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_direct_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
+                              radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
+    // direct_mis() with the emitter chosen through `pick` (trt_direct_mis_pick): `pick` must be pick_table(table) - the power table -
+    // and `total_power` the total it reported; the lobe ray's hit on a light is weighted by the same probability.
+    void direct_mis_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
+                         const trt_direct_mis_params& p, float total_power, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr,
+                         trt_stats* stats = nullptr) {
+        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_direct_mis_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
+                                  total_power, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
     // What radiance() / gather() estimate, with the lights aimed at (trt_nee): the path of every sample is theirs bit for bit (p.gather:
     // path, source - TRT_PASSES_RAYS, _COSINE, _CONE - and spread), at every Lambertian hit that leaves bounce budget one shadow ray goes
     // to `table` as in direct(), and a light the path then reaches by a diffuse scatter counts as black.  `table` should be emitters():

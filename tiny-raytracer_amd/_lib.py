@@ -147,6 +147,11 @@ class Emitter(C.Structure):
                 ("area", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class EmitterPick(C.Structure):
+    """tinyrt.h trt_emitter_pick: one record of the alias table a PICK direct-light query chooses its emitter through (16 bytes)."""
+    _fields_ = [("q", C.c_float), ("alias", C.c_uint32), ("prob", C.c_float), ("reserved", C.c_uint32)]
+
+
 class DirectParams(C.Structure):
     """tinyrt.h trt_direct_params: trt_radiance_params (its max_bounces and background are not read) and the share of the distance to
     the emitter point the shadow ray covers (96 bytes)."""
@@ -321,6 +326,17 @@ SIGNATURES = {
     "trt_direct_mis_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_direct_mis_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_emitter_pick_build": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "trt_direct_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DirectParams), C.c_void_p,
+                                  C.c_void_p, C.POINTER(Stats)]),
+    "trt_direct_pick_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DirectParams),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_direct_pick_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_direct_mis_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams),
+                                      C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_direct_mis_pick_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams),
+                                             C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_direct_mis_pick_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import (BACKEND_MEGAKERNEL, BACKEND_WAVEFRONT, DIELECTRIC, LAMBERTIAN, LIGHT, METAL, CameraPOD, Material,
                    RenderParams, SampledColor, SamplePoint, SceneInfo, SceneOptions, Stats, TinyRTError, Tuning, Vec3, check, lib)
-from .lights import EMITTER_DTYPE
+from .lights import EMITTER_DTYPE, PICK_DTYPE
 
 
 def _v(v):
@@ -387,8 +387,18 @@ class Scene:
             raise ValueError("emitters must be a one-dimensional record array of lights.EMITTER_DTYPE")
         return e
 
+    @staticmethod
+    def _pick_and_total(pick, mis):
+        """pick= as direct() takes it: the records, or (records, total) as lights.pick_table returns them; mis needs the total."""
+        total = None
+        if isinstance(pick, tuple):
+            pick, total = pick
+        if mis is not None and total is None:
+            raise ValueError("with mis, pick must be (records, total) as lights.pick_table(table) returns them")
+        return pick, total
+
     def direct(self, items, emitters, samples_per_item, shadow_end=None, seed=1, first_stream=0, sample_begin=0, sample_end=0,
-               accumulate=False, radiance=None, moment2=None, mis=None):
+               accumulate=False, radiance=None, moment2=None, mis=None, pick=None):
         """trt_direct: the light that reaches surfels float32 [n, 6] (point, axis; used as given) straight from the emitters of a table
         (emitters(), lights.quad / lights.sphere records, or any mix).  Each of samples_per_item = K samples picks an emitter uniformly and
         a point on it from RNG stream (seed, first_stream + i * K + s, 1), and asks occluded()'s question of the normalised ray towards
@@ -400,7 +410,11 @@ class Scene:
         0xFFFFFFFF)), and a light of the scene is counted both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the
         lobe ray's hit on a light by its complement, q(x) = x or x * x: the same expectation without the 1/d2 tail of surfels beside a
         lamp, for one closest-hit walk more per sample (rays = occlusion walks + samples).  `emitters` must then hold exactly the scene's
-        own lights (emitters()), each once, plus any virtual ones; anything else is an error."""
+        own lights (emitters()), each once, plus any virtual ones; anything else is an error.
+        pick = lights.pick_table(emitters) (trt_direct_pick; with mis trt_direct_mis_pick): the emitter is chosen through that alias
+        table, by power or by the weights the table was built from, not uniformly - one draw more per sample, far less noise where the
+        emitters' powers differ much.  The records alone will do without mis; with mis the (records, total) pair is needed and the table
+        must be the power table (weights=None).  pick=None: the calls and bytes of before."""
         r, _ = _rays_and_t_max(items, None)
         n = len(r)
         e = self._emitter_table(emitters)
@@ -412,26 +426,51 @@ class Scene:
         for a in (radiance, moment2):
             assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
         st = Stats()
-        fn = lib.trt_direct if mis is None else lib.trt_direct_mis
-        check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
-                 radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        out = (radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st))
+        if pick is None:
+            fn = lib.trt_direct if mis is None else lib.trt_direct_mis
+            check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p), *out))
+            return radiance, moment2, st.as_dict()
+        pick, total = self._pick_and_total(pick, mis)
+        k = np.ascontiguousarray(pick)
+        if k.dtype != PICK_DTYPE or k.shape != (len(e),):
+            raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
+        head = (self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, k.ctypes.data if len(k) else None, len(e), C.byref(p))
+        if mis is None:
+            check(lib.trt_direct_pick(*head, *out))
+        else:
+            check(lib.trt_direct_mis_pick(*head, C.c_float(total), *out))
         return radiance, moment2, st.as_dict()
 
-    def direct_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+    def direct_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, pick=None,
+                      **params):
         """Enqueue direct() on buffers already in HBM (device pointers as integers: n x 24 bytes of surfels, n_emitters x 80 bytes of
         trt_emitter records, n x 12 bytes of sums each) on the current device; asynchronous on the stream, allocates nothing.  `params`:
         direct()'s keywords, samples_per_item and mis included (trt_direct_mis_device where mis is given: the device form cannot check the
-        table rule)."""
+        table rule).  pick: the device pointer of the n_emitters x 16 bytes of lights.pick_table's records (trt_direct_pick_device), or
+        with mis (pointer, total) (trt_direct_mis_pick_device); the device form checks neither table."""
         p = self._direct_params(**params)
-        fn = lib.trt_direct_mis_device if isinstance(p, _lib.DirectMisParams) else lib.trt_direct_device
-        check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
-                 C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+        weighted = isinstance(p, _lib.DirectMisParams)
+        tail = (C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr))
+        if pick is None:
+            fn = lib.trt_direct_mis_device if weighted else lib.trt_direct_device
+            check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p), *tail))
+            return
+        d_pick_ptr, total = self._pick_and_total(pick, params.get("mis"))
+        head = (self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), C.c_void_p(d_pick_ptr), int(n_emitters), C.byref(p))
+        if weighted:
+            check(lib.trt_direct_mis_pick_device(*head, C.c_float(total), *tail))
+        else:
+            check(lib.trt_direct_pick_device(*head, *tail))
 
-    def direct_plan(self, n, compute_units=0, mis=None):
-        """trt_direct_launch_plan (mis given: trt_direct_mis_launch_plan): how direct() launches n surfels on this scene, as a dict with
-        ambient_plan()'s fields."""
+    def direct_plan(self, n, compute_units=0, mis=None, pick=None):
+        """trt_direct_launch_plan (mis given: trt_direct_mis_launch_plan; pick given, as anything but None: the _pick_ plans): how
+        direct() launches n surfels on this scene, as a dict with ambient_plan()'s fields."""
         plan = _lib.QueryPlan()
-        fn = lib.trt_direct_launch_plan if mis is None else lib.trt_direct_mis_launch_plan
+        if pick is None:
+            fn = lib.trt_direct_launch_plan if mis is None else lib.trt_direct_mis_launch_plan
+        else:
+            fn = lib.trt_direct_pick_launch_plan if mis is None else lib.trt_direct_mis_pick_launch_plan
         check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 

@@ -19,6 +19,7 @@
 // ray from the surfel, whose hit on a light adds emission * wb (mis_weight.h mis_hit_weight, shared with nee.hip).  Up to two walks per
 // sample go through ONE walk call site, nee_kernel's way.  direct_kernel is instruction for instruction what it was; the
 // two queries share their checks, launcher and both forms' bodies.
+#include "emitter_pick.h"
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -54,6 +55,17 @@ struct DirectArgs {
     FlatReuse flat_reuse;
 };
 
+// What a PICK kernel is handed besides: the alias table (tinyrt.h trt_emitter_pick, n_emitters x 4 words).  A struct of its own around
+// DirectArgs, so that the kernel arguments of the uniform kernels lie where they lay.
+struct DirectPickArgs {
+    DirectArgs d;
+    const float* pick;
+};
+TRT_DEV const DirectArgs& direct_args(const DirectArgs& a) { return a; }
+TRT_DEV const DirectArgs& direct_args(const DirectPickArgs& a) { return a.d; }
+TRT_DEV const float* pick_table(const DirectArgs&) { return nullptr; }
+TRT_DEV const float* pick_table(const DirectPickArgs& a) { return a.pick; }
+
 // The six sums of one item: read where a call continues them, written once when the item's last sample has folded.
 struct DirectSums {
     V3 rad, m2;
@@ -80,9 +92,12 @@ TRT_DEV void dir_fold(DirectSums& a, const V3& c, float inv_k) {
     a.m2 = a.m2 + (c * c) * inv_k;
 }
 
-template <int MODE, int WALK, int THREADS, int MINW>
-__global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, DirectArgs da, const float4* __restrict__ leaf_list,
-                                                                    const uint4* __restrict__ nodes16) {
+// PICK: the emitter of a sample is chosen through the alias table (trt_direct_pick; gather_draw.h AliasPick), one draw and two loads more.
+template <int MODE, int WALK, int THREADS, int MINW, bool PICK = false>
+__global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, std::conditional_t<PICK, DirectPickArgs, DirectArgs> args,
+                                                                    const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16) {
+    const DirectArgs& da = direct_args(args);
+    const float* __restrict__ const pick = pick_table(args);
     stage_scene_to_lds<MODE>(scd);
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, da.flat_reuse);
     const SceneAcc<MODE> sc{scd.blob, scd.L};
@@ -128,7 +143,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, Dir
                 // ---- start: the item's next sample draws its emitter point and shadow ray (stream (seed, j, 1)) ----
                 if (!has_ray) {
                     Rng g = rng_seed(da.seed_key, da.first_stream + idx * da.samples_per_item + s, 1u);
-                    const DirectSample smp = direct_draw(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    const DirectSample smp = direct_draw_item<PICK, DirectSample>(items, idx, emitters, pick, da.n_emitters, da.shadow_end, g);
                     ray = smp.ray; c = smp.c; t_max = smp.t_max; live = smp.live;
                     walks = live && t_max > kTMin;                          // else dead, or an empty range: nothing is walked
                     has_ray = true;
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_kernel(SceneDev scd, Dir
                 DirectSums acc = dir_begin(da, idx);
                 for (uint32_t s = da.sample_begin; s != da.sample_end; s++) {
                     Rng g = rng_seed(da.seed_key, da.first_stream + idx * da.samples_per_item + s, 1u);
-                    const DirectSample smp = direct_draw(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    const DirectSample smp = direct_draw_item<PICK, DirectSample>(items, idx, emitters, pick, da.n_emitters, da.shadow_end, g);
                     n_samples++;
                     uint32_t prim = PRIM_NONE;
                     if (smp.live && smp.t_max > kTMin) {
@@ -186,6 +201,18 @@ struct DirectMisArgs {
     DirectArgs d;                    // direct_kernel's, read the same way
     uint32_t heuristic;              // enum trt_mis_heuristic, wave-uniform
 };
+// ... of a PICK kernel: the alias table and the table's total power, by which a light hit finds its own choice probability.
+struct DirectMisPickArgs {
+    DirectMisArgs m;
+    const float* pick;
+    float total_power;
+};
+TRT_DEV const DirectMisArgs& direct_mis_args(const DirectMisArgs& a) { return a; }
+TRT_DEV const DirectMisArgs& direct_mis_args(const DirectMisPickArgs& a) { return a.m; }
+TRT_DEV const float* pick_table(const DirectMisArgs&) { return nullptr; }
+TRT_DEV const float* pick_table(const DirectMisPickArgs& a) { return a.pick; }
+TRT_DEV float pick_total(const DirectMisArgs&) { return 0.0f; }
+TRT_DEV float pick_total(const DirectMisPickArgs& a) { return a.total_power; }
 
 // The shadow sample's share of a drawn sample: 1 / (1 + q(p_bsdf / p_light)); a virtual emitter cannot be hit and counts in full.
 TRT_DEV float mis_shadow_weight(const WeightedDirectSample& w, uint32_t heuristic) {
@@ -194,18 +221,25 @@ TRT_DEV float mis_shadow_weight(const WeightedDirectSample& w, uint32_t heuristi
 }
 // What the lobe ray of a sample adds, T_b: nothing (false) on a miss or a hit on anything but a light, else emission * wb with csh from the
 // item's axis as given (re-read: three registers less per lane while the walks run; a light hit is the rare case).
-template <int MODE>
+// PICK: the light's choice probability is its share of total_power (mis_weight.h, the overload), not 1 / E.
+template <int MODE, bool PICK>
 TRT_DEV bool mis_lobe_term(const SceneAcc<MODE>& sc, const float* __restrict__ items, uint32_t idx, const Ray& ray, uint32_t prim, float t,
-                           uint32_t n_emitters, uint32_t heuristic, V3& tb) {
+                           uint32_t n_emitters, float total_power, uint32_t heuristic, V3& tb) {
     if (prim == PRIM_NONE) return false;
     const uint32_t mat = prim_material<MODE>(sc, prim);
     if (sc.material_kind(mat) != TRT_LIGHT) return false;
     const float* const it = items + 6ull * idx;
     const float csh = dot(v3(it[3], it[4], it[5]), ray.d);
     const V3 normal = hit_unit_normal<MODE>(sc, prim, ray, t);
-    const float wb = mis_hit_weight<MODE>(sc, prim, ray, normal, t, csh, n_emitters, heuristic);
-    const float4 m = sc.material(mat);
-    tb = v3(m.x, m.y, m.z) * wb;
+    if constexpr (PICK) {
+        const float4 m = sc.material(mat);
+        const V3 emission = v3(m.x, m.y, m.z);
+        tb = emission * mis_hit_weight<MODE>(sc, prim, ray, normal, t, csh, emission, total_power, heuristic);
+    } else {
+        const float wb = mis_hit_weight<MODE>(sc, prim, ray, normal, t, csh, n_emitters, heuristic);
+        const float4 m = sc.material(mat);
+        tb = v3(m.x, m.y, m.z) * wb;
+    }
     return true;
 }
 
@@ -214,9 +248,12 @@ TRT_DEV bool mis_lobe_term(const SceneAcc<MODE>& sc, const float* __restrict__ i
 // shadow sample is drawn on stream (seed, j, 1) exactly as direct_kernel draws it, the lobe ray on (seed, j, 0xFFFFFFFF) once the shadow
 // walk is over: a lane keeps one ray.  `c` holds T_l while `lit` says it counts; the lobe ray's term joins it or stands alone.
 constexpr uint32_t kLobeStreamWord = 0xFFFFFFFFu;
-template <int MODE, int WALK, int THREADS, int MINW>
-__global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd, DirectMisArgs ma, const float4* __restrict__ leaf_list,
-                                                                        const uint4* __restrict__ nodes16) {
+template <int MODE, int WALK, int THREADS, int MINW, bool PICK = false>
+__global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd, std::conditional_t<PICK, DirectMisPickArgs, DirectMisArgs> args,
+                                                                        const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16) {
+    const DirectMisArgs& ma = direct_mis_args(args);
+    const float* __restrict__ const pick = pick_table(args);
+    const float total_power = pick_total(args);
     const DirectArgs& da = ma.d;
     stage_scene_to_lds<MODE>(scd);
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, da.flat_reuse);
@@ -267,7 +304,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd,
                 // ---- start: the item's next sample draws its emitter point and shadow ray (stream (seed, j, 1)) ----
                 if (phase == PH_START) {
                     Rng g = rng_seed(da.seed_key, stream, 1u);
-                    const WeightedDirectSample w = direct_draw_weighted(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    const WeightedDirectSample w = direct_draw_item<PICK, WeightedDirectSample>(items, idx, emitters, pick, da.n_emitters, da.shadow_end, g);
                     c = w.c * mis_shadow_weight(w, ma.heuristic);
                     lit = w.live;                                           // until its walk finds something
                     n_samples++;
@@ -292,7 +329,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd,
                         phase = PH_LOBE_DRAW;                               // drawn and walked in the next round
                     } else {
                         V3 tb;
-                        if (mis_lobe_term<MODE>(sc, items, idx, ray, tr.prim_best, tr.t_best, da.n_emitters, ma.heuristic, tb)) {
+                        if (mis_lobe_term<MODE, PICK>(sc, items, idx, ray, tr.prim_best, tr.t_best, da.n_emitters, total_power, ma.heuristic, tb)) {
                             c = lit ? c + tb : tb;
                             lit = true;
                         }
@@ -315,7 +352,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd,
                 for (uint32_t s = da.sample_begin; s != da.sample_end; s++) {
                     const uint32_t stream = da.first_stream + idx * da.samples_per_item + s;
                     Rng g = rng_seed(da.seed_key, stream, 1u);
-                    const WeightedDirectSample w = direct_draw_weighted(items, idx, emitters, da.n_emitters, da.shadow_end, g);
+                    const WeightedDirectSample w = direct_draw_item<PICK, WeightedDirectSample>(items, idx, emitters, pick, da.n_emitters, da.shadow_end, g);
                     n_samples++;
                     V3 c = w.c * mis_shadow_weight(w, ma.heuristic);
                     bool lit = w.live;
@@ -341,7 +378,7 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd,
                             if (prim != PRIM_NONE) lit = false;
                         } else {
                             V3 tb;
-                            if (mis_lobe_term<MODE>(sc, items, idx, ray, prim, t, da.n_emitters, ma.heuristic, tb)) {
+                            if (mis_lobe_term<MODE, PICK>(sc, items, idx, ray, prim, t, da.n_emitters, total_power, ma.heuristic, tb)) {
                                 c = lit ? c + tb : tb;
                                 lit = true;
                             }
@@ -386,8 +423,37 @@ const BatchKernel kDirectMisKernels[] = {
     TRT_DIRECT_MIS(MODE_GLOBAL, WALK_REGS, 256, 5),
 };
 #undef TRT_DIRECT_MIS
-static_assert(sizeof(kDirectMisKernels) == sizeof(kDirectKernels), "one weighted instantiation per shape");
+#define TRT_DIRECT_PICK(MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&direct_kernel<MODE, WALK, THREADS, MINW, true>), MODE, WALK, THREADS, MINW}
+#define TRT_DIRECT_MIS_PICK(MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&direct_mis_kernel<MODE, WALK, THREADS, MINW, true>), MODE, WALK, THREADS, MINW}
+// The PICK kernels (trt_direct_pick, trt_direct_mis_pick): the same shapes; the alias draw lives and dies ahead of the emitter record's
+// load.  Bounds by the same rule (profiles/direct_pick_resource_usage.txt).
+const BatchKernel kDirectPickKernels[] = {
+    TRT_DIRECT_PICK(MODE_LDS, WALK_FLAT, 256, 7),
+    TRT_DIRECT_PICK(MODE_LDS, WALK_LDS_STACK, 256, 8),
+    TRT_DIRECT_PICK(MODE_LDS, WALK_LDS_STACK, 768, 8),
+    TRT_DIRECT_PICK(MODE_LDS, WALK_REGS, 512, 7),
+    TRT_DIRECT_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 7),
+    TRT_DIRECT_PICK(MODE_GLOBAL, WALK_REGS, 256, 6),
+};
+const BatchKernel kDirectMisPickKernels[] = {
+    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5),
+    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 7),
+    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 7),
+    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5),
+    TRT_DIRECT_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 7),
+    TRT_DIRECT_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5),
+};
+#undef TRT_DIRECT_PICK
+#undef TRT_DIRECT_MIS_PICK
+static_assert(sizeof(kDirectMisKernels) == sizeof(kDirectKernels) && sizeof(kDirectPickKernels) == sizeof(kDirectKernels) &&
+              sizeof(kDirectMisPickKernels) == sizeof(kDirectKernels), "one weighted and one PICK instantiation per shape");
 constexpr size_t kDirectShapes = sizeof(kDirectKernels) / sizeof(kDirectKernels[0]);
+// The kernels of a query: [mis][pick].
+const BatchKernel* direct_kernels(bool mis, bool pick) {
+    return mis ? (pick ? kDirectMisPickKernels : kDirectMisKernels) : (pick ? kDirectPickKernels : kDirectKernels);
+}
 
 // What a call asks of the device, after the checks.
 struct DirectCall {
@@ -397,11 +463,13 @@ struct DirectCall {
     float shadow_end;
     bool mis = false;                // trt_direct_mis: the weighted kernels, with `heuristic`
     uint32_t heuristic = 0u;
+    bool pick = false;               // trt_direct_pick / trt_direct_mis_pick: the PICK kernels, with an alias table (and `total_power`)
+    float total_power = 0.0f;
     bool nothing() const { return ra.sample_begin == ra.sample_end; }       // an empty sample range: no sample is drawn
 };
 
-hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float* d_items, uint32_t n, const float* d_emitters, float* d_radiance,
-                         float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float* d_items, uint32_t n, const float* d_emitters, const float* d_pick,
+                         float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (c.nothing()) {
         // the sums start at 0, or stay
@@ -410,14 +478,17 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, c.mis ? kDirectMisKernels : kDirectKernels, kDirectShapes, b);
+    const hipError_t e = batch_prepare(scd, n, direct_kernels(c.mis, c.pick), kDirectShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     DirectArgs da{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
                   c.first_stream, c.ra.seed_key, c.ra.sample_begin, c.ra.sample_end, c.ra.accumulate, c.n_emitters, c.ra.inv_spp, c.shadow_end,
                   qs.flat_reuse};
     DirectMisArgs ma{da, c.heuristic};
-    void* args[] = {&scd, c.mis ? static_cast<void*>(&ma) : static_cast<void*>(&da), &b.leaf_list, &b.nodes16};
+    DirectPickArgs pa{da, d_pick};
+    DirectMisPickArgs mpa{ma, d_pick, c.total_power};
+    void* const query = c.mis ? (c.pick ? static_cast<void*>(&mpa) : static_cast<void*>(&ma)) : (c.pick ? static_cast<void*>(&pa) : static_cast<void*>(&da));
+    void* args[] = {&scd, query, &b.leaf_list, &b.nodes16};
     return batch_launch(b, args, stream);
 }
 
@@ -453,23 +524,25 @@ int direct_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const
     return TRT_OK;
 }
 
-// The two forms after their checks, for trt_direct and trt_direct_mis alike: `c` says which kernels.
-int direct_on_device(trt_scene* s, const DirectCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, float* d_radiance,
-                     float* d_moment2, uint64_t* d_counters, void* stream) {
+// The two forms after their checks, for the four queries alike: `c` says which kernels, `d_pick` / `pick` is the alias table of a PICK query.
+int direct_on_device(trt_scene* s, const DirectCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters,
+                     const trt_emitter_pick* d_pick, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
     return sample_query_on_device(s, n, "direct-light query launch", [&](const QueryScene& qs) {
-        return launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
-                             reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+        return launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters),
+                             reinterpret_cast<const float*>(d_pick), d_radiance, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),
+                             static_cast<hipStream_t>(stream));
     });
 }
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).
-int direct_on_host(trt_scene* s, const DirectCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters,
-                   float* radiance, float* moment2, trt_stats* stats) {
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters | pick table, if any).
+int direct_on_host(trt_scene* s, const DirectCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick,
+                   uint32_t n_emitters, float* radiance, float* moment2, trt_stats* stats) {
     const size_t sums = (size_t)n * 12u;
-    const SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                       "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                 "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    if (c.pick) { h.table2 = pick; h.table2_b = (size_t)n_emitters * sizeof(trt_emitter_pick); h.table2_what = "hipMemcpy of the pick table"; }
     return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "direct-light query buffers", "direct-light query launch", stats,
                                 [&](const QueryScene& qs, const SampleDev& d) {
-                                    return launch_direct(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                    return launch_direct(qs, c, d.items, n, d.table, d.table2, d.sums, d.sums2, d.counters, nullptr);
                                 });
 }
 
@@ -490,7 +563,7 @@ int trt_direct_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const tr
     trt::DirectCall c;
     const int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
 }
 
 // The table's entries are checked where n > 0, ahead of any device work.
@@ -502,7 +575,7 @@ int trt_direct(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter
         if (rc != TRT_OK) return rc;
         rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        return trt::direct_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+        return trt::direct_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
     });
 }
 
@@ -524,7 +597,7 @@ int trt_direct_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, cons
     trt::DirectCall c;
     const int rc = trt::direct_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
 }
 
 int trt_direct_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_mis_params* p,
@@ -539,13 +612,95 @@ int trt_direct_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emi
             rc = trt::nee_mis_table_check(s, emitters, n_emitters);
             if (rc != TRT_OK) return rc;
         }
-        return trt::direct_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+        return trt::direct_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
     });
 }
 
 // The weighted kernels' table: the same shapes, its own bounds.
 int trt_direct_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
     return trt::batch_launch_plan(s, n, compute_units, trt::kDirectMisKernels, trt::kDirectShapes, out);
+}
+
+// ---- the PICK queries: the emitter chosen by power (or the caller's weights) through an alias table ----
+int trt_emitter_pick_build(const trt_emitter* emitters, uint32_t n_emitters, const float* weights, trt_emitter_pick* out, float* total) {
+    return trt::host_form([&]() -> int { return trt::pick_build(emitters, n_emitters, weights, out, total); });
+}
+
+// The device form checks the pointer only: the kernel's clamp keeps a wrong table's reads inside the E records.
+int trt_direct_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
+                           uint32_t n_emitters, const trt_direct_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::DirectCall c;
+    int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    rc = trt::pick_pointer_check(n, d_pick);
+    if (rc != TRT_OK) return rc;
+    c.pick = true;
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_direct_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
+                    const trt_direct_params* p, float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::DirectCall c;
+        int rc = trt::direct_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        rc = trt::pick_pointer_check(n, pick);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_entries_check(pick, n_emitters);
+            if (rc != TRT_OK) return rc;
+        }
+        c.pick = true;
+        return trt::direct_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
+    });
+}
+
+int trt_direct_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectPickKernels, trt::kDirectShapes, out);
+}
+
+// The device form can read neither table: both table rules are the caller's to keep.
+int trt_direct_mis_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
+                               uint32_t n_emitters, const trt_direct_mis_params* p, float total_power, float* d_radiance, float* d_moment2,
+                               uint64_t* d_counters, void* stream) {
+    trt::DirectCall c;
+    int rc = trt::direct_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    rc = trt::pick_pointer_check(n, d_pick);
+    if (rc != TRT_OK) return rc;
+    c.pick = true;
+    c.total_power = total_power;
+    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_direct_mis_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
+                        const trt_direct_mis_params* p, float total_power, float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::DirectCall c;
+        int rc = trt::direct_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        rc = trt::pick_pointer_check(n, pick);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_entries_check(pick, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_power_check(emitters, pick, n_emitters, total_power);
+            if (rc != TRT_OK) return rc;
+        }
+        c.pick = true;
+        c.total_power = total_power;
+        return trt::direct_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
+    });
+}
+
+int trt_direct_mis_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectMisPickKernels, trt::kDirectShapes, out);
 }
 
 }  // extern "C"

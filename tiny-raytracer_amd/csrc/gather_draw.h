@@ -75,13 +75,39 @@ struct WeightedDirectSample : DirectSample {
     float wgt;
     uint32_t geometry;
 };
+// How step 2 chooses the emitter.  UniformPick: e = the slot of the first draw, probability 1 / E (trt_direct, trt_nee and their weighted
+// forms).  AliasPick (trt_direct_pick, trt_direct_mis_pick): one draw more decides between the slot and its alias in a caller-supplied
+// Walker/Vose table (tinyrt.h trt_emitter_pick: 4 words a record - q, alias, prob, reserved), and step 5 divides by the chosen record's
+// `prob` where the uniform choice multiplies by E:
+//   u0 = random; k = min(uint32(u0 * float(E)), E - 1); u1 = random; e = u1 < q[k] ? k : min(alias[k], E - 1)      (a NaN q takes the alias)
+//   scale = (area / prob[e]) * (1 / pi)
+// Two vector loads more through the lane's own index, both ahead of the emitter record's; the min keeps every read inside the E records
+// whatever the table holds.
+struct UniformPick {
+    TRT_DEV uint32_t choose(uint32_t slot, uint32_t, Rng&, float&) const { return slot; }
+    TRT_DEV float scale(float area, float fe, float) const { return (area * fe) * 0.318309886f; }
+};
+struct AliasPick {
+    const float* __restrict__ table;
+    TRT_DEV uint32_t choose(uint32_t slot, uint32_t n_emitters, Rng& g, float& prob) const {
+        const float u1 = rng_random(g);
+        const float* __restrict__ const rec = table + 4ull * slot;
+        const uint32_t alias = __float_as_uint(rec[1]);
+        const uint32_t e = u1 < rec[0] ? slot : (alias < n_emitters - 1u ? alias : n_emitters - 1u);
+        prob = table[4ull * e + 2u];
+        return e;
+    }
+    TRT_DEV float scale(float area, float, float prob) const { return (area / prob) * 0.318309886f; }
+};
 // ONE body for the surfel of an item (direct.hip) and for a surfel held in registers (nee.hip): `surfel()` returns (point, normal) as
-// a Ray and is called after the draws, where an item is loaded so that its six registers are free while the draws run.
-template <class Surfel, class Sample = DirectSample>
-TRT_DEV Sample direct_draw_from(Surfel surfel, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {
+// a Ray and is called after the draws, where an item is loaded so that its six registers are free while the draws run.  The choice and
+// step 5's scale are the policy's, resolved at compile time: with the default policy the code is the code it was.
+template <class Surfel, class Sample = DirectSample, class Pick = UniformPick>
+TRT_DEV Sample direct_draw_from(Surfel surfel, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g, Pick policy = Pick{}) {
     const float fe = (float)n_emitters;
     const uint32_t pick = (uint32_t)(rng_random(g) * fe);
-    const float* __restrict__ const em = emitters + 20ull * (pick < n_emitters - 1u ? pick : n_emitters - 1u);
+    float prob = 0.0f;
+    const float* __restrict__ const em = emitters + 20ull * policy.choose(pick < n_emitters - 1u ? pick : n_emitters - 1u, n_emitters, g, prob);
     const V3 a = v3(em[2], em[3], em[4]);
     V3 y, nl;
     if (__float_as_uint(em[0]) == 1u) {
@@ -98,7 +124,7 @@ TRT_DEV Sample direct_draw_from(Surfel surfel, const float* __restrict__ emitter
     const float d2 = dot(w, w);
     const float cs = dot(item.d, w);
     const float cl = __builtin_fabsf(dot(nl, w));
-    const float scale = (em[17] * fe) * 0.318309886f;
+    const float scale = policy.scale(em[17], fe, prob);
     const float wgt = ((cs * cl) / (d2 * d2)) * scale;
     Sample smp;
     smp.live = cs > 0.0f && d2 > 0.0f && __builtin_fabsf(wgt) < __builtin_inff();
@@ -120,6 +146,14 @@ TRT_DEV WeightedDirectSample direct_draw_weighted(const float* __restrict__ item
                                                   uint32_t n_emitters, float shadow_end, Rng& g) {
     auto surfel = [&] { return rad_load_ray(items, idx); };
     return direct_draw_from<decltype(surfel), WeightedDirectSample>(surfel, emitters, n_emitters, shadow_end, g);
+}
+// The two draws of the direct-light kernels behind one name: PICK chooses the emitter through the alias table (direct.hip, PICK kernels).
+template <bool PICK, class Sample>
+TRT_DEV Sample direct_draw_item(const float* __restrict__ items, uint32_t idx, const float* __restrict__ emitters, const float* __restrict__ pick,
+                                uint32_t n_emitters, float shadow_end, Rng& g) {
+    auto surfel = [&] { return rad_load_ray(items, idx); };
+    if constexpr (PICK) return direct_draw_from<decltype(surfel), Sample, AliasPick>(surfel, emitters, n_emitters, shadow_end, g, AliasPick{pick});
+    else return direct_draw_from<decltype(surfel), Sample>(surfel, emitters, n_emitters, shadow_end, g);
 }
 // The same sample for a vertex of a path (nee.hip): x the point, n the unit normal on the side the light is gathered on.
 TRT_DEV DirectSample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, uint32_t n_emitters, float shadow_end, Rng& g) {

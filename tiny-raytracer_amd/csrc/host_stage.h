@@ -109,11 +109,13 @@ struct SampleHost {
     const void* table; size_t table_b; const char* table_what;      // a second input (the emitter table), or nullptr
     float* sums; size_t sums_b;                                      // the required output
     float* sums2; size_t sums2_b; const char* sums2_what;            // the optional output (nullptr: not wanted), and what its upload is called
+    const void* table2 = nullptr; size_t table2_b = 0; const char* table2_what = "";      // a third input (the emitter pick table), or nullptr
 };
 struct SampleDev {
     const float *items, *table;
     float *sums, *sums2;             // sums2: nullptr where the caller's is
     unsigned long long* counters;
+    const float* table2;             // nullptr where the caller's is
 };
 // The host form after the unit's checks (inside host_form).  Device copies of the inputs and of the sums are the call's own (one
 // allocation), one stream-ordered sequence on the default stream, complete when the call returns.  The running sums go up only when
@@ -135,16 +137,19 @@ int sample_query_on_host(trt_scene* s, uint32_t n, const SampleHost& h, bool acc
     const size_t r_items = st.reserve(h.items_b), r_table = st.reserve(h.table_b, h.table != nullptr), r_sums = st.reserve(h.sums_b),
                  r_sums2 = st.reserve(h.sums2_b, h.sums2 != nullptr);
     st.reserve_counters();
+    const size_t r_table2 = st.reserve(h.table2_b, h.table2 != nullptr);    // behind the counters: the other regions lie where they lay
     st.alloc();
     st.up(r_items, h.items, h.items_b, h.items_what);
     st.up(r_table, h.table, h.table_b, h.table_what);
+    st.up(r_table2, h.table2, h.table2_b, h.table2_what);
     st.zero_counters();
     // the running sums a pass continues go up; a pass that starts them reads nothing
     if (accumulate) st.up(r_sums, h.sums, h.sums_b, "hipMemcpy of the sums");
     if (accumulate) st.up(r_sums2, h.sums2, h.sums2_b, h.sums2_what);
     st.time_begin();
     if (st.ok())
-        st.run(launch(qs, SampleDev{st.ptr<float>(r_items), st.ptr<float>(r_table), st.ptr<float>(r_sums), st.ptr<float>(r_sums2), st.counters()}), what);
+        st.run(launch(qs, SampleDev{st.ptr<float>(r_items), st.ptr<float>(r_table), st.ptr<float>(r_sums), st.ptr<float>(r_sums2), st.counters(),
+                                st.ptr<float>(r_table2)}), what);
     const bool wrote = !(accumulate && nothing);
     if (wrote) st.down(h.sums, r_sums, h.sums_b, "hipMemcpy of the results");
     if (wrote) st.down(h.sums2, r_sums2, h.sums2_b, "hipMemcpy of the results");

@@ -33,6 +33,29 @@ TRT_DEV float mis_hit_weight(const SceneAcc<MODE>& sc, uint32_t prim, const Ray&
     const float qg = heuristic == TRT_MIS_POWER ? g * g : g;
     return csh > 0.0f && __builtin_fabsf(qg) < __builtin_inff() ? qg / (1.0f + qg) : 1.0f;
 }
+// ... where the emitter was chosen by power through an alias table (trt_direct_mis_pick): the light's choice probability is not 1 / E but
+// ph = power / total_power, recomputed from the hit in the builder's operations (tinyrt.h trt_emitter_pick_build; `emission` is the hit
+// material's colour) so that it has the bits of the table's prob for that light.  An overload, not a run-time branch: the uniform form
+// above stands as it stood, and nee_kernel and direct_mis_kernel compile to the instructions they had.
+template <int MODE>
+TRT_DEV float mis_hit_weight(const SceneAcc<MODE>& sc, uint32_t prim, const Ray& ray, const V3& normal, float t, float csh, const V3& emission,
+                             float total_power, uint32_t heuristic) {
+    const uint32_t pidx = prim & PRIM_INDEX_MASK;
+    float area;
+    if (prim & PRIM_QUAD_BIT) {
+        const float4 q0 = sc.quad(0, pidx);
+        area = __builtin_sqrtf((q0.x * q0.x + q0.y * q0.y) + q0.z * q0.z);
+    } else {
+        const float r = sc.sphere(pidx).w;
+        area = 12.566371f * (r * r);
+    }
+    const float clh = __builtin_fabsf(dot(normal, ray.d));
+    const float pw = ((0.2126f * emission.x + 0.7152f * emission.y) + 0.0722f * emission.z) * area;
+    const float ph = pw / total_power;
+    const float g = ((csh * clh) / (t * t)) * ((area / ph) * 0.318309886f);
+    const float qg = heuristic == TRT_MIS_POWER ? g * g : g;
+    return csh > 0.0f && __builtin_fabsf(qg) < __builtin_inff() ? qg / (1.0f + qg) : 1.0f;
+}
 
 // The unit normal of HitRecord::new (hittable/mod.rs:28-48) for the primitive `ray` hits at t, as rt_path.h shade_body builds it, less the
 // facing: the quad's n.normalized() as packed, the sphere's (ray.at(t) - centre).normalized().

@@ -15,6 +15,9 @@ from ._lib import Vec3, lib
 EMITTER_DTYPE = np.dtype([("kind", np.uint32), ("geometry", np.uint32), ("a", np.float32, (3,)), ("b", np.float32, (3,)), ("c", np.float32, (3,)),
                           ("normal", np.float32, (3,)), ("color", np.float32, (3,)), ("area", np.float32), ("reserved", np.uint32, (2,))])
 assert EMITTER_DTYPE.itemsize == C.sizeof(_lib.Emitter) == 80
+# tinyrt.h trt_emitter_pick as a numpy record (16 bytes)
+PICK_DTYPE = np.dtype([("q", np.float32), ("alias", np.uint32), ("prob", np.float32), ("reserved", np.uint32)])
+assert PICK_DTYPE.itemsize == C.sizeof(_lib.EmitterPick) == 16
 SPHERE, QUAD = _lib.EMITTER_SPHERE, _lib.EMITTER_QUAD
 NO_GEOMETRY = _lib.NO_GEOMETRY
 
@@ -41,3 +44,23 @@ def table(*parts):
     """One contiguous table from records and tables, in the order given."""
     parts = [np.ascontiguousarray(p, EMITTER_DTYPE).reshape(-1) for p in parts]
     return np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, EMITTER_DTYPE)
+
+
+def pick_table(table, weights=None):
+    """trt_emitter_pick_build: (records, total) - the alias table (PICK_DTYPE, one record per emitter) through which direct(pick=...)
+    chooses emitter e with probability weights[e] / total, and that total.  weights=None: each emitter's power (luminance of its colour
+    x area), the table direct(mis=..., pick=...) needs; else float32 [E], finite and non-negative with a positive sum (direct() without
+    mis only).  Host only, deterministic."""
+    t = np.ascontiguousarray(table)
+    if t.dtype != EMITTER_DTYPE or t.ndim != 1:
+        raise ValueError("table must be a one-dimensional record array of lights.EMITTER_DTYPE")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.shape != (len(t),):
+            raise ValueError("weights must be float32 [len(table)]")
+    out = np.zeros(len(t), PICK_DTYPE)
+    total = C.c_float(0.0)
+    _lib.check(lib.trt_emitter_pick_build(t.ctypes.data if len(t) else None, len(t), w.ctypes.data if w is not None and len(w) else None,
+                                          out.ctypes.data if len(t) else None, C.byref(total)))
+    return out, np.float32(total.value)
