@@ -579,6 +579,19 @@ extern "C" {
                                       d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_direct_mis_params, total_power: f32,
                                       d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_direct_mis_pick_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_nee_pick(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
+                        n_emitters: u32, p: *const trt_nee_params, radiance: *mut f32, moment2: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_nee_pick_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter,
+                               d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_nee_params, d_radiance: *mut f32,
+                               d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_nee_pick_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_nee_mis_pick(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
+                            n_emitters: u32, p: *const trt_nee_mis_params, total_power: f32, radiance: *mut f32, moment2: *mut f32,
+                            stats: *mut trt_stats) -> c_int;
+    pub fn trt_nee_mis_pick_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter,
+                                   d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_nee_mis_params, total_power: f32,
+                                   d_radiance: *mut f32, d_moment2: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_nee_mis_pick_launch_plan(s: *const trt_scene, n: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
     pub fn trt_probe_params_default(out: *mut trt_probe_params);
     pub fn trt_probe(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
                      stats: *mut trt_stats) -> c_int;

@@ -604,6 +604,56 @@ impl World {
         Ok((radiance, moment2))
     }
 
+    /// `nee` with the emitter of every vertex's shadow ray chosen through `pick` (`trt_nee_pick`; `pick_table`) - by power or by the
+    /// weights the table was built from, not uniformly: one draw more per vertex, far less noise where the emitters' powers differ much.
+    pub fn nee_pick(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], pick: &[sys::trt_emitter_pick], samples_per_item: u32,
+                    source: PassesSource, source_is_diffuse: bool, shadow_end: Float, max_bounces: u32, background: Vec3, seed: u32,
+                    first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        if pick.len() != emitters.len() {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "the pick table needs one record per emitter".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let params = nee_params(samples_per_item, source, source_is_diffuse, shadow_end, max_bounces, background, seed, first_stream);
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_nee_pick(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), pick.as_ptr(),
+                              emitters.len() as u32, &params, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
+    /// `nee_mis` with the emitter chosen through `pick` (`trt_nee_mis_pick`): `pick` must be `pick_table(emitters, None)` - the power
+    /// table - and `total_power` the total it reported; a light reached after a diffuse scatter is weighted by the same probability.
+    pub fn nee_mis_pick(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], pick: &[sys::trt_emitter_pick], total_power: Float,
+                        samples_per_item: u32, source: PassesSource, source_is_diffuse: bool, heuristic: MisHeuristic, shadow_end: Float,
+                        max_bounces: u32, background: Vec3, seed: u32, first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        if pick.len() != emitters.len() {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "the pick table needs one record per emitter".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_nee_mis_params::default();
+        unsafe { sys::trt_nee_mis_params_default(&mut params) };
+        params.nee = nee_params(samples_per_item, source, source_is_diffuse, shadow_end, max_bounces, background, seed, first_stream);
+        params.heuristic = match heuristic {
+            MisHeuristic::Balance => sys::TRT_MIS_BALANCE,
+            MisHeuristic::Power => sys::TRT_MIS_POWER,
+        };
+        let mut radiance = vec![0.0 as Float; items.len() * 3];
+        let mut moment2 = vec![0.0 as Float; items.len() * 3];
+        check(unsafe {
+            sys::trt_nee_mis_pick(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), pick.as_ptr(),
+                                  emitters.len() as u32, &params, total_power, radiance.as_mut_ptr(), moment2.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((radiance, moment2))
+    }
+
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.
     pub fn trim(&mut self) -> Result<(), Error> {
         if self.scene.is_null() {

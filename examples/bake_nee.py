@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bake the full light of the Cornell box's floor with the lights aimed at at every bounce -> nee.png, beside the same light found by
 chance -> gather.png.
-   python examples/bake_nee.py [SIZE K] [--mis balance|power] [--direct-mis balance|power]
+   python examples/bake_nee.py [SIZE K] [--mis balance|power] [--direct-mis balance|power] [--pick]
 bake.quad_texels lays SIZE x SIZE surfels over the floor quad.  Scene.direct (trt_direct) aims every sample at the lamp from the texel
 itself; Scene.nee (trt_nee) with source_is_diffuse=True traces the cosine-distributed paths Scene.gather traces, hides the lamp where a
 path reaches it by a diffuse bounce and sends one shadow ray to it from every diffuse vertex instead: the texel's indirect light.  Their sum
@@ -12,6 +12,11 @@ rays sent from vertices beside the lamp.
 
 --direct-mis takes the direct part from trt_direct_mis, which weights the texel's own shadow ray against a cosine-lobe ray from the texel:
 with both flags no term of the bake is unbounded, which matters for texels beside the lamp (not the floor's).
+
+--pick bakes the many-light room of examples/bake_direct.py --pick - sixty small sphere lights of a twentieth of the lamp's colour along
+the walls - and chooses the emitter of every shadow ray, the texel's own and those of the path's vertices, through lights.pick_table's alias
+table (trt_direct_pick and trt_nee_pick; with the mis flags trt_direct_mis_pick and trt_nee_mis_pick): by power, where the uniform choice
+sends sixty of sixty-one shadow rays to six percent of the light.  The same bake with the uniform choice is printed beside it.
 
 The lamp is lowered from y = 100 to y = 99 here, as in examples/bake_direct.py: in the stock box it lies in the ceiling's plane."""
 import os
@@ -34,13 +39,23 @@ if "--direct-mis" in argv:
     at = argv.index("--direct-mis")
     direct_mis = argv[at + 1]
     del argv[at:at + 2]
+pick = "--pick" in argv
+if pick:
+    argv.remove("--pick")
 size, spp = (int(a) for a in argv[:2]) if len(argv) >= 2 else (256, 64)
 desc = trt.scenes.cornell(2, 2)                                              # the camera of the description is not used
 geos = list(desc["geometries"])
 kind, corner, u, v, material = geos[2]
 assert kind == "quad" and material == "light"
 geos[2] = (kind, (corner[0], 99.0, corner[2]), u, v, material)
-desc = dict(desc, geometries=geos)
+materials = list(desc["materials"])
+if pick:                                                                    # the many-light room: 20 dim spheres on each of three walls
+    lamp = [m for m in materials if m[0] == "light"][0]
+    materials.append(("dim_light", lamp[1], tuple(0.05 * c for c in lamp[2]), 0.0))
+    for y in (20.0, 40.0, 60.0, 80.0):
+        for a in (10.0, 30.0, 50.0, 70.0, 90.0):
+            geos += [("sphere", (2.0, y, a), 1.0, "dim_light"), ("sphere", (98.0, y, a), 1.0, "dim_light"), ("sphere", (a, y, 98.0), 1.0, "dim_light")]
+desc = dict(desc, materials=materials, geometries=geos)
 scene = trt.world_from_description(desc)[0].get_bvh()
 kind, corner, u, v, _ = desc["geometries"][3]
 assert kind == "quad"
@@ -48,8 +63,9 @@ items = trt.bake.quad_texels(corner, u, v, size, size, flip=True)            # t
 table = scene.emitters()
 path = dict(max_bounces=5, background=(0.0, 0.0, 0.0))
 t0 = time.perf_counter()
-direct, d_m2, dst = scene.direct(items, table, spp, moment2=True, mis=direct_mis)
-indirect, i_m2, ist = scene.nee(items, table, spp, source="cosine", source_is_diffuse=True, moment2=True, mis=mis, **path)
+pick_table = trt.lights.pick_table(table) if pick else None
+direct, d_m2, dst = scene.direct(items, table, spp, moment2=True, mis=direct_mis, pick=pick_table)
+indirect, i_m2, ist = scene.nee(items, table, spp, source="cosine", source_is_diffuse=True, moment2=True, mis=mis, pick=pick_table, **path)
 t1 = time.perf_counter()
 gather, g_m2, gst = scene.gather(items, spp, lobe="cosine", moment2=True, **path)
 t2 = time.perf_counter()
@@ -69,3 +85,11 @@ print(f"{size}x{size} texels of the floor, {spp} samples each: direct + nee mean
       f"(standard error of a texel {float(err_nee.mean()):.4f}; {dst['rays'] + ist['rays']} rays, {(t1 - t0) * 1e3:.1f} ms) -> nee.png; "
       f"gather mean {float(gather[:, 0].mean()):.4f} (standard error {float(err_gather.mean()):.4f}; {gst['rays']} rays, "
       f"{(t2 - t1) * 1e3:.1f} ms) -> gather.png")
+if pick:
+    # the same bake with the uniform choice: the same expectation, the noise the table is for
+    u_direct, u_d_m2, _ = scene.direct(items, table, spp, moment2=True, mis=direct_mis)
+    u_indirect, u_i_m2, _ = scene.nee(items, table, spp, source="cosine", source_is_diffuse=True, moment2=True, mis=mis, **path)
+    err_uniform = np.sqrt(texel_error(u_direct, u_d_m2) ** 2 + texel_error(u_indirect, u_i_m2) ** 2)
+    print(f"{len(table)} emitters, the lamp {float(pick_table[0]['prob'].max()):.3f} of the power: uniform choice mean "
+          f"{float((u_direct + u_indirect)[:, 0].mean()):.4f} (standard error of a texel {float(err_uniform.mean()):.4f}); of the indirect part alone "
+          f"{float(texel_error(u_indirect, u_i_m2).mean()):.4f} uniform, {float(texel_error(indirect, i_m2).mean()):.4f} by power")

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """A frame of the Cornell box through the queries, with the lamp aimed at at every diffuse hit -> nee_frame.png.
-   python examples/render_nee.py [W H SPP] [--mis balance|power]
+   python examples/render_nee.py [W H SPP] [--mis balance|power] [--pick]
 Everything stays in HBM.  For sample s of SPP the camera writes the frame's primary rays (trt_primary_rays_device: the rays the render
 traces for that sample) and Scene.nee_device (trt_nee_device, source "rays") folds one sample per pixel into the running sums: K = SPP,
 the sample range [s, s + 1), accumulate from the second pass on - the frame in passes that tinyrt.h describes for trt_passes.  The first
 hit of a camera ray is no diffuse vertex (source_is_diffuse = 0): the lamp is seen where the camera looks at it, and hidden where a path
 reaches it by a diffuse bounce, because the shadow ray from that bounce has already counted it.  With --mis (trt_nee_mis_device) the
 shadow ray and that hit are both counted, weighted by their densities.  (The stock box's lamp is coplanar with the ceiling, where the two
-disagree about visibility: tinyrt.h, limits.)"""
+disagree about visibility: tinyrt.h, limits.)  With --pick the emitter of every shadow ray is chosen through lights.pick_table's alias table
+(trt_nee_pick_device; with --mis trt_nee_mis_pick_device): the box has one lamp, so the frame's expectation and noise are the same and the
+run shows what the extra draw costs."""
 import os
 import sys
 import time
@@ -21,6 +23,9 @@ if "--mis" in argv:
     at = argv.index("--mis")
     mis = argv[at + 1]
     del argv[at:at + 2]
+pick = "--pick" in argv
+if pick:
+    argv.remove("--pick")
 w, h, spp = (int(a) for a in argv[:3]) if len(argv) >= 3 else (300, 300, 64)
 import torch
 
@@ -33,13 +38,18 @@ d_sum = torch.zeros(n * 3, dtype=torch.float32, device="cuda:0")
 d_m2 = torch.zeros(n * 3, dtype=torch.float32, device="cuda:0")
 d_table = torch.from_numpy(table.view("uint8").copy()).to("cuda:0")
 ctr = torch.zeros(16, dtype=torch.int64, device="cuda:0")
+pick_arg = None
+if pick:
+    records, total = trt.lights.pick_table(table)
+    d_pick = torch.from_numpy(records.view("uint8").copy()).to("cuda:0")
+    pick_arg = d_pick.data_ptr() if mis is None else (d_pick.data_ptr(), total)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for s in range(spp):
     camera.primary_rays_device(s, spp, d_rays.data_ptr(), seed=1)
     scene.nee_device(d_rays.data_ptr(), n, d_table.data_ptr(), len(table), d_sum.data_ptr(), d_m2.data_ptr(), d_counters_ptr=ctr.data_ptr(),
                      samples_per_item=spp, source="rays", max_bounces=20, background=(0.001, 0.001, 0.001), seed=1, sample_begin=s,
-                     sample_end=s + 1, accumulate=s > 0, mis=mis)
+                     sample_end=s + 1, accumulate=s > 0, mis=mis, pick=pick_arg)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 frame = d_sum.view(h, w, 3).cpu().numpy()

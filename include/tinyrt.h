@@ -55,7 +55,8 @@ extern "C" {
  *              trt_nee_mis, trt_nee_mis_device, trt_nee_mis_launch_plan; trt_direct_mis_params, trt_direct_mis_params_default,
  *              trt_direct_mis, trt_direct_mis_device, trt_direct_mis_launch_plan; trt_emitter_pick, trt_emitter_pick_build,
  *              trt_direct_pick, trt_direct_pick_device, trt_direct_pick_launch_plan, trt_direct_mis_pick, trt_direct_mis_pick_device,
- *              trt_direct_mis_pick_launch_plan. */
+ *              trt_direct_mis_pick_launch_plan; trt_nee_pick, trt_nee_pick_device, trt_nee_pick_launch_plan, trt_nee_mis_pick,
+ *              trt_nee_mis_pick_device, trt_nee_mis_pick_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -1024,7 +1025,8 @@ int trt_direct_mis_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_
  * lamp and sixty dim lights sixty of sixty-one shadow rays go to a few percent of the light, and the one that reaches the lamp is scaled
  * by E.  trt_direct_pick and trt_direct_mis_pick are the same two queries with the emitter chosen through a Walker/Vose alias table the
  * caller builds once per emitter table: probability prob[e], one draw and two loads more per sample.  trt_direct,
- * trt_direct_mis and the next-event queries are unchanged and still choose uniformly.
+ * trt_direct_mis, trt_nee and trt_nee_mis are unchanged and still choose uniformly; the next-event queries have PICK forms of their own
+ * (trt_nee_pick, trt_nee_mis_pick below).
  *
  * The pick table: E records, record k for slot k AND for emitter k.  trt_emitter_pick_build is host only, needs no device and is
  * deterministic - the same input gives the same bytes:
@@ -1102,6 +1104,58 @@ int trt_direct_mis_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n,
                                const trt_emitter_pick *d_pick, uint32_t n_emitters, const trt_direct_mis_params *p, float total_power,
                                float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
 int trt_direct_mis_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Next-event queries that choose the emitter by power: the same alias table at every diffuse vertex ----
+ * trt_nee and trt_nee_mis draw the emitter of every vertex's shadow ray with probability 1 / E.  A sample runs up to B - 1 such draws
+ * against the direct query's one, so in a room whose lights differ in power most of a bake's shadow rays are spent here.  trt_nee_pick and
+ * trt_nee_mis_pick are the same two queries with every vertex draw taken through the pick table above (trt_emitter_pick,
+ * trt_emitter_pick_build): one draw and two loads more per vertex.  `pick` and `total_power` stand where
+ * trt_direct_pick / trt_direct_mis_pick have them.
+ *
+ * trt_nee_pick.  The contract is trt_nee's, word for word, except the vertex draw: on stream (seed, j, 2 + d) it uses steps 2 and 5 of
+ * trt_direct_pick in place of trt_direct's -
+ *    u0 = random(g);  k = min(uint32(u0 * float(E)), E - 1);  u1 = random(g);  e = (u1 < pick[k].q) ? k : min(pick[k].alias, E - 1)
+ *    scale = (area / pick[e].prob) * 0.318309886f
+ * - one draw more per vertex than trt_nee.  The min on the alias is contract here too: no table the device form is handed makes the kernel
+ * read outside the E records of either table.  A NaN q takes the alias; prob == 0, or any prob that makes wgt no finite number, is a dead
+ * sample.  The path and its streams, the hiding of diffusely reached lights, source_is_diffuse, the last-vertex rule, the fold, sample
+ * ranges and accumulate, both split invariances, the output bounds and the counters are trt_nee's.  With max_bounces == 1 no vertex draws
+ * and the result is trt_gather's (trt_nee's) bit for bit.
+ *  - Errors: trt_nee's, in trt_nee's order, as far as its table size and reserved words; then with n > 0 a NULL `pick`; then, HOST FORM
+ *    ONLY, trt_nee's check of the emitter records, then trt_direct_pick's checks of the pick records, in their order.  THE DEVICE FORM
+ *    CHECKS ONLY THE POINTER: with a table whose prob is not the probability its q and alias imply the result is biased; the reads stay
+ *    in bounds regardless.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM.  n == 0 succeeds and touches nothing.
+ *  - trt_nee_pick: host buffers, the pick table in the call's one device allocation.  trt_nee_pick_device: `d_pick` in HBM, n_emitters x
+ *    16 bytes, 4-byte aligned; allocates nothing.
+ *
+ * trt_nee_mis_pick.  The contract is trt_nee_mis', with `total_power` = the builder's *total, and two changes:
+ *  - The shadow sample is drawn as above;  wl = 1 / (1 + q(wgt)), 1 for a virtual emitter, as before.
+ *  - A light reached after a diffuse scatter at hit >= 2 is weighed with the light's own choice probability in place of 1 / E, as in
+ *    trt_direct_mis_pick:
+ *      pw = ((0.2126f * em.x + 0.7152f * em.y) + 0.0722f * em.z) * area      (em the hit material's emitted colour, area the hit primitive's own)
+ *      ph = pw / total_power
+ *      g = ((csh * clh) / (t * t)) * ((area / ph) * 0.318309886f)
+ *    wb is unchanged: 1 when csh <= 0 or q(g) is not finite, which covers a black light (ph = 0).  ph has the bits of prob[e] of that
+ *    light, so the two weights of one point sum to 1 as in trt_nee_mis.
+ *  A light at hit 1 under source_is_diffuse stays hidden in full, as in trt_nee_mis.
+ *  - Table rule: trt_nee_mis' AND the pick table is the power-rule table (weights == NULL) of that emitter table.  The host form checks,
+ *    after trt_nee_mis' argument checks, the pointer, the emitter records and the pick records: trt_nee_mis' table rule, then total_power
+ *    positive and finite, then pick[e].prob bit for bit against power_e / total_power for every e.  THE DEVICE FORM CANNOT CHECK EITHER
+ *    RULE: with a caller-weighted table or another total the weights do not sum to 1 and the result is biased.
+ * The launch plans: trt_nee_launch_plan's rule and fields over the PICK kernels' own tables. */
+int trt_nee_pick(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, const trt_emitter_pick *pick,
+                 uint32_t n_emitters, const trt_nee_params *p, float *radiance, float *moment2, trt_stats *stats);
+int trt_nee_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters, const trt_emitter_pick *d_pick,
+                        uint32_t n_emitters, const trt_nee_params *p, float *d_radiance, float *d_moment2, uint64_t *d_counters,
+                        void *stream);
+int trt_nee_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+int trt_nee_mis_pick(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters, const trt_emitter_pick *pick,
+                     uint32_t n_emitters, const trt_nee_mis_params *p, float total_power, float *radiance, float *moment2,
+                     trt_stats *stats);
+int trt_nee_mis_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters,
+                            const trt_emitter_pick *d_pick, uint32_t n_emitters, const trt_nee_mis_params *p, float total_power,
+                            float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
+int trt_nee_mis_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

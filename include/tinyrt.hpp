@@ -218,6 +218,27 @@ public:
         check(trt_nee_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
                           moment2 ? moment2->data() : nullptr, stats));
     }
+    // nee() with the emitter of every vertex's shadow ray chosen through `pick` (trt_nee_pick; pick_table() above) - by power, not
+    // uniformly: one draw more per vertex, far less noise where the emitters' powers differ much.
+    void nee_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
+                  const trt_nee_params& p, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
+        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_nee_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
+                           radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
+    // nee_mis() with the emitter chosen through `pick` (trt_nee_mis_pick): `pick` must be pick_table(table) - the power table - and
+    // `total_power` the total it reported; a light reached after a diffuse scatter is weighted by the same probability.
+    void nee_mis_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
+                      const trt_nee_mis_params& p, float total_power, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr,
+                      trt_stats* stats = nullptr) {
+        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(trt_nee_mis_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
+                               total_power, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+    }
     // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
     // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
     // gather() does and adds colour * Y_k(direction) / K to coefficient k of the item.  `sh` becomes p.bands^2 x 3 floats per item - real

@@ -337,6 +337,16 @@ SIGNATURES = {
     "trt_direct_mis_pick_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DirectMisParams),
                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_direct_mis_pick_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_nee_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeParams), C.c_void_p,
+                               C.c_void_p, C.POINTER(Stats)]),
+    "trt_nee_pick_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeParams),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_nee_pick_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_nee_mis_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeMisParams),
+                                   C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_nee_mis_pick_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeMisParams),
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_nee_mis_pick_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_probe_params_default": (None, [C.POINTER(ProbeParams)]),
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -602,7 +602,7 @@ class Scene:
 
     def nee(self, items, emitters, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, max_bounces=50,
             background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None, accumulate=False, radiance=None, moment2=None,
-            mis=None):
+            mis=None, pick=None):
         """trt_nee: what radiance() (source "rays": items float32 [n, 6] are rays, used as given) or gather() (source "cosine" or "cone":
         items are surfels) estimates, with the lights aimed at: the path of every sample is gather()'s bit for bit, at every Lambertian
         hit that leaves bounce budget one shadow ray goes to the emitter table as in direct() (stream (seed, j, 2 + scatters before)), and
@@ -614,7 +614,11 @@ class Scene:
         mis = "balance" | "power" (trt_nee_mis): the same paths and shadow rays, but a light reached after a diffuse scatter (from the
         second hit on) is counted both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the hit by its complement,
         q(x) = x or x * x: the same expectation without the 1/d2 tail of shadow samples beside a lamp.  `emitters` must then hold
-        exactly the scene's own lights (emitters()), each once, plus any virtual ones; anything else is an error."""
+        exactly the scene's own lights (emitters()), each once, plus any virtual ones; anything else is an error.
+        pick = lights.pick_table(emitters) (trt_nee_pick; with mis trt_nee_mis_pick): every vertex's emitter is chosen through that alias
+        table, by power or by the weights the table was built from, not uniformly - one draw more per vertex, as in direct().  The
+        records alone will do without mis; with mis the (records, total) pair is needed and the table must be the power table
+        (weights=None).  pick=None: the calls and bytes of before."""
         r, _ = _rays_and_t_max(items, None)
         n = len(r)
         e = self._emitter_table(emitters)
@@ -627,26 +631,51 @@ class Scene:
         for a in (radiance, moment2):
             assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
         st = Stats()
-        fn = lib.trt_nee if mis is None else lib.trt_nee_mis
-        check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p),
-                 radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st)))
+        out = (radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st))
+        if pick is None:
+            fn = lib.trt_nee if mis is None else lib.trt_nee_mis
+            check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p), *out))
+            return radiance, moment2, st.as_dict()
+        pick, total = self._pick_and_total(pick, mis)
+        k = np.ascontiguousarray(pick)
+        if k.dtype != PICK_DTYPE or k.shape != (len(e),):
+            raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
+        head = (self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, k.ctypes.data if len(k) else None, len(e), C.byref(p))
+        if mis is None:
+            check(lib.trt_nee_pick(*head, *out))
+        else:
+            check(lib.trt_nee_mis_pick(*head, C.c_float(total), *out))
         return radiance, moment2, st.as_dict()
 
-    def nee_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+    def nee_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, pick=None,
+                   **params):
         """Enqueue nee() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n_emitters x 80 bytes of
         trt_emitter records, n x 12 bytes of sums each) on the current device; asynchronous on the stream, allocates nothing.  `params`:
         nee()'s keywords, samples_per_item and mis included (trt_nee_mis_device where mis is given: the device form cannot check the
-        table rule)."""
+        table rule).  pick: the device pointer of the n_emitters x 16 bytes of lights.pick_table's records (trt_nee_pick_device), or with
+        mis (pointer, total) (trt_nee_mis_pick_device); the device form checks neither table."""
         p = self._nee_params(**params)
-        fn = lib.trt_nee_mis_device if isinstance(p, _lib.NeeMisParams) else lib.trt_nee_device
-        check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p),
-                 C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+        weighted = isinstance(p, _lib.NeeMisParams)
+        tail = (C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr))
+        if pick is None:
+            fn = lib.trt_nee_mis_device if weighted else lib.trt_nee_device
+            check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p), *tail))
+            return
+        d_pick_ptr, total = self._pick_and_total(pick, params.get("mis"))
+        head = (self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), C.c_void_p(d_pick_ptr), int(n_emitters), C.byref(p))
+        if weighted:
+            check(lib.trt_nee_mis_pick_device(*head, C.c_float(total), *tail))
+        else:
+            check(lib.trt_nee_pick_device(*head, *tail))
 
-    def nee_plan(self, n, compute_units=0, mis=None):
-        """trt_nee_launch_plan (mis given: trt_nee_mis_launch_plan): how nee() launches n items on this scene, as a dict with
-        gather_plan()'s fields."""
+    def nee_plan(self, n, compute_units=0, mis=None, pick=None):
+        """trt_nee_launch_plan (mis given: trt_nee_mis_launch_plan; pick given, as anything but None: the _pick_ plans): how nee() launches
+        n items on this scene, as a dict with gather_plan()'s fields."""
         plan = _lib.QueryPlan()
-        fn = lib.trt_nee_launch_plan if mis is None else lib.trt_nee_mis_launch_plan
+        if pick is None:
+            fn = lib.trt_nee_launch_plan if mis is None else lib.trt_nee_mis_launch_plan
+        else:
+            fn = lib.trt_nee_pick_launch_plan if mis is None else lib.trt_nee_mis_pick_launch_plan
         check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 

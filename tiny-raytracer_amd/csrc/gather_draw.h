@@ -164,6 +164,15 @@ TRT_DEV WeightedDirectSample direct_draw_at_weighted(const V3& x, const V3& n, c
     auto surfel = [&] { Ray r; r.o = x; r.d = n; return r; };
     return direct_draw_from<decltype(surfel), WeightedDirectSample>(surfel, emitters, n_emitters, shadow_end, g);
 }
+// The two draws of the next-event kernels behind one name, as direct_draw_item is for the items: PICK chooses the emitter through the alias
+// table (nee.hip, PICK kernels); without it the sample is direct_draw_at's / direct_draw_at_weighted's and `pick` is not read.
+template <bool PICK, class Sample>
+TRT_DEV Sample direct_draw_at(const V3& x, const V3& n, const float* __restrict__ emitters, const float* __restrict__ pick, uint32_t n_emitters,
+                              float shadow_end, Rng& g) {
+    auto surfel = [&] { Ray r; r.o = x; r.d = n; return r; };
+    if constexpr (PICK) return direct_draw_from<decltype(surfel), Sample, AliasPick>(surfel, emitters, n_emitters, shadow_end, g, AliasPick{pick});
+    else return direct_draw_from<decltype(surfel), Sample>(surfel, emitters, n_emitters, shadow_end, g);
+}
 
 // The lobe of a launch: 0 for a radiance query (the items are rays), else what trt_gather_params carries.
 struct Lobe {

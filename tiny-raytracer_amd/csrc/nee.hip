@@ -31,6 +31,12 @@
 // wb = q(g) / (1 + q(g)) (mis_weight.h mis_hit_weight) in the branch where shade has ended the path: cold, since a light always ends it.  A lane
 // carries csh, the cosine of its last Lambertian scatter, besides.  The MIS = false instantiations are instruction for instruction what
 // they were without the parameter; the two entry points share their checks, launcher and both forms' bodies with trt_nee.
+//
+// trt_nee_pick / trt_nee_mis_pick (tinyrt.h) are the same kernel with PICK = true: every vertex draw goes through the alias table of
+// direct.hip's PICK queries (gather_draw.h AliasPick: one draw and two loads more), and the weighted hit takes the light's choice
+// probability from the hit itself (mis_weight.h, the overload with total_power).  The table's checks are emitter_pick.h's, the ones
+// direct.hip applies.  The PICK = false instantiations are instruction for instruction what they were.
+#include "emitter_pick.h"
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -64,14 +70,33 @@ struct NeeArgs {
     uint32_t source_is_diffuse;      // after_diffuse at the first hit
     uint32_t heuristic;              // enum trt_mis_heuristic, wave-uniform (the MIS kernels; the others do not read it)
 };
+// What a PICK kernel is handed besides (trt_nee_pick, trt_nee_mis_pick): the alias table (tinyrt.h trt_emitter_pick, n_emitters x 4 words)
+// and the table's total power, by which a light hit finds its own choice probability (the weighted kernels; the others do not read it).
+// A struct of its own around NeeArgs, as direct.hip DirectPickArgs is: the kernel arguments of the uniform kernels lie where they lay.
+struct NeePickArgs {
+    NeeArgs g;
+    const float* pick;
+    float total_power;
+};
+TRT_DEV const NeeArgs& nee_args(const NeeArgs& a) { return a; }
+TRT_DEV const NeeArgs& nee_args(const NeePickArgs& a) { return a.g; }
+TRT_DEV const float* nee_pick_table(const NeeArgs&) { return nullptr; }
+TRT_DEV const float* nee_pick_table(const NeePickArgs& a) { return a.pick; }
+TRT_DEV float nee_pick_total(const NeeArgs&) { return 0.0f; }
+TRT_DEV float nee_pick_total(const NeePickArgs& a) { return a.total_power; }
 constexpr int NEE_RAYS = 0, NEE_LOBE = 1;      // nee_kernel's SOURCE: the items are rays | surfels whose lobe is NeeArgs::source
 
 // ra.sample_begin < ra.sample_end and ra.max_bounces > 0 (launch_nee: nothing to trace launches query_plan.h batch_zero or nothing)
 // MIS (tinyrt.h trt_nee_mis): the same rounds, walks and draws; a shadow sample is scaled by wl, and a light the path reaches after a
 // diffuse scatter at hit >= 2 adds its emission scaled by wb where the plain kernel adds nothing.  A lane carries csh, one register more.
-template <int MODE, int WALK, int THREADS, int MINW, int SOURCE, bool MIS>
-__global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, RenderArgs ra, NeeArgs ga, const float4* __restrict__ leaf_list,
-                                                                 const uint4* __restrict__ nodes16) {
+// PICK (trt_nee_pick, trt_nee_mis_pick): the emitter of a vertex's shadow ray is chosen through the alias table (gather_draw.h AliasPick),
+// one draw and two loads more per vertex; the weighted light hit takes its choice probability from the hit material and total_power.
+template <int MODE, int WALK, int THREADS, int MINW, int SOURCE, bool MIS, bool PICK = false>
+__global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, RenderArgs ra, std::conditional_t<PICK, NeePickArgs, NeeArgs> args,
+                                                                 const float4* __restrict__ leaf_list, const uint4* __restrict__ nodes16) {
+    const NeeArgs& ga = nee_args(args);
+    [[maybe_unused]] const float* __restrict__ const pick = nee_pick_table(args);
+    [[maybe_unused]] const float total_power = nee_pick_total(args);
     stage_scene_to_lds<MODE>(scd);
     const FlatReuse flat_reuse = axis_quads_to_lds<MODE, false, WALK>(scd, ra.flat_reuse);
     const SceneAcc<MODE> sc{scd.blob, scd.L};
@@ -156,9 +181,16 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
                         // a light reached by a diffuse scatter at hit >= 2 (a light leaves remain and the ray as they were): the shadow ray of
                         // the vertex before has counted it with wl, the hit counts with wb.  Cold: the path has ended.
                         if (info.kind == TRT_LIGHT && after_diffuse && p.remain != ra.max_bounces) {
-                            const float wb = mis_hit_weight<MODE>(sc, hit_prim, p.ray, info.normal, hit_t, csh, ga.n_emitters, ga.heuristic);
-                            const float4 m = sc.material(prim_material<MODE>(sc, hit_prim));
-                            p.color = p.color + p.atten * (v3(m.x, m.y, m.z) * wb);
+                            if constexpr (PICK) {
+                                const float4 m = sc.material(prim_material<MODE>(sc, hit_prim));
+                                const V3 emission = v3(m.x, m.y, m.z);
+                                const float wb = mis_hit_weight<MODE>(sc, hit_prim, p.ray, info.normal, hit_t, csh, emission, total_power, ga.heuristic);
+                                p.color = p.color + p.atten * (emission * wb);
+                            } else {
+                                const float wb = mis_hit_weight<MODE>(sc, hit_prim, p.ray, info.normal, hit_t, csh, ga.n_emitters, ga.heuristic);
+                                const float4 m = sc.material(prim_material<MODE>(sc, hit_prim));
+                                p.color = p.color + p.atten * (v3(m.x, m.y, m.z) * wb);
+                            }
                         }
                     }
                     // imager.rs:35,50 and the second moment beside it, in the operation order of pixels_kernel
@@ -184,14 +216,14 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
                         DirectSample smp;
                         [[maybe_unused]] float wl = 1.0f;
                         if constexpr (MIS) {
-                            const WeightedDirectSample w = direct_draw_at_weighted(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
+                            const WeightedDirectSample w = direct_draw_at<PICK, WeightedDirectSample>(p.ray.o, info.normal, emitters, pick, ga.n_emitters, ga.shadow_end, g);
                             smp = w;
                             csh = dot(info.normal, p.ray.d);
                             // the shadow sample's share: 1 / (1 + q(p_bsdf / p_light)); a virtual emitter cannot be hit and counts in full
                             const float qw = ga.heuristic == TRT_MIS_POWER ? w.wgt * w.wgt : w.wgt;
                             if (w.geometry != 0xFFFFFFFFu) wl = 1.0f / (1.0f + qw);
                         } else {
-                            smp = direct_draw_at(p.ray.o, info.normal, emitters, ga.n_emitters, ga.shadow_end, g);
+                            smp = direct_draw_at<PICK, DirectSample>(p.ray.o, info.normal, emitters, pick, ga.n_emitters, ga.shadow_end, g);
                         }
                         V3 c = smp.c;
                         if constexpr (MIS) c = c * wl;
@@ -288,9 +320,57 @@ const BatchKernel kNeeMisLobeKernels[] = {
 };
 #undef TRT_NEE
 #undef TRT_NEE_MIS
+#define TRT_NEE_PICK(MODE, WALK, THREADS, MINW, SOURCE) \
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, false, true>), MODE, WALK, THREADS, MINW}
+#define TRT_NEE_MIS_PICK(MODE, WALK, THREADS, MINW, SOURCE) \
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, true, true>), MODE, WALK, THREADS, MINW}
+// The PICK kernels (trt_nee_pick, trt_nee_mis_pick): the same shapes.  u1, q and the alias die before the emitter record is loaded, the
+// table pointer is wave-uniform; bounds by the same rule, read per shape off both sources (profiles/nee_pick_resource_usage.txt).
+const BatchKernel kNeePickRayKernels[] = {
+    TRT_NEE_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
+    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_RAYS),
+    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_RAYS),
+    TRT_NEE_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
+    TRT_NEE_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
+    TRT_NEE_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
+};
+const BatchKernel kNeePickLobeKernels[] = {
+    TRT_NEE_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
+    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_LOBE),
+    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_LOBE),
+    TRT_NEE_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
+    TRT_NEE_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
+    TRT_NEE_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
+};
+const BatchKernel kNeeMisPickRayKernels[] = {
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_RAYS),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
+    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
+    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
+};
+const BatchKernel kNeeMisPickLobeKernels[] = {
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_LOBE),
+    TRT_NEE_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
+    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
+    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
+};
+#undef TRT_NEE_PICK
+#undef TRT_NEE_MIS_PICK
 constexpr size_t kNeeShapes = sizeof(kNeeRayKernels) / sizeof(kNeeRayKernels[0]);
 static_assert(sizeof(kNeeLobeKernels) == sizeof(kNeeRayKernels), "one lobe instantiation per shape");
 static_assert(sizeof(kNeeMisRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeeMisLobeKernels) == sizeof(kNeeRayKernels), "one weighted instantiation per shape and source");
+static_assert(sizeof(kNeePickRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeePickLobeKernels) == sizeof(kNeeRayKernels) &&
+              sizeof(kNeeMisPickRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeeMisPickLobeKernels) == sizeof(kNeeRayKernels),
+              "one PICK instantiation per shape, source and weighting");
+// The kernels of a query: [mis][pick][the items are rays].
+const BatchKernel* nee_kernels(bool mis, bool pick, bool rays) {
+    if (pick) return mis ? (rays ? kNeeMisPickRayKernels : kNeeMisPickLobeKernels) : (rays ? kNeePickRayKernels : kNeePickLobeKernels);
+    return mis ? (rays ? kNeeMisRayKernels : kNeeMisLobeKernels) : (rays ? kNeeRayKernels : kNeeLobeKernels);
+}
 
 // What a call asks of the device, after the checks.
 struct NeeCall {
@@ -303,11 +383,13 @@ struct NeeCall {
     uint32_t source_is_diffuse;
     bool mis = false;                // trt_nee_mis: the weighted kernels, with `heuristic`
     uint32_t heuristic = 0u;
+    bool pick = false;               // trt_nee_pick / trt_nee_mis_pick: the PICK kernels, with an alias table (and `total_power`)
+    float total_power = 0.0f;
     bool nothing() const { return ra.sample_begin == ra.sample_end || ra.max_bounces == 0u; }
 };
 
-hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_items, uint32_t n, const float* d_emitters, float* d_radiance,
-                      float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
+hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_items, uint32_t n, const float* d_emitters, const float* d_pick,
+                      float* d_radiance, float* d_moment2, unsigned long long* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (c.nothing()) {
         // nothing to trace: a path with no bounce budget returns colour 0 (cpu.rs:43-47,64); the sums start at 0, or stay
@@ -316,16 +398,15 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const bool rays = c.source == TRT_PASSES_RAYS;
-    const BatchKernel* const table = c.mis ? (rays ? kNeeMisRayKernels : kNeeMisLobeKernels) : (rays ? kNeeRayKernels : kNeeLobeKernels);
-    const hipError_t e = batch_prepare(scd, n, table, kNeeShapes, b);
+    const hipError_t e = batch_prepare(scd, n, nee_kernels(c.mis, c.pick, c.source == TRT_PASSES_RAYS), kNeeShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     RenderArgs ra = c.ra;
     ra.flat_reuse = qs.flat_reuse;
     NeeArgs ga{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
                c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse, c.heuristic};
-    void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
+    NeePickArgs pa{ga, d_pick, c.total_power};
+    void* args[] = {&scd, &ra, c.pick ? static_cast<void*>(&pa) : static_cast<void*>(&ga), &b.leaf_list, &b.nodes16};
     return batch_launch(b, args, stream);
 }
 
@@ -369,23 +450,25 @@ int nee_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const tr
     return TRT_OK;
 }
 
-// The two forms after their checks, for trt_nee and trt_nee_mis alike: `c` says which kernels.
-int nee_on_device(trt_scene* s, const NeeCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, float* d_radiance, float* d_moment2,
-                  uint64_t* d_counters, void* stream) {
+// The two forms after their checks, for the four queries alike: `c` says which kernels, `d_pick` / `pick` is the alias table of a PICK query.
+int nee_on_device(trt_scene* s, const NeeCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
+                  float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
     return sample_query_on_device(s, n, "next-event query launch", [&](const QueryScene& qs) {
-        return launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters), d_radiance, d_moment2,
-                          reinterpret_cast<unsigned long long*>(d_counters), static_cast<hipStream_t>(stream));
+        return launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters),
+                          reinterpret_cast<const float*>(d_pick), d_radiance, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),
+                          static_cast<hipStream_t>(stream));
     });
 }
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters).
-int nee_on_host(trt_scene* s, const NeeCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, float* radiance,
-                float* moment2, trt_stats* stats) {
+// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters | pick table, if any).
+int nee_on_host(trt_scene* s, const NeeCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick,
+                uint32_t n_emitters, float* radiance, float* moment2, trt_stats* stats) {
     const size_t sums = (size_t)n * 12u;
-    const SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                       "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
+                 "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
+    if (c.pick) { h.table2 = pick; h.table2_b = (size_t)n_emitters * sizeof(trt_emitter_pick); h.table2_what = "hipMemcpy of the pick table"; }
     return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "next-event query buffers", "next-event query launch", stats,
                                 [&](const QueryScene& qs, const SampleDev& d) {
-                                    return launch_nee(qs, c, d.items, n, d.table, d.sums, d.sums2, d.counters, nullptr);
+                                    return launch_nee(qs, c, d.items, n, d.table, d.table2, d.sums, d.sums2, d.counters, nullptr);
                                 });
 }
 
@@ -407,7 +490,7 @@ int trt_nee_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_e
     trt::NeeCall c;
     const int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
 }
 
 // The table's entries are checked where n > 0, ahead of any device work.
@@ -419,7 +502,7 @@ int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* e
         if (rc != TRT_OK) return rc;
         rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
         if (rc != TRT_OK) return rc;
-        return trt::nee_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+        return trt::nee_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
     });
 }
 
@@ -441,7 +524,7 @@ int trt_nee_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const t
     trt::NeeCall c;
     const int rc = trt::nee_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
     if (rc != TRT_OK) return rc;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
 }
 
 int trt_nee_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
@@ -456,13 +539,92 @@ int trt_nee_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitte
             rc = trt::nee_mis_table_check(s, emitters, n_emitters);
             if (rc != TRT_OK) return rc;
         }
-        return trt::nee_on_host(s, c, items, n, emitters, n_emitters, radiance, moment2, stats);
+        return trt::nee_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
     });
 }
 
 // The weighted kernels' table: the same shapes, its own bounds.
 int trt_nee_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
     return trt::batch_launch_plan(s, n, compute_units, trt::kNeeMisLobeKernels, trt::kNeeShapes, out);
+}
+
+// ---- the PICK queries: the emitter of every vertex's shadow ray chosen by power (or the caller's weights) through an alias table ----
+// The device form checks the pointer only: the kernel's clamp keeps a wrong table's reads inside the E records.
+int trt_nee_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
+                        uint32_t n_emitters, const trt_nee_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
+    trt::NeeCall c;
+    int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    rc = trt::pick_pointer_check(n, d_pick);
+    if (rc != TRT_OK) return rc;
+    c.pick = true;
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_nee_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
+                 const trt_nee_params* p, float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::NeeCall c;
+        int rc = trt::nee_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        rc = trt::pick_pointer_check(n, pick);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_entries_check(pick, n_emitters);
+            if (rc != TRT_OK) return rc;
+        }
+        c.pick = true;
+        return trt::nee_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
+    });
+}
+
+// The PICK kernels' tables: the same shapes, their own bounds.
+int trt_nee_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kNeePickLobeKernels, trt::kNeeShapes, out);
+}
+
+// The device form can read neither table: both table rules are the caller's to keep.
+int trt_nee_mis_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
+                            uint32_t n_emitters, const trt_nee_mis_params* p, float total_power, float* d_radiance, float* d_moment2,
+                            uint64_t* d_counters, void* stream) {
+    trt::NeeCall c;
+    int rc = trt::nee_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    rc = trt::pick_pointer_check(n, d_pick);
+    if (rc != TRT_OK) return rc;
+    c.pick = true;
+    c.total_power = total_power;
+    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+}
+
+int trt_nee_mis_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
+                     const trt_nee_mis_params* p, float total_power, float* radiance, float* moment2, trt_stats* stats) {
+    return trt::host_form([&]() -> int {
+        trt::NeeCall c;
+        int rc = trt::nee_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        rc = trt::pick_pointer_check(n, pick);
+        if (rc != TRT_OK) return rc;
+        if (n > 0u) {
+            rc = trt::emitter_entries_check(emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_entries_check(pick, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
+            if (rc != TRT_OK) return rc;
+            rc = trt::pick_power_check(emitters, pick, n_emitters, total_power);
+            if (rc != TRT_OK) return rc;
+        }
+        c.pick = true;
+        c.total_power = total_power;
+        return trt::nee_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
+    });
+}
+
+int trt_nee_mis_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeMisPickLobeKernels, trt::kNeeShapes, out);
 }
 
 }  // extern "C"
