@@ -1289,6 +1289,15 @@ int trt_kernel_timing_end(double *total_ms, uint32_t *launches);
  * a kernel trace of the call shows, for profiles and benchmark records.  "" on invalid arguments. */
 const char *trt_dominant_kernel(const trt_scene *s, const trt_camera *cam, const trt_render_params *p);
 
+/* The lock-step kernel compiled per scene at run time (environment TRT_FLAT_LITERAL: 0 never, 1 at the first streamed render of a scene,
+ * unset: at the first render call of 2^26 samples or more): a scene of at most 32 primitives gets its own build of the streamed kernel
+ * with its leaf planes as literals in the instruction stream - the same frame, bit for bit, faster.  The compiler (hiprtc) is looked for
+ * at run time; if it is missing, or compiling or loading fails, the scene renders through the built-in kernel and no call fails.
+ * _compilations: compilations this process has started.  _diagnostic: why the last one that failed did, "" if none has (the string is
+ * the calling thread's until its next call). */
+uint64_t trt_flat_literal_compilations(void);
+const char *trt_flat_literal_diagnostic(void);
+
 /* ---- library ---- */
 const char *trt_last_error(void);
 int trt_device_count(void);               /* gfx950 devices visible; 0 without a GPU (never an error) */

@@ -385,6 +385,8 @@ SIGNATURES = {
     "trt_device_count": (C.c_int, []),
     "trt_set_device": (C.c_int, [C.c_int]),
     "trt_abi_version": (C.c_uint32, []),
+    "trt_flat_literal_compilations": (C.c_uint64, []),
+    "trt_flat_literal_diagnostic": (C.c_char_p, []),
 }
 
 

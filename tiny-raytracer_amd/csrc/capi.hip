@@ -119,6 +119,9 @@ struct Defaults {
     bool flat_reuse = true;                       // TRT_FLAT_REUSE=0: the lock-step leaf walk computes every leaf box in full (A/B runs, tests)
     bool axis_quads = true;                       // TRT_AXIS_QUADS=0: the lock-step kernel keeps the generic quad test on axis-exact scenes too (A/B runs, tests)
     bool nearest_first = true;                    // TRT_NEAREST_FIRST=0: the lock-step kernel keeps the walk-order leaf phase on all-axis-exact-quad scenes too (A/B runs, tests)
+    uint32_t flat_literal = 2;                    // TRT_FLAT_LITERAL: the lock-step kernel compiled per scene at run time (literal_kernel.h): 0 never, 1 at the first
+                                                  // streamed render of the scene, unset (2): at the first render call of kLiteralAutoSamples samples or more
+    bool flat_literal_test_fail = false;          // TRT_FLAT_LITERAL_TEST_FAIL=1: that compilation is handed an empty source (tests of the fallback)
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -143,6 +146,8 @@ const Defaults& defaults() {
         if (const char* e = env("TRT_FLAT_REUSE")) x.flat_reuse = atoi(e) != 0;
         if (const char* e = env("TRT_AXIS_QUADS")) x.axis_quads = atoi(e) != 0;
         if (const char* e = env("TRT_NEAREST_FIRST")) x.nearest_first = atoi(e) != 0;
+        if (const char* e = env("TRT_FLAT_LITERAL")) x.flat_literal = atoi(e) != 0 ? 1u : 0u;
+        if (const char* e = env("TRT_FLAT_LITERAL_TEST_FAIL")) x.flat_literal_test_fail = atoi(e) != 0;
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -295,6 +300,19 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
             s->cache.set_short_samples(dev, (rc == TRT_OK && samples < wanted) ? samples : 0u);
         }
         if (rc != TRT_OK) return rc;
+        // the scene's own kernel (literal_kernel.h): the streamed launcher finds this request for the length of its call
+        LiteralRequest lit;
+        const SceneLayout& L = s->host.layout;
+        if (streamed && defaults().flat_literal != 0u && L.flat_walk != 0u && L.n_leaves > 0u &&
+            s->host.blob.size() >= 16u * ((size_t)L.off_leaf_list + 2u * (size_t)L.n_leaves)) {
+            lit.slot = s->cache.literal_kernel(dev);
+            lit.leaf_list = s->host.blob.data() + 16u * (size_t)L.off_leaf_list;
+            lit.n_leaves = L.n_leaves;
+            const uint64_t call_samples = (uint64_t)cam->width * rows * (ra.sample_end - ra.sample_begin);
+            lit.wanted = defaults().flat_literal == 1u || call_samples >= kLiteralAutoSamples;
+            lit.empty_source = defaults().flat_literal_test_fail;
+        }
+        const LiteralScope lit_scope(lit.slot ? &lit : nullptr);
         hipError_t le;
         if (streamed && d_moment2) {
             le = launch_moments ? launch_moments(sc, cd, ra, tn, ws->ptr, ws->bytes, d_accum, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),

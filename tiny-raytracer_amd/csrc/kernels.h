@@ -94,6 +94,7 @@ inline uint32_t scene_lds_bytes(const SceneLayout& L) { return scene_mode(L) == 
 // Regions of LDS and of staged device buffers begin at multiples of 16 bytes.
 inline size_t q_align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 
+#ifndef __HIPCC_RTC__      // the launchers: host declarations (scene.h says what the run-time compiled unit takes)
 // Optional device timing of the dominant kernel (trt_kernel_timing_begin / _end, capi.hip): while enabled, a launcher
 // brackets every launch of its dominant kernel with timing_mark(stream, true) / timing_mark(stream, false), which record
 // HIP events on the launch stream.  No-ops while disabled.
@@ -115,7 +116,9 @@ size_t wavefront_workspace_bytes(uint32_t width, uint32_t rows);
 hipError_t launch_wavefront(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, float* d_accum,
                             unsigned long long* d_counters, bool stats, hipStream_t stream);
 
+#endif
 // Streamed backend (streamed.hip): samples are work items; radiances go to an HBM buffer and are folded in order.
+#ifndef __HIPCC_RTC__
 uint32_t streamed_chunk_spp(uint32_t width, uint32_t rows, uint32_t radiance_gb);   // samples per pixel per tracing / fold launch pair (bounds the radiance buffer)
 size_t streamed_workspace_bytes(uint32_t width, uint32_t rows, uint32_t samples, uint32_t radiance_gb);   // samples = sample_end - sample_begin of the render
 // Samples per pixel a workspace of `bytes` holds for this image (what launch_streamed may trace per launch with the scratch it was granted).
@@ -124,6 +127,7 @@ uint32_t streamed_chunk_that_fits(uint32_t width, uint32_t rows, size_t bytes);
 // what trt_streamed_launch_plan reports).  The kernel's view of its dynamic LDS - scene copy | leaf stack (threads x slots x 8 B) | ray
 // pool (36 B per lane) - is stream_plan.h LdsLayout and nothing else; launch_streamed refuses a plan whose parts do not add up
 // (hipErrorInvalidConfiguration).
+#endif
 struct StreamLaunchPlan {
     int mode, threads, waves_per_simd;      // scene mode, lanes per workgroup, waves per SIMD the grid is sized for
     uint32_t wg_per_cu, slots;              // resident workgroups per CU; postponed-leaf slots per lane
@@ -136,6 +140,7 @@ struct StreamLaunchPlan {
     bool kernel_pool, kernel_stats;
     const char* kernel_name;
 };
+#ifndef __HIPCC_RTC__
 // `workspace_bytes`: what the caller was granted (at least streamed_workspace_bytes for one sample): the launches are sized to it.
 hipError_t launch_streamed(const SceneDev& sc, const CameraDev& cam, const RenderArgs& ra, const trt_tuning& tn, void* workspace, size_t workspace_bytes,
                            float* d_accum, unsigned long long* d_counters, bool stats, hipStream_t stream);
@@ -154,5 +159,6 @@ hipError_t launch_tonemap_u8(const float* d_accum, unsigned long long npixels, f
 
 hipError_t launch_sample_batch(const SceneDev& sc, const trt_sample_point* d_in, uint32_t n, trt_sampled_color* d_out,
                                const RenderArgs& ra, unsigned long long* d_counters, bool stats, hipStream_t stream);
+#endif
 
 }  // namespace trt

@@ -664,6 +664,28 @@ TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restr
     return stk + ((top - stk_off) >> 3);
 }
 
+#ifdef TRT_FLAT_LITERAL_ASM
+// box_loop_flat for ONE scene, in the unit compiled at run time for it (streamed.hip): TRT_FLAT_LITERAL_ASM is the text flat_literal.h
+// writes for the scene's leaf list - the same box steps unrolled over the leaves, planes and links as literals, the reuse schedule and the
+// pair loop resolved when the text was written.  Same contract: `i` in and out (even, or n), the lane's new stack top returned.  The leaf
+// list and the schedule are in the text, so neither is an argument; s[36:38] serve the jump of an entry at i > 0.
+TRT_DEV float2* box_loop_flat_literal(const Trav& tr, const V3& o, uint32_t& i, float2* stk, float2* limit) {
+    const uint32_t stk_off = lds_offset(stk);
+    uint32_t top = stk_off;
+    const uint32_t lim = lds_offset(limit);
+    unsigned long long m;
+    float t0, t1, xe, xx, ye, yx, ze, zx, st, lk;
+    asm volatile(
+        TRT_FLAT_LITERAL_ASM
+        : [i] "+s"(i), [top] "+v"(top), [m] "=&s"(m), [t0] "=&v"(t0), [t1] "=&v"(t1), [xe] "=&v"(xe), [xx] "=&v"(xx),
+          [ye] "=&v"(ye), [yx] "=&v"(yx), [ze] "=&v"(ze), [zx] "=&v"(zx), [st] "=&v"(st), [lk] "=&v"(lk)
+        : [lim] "v"(lim), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(tr.inv.x), [iy] "v"(tr.inv.y),
+          [iz] "v"(tr.inv.z), [tb] "v"(tr.t_best), [tmin] "s"(kTMin)
+        : "vcc", "scc", "memory", "s36", "s37", "s38");
+    return stk + ((top - stk_off) >> 3);
+}
+#endif
+
 // One leaf box of walk_flat's C++ loop with box_loop_flat's interval reuse: the axes whose bit is clear in `fresh` are computed (min / max
 // of the two plane distances), the others are kept from the previous leaf; then slab_fast_entry's combination, operation for operation.
 struct FlatIntervals {
@@ -716,7 +738,11 @@ TRT_DEV void walk_flat(const SceneAcc<MODE>& sc, const float4* __restrict__ leaf
     if constexpr (kAsmBoxLoop && !STATS) {
         float2* const lim = stk + 64u * (slots - 2u);
         do {
+#ifdef TRT_FLAT_LITERAL_ASM
+            float2* const top = box_loop_flat_literal(tr, ray.o, i, stk, lim);
+#else
             float2* const top = box_loop_flat(tr, ray.o, leaf_list, i, n, stk, lim, reuse);
+#endif
             TRT_CLK(ctr, 1);
             phase(top);
             TRT_CLK(ctr, 2);

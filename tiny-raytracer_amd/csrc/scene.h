@@ -22,11 +22,17 @@
 
 #include <stdint.h>
 
+// __HIPCC_RTC__: the unit that streamed.hip compiles at run time (stream_pool.h) reads this header from an embedded copy, where there is
+// no standard library and no directory tree: it takes the device-side declarations alone.
+#ifndef __HIPCC_RTC__
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/tinyrt.h"
+#else
+#include "tinyrt.h"
+#endif
 
 namespace trt {
 
@@ -35,6 +41,7 @@ struct F4 { float x, y, z, w; };            // 16-byte plane element (float4 on 
 enum : uint32_t { PRIM_NONE = 0xFFFFFFFFu, PRIM_QUAD_BIT = 0x40000000u, PRIM_INDEX_MASK = 0x3FFFFFFFu,
                   NODE_INNER_BIT = 0x80000000u };         // node link: inner -> NODE_INNER_BIT | first child; leaf -> primitive ref
 
+#ifndef __HIPCC_RTC__
 struct Geometry {
     uint32_t kind;                           // 0 sphere, 1 quad
     uint32_t material;
@@ -46,6 +53,7 @@ struct World {
     std::vector<trt_material> materials;
     std::unordered_map<std::string, uint32_t> material_index;   // world.rs:12
 };
+#endif
 
 // Packed scene: one blob of 16-byte elements.  The first `hot_bytes` are everything a render
 // touches per ray and are what small scenes copy into LDS; the reference tree follows.
@@ -90,6 +98,7 @@ constexpr uint32_t kLdsSceneMaxBytes = 64u * 1024u;
 constexpr uint32_t kLeafListPad = 4;          // copies of the last leaf behind the leaf list (walk_flat reads ahead without clamping)
 constexpr uint32_t kFlatWalkMaxLeaves = 32;   // at most this many primitives: lock-step leaf list instead of the culling tree
 
+#ifndef __HIPCC_RTC__
 struct NodeDump {                            // pre-order inspection copy of one tree
     std::vector<float> bbox6;
     std::vector<int32_t> prim_geo;           // geometry insertion index or -1
@@ -125,5 +134,6 @@ void emitter_init_sphere(trt_emitter& out, trt_vec3 centre, float radius, trt_ve
 
 // Image finalisation (imager.rs:52-53; utils/image.rs:92-111)
 void tonemap_u8(const float* accum, uint32_t npixels, float gamma, uint8_t* rgb);
+#endif
 
 }  // namespace trt

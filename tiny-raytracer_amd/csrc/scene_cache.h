@@ -17,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "literal_kernel.h"
 #include "scene_query.h"
 
 namespace trt {
@@ -80,6 +81,7 @@ class SceneCache {
             }
             for (RenderCtx* c : dc.ctx) context_destroy(c);               // after the workspaces: their events were recorded on these streams
             for (Cached& u : dc.up) if (u.ptr) (void)hipFree(u.ptr);
+            dc.literal.release();                                         // the scene's own kernel (literal_kernel.h): no render is in flight any more
         }
     }
     // idle scratch (workspaces + context frames) kept per device: trt_scene_options.scratch_cap_bytes.  Set before the handle is shared.
@@ -305,6 +307,8 @@ class SceneCache {
     }
     uint32_t short_samples(int dev) { std::lock_guard<std::mutex> lock(mu_); return dev_[dev].short_samples; }
     void set_short_samples(int dev, uint32_t samples) { std::lock_guard<std::mutex> lock(mu_); dev_[dev].short_samples = samples; }
+    // The scene's run-time compiled kernel on `dev` (literal_kernel.h): compiled at most once per scene and device, it has its own lock.
+    LiteralKernel* literal_kernel(int dev) { std::lock_guard<std::mutex> lock(mu_); return &dev_[dev].literal; }      // (references into an unordered_map stay valid)
   private:
     struct Cached { void* ptr = nullptr; bool busy = false; };      // ptr: in HBM once uploaded; busy: a thread is uploading it
     struct DeviceCache {
@@ -312,6 +316,7 @@ class SceneCache {
         std::vector<Workspace*> ws;
         std::vector<RenderCtx*> ctx;
         uint32_t short_samples = 0;
+        LiteralKernel literal;
     };
     static bool ws_finished(Workspace* w) {                           // call with the lock held, entry not busy
         if (!w->recorded) return true;

@@ -20,12 +20,16 @@
 // two launches per chunk of samples (sized to a radiance buffer of at most 16 GB: streamed_chunk_spp) instead of one.  stream_sample_kernel keeps the
 // primary-ray stock of kernels.hip (items are taken ahead); stream_pool_kernel, used for small LDS scenes, generates the
 // primary rays of a whole wave at once into an LDS pool.
+#include <mutex>
 #include <string>
 
+#include "flat_literal_rtc.h"
 #include "host_stage.h"
 #include "kernels.h"
+#include "literal_kernel.h"
 #include "rt_path.h"
 #include "stream_plan.h"
+#include "stream_pool.h"
 #include "wave_run.h"
 
 namespace trt {
@@ -150,174 +154,6 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_sample_kernel(SceneDev s
     flush_counters<STATS>(counters, n_samples, n_rays, ctr);
 }
 
-
-// ------------------------------------------------------------------------------------------------------------------
-// Same kernel with the primary rays of a whole wave generated at once.  In the kernel above a lane keeps one primary
-// ray in stock (9 VGPRs) and the generation code runs whenever some lane is out of stock: 0.45 times per bounce
-// round with 30 % of the lanes busy.  Here an empty per-wave pool in LDS (64 entries x 36 bytes behind the leaf
-// stack) is refilled by ALL 64 lanes - the next 64 items of the batch, off-image ones dropped, entries compacted by
-// ballot rank - and lanes whose path ended take entries by rank: generation runs once per ~7 rounds with every lane
-// busy, and the stock registers are gone.  Which lane traces which sample changes; every sample's radiance does not
-// (RNG keyed by pixel and sample, radiance stored per sample, folded in order).  Used where the pool costs no resident
-// workgroup (small LDS scene copies, scenes in global memory).
-// ------------------------------------------------------------------------------------------------------------------
-// The streamed kernels' argument list as the kernel-argument segment lays it out (every argument at its natural alignment, in order).
-// stream_pool_kernel reads the arguments that only its refill branch needs - the camera, the band layout, the tile arithmetic: ~40 words,
-// used once per ~7 rounds - from that segment INSIDE the branch instead of taking them from the by-value parameters: those are loaded at
-// kernel entry and stay live in SGPRs over the whole round loop, where the walk pins s[36:51] besides, and the compiler moved the overflow
-// through a VGPR's lanes (v_writelane / v_readlane, a vector instruction each) on the path every round takes.  The empty asm makes the
-// pointer opaque, so the loads (scalar loads, wave-uniform) can neither be merged with the entry loads nor hoisted out of the branch.
-struct StreamKernargs {
-    SceneDev scd; CameraDev cam; RenderArgs ra;
-    float* colors; uint32_t* batch_counter; unsigned long long* counters;
-    uint32_t tiles_x, n_tiles, n_batches, batch_spp;
-    const float4* leaf_list; const uint4* nodes16;
-};
-struct StreamTileArgs { uint32_t tiles_x, n_tiles, n_batches, batch_spp; };
-template <class T>
-TRT_DEV T kernarg_reload(size_t offset) {
-    static_assert(sizeof(T) % 4 == 0, "whole words");
-    typedef const __attribute__((address_space(4))) uint32_t* WordPtr;
-    WordPtr w = (WordPtr)__builtin_amdgcn_kernarg_segment_ptr() + offset / 4;
-    asm volatile("" : "+s"(w));
-    uint32_t words[sizeof(T) / 4];
-#pragma unroll
-    for (uint32_t i = 0; i < sizeof(T) / 4; i++) words[i] = w[i];
-    T v;
-    __builtin_memcpy(&v, words, sizeof(T));
-    return v;
-}
-
-template <int MODE, bool STATS, int MINW = 1, int THREADS = 256, int WALK = WALK_RUNTIME, bool LAZY = false>
-__global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd, CameraDev cam_entry, RenderArgs ra,
-                                                                           float* __restrict__ colors_entry,
-                                                                           uint32_t* __restrict__ batch_counter_entry,
-                                                                           unsigned long long* __restrict__ counters,
-                                                                           uint32_t tiles_x_entry, uint32_t n_tiles_entry, uint32_t n_batches_entry, uint32_t batch_spp_entry,
-                                                                           const float4* __restrict__ leaf_list,
-                                                                           const uint4* __restrict__ nodes16) {
-    stage_scene_to_lds<MODE>(scd);
-    const FlatReuse flat_reuse = axis_quads_to_lds<MODE, STATS, WALK>(scd, ra.flat_reuse);      // axis-exact quads: the LDS copy's records rewritten (rt_path.h)
-    const SceneAcc<MODE> sc{scd.blob, scd.L};
-    const uint32_t lane = threadIdx.x & 63u;
-    const V3 background = v3(ra.background[0], ra.background[1], ra.background[2]);
-    char* const lds_tail = lds_behind_scene(sc);
-    float2* const leaf_stack = reinterpret_cast<float2*>(lds_tail) + (threadIdx.x >> 6) * (64u * ra.leaf_slots) + lane;
-    // the pool: field f of entry e at pool[f * 64 + e]; behind the leaf stack (stream_plan.h LdsLayout::stack_bytes, one stack)
-    uint32_t* const pool = reinterpret_cast<uint32_t*>(lds_tail + (size_t)THREADS * ra.leaf_slots * sizeof(float2)) + (threadIdx.x >> 6) * (64u * kPoolDwords);
-
-    uint32_t tile_x0 = 0, tile_row0 = 0, tile_slot0 = 0, ds0 = 0, items_per_batch = 0, cursor = 0;    // wave-uniform work cursor
-    uint32_t pool_head = 0, pool_count = 0;                                            // wave-uniform
-    bool exhausted = false;
-
-    Path p;
-    p.remain = 0u;
-    bool has_path = false;
-    uint32_t out_idx = 0;
-    uint32_t n_samples = 0, n_rays = 0;
-    Counters<STATS> ctr;
-    // resumable walks (rt_path.h walk_compact, walk_fast_lds): a round's walk phase ends once only a few lanes still walk; they carry
-    // their walk into the next round (100 k spheres: 324 trips per round for 222 box steps per ray, +10 %; random-spheres: see DESIGN 13)
-    constexpr bool kResumable = !STATS && (WALK == WALK_COMPACT || WALK == WALK_LDS_STACK);
-    bool walking = false;                                                         // this lane's walk is parked in its leaf stack (kResumable only)
-
-    TRT_CLK_START(ctr);
-    for (;;) {
-        // ---- lanes without a path take pool entries; an empty pool is refilled by the whole wave ----
-        for (;;) {
-            const uint64_t need = __builtin_amdgcn_ballot_w64(!has_path);
-            if (need == 0ull) break;
-            if (pool_count == 0u) {
-                if (exhausted) break;
-                // refill-only arguments, read here and not carried through the rounds (kernarg_reload above)
-                const CameraDev cam = kernarg_reload<CameraDev>(offsetof(StreamKernargs, cam));
-                const RenderArgs rr = kernarg_reload<RenderArgs>(offsetof(StreamKernargs, ra));
-                const StreamTileArgs ta = kernarg_reload<StreamTileArgs>(offsetof(StreamKernargs, tiles_x));
-                const uint32_t n_spp = rr.sample_end - rr.sample_begin;
-                if (cursor >= items_per_batch) {
-                    uint32_t* const batch_counter = kernarg_reload<uint32_t*>(offsetof(StreamKernargs, batch_counter));
-                    const uint32_t tiles_x = ta.tiles_x, n_tiles = ta.n_tiles, n_batches = ta.n_batches, batch_spp = ta.batch_spp;
-                    uint32_t b = 0;
-                    if (lane == 0u) b = atomicAdd(batch_counter, 1u);
-                    b = __builtin_amdgcn_readfirstlane(b);
-                    if (b >= n_batches) { exhausted = true; break; }
-                    const uint32_t tile = b % n_tiles;                                    // consecutive batches: neighbouring tiles, same samples
-                    ds0 = (b / n_tiles) * batch_spp;
-                    tile_x0 = (tile % tiles_x) * 8u;
-                    tile_row0 = (tile / tiles_x) * 8u;
-                    tile_slot0 = tile * n_spp * 64u;
-                    items_per_batch = 64u * (n_spp - ds0 < batch_spp ? n_spp - ds0 : batch_spp);
-                    cursor = 0;
-                }
-                // the next 64 items: one 8x8 tile at one sample index
-                const uint32_t item = cursor + lane;
-                cursor += 64u;
-                const uint32_t ds = ds0 + (item >> 6);
-                const uint32_t x = tile_x0 + (lane & 7u), row = tile_row0 + (lane >> 3);
-                const bool valid = x < cam.width && row < rr.rows_local;                  // off-image items of an edge tile are dropped
-                const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-                if (valid) {
-                    if constexpr (STATS) { if (first_active_lane()) ctr.w_gen++; }
-                    const uint32_t y = image_row(rr, row);
-                    Rng rng = rng_seed(rr.seed_key, y * cam.width + x, rr.sample_begin + ds);        // cpu.rs:42-45
-                    const Ray ray = primary_ray(cam, x, y, rng);
-                    const uint32_t e = wave_rank(vmask);
-                    pool[0u * 64u + e] = __float_as_uint(ray.o.x); pool[1u * 64u + e] = __float_as_uint(ray.o.y); pool[2u * 64u + e] = __float_as_uint(ray.o.z);
-                    pool[3u * 64u + e] = __float_as_uint(ray.d.x); pool[4u * 64u + e] = __float_as_uint(ray.d.y); pool[5u * 64u + e] = __float_as_uint(ray.d.z);
-                    pool[6u * 64u + e] = rng.s0; pool[7u * 64u + e] = rng.s1;
-                    pool[8u * 64u + e] = tile_slot0 + ds * 64u + lane;
-                }
-                pool_head = 0u;
-                pool_count = (uint32_t)__builtin_popcountll(vmask);
-                if (pool_count == 0u) continue;                                           // a tile row entirely off the image
-            }
-            const uint32_t rank = wave_rank(need);
-            if (!has_path && rank < pool_count) {
-                const uint32_t e = pool_head + rank;
-                p.ray.o = v3(__uint_as_float(pool[0u * 64u + e]), __uint_as_float(pool[1u * 64u + e]), __uint_as_float(pool[2u * 64u + e]));
-                p.ray.d = v3(__uint_as_float(pool[3u * 64u + e]), __uint_as_float(pool[4u * 64u + e]), __uint_as_float(pool[5u * 64u + e]));
-                p.rng.s0 = pool[6u * 64u + e]; p.rng.s1 = pool[7u * 64u + e];
-                out_idx = pool[8u * 64u + e];
-                p.color = v3(0.0f, 0.0f, 0.0f);
-                p.atten = v3(1.0f, 1.0f, 1.0f);
-                p.remain = ra.max_bounces;
-                has_path = true;
-                n_samples++;
-            }
-            const uint32_t wanted = (uint32_t)__builtin_popcountll(need);
-            const uint32_t taken = wanted < pool_count ? wanted : pool_count;
-            pool_head += taken;
-            pool_count -= taken;
-        }
-        if (__builtin_amdgcn_ballot_w64(has_path) == 0ull) break;                         // nothing left to trace: the batches are used up
-        TRT_CLK(ctr, 0);
-        if (has_path) {
-            if constexpr (STATS) { if (first_active_lane()) ctr.w_rounds++; }
-            if constexpr (kResumable) {
-                Trav tr = trav_begin<MODE, WALK == WALK_COMPACT>(sc, p.ray, false);                              // see stream_sample_kernel
-                if (walking) trav_unpark(leaf_stack, tr); else n_rays++;
-                const uint32_t entered = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
-                walking = !closest_hit_resume<MODE, STATS, WALK>(sc, p.ray, tr, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, ra.stragglers, entered);
-                if (!walking) {
-                    if (shade_hit<MODE, STATS, LAZY>(sc, p, tr.prim_best, tr.t_best, background, ctr)) {
-                        radiance_store(kernarg_reload<float*>(offsetof(StreamKernargs, colors)), out_idx, p.color);       // the pointer: as the refill arguments
-                        has_path = false;
-                    }
-                }
-            } else {
-                n_rays++;
-                float t;
-                const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, flat_reuse);
-                if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
-                    radiance_store(kernarg_reload<float*>(offsetof(StreamKernargs, colors)), out_idx, p.color);       // the pointer: as the refill arguments
-                    has_path = false;
-                }
-            }
-        }
-        TRT_CLK(ctr, 3);
-    }
-    flush_counters<STATS>(counters, n_samples, n_rays, ctr);
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // The pool kernel for scenes in global memory with TWO paths per lane (rt_path.h walk_compact2): slot A and slot B of a lane are two
@@ -576,6 +412,82 @@ const void* const kStreamKernelFns[] = {
 #undef TRT_FN_DUAL
 static_assert(sizeof(kStreamKernelFns) / sizeof(kStreamKernelFns[0]) == kStreamKernelCount, "one address per shape row");
 
+// ---- the scene's own kernel (flat_literal.h, literal_kernel.h) ----
+// Compilations started (each scene and device: at most one), and why the last one that failed did: a diagnostic, never an error of a
+// render - the scene then runs the kernel built ahead of time, which computes the same frame.
+std::mutex g_literal_mu;
+unsigned long long g_literal_compilations = 0;
+std::string g_literal_diagnostic;
+thread_local std::string t_literal_diagnostic_copy;
+
+void literal_unload(void* module) {
+    (void)hipModuleUnload(static_cast<hipModule_t>(module));
+    (void)hipGetLastError();
+}
+
+// Compiles and loads `slot`'s kernel for the current device (called by the one thread that moved the slot to COMPILING).
+bool literal_build(LiteralKernel& slot, const LiteralRequest& rq, const FlatReuse& reuse, int minw, std::string& why) {
+    {
+        std::lock_guard<std::mutex> lock(g_literal_mu);
+        g_literal_compilations++;
+    }
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); why = "no device properties"; return false; }
+    std::string arch(prop.gcnArchName);
+    arch = arch.substr(0, arch.find(':'));                                          // "gfx950:sramecc+:xnack-" -> "gfx950"
+    const uint32_t masks[3] = {reuse.x, reuse.y, reuse.z};
+    std::string text, source;
+    if (!rq.empty_source) {
+        if (!flat_literal_asm(rq.leaf_list, rq.n_leaves, masks, text)) { why = "leaf list refused"; return false; }
+        source = flat_literal_source(text);
+    }
+    FlatLiteralBuild built;
+    if (!flat_literal_compile(source, minw, arch.c_str(), reinterpret_cast<const void*>(&hipModuleLoadData), built)) { why = "hiprtc: " + built.log; return false; }
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    hipError_t e = hipModuleLoadData(&mod, built.code.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&fn, mod, built.kernel.c_str());
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (mod) (void)hipModuleUnload(mod);
+        why = std::string("module load: ") + hipGetErrorString(e);
+        return false;
+    }
+    slot.module = mod; slot.function = fn; slot.minw = minw; slot.unload = &literal_unload;
+    return true;
+}
+
+// The kernel of this render's scene for the plan `pl`, or null: the kernel built ahead of time runs.  Only the production launch takes it -
+// no counters, the lock-step walk on an LDS scene, the plan's own specialised pool instantiation, dynamic LDS within the default limit.
+hipFunction_t literal_kernel_for(const StreamLaunchPlan& pl, const RenderArgs& ra, bool stats) {
+    const LiteralRequest* rq = t_literal_request;
+#ifdef TRT_PHASE_CLOCK
+    return nullptr;                          // the diagnostic build measures the kernels built with its clock
+#endif
+    if (!kAsmBoxLoop) return nullptr;        // the C++-loops build (TRT_ASM_BOX_LOOP=0) exists to run the C++ loops
+    if (!rq || !rq->slot || stats || !pl.specialised || !pl.pool || pl.dual || pl.walk != WALK_FLAT || pl.mode != MODE_LDS || ra.ref_tree ||
+        pl.kernel_walk != WALK_FLAT || pl.threads != 256 || pl.lds_bytes > 48u * 1024u || rq->n_leaves > kFlatLiteralMaxLeaves) return nullptr;
+    LiteralKernel& slot = *rq->slot;
+    std::unique_lock<std::mutex> lock(slot.mu);
+    while (slot.state == LiteralKernel::COMPILING) slot.cv.wait(lock);
+    if (slot.state == LiteralKernel::UNTRIED && rq->wanted) {
+        slot.state = LiteralKernel::COMPILING;
+        lock.unlock();
+        std::string why;
+        const bool ok = literal_build(slot, *rq, ra.flat_reuse, pl.kernel_minw, why);
+        if (!ok) {
+            std::lock_guard<std::mutex> g(g_literal_mu);
+            g_literal_diagnostic = "lock-step kernel not compiled for its scene, the built-in kernel runs: " + why;
+        }
+        lock.lock();
+        slot.state = ok ? LiteralKernel::READY : LiteralKernel::FAILED;
+        slot.cv.notify_all();
+    }
+    if (slot.state != LiteralKernel::READY || slot.minw != pl.kernel_minw) return nullptr;
+    return static_cast<hipFunction_t>(slot.function);
+}
+
 }  // namespace
 
 // d_moment2 == nullptr: the frame only.
@@ -600,6 +512,8 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
     const StreamLaunchPlan pl = streamed_launch_plan(sc.L, ra_all, tn, stats);
     if (pl.kernel_index < 0 || (size_t)pl.kernel_index >= kStreamKernelCount) return hipErrorInvalidDeviceFunction;      // no instantiation for this plan: a bug, never a fallback
     const void* const kernel = kStreamKernelFns[pl.kernel_index];
+    // the same instantiation compiled for this scene, if the scene has one or is due one now (module API; the same arguments)
+    const hipFunction_t literal = literal_kernel_for(pl, ra_all, stats);
     // the kernel's assumptions about its dynamic LDS, checked where the launch is made (scene copy | leaf stack | ray pool)
     const LdsLayout lds = plan_lds_layout(pl);
     if (lds.total() != pl.lds_bytes || !lds.fits(1u) || pl.kernel_threads != pl.threads || (pl.pool && !pl.lds_stack) ||
@@ -635,7 +549,8 @@ static hipError_t launch_streamed_folds(const SceneDev& sc, const CameraDev& cam
         if (e != hipSuccess) return e;
         void* args[] = {&scd, &camd, &ra, &colors, &batch_counter, &d_counters, &tiles_x, &n_tiles, &n_batches, &batch_spp, &leaf_list, &nodes16};
         timing_mark(stream, true);
-        e = hipLaunchKernel(kernel, dim3(grid_x), dim3((uint32_t)pl.threads), args, pl.lds_bytes, stream);
+        if (literal) e = hipModuleLaunchKernel(literal, grid_x, 1u, 1u, (uint32_t)pl.threads, 1u, 1u, (uint32_t)pl.lds_bytes, stream, args, nullptr);
+        else e = hipLaunchKernel(kernel, dim3(grid_x), dim3((uint32_t)pl.threads), args, pl.lds_bytes, stream);
         timing_mark(stream, false);
         if (e != hipSuccess) return e;
         const uint32_t fold_blocks = (n_tiles + 3u) / 4u;                           // four tiles (waves) per workgroup
@@ -688,6 +603,19 @@ int trt_variance_device(const float* d_accum, const float* d_moment2, uint32_t n
     const hipError_t e = trt::launch_variance(d_accum, d_moment2, npixels, samples_per_pixel, d_variance, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return trt::query_fail_hip(e, "variance launch");
     return TRT_OK;
+}
+
+// Diagnostics of the scenes' own kernels (literal_kernel.h; TRT_FLAT_LITERAL): how many compilations this process has started, and why the
+// last one that failed did ("" if none has; the string is the calling thread's until its next call).  A failed compilation is never an
+// error of a render.
+uint64_t trt_flat_literal_compilations(void) {
+    std::lock_guard<std::mutex> lock(trt::g_literal_mu);
+    return trt::g_literal_compilations;
+}
+const char* trt_flat_literal_diagnostic(void) {
+    std::lock_guard<std::mutex> lock(trt::g_literal_mu);
+    trt::t_literal_diagnostic_copy = trt::g_literal_diagnostic;
+    return trt::t_literal_diagnostic_copy.c_str();
 }
 
 // Host form: device copies of the call's own, the same kernel, complete when the call returns.  There is no CPU path.
