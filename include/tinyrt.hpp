@@ -147,10 +147,9 @@ public:
     // p.path.accumulate is set.  Start `p` from trt_direct_params_default.
     void direct(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_direct_params& p, std::vector<float>& radiance,
                 std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_direct(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
-                         moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, nullptr, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_direct(q.scene, q.items, q.n, q.table, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // direct() with multiple importance sampling (trt_direct_mis): every sample also sends one cosine-lobe ray from the surfel, and a light
     // of the scene counts both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the lobe ray's hit on a light by the
@@ -159,10 +158,9 @@ public:
     // virtual ones; anything else is an error.  Start `p` from trt_direct_mis_params_default.
     void direct_mis(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_direct_mis_params& p,
                     std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_direct_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
-                             moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, nullptr, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_direct_mis(q.scene, q.items, q.n, q.table, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // The alias table over `table` (trt_emitter_pick_build) through which direct_pick() and direct_mis_pick() choose their emitter: by
     // power (weights == nullptr; the table direct_mis_pick() needs) or by `weights`, table.size() finite non-negative values.  `total`
@@ -176,22 +174,18 @@ public:
     // far less noise where the emitters' powers differ much.
     void direct_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
                      const trt_direct_params& p, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_direct_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
-                              radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, &pick, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_direct_pick(q.scene, q.items, q.n, q.table, q.pick, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // direct_mis() with the emitter chosen through `pick` (trt_direct_mis_pick): `pick` must be pick_table(table) - the power table -
     // and `total_power` the total it reported; the lobe ray's hit on a light is weighted by the same probability.
     void direct_mis_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
                          const trt_direct_mis_params& p, float total_power, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr,
                          trt_stats* stats = nullptr) {
-        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_direct_mis_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
-                                  total_power, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, &pick, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_direct_mis_pick(q.scene, q.items, q.n, q.table, q.pick, q.n_emitters, &p, total_power, q.radiance, q.moment2, stats);
+        });
     }
     // What radiance() / gather() estimate, with the lights aimed at (trt_nee): the path of every sample is theirs bit for bit (p.gather:
     // path, source - TRT_PASSES_RAYS, _COSINE, _CONE - and spread), at every Lambertian hit that leaves bounce budget one shadow ray goes
@@ -201,10 +195,9 @@ public:
     // trt_nee_params_default.
     void nee(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_nee_params& p, std::vector<float>& radiance,
              std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_nee(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
-                      moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, nullptr, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_nee(q.scene, q.items, q.n, q.table, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // nee() with multiple importance sampling (trt_nee_mis): the same paths and shadow rays, but a light reached after a diffuse scatter
     // (from the second hit on) counts both ways, the shadow sample scaled by 1 / (1 + q(p_bsdf / p_light)) and the hit by the complement,
@@ -213,31 +206,26 @@ public:
     // `p` from trt_nee_mis_params_default.
     void nee_mis(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const trt_nee_mis_params& p, std::vector<float>& radiance,
                  std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_nee_mis(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), (uint32_t)table.size(), &p, radiance.data(),
-                          moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, nullptr, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_nee_mis(q.scene, q.items, q.n, q.table, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // nee() with the emitter of every vertex's shadow ray chosen through `pick` (trt_nee_pick; pick_table() above) - by power, not
     // uniformly: one draw more per vertex, far less noise where the emitters' powers differ much.
     void nee_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
                   const trt_nee_params& p, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr, trt_stats* stats = nullptr) {
-        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_nee_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
-                           radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, &pick, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_nee_pick(q.scene, q.items, q.n, q.table, q.pick, q.n_emitters, &p, q.radiance, q.moment2, stats);
+        });
     }
     // nee_mis() with the emitter chosen through `pick` (trt_nee_mis_pick): `pick` must be pick_table(table) - the power table - and
     // `total_power` the total it reported; a light reached after a diffuse scatter is weighted by the same probability.
     void nee_mis_pick(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>& pick,
                       const trt_nee_mis_params& p, float total_power, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr,
                       trt_stats* stats = nullptr) {
-        if (pick.size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
-        radiance.resize(items.size() * 3);
-        if (moment2) moment2->resize(items.size() * 3);
-        check(trt_nee_mis_pick(get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick.data(), (uint32_t)table.size(), &p,
-                               total_power, radiance.data(), moment2 ? moment2->data() : nullptr, stats));
+        emitter_query(items, table, &pick, radiance, moment2, [&](const EmitterQuery& q) {
+            return trt_nee_mis_pick(q.scene, q.items, q.n, q.table, q.pick, q.n_emitters, &p, total_power, q.radiance, q.moment2, stats);
+        });
     }
     // The radiance arriving at caller-supplied points as a function of direction (trt_probe): for each of p.path.samples_per_ray samples
     // the device draws a first ray uniformly over the sphere, or over the hemisphere about the item's axis (p.domain), traces it as
@@ -266,6 +254,26 @@ public:
 
 private:
     void invalidate() { if (scene_) { trt_scene_destroy(scene_); scene_ = nullptr; } }
+    // What the eight direct*() / nee*() queries share: the pick table's size, the sizes of the sums, the call and its error.  `call` is the
+    // C entry point with the query's own parameters bound, handed the buffers as EmitterQuery holds them.
+    struct EmitterQuery {
+        trt_scene* scene;
+        const trt_ray* items;
+        uint32_t n;
+        const trt_emitter* table;
+        const trt_emitter_pick* pick;    // nullptr: no pick table
+        uint32_t n_emitters;
+        float *radiance, *moment2;
+    };
+    template <class Call>
+    void emitter_query(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& table, const std::vector<trt_emitter_pick>* pick,
+                       std::vector<float>& radiance, std::vector<float>* moment2, Call&& call) {
+        if (pick && pick->size() != table.size()) throw Error(TRT_ERR_INVALID_ARG, "the pick table needs one record per emitter");
+        radiance.resize(items.size() * 3);
+        if (moment2) moment2->resize(items.size() * 3);
+        check(call(EmitterQuery{get_bvh(), items.data(), (uint32_t)items.size(), table.data(), pick ? pick->data() : nullptr, (uint32_t)table.size(),
+                                radiance.data(), moment2 ? moment2->data() : nullptr}));
+    }
     trt_world* w_ = nullptr;
     trt_scene* scene_ = nullptr;
     trt_scene_options options_{};

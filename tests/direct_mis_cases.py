@@ -31,7 +31,7 @@ BALANCE, POWER = NM.BALANCE, NM.POWER
 HEURISTICS = NM.HEURISTICS
 LOBE_WORD = 0xFFFFFFFF                                                      # the stream word of the lobe ray
 ORC_LAMBERTIAN, ORC_LIGHT = 0, 3                                            # rt_oracle.h
-# (case, the scene of walk_ray_cases.scene it is made from, scene options): one per kernel shape of direct.hip kDirectMisKernels
+# (case, the scene of walk_ray_cases.scene it is made from, scene options): one per kernel shape of direct.hip kDirectKernels[pick][mis], the weighted tables
 CASES = (("cornell", "cornell", {}), ("prims33", "prims33", {}), ("random_spheres_lit", "random_spheres", {}), ("prims600", "prims600", {}),
          ("grid3000_lit", "grid3000", {}), ("grid3000_lit", "grid3000", dict(compact_nodes=0)))
 SCENES = ("cornell", "prims33", "random_spheres_lit", "prims600", "grid3000_lit")

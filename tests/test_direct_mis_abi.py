@@ -20,7 +20,7 @@ NAMES = {"trt_direct_mis_params_default": (None, 1), "trt_direct_mis": (C.c_int,
          "trt_direct_mis_launch_plan": (C.c_int, 4)}
 N = A.N
 _invalid = A._invalid
-# direct.hip kDirectMisKernels (profiles/direct_mis_resource_usage.txt): (scene mode, walk, threads) -> launch bound
+# direct.hip kDirectKernels[pick][mis], the weighted tables (profiles/direct_mis_resource_usage.txt): (scene mode, walk, threads) -> launch bound
 BOUNDS = {(1, 2, 256): 5, (1, 1, 256): 7, (1, 1, 768): 7, (1, 5, 512): 5, (0, 3, 256): 7, (0, 5, 256): 5}
 
 

@@ -265,3 +265,94 @@ def test_the_plan_symbols(trt):
                 assert G.plan_shape(q) == shape
         shapes.add(shape[:3])
     assert len(shapes) == 6
+
+
+# ---- the order of the checks, pair by pair: one call breaks two adjacent rules of the documented list, the earlier one is reported ----
+def _entry_call(trt, family, mis, pick, device, c):
+    """One call of trt_<family>[_mis][_pick][_device] with the arguments of `c` (a dict; tables are numpy arrays or None)."""
+    fn = getattr(trt.lib, "trt_" + family + ("_mis" if mis else "") + ("_pick" if pick else "") + ("_device" if device else ""))
+    ptr = lambda a: None if a is None else a.ctypes.data
+    args = [c["s"], ptr(c["items"]), c["n"], ptr(c["table"])] + ([ptr(c["pick"])] if pick else []) + [c["E"], C.byref(c["p"]) if c["p"] is not None else None]
+    args += ([C.c_float(c["total"])] if mis and pick else []) + [ptr(c["rad"]), ptr(c["m2"])] + ([None, None] if device else [None])
+    return fn(*args)
+
+
+def _set(key, value):
+    return lambda c: c.__setitem__(key, value)
+
+
+def _record(which, field, at, value):
+    """Breaks one word of one record of the emitter table or of the pick table (the caller's copy)."""
+    def fault(c):
+        c[which] = c[which].copy()
+        c[which][field][at] = value
+    return fault
+
+
+def _ladder_faults(mis, pick, device, table_rule_first, E):
+    """What follows the family's own parameter checks, in tinyrt.h's order: the pick pointer (both forms), then - host form only - the
+    emitter records, the pick records and the weighted queries' table rule (trt_direct_mis_pick: before the pick records;
+    trt_nee_mis_pick: behind them), total_power and prob."""
+    out = [("null argument", _set("pick", None))] if pick else []
+    if device:
+        return out
+    out += [("emitter kind", _record("table", "kind", 0, 2)), ("reserved words of an emitter", _record("table", "reserved", (0, 0), 1))]
+    rule = [("lights", _record("table", "geometry", 0, 3))] if mis else []          # geometry 3 of the box is its floor: no light
+    records = [("q must", _record("pick", "q", 0, 2.0)), ("alias must", _record("pick", "alias", 0, E)), ("prob must", _record("pick", "prob", 0, 2.0)),
+               ("reserved words must be zero", _record("pick", "reserved", 0, 1)), ("prob 0", _record("pick", "prob", 1, 0.0))] if pick else []
+    out += rule + records if table_rule_first else records + rule
+    if mis and pick:
+        def off_by_an_ulp(c):
+            c["pick"] = c["pick"].copy()
+            c["pick"]["prob"][1] = np.nextafter(c["pick"]["prob"][1], np.float32(1.0))
+        out += [("total_power must", _set("total", float("nan"))), ("power / total_power", off_by_an_ulp)]
+    return out
+
+
+def _walk_adjacent_pairs(trt, faults, fresh, call, impossible=()):
+    """Every fault alone is reported under its own words; every two neighbours together under the earlier one's."""
+    for k, (word, fault) in enumerate(faults):
+        c = fresh()
+        fault(c)
+        _invalid(trt, call(c), word)
+        if k + 1 < len(faults) and (word, faults[k + 1][0]) not in impossible:
+            faults[k + 1][1](c)
+            _invalid(trt, call(c), word)
+
+
+def _pair_fixture(trt, sc, params):
+    items = np.zeros((N, 6), np.float32)
+    items[:, 4] = 1.0
+    table = _table(trt, sc)
+    pick, total = trt.lights.pick_table(table)
+    assert len(table) == 2 and pick["q"][1] > 0.0
+    return lambda: dict(s=sc._h, items=items, n=N, table=table, pick=pick, E=len(table), p=params(), total=float(total), rad=np.full((N, 3), 7.0, np.float32),
+                        m2=np.full((N, 3), 7.0, np.float32))
+
+
+@pytest.mark.parametrize("device", (False, True))
+@pytest.mark.parametrize("pick", (False, True))
+@pytest.mark.parametrize("mis", (False, True))
+def test_adjacent_checks_are_reported_in_the_documented_order(trt, mis, pick, device):
+    """trt_direct, trt_direct_mis, trt_direct_pick, trt_direct_mis_pick and their device forms: the whole documented list of each, walked
+    pair by pair.  Among them: a table that breaks the table rule and holds a bad pick record gives trt_direct_mis_pick the table-rule
+    message (trt_nee_mis_pick reports the record: tests/test_nee_pick_abi.py)."""
+    sc = A._scene(trt)
+    fresh = _pair_fixture(trt, sc, (lambda: AM._params(trt)) if mis else (lambda: A._params(trt)))
+    own = (lambda c: c["p"].direct) if mis else (lambda c: c["p"])
+
+    def path(field, value):
+        return lambda c: setattr(own(c).path, field, value)
+
+    def word(of, k):
+        return lambda c: of(c).reserved.__setitem__(k, 1)
+
+    faults = [("null argument", _set("p", None)), ("null argument", _set("s", None)), ("null buffer", _set("items", None)), ("null buffer", _set("rad", None)),
+              ("samples_per_ray must", path("samples_per_ray", 0)), ("sample range", path("sample_begin", 5)),
+              ("reserved words must be zero", word(lambda c: own(c).path, 3)), ("2^32", path("first_stream", 2 ** 32 - N * 4 + 1)),
+              ("null emitter table", _set("table", None)), ("n_emitters must", _set("E", 0)),
+              ("shadow_end must", lambda c: setattr(own(c), "shadow_end", float("nan"))), ("reserved words must be zero", word(own, 6))]
+    if mis:
+        faults += [("heuristic must", lambda c: setattr(c["p"], "heuristic", 2)), ("reserved words must be zero", word(lambda c: c["p"], 6))]
+    faults += _ladder_faults(mis, pick, device, True, 2)
+    _walk_adjacent_pairs(trt, faults, fresh, lambda c: _entry_call(trt, "direct", mis, pick, device, c))

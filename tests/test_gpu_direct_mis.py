@@ -5,7 +5,7 @@ The reference is tests/direct_mis_cases.py: direct_cases' shadow sample with the
 (seed, j, 0xFFFFFFFF) whose hit on a light counts with wb.  Items, streams and table are tests/test_gpu_direct.py's: 324 surfels per scene
 (a full run of 256 and a ragged one of 68, with the NaN, zero, inf and 1e-9 items), K = 8, seed 5, first_stream 1000, the scene's own
 emitters followed by a virtual quad and a virtual sphere.  One scene per kernel shape, with the shape and launch bound that
-Scene.direct_plan(n, mis=...) reports asserted, so all six instantiations of direct.hip kDirectMisKernels run; random_spheres and grid3000
+Scene.direct_plan(n, mis=...) reports asserted, so all six instantiations of direct.hip kDirectKernels[pick][mis], the weighted tables run; random_spheres and grid3000
 are the variants with lights of direct_mis_cases.with_lights.  BALANCE on all six, POWER on the two whose fixtures hold the most weighted
 terms (tests/README_direct_mis.md).  tests/test_direct_mis_cases.py asserts without a GPU that this reference is not vacuous."""
 import numpy as np
@@ -21,7 +21,7 @@ K, SEED, FIRST = M.K, M.SEED, M.FIRST_STREAM
 N = M.N_ITEMS
 GUARD = 64                                                                  # entries on either side of a device buffer
 FILL = 0xCD
-# direct.hip kDirectMisKernels: (scene mode, walk, threads) -> launch bound (profiles/direct_mis_resource_usage.txt)
+# direct.hip kDirectKernels[pick][mis], the weighted tables: (scene mode, walk, threads) -> launch bound (profiles/direct_mis_resource_usage.txt)
 BOUNDS = {(1, 2, 256): 5, (1, 1, 256): 7, (1, 1, 768): 7, (1, 5, 512): 5, (0, 3, 256): 7, (0, 5, 256): 5}
 KW = dict(samples_per_item=K, seed=SEED, first_stream=FIRST)
 

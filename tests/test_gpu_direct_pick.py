@@ -23,7 +23,7 @@ N = 257
 CUT = 65
 GUARD = 64                                                                  # entries on either side of a device buffer
 FILL = 0xCD
-# direct.hip kDirectPickKernels / kDirectMisPickKernels: (scene mode, walk, threads) -> launch bound (profiles/direct_pick_resource_usage.txt)
+# direct.hip kDirectKernels[pick][mis], the PICK tables: (scene mode, walk, threads) -> launch bound (profiles/direct_pick_resource_usage.txt)
 BOUNDS = {None: {(1, 2, 256): 7, (1, 1, 256): 8, (1, 1, 768): 8, (1, 5, 512): 7, (0, 3, 256): 7, (0, 5, 256): 6},
           "mis": {(1, 2, 256): 5, (1, 1, 256): 7, (1, 1, 768): 7, (1, 5, 512): 5, (0, 3, 256): 7, (0, 5, 256): 5}}
 KW = dict(samples_per_item=K, seed=SEED, first_stream=FIRST)

@@ -22,7 +22,7 @@ N = M.N_ITEMS
 GUARD = 64                                                                  # entries on either side of a device buffer
 FILL = 0xCD
 SOURCES = M.SOURCES
-# nee.hip kNeeMisRayKernels / kNeeMisLobeKernels: (scene mode, walk, threads) -> launch bound (profiles/nee_mis_resource_usage.txt)
+# nee.hip kNeeKernels[pick][mis][source], the weighted tables: (scene mode, walk, threads) -> launch bound (profiles/nee_mis_resource_usage.txt)
 BOUNDS = {(1, 2, 256): 5, (1, 1, 256): 5, (1, 1, 768): 5, (1, 5, 512): 5, (0, 3, 256): 5, (0, 5, 256): 5}
 
 

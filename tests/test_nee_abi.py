@@ -281,7 +281,7 @@ RAY_COUNTS = (1, 64, 257, 324, 100003, 2 ** 32 - 1)                          # t
 # of a batch too long for 256 items per wave
 FROM_THE_BOUND = ("kernel_waves_per_simd", "workgroups_per_cu", "wave_slots")
 FROM_THE_SLOTS = ("rays_per_wave", "waves", "workgroups")
-# nee.hip kNeeRayKernels / kNeeLobeKernels (profiles/nee_resource_usage.txt): (scene mode, walk, threads) -> launch bound
+# nee.hip kNeeKernels[pick][mis][source], the plain tables (profiles/nee_resource_usage.txt): (scene mode, walk, threads) -> launch bound
 BOUNDS = {(1, 2, 256): 5, (1, 1, 256): 6, (1, 1, 768): 6, (1, 5, 512): 5, (0, 3, 256): 5, (0, 5, 256): 5}
 
 

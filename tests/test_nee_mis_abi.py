@@ -263,7 +263,7 @@ def test_the_plan_symbol_checks_its_arguments(trt):
     assert sc.nee_plan(1, 304, mis="power")["compute_units"] == 304
 
 
-# nee.hip kNeeMisRayKernels / kNeeMisLobeKernels (profiles/nee_mis_resource_usage.txt): (scene mode, walk, threads) -> launch bound
+# nee.hip kNeeKernels[pick][mis][source], the weighted tables (profiles/nee_mis_resource_usage.txt): (scene mode, walk, threads) -> launch bound
 BOUNDS = {(1, 2, 256): 5, (1, 1, 256): 5, (1, 1, 768): 5, (1, 5, 512): 5, (0, 3, 256): 5, (0, 5, 256): 5}
 
 

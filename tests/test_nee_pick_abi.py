@@ -239,3 +239,38 @@ def test_the_plan_symbols(trt):
                 assert G.plan_shape(q) == shape
         shapes.add(shape[:3])
     assert len(shapes) == 6
+
+
+@pytest.mark.parametrize("device", (False, True))
+@pytest.mark.parametrize("pick", (False, True))
+@pytest.mark.parametrize("mis", (False, True))
+def test_adjacent_checks_are_reported_in_the_documented_order(trt, mis, pick, device):
+    """trt_nee, trt_nee_mis, trt_nee_pick, trt_nee_mis_pick and their device forms: the whole documented list of each, walked pair by
+    pair (tests/test_direct_pick_abi.py has the walk).  Among them: a table that breaks the table rule and holds a bad pick record gives
+    trt_nee_mis_pick the pick-record message, where trt_direct_mis_pick reports the table rule."""
+    import test_direct_pick_abi as DP
+    sc = A._scene(trt)
+    fresh = DP._pair_fixture(trt, sc, (lambda: AM._params(trt)) if mis else (lambda: A._params(trt)))
+    own = (lambda c: c["p"].nee) if mis else (lambda c: c["p"])
+
+    def path(field, value):
+        return lambda c: setattr(own(c).gather.path, field, value)
+
+    def word(of, k):
+        return lambda c: of(c).reserved.__setitem__(k, 1)
+
+    def cone_spread(c):
+        own(c).gather.lobe, own(c).gather.spread = trt._lib.PASSES_CONE, -1.0
+
+    faults = [("null argument", DP._set("p", None)), ("null argument", DP._set("s", None)), ("null buffer", DP._set("items", None)),
+              ("null buffer", DP._set("rad", None)), ("samples_per_ray must", path("samples_per_ray", 0)), ("sample range", path("sample_begin", 5)),
+              ("reserved words must be zero", word(lambda c: own(c).gather.path, 3)), ("2^32", path("first_stream", 2 ** 32 - N * 4 + 1)),
+              ("source must", lambda c: setattr(own(c).gather, "lobe", 3)), ("spread", cone_spread),
+              ("reserved words must be zero", word(lambda c: own(c).gather, 3)), ("null emitter table", DP._set("table", None)),
+              ("n_emitters must", DP._set("E", 0)), ("shadow_end must", lambda c: setattr(own(c), "shadow_end", float("nan"))),
+              ("source_is_diffuse must", lambda c: setattr(own(c), "source_is_diffuse", 2)), ("reserved words must be zero", word(own, 3))]
+    if mis:
+        faults += [("heuristic must", lambda c: setattr(c["p"], "heuristic", 2)), ("reserved words must be zero", word(lambda c: c["p"], 6))]
+    faults += DP._ladder_faults(mis, pick, device, False, 2)
+    # the spread is only read of a cone: a source that is none cannot also have a bad spread
+    DP._walk_adjacent_pairs(trt, faults, fresh, lambda c: DP._entry_call(trt, "nee", mis, pick, device, c), impossible={("source must", "spread")})

@@ -373,12 +373,7 @@ class Scene:
         path.sample_begin, path.sample_end, path.accumulate = int(sample_begin), int(sample_end), 1 if accumulate else 0
         if shadow_end is not None:
             p.shadow_end = float(shadow_end)
-        if mis is None:
-            return p
-        m = _lib.DirectMisParams()
-        lib.trt_direct_mis_params_default(C.byref(m))
-        m.direct, m.heuristic = p, Scene.MIS[mis]
-        return m
+        return Scene._with_mis("direct", p, mis)
 
     @staticmethod
     def _emitter_table(emitters):
@@ -415,32 +410,8 @@ class Scene:
         table, by power or by the weights the table was built from, not uniformly - one draw more per sample, far less noise where the
         emitters' powers differ much.  The records alone will do without mis; with mis the (records, total) pair is needed and the table
         must be the power table (weights=None).  pick=None: the calls and bytes of before."""
-        r, _ = _rays_and_t_max(items, None)
-        n = len(r)
-        e = self._emitter_table(emitters)
-        p = self._direct_params(samples_per_item, shadow_end, seed, first_stream, sample_begin, sample_end, accumulate, mis)
-        if radiance is None:
-            radiance = np.zeros((n, 3), np.float32)
-        if moment2 is True:
-            moment2 = np.zeros((n, 3), np.float32)
-        for a in (radiance, moment2):
-            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
-        st = Stats()
-        out = (radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st))
-        if pick is None:
-            fn = lib.trt_direct if mis is None else lib.trt_direct_mis
-            check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p), *out))
-            return radiance, moment2, st.as_dict()
-        pick, total = self._pick_and_total(pick, mis)
-        k = np.ascontiguousarray(pick)
-        if k.dtype != PICK_DTYPE or k.shape != (len(e),):
-            raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
-        head = (self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, k.ctypes.data if len(k) else None, len(e), C.byref(p))
-        if mis is None:
-            check(lib.trt_direct_pick(*head, *out))
-        else:
-            check(lib.trt_direct_mis_pick(*head, C.c_float(total), *out))
-        return radiance, moment2, st.as_dict()
+        return self._emitter_query("direct", items, emitters, pick, radiance, moment2, samples_per_item=samples_per_item, shadow_end=shadow_end, seed=seed,
+                                   first_stream=first_stream, sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate, mis=mis)
 
     def direct_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, pick=None,
                       **params):
@@ -449,29 +420,73 @@ class Scene:
         direct()'s keywords, samples_per_item and mis included (trt_direct_mis_device where mis is given: the device form cannot check the
         table rule).  pick: the device pointer of the n_emitters x 16 bytes of lights.pick_table's records (trt_direct_pick_device), or
         with mis (pointer, total) (trt_direct_mis_pick_device); the device form checks neither table."""
-        p = self._direct_params(**params)
-        weighted = isinstance(p, _lib.DirectMisParams)
-        tail = (C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr))
-        if pick is None:
-            fn = lib.trt_direct_mis_device if weighted else lib.trt_direct_device
-            check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p), *tail))
-            return
-        d_pick_ptr, total = self._pick_and_total(pick, params.get("mis"))
-        head = (self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), C.c_void_p(d_pick_ptr), int(n_emitters), C.byref(p))
-        if weighted:
-            check(lib.trt_direct_mis_pick_device(*head, C.c_float(total), *tail))
-        else:
-            check(lib.trt_direct_pick_device(*head, *tail))
+        self._emitter_query_device("direct", d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr, d_counters_ptr, stream_ptr, pick, params)
 
     def direct_plan(self, n, compute_units=0, mis=None, pick=None):
         """trt_direct_launch_plan (mis given: trt_direct_mis_launch_plan; pick given, as anything but None: the _pick_ plans): how
         direct() launches n surfels on this scene, as a dict with ambient_plan()'s fields."""
+        return self._emitter_query_plan("direct", n, compute_units, mis, pick)
+
+    # ---- what the eight queries over an emitter table share: {direct, nee} x {plain, mis} x {uniform, pick} ----
+    @staticmethod
+    def _with_mis(family, p, mis):
+        """`p` as it is, or with mis the family's weighted parameters around it: trt_<family>_mis_params with their defaults."""
+        if mis is None:
+            return p
+        m = {"direct": _lib.DirectMisParams, "nee": _lib.NeeMisParams}[family]()
+        getattr(lib, "trt_%s_mis_params_default" % family)(C.byref(m))
+        setattr(m, family, p)
+        m.heuristic = Scene.MIS[mis]
+        return m
+
+    @staticmethod
+    def _emitter_symbol(family, mis, pick, form=""):
+        """trt_<family>[_mis][_pick]<form>: form is "", "_device" or "_launch_plan"; pick counts as given when it is anything but None."""
+        return getattr(lib, "trt_" + family + ("" if mis is None else "_mis") + ("" if pick is None else "_pick") + form)
+
+    def _emitter_query(self, family, items, emitters, pick, radiance, moment2, **params):
+        """The host form of direct() / nee(): `params` are the keywords of the family's _params function, mis among them."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        e = self._emitter_table(emitters)
+        p = getattr(self, "_%s_params" % family)(**params)
+        mis = params["mis"]
+        if radiance is None:
+            radiance = np.zeros((n, 3), np.float32)
+        if moment2 is True:
+            moment2 = np.zeros((n, 3), np.float32)
+        for a in (radiance, moment2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
+        st = Stats()
+        args = [self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p)]
+        if pick is not None:                                                # the records stand behind the table, the total behind the parameters
+            pick, total = self._pick_and_total(pick, mis)
+            k = np.ascontiguousarray(pick)
+            if k.dtype != PICK_DTYPE or k.shape != (len(e),):
+                raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
+            args.insert(4, k.ctypes.data if len(k) else None)
+            if mis is not None:
+                args.append(C.c_float(total))
+        check(self._emitter_symbol(family, mis, pick)(*args, radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None,
+                                                      C.byref(st)))
+        return radiance, moment2, st.as_dict()
+
+    def _emitter_query_device(self, family, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr, d_counters_ptr, stream_ptr, pick, params):
+        """The device form of direct() / nee(): pick is the table's device pointer, or with mis (pointer, total)."""
+        p = getattr(self, "_%s_params" % family)(**params)
+        mis = params.get("mis")
+        args = [self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p)]
+        if pick is not None:
+            d_pick_ptr, total = self._pick_and_total(pick, mis)
+            args.insert(4, C.c_void_p(d_pick_ptr))
+            if mis is not None:
+                args.append(C.c_float(total))
+        check(self._emitter_symbol(family, mis, pick, "_device")(*args, C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr),
+                                                                 C.c_void_p(stream_ptr)))
+
+    def _emitter_query_plan(self, family, n, compute_units, mis, pick):
         plan = _lib.QueryPlan()
-        if pick is None:
-            fn = lib.trt_direct_launch_plan if mis is None else lib.trt_direct_mis_launch_plan
-        else:
-            fn = lib.trt_direct_pick_launch_plan if mis is None else lib.trt_direct_mis_pick_launch_plan
-        check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
+        check(self._emitter_symbol(family, mis, pick, "_launch_plan")(self._h, int(n), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
     # ---- probe queries (tinyrt.h trt_probe): spherical-harmonic radiance from first rays the device draws over the sphere ----
@@ -593,12 +608,7 @@ class Scene:
         p.gather.lobe, p.gather.spread, p.source_is_diffuse = cls.SOURCES[source], float(spread), int(source_is_diffuse)
         if shadow_end is not None:
             p.shadow_end = float(shadow_end)
-        if mis is None:
-            return p
-        m = _lib.NeeMisParams()
-        lib.trt_nee_mis_params_default(C.byref(m))
-        m.nee, m.heuristic = p, cls.MIS[mis]
-        return m
+        return cls._with_mis("nee", p, mis)
 
     def nee(self, items, emitters, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, max_bounces=50,
             background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None, accumulate=False, radiance=None, moment2=None,
@@ -619,33 +629,9 @@ class Scene:
         table, by power or by the weights the table was built from, not uniformly - one draw more per vertex, as in direct().  The
         records alone will do without mis; with mis the (records, total) pair is needed and the table must be the power table
         (weights=None).  pick=None: the calls and bytes of before."""
-        r, _ = _rays_and_t_max(items, None)
-        n = len(r)
-        e = self._emitter_table(emitters)
-        p = self._nee_params(samples_per_item, source, spread, shadow_end, source_is_diffuse, mis, max_bounces=max_bounces, background=background,
-                             seed=seed, first_stream=first_stream, sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
-        if radiance is None:
-            radiance = np.zeros((n, 3), np.float32)
-        if moment2 is True:
-            moment2 = np.zeros((n, 3), np.float32)
-        for a in (radiance, moment2):
-            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
-        st = Stats()
-        out = (radiance.ctypes.data if n else None, moment2.ctypes.data if moment2 is not None and n else None, C.byref(st))
-        if pick is None:
-            fn = lib.trt_nee if mis is None else lib.trt_nee_mis
-            check(fn(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, len(e), C.byref(p), *out))
-            return radiance, moment2, st.as_dict()
-        pick, total = self._pick_and_total(pick, mis)
-        k = np.ascontiguousarray(pick)
-        if k.dtype != PICK_DTYPE or k.shape != (len(e),):
-            raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
-        head = (self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, k.ctypes.data if len(k) else None, len(e), C.byref(p))
-        if mis is None:
-            check(lib.trt_nee_pick(*head, *out))
-        else:
-            check(lib.trt_nee_mis_pick(*head, C.c_float(total), *out))
-        return radiance, moment2, st.as_dict()
+        return self._emitter_query("nee", items, emitters, pick, radiance, moment2, samples_per_item=samples_per_item, source=source, spread=spread,
+                                   shadow_end=shadow_end, source_is_diffuse=source_is_diffuse, mis=mis, max_bounces=max_bounces, background=background,
+                                   seed=seed, first_stream=first_stream, sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
 
     def nee_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr=0, d_counters_ptr=0, stream_ptr=0, pick=None,
                    **params):
@@ -654,30 +640,12 @@ class Scene:
         nee()'s keywords, samples_per_item and mis included (trt_nee_mis_device where mis is given: the device form cannot check the
         table rule).  pick: the device pointer of the n_emitters x 16 bytes of lights.pick_table's records (trt_nee_pick_device), or with
         mis (pointer, total) (trt_nee_mis_pick_device); the device form checks neither table."""
-        p = self._nee_params(**params)
-        weighted = isinstance(p, _lib.NeeMisParams)
-        tail = (C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr), C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr))
-        if pick is None:
-            fn = lib.trt_nee_mis_device if weighted else lib.trt_nee_device
-            check(fn(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), int(n_emitters), C.byref(p), *tail))
-            return
-        d_pick_ptr, total = self._pick_and_total(pick, params.get("mis"))
-        head = (self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), C.c_void_p(d_pick_ptr), int(n_emitters), C.byref(p))
-        if weighted:
-            check(lib.trt_nee_mis_pick_device(*head, C.c_float(total), *tail))
-        else:
-            check(lib.trt_nee_pick_device(*head, *tail))
+        self._emitter_query_device("nee", d_items_ptr, n, d_emitters_ptr, n_emitters, d_radiance_ptr, d_moment2_ptr, d_counters_ptr, stream_ptr, pick, params)
 
     def nee_plan(self, n, compute_units=0, mis=None, pick=None):
         """trt_nee_launch_plan (mis given: trt_nee_mis_launch_plan; pick given, as anything but None: the _pick_ plans): how nee() launches
         n items on this scene, as a dict with gather_plan()'s fields."""
-        plan = _lib.QueryPlan()
-        if pick is None:
-            fn = lib.trt_nee_launch_plan if mis is None else lib.trt_nee_mis_launch_plan
-        else:
-            fn = lib.trt_nee_pick_launch_plan if mis is None else lib.trt_nee_mis_pick_launch_plan
-        check(fn(self._h, int(n), int(compute_units), C.byref(plan)))
-        return plan.as_dict()
+        return self._emitter_query_plan("nee", n, compute_units, mis, pick)
 
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:

@@ -18,8 +18,9 @@
 // the shadow sample scaled by wl = 1 / (1 + q(wgt)) (1 for a virtual emitter) and, on stream (seed, j, 0xFFFFFFFF), the gather's cosine
 // ray from the surfel, whose hit on a light adds emission * wb (mis_weight.h mis_hit_weight, shared with nee.hip).  Up to two walks per
 // sample go through ONE walk call site, nee_kernel's way.  direct_kernel is instruction for instruction what it was; the
-// two queries share their checks, launcher and both forms' bodies.
+// queries' host side - checks, both forms' bodies - is emitter_query.h's, shared with nee.hip.
 #include "emitter_pick.h"
+#include "emitter_query.h"
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -395,76 +396,37 @@ __global__ __launch_bounds__(THREADS, MINW) void direct_mis_kernel(SceneDev scd,
 
 namespace {
 
-#define TRT_DIRECT(MODE, WALK, THREADS, MINW) \
-    BatchKernel{reinterpret_cast<const void*>(&direct_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
-// the (scene mode, walk, workgroup shape) set of the other batch units, with the register-slot fallback (query_plan.h), so that every
-// scene has a kernel.  A lane carries what a lane of the ambient query carries plus the sample's colour, its t_max and two sums more: the
-// launch bounds are the highest at which the instantiation uses no scratch memory and spills no vector register
-// (profiles/direct_resource_usage.txt).  The plan reports the bound (kernel_waves_per_simd).
-const BatchKernel kDirectKernels[] = {
-    TRT_DIRECT(MODE_LDS, WALK_FLAT, 256, 7),
-    TRT_DIRECT(MODE_LDS, WALK_LDS_STACK, 256, 8),
-    TRT_DIRECT(MODE_LDS, WALK_LDS_STACK, 768, 8),
-    TRT_DIRECT(MODE_LDS, WALK_REGS, 512, 7),
-    TRT_DIRECT(MODE_GLOBAL, WALK_COMPACT, 256, 7),
-    TRT_DIRECT(MODE_GLOBAL, WALK_REGS, 256, 6),
+// The (scene mode, walk, workgroup shape) set of the other batch units, with the register-slot fallback (query_plan.h), so that every
+// scene has a kernel: the six shapes, written once.  A table is one kernel template with one PICK over them; its launch bounds, one per
+// shape in this order, are all that a table says of its own.  The plan reports the bound (kernel_waves_per_simd).
+#define TRT_DIRECT_ROW(KERNEL, PICK, MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&KERNEL<MODE, WALK, THREADS, MINW, PICK>), MODE, WALK, THREADS, MINW}
+#define TRT_DIRECT_TABLE(KERNEL, PICK, LDS_FLAT, LDS_STACK_256, LDS_STACK_768, LDS_REGS, GLOBAL_COMPACT, GLOBAL_REGS)                              \
+    {TRT_DIRECT_ROW(KERNEL, PICK, MODE_LDS, WALK_FLAT, 256, LDS_FLAT), TRT_DIRECT_ROW(KERNEL, PICK, MODE_LDS, WALK_LDS_STACK, 256, LDS_STACK_256), \
+     TRT_DIRECT_ROW(KERNEL, PICK, MODE_LDS, WALK_LDS_STACK, 768, LDS_STACK_768), TRT_DIRECT_ROW(KERNEL, PICK, MODE_LDS, WALK_REGS, 512, LDS_REGS), \
+     TRT_DIRECT_ROW(KERNEL, PICK, MODE_GLOBAL, WALK_COMPACT, 256, GLOBAL_COMPACT), TRT_DIRECT_ROW(KERNEL, PICK, MODE_GLOBAL, WALK_REGS, 256, GLOBAL_REGS)}
+constexpr size_t kDirectShapes = 6;
+// The kernels of a query: [pick][mis].
+//  - direct_kernel: a lane carries what a lane of the ambient query carries plus the sample's colour, its t_max and two sums more: the
+//    launch bounds are the highest at which the instantiation uses no scratch memory and spills no vector register
+//    (profiles/direct_resource_usage.txt).
+//  - direct_mis_kernel (trt_direct_mis): a lane carries a whole ray where direct_kernel's any-hit walk carries less, and the light-hit
+//    weight besides: bounds by the same rule (profiles/direct_mis_resource_usage.txt).
+//  - PICK (trt_direct_pick, trt_direct_mis_pick): the alias draw lives and dies ahead of the emitter record's load.  Bounds by the same
+//    rule (profiles/direct_pick_resource_usage.txt).
+const BatchKernel kDirectKernels[2][2][kDirectShapes] = {
+    {TRT_DIRECT_TABLE(direct_kernel, false, 7, 8, 8, 7, 7, 6), TRT_DIRECT_TABLE(direct_mis_kernel, false, 5, 7, 7, 5, 7, 5)},
+    {TRT_DIRECT_TABLE(direct_kernel, true, 7, 8, 8, 7, 7, 6), TRT_DIRECT_TABLE(direct_mis_kernel, true, 5, 7, 7, 5, 7, 5)},
 };
-#undef TRT_DIRECT
-#define TRT_DIRECT_MIS(MODE, WALK, THREADS, MINW) \
-    BatchKernel{reinterpret_cast<const void*>(&direct_mis_kernel<MODE, WALK, THREADS, MINW>), MODE, WALK, THREADS, MINW}
-// The weighted kernels (trt_direct_mis): the same shapes.  A lane carries a whole ray where direct_kernel's any-hit walk carries less, and
-// the light-hit weight besides: bounds by the same rule (profiles/direct_mis_resource_usage.txt).
-const BatchKernel kDirectMisKernels[] = {
-    TRT_DIRECT_MIS(MODE_LDS, WALK_FLAT, 256, 5),
-    TRT_DIRECT_MIS(MODE_LDS, WALK_LDS_STACK, 256, 7),
-    TRT_DIRECT_MIS(MODE_LDS, WALK_LDS_STACK, 768, 7),
-    TRT_DIRECT_MIS(MODE_LDS, WALK_REGS, 512, 5),
-    TRT_DIRECT_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 7),
-    TRT_DIRECT_MIS(MODE_GLOBAL, WALK_REGS, 256, 5),
-};
-#undef TRT_DIRECT_MIS
-#define TRT_DIRECT_PICK(MODE, WALK, THREADS, MINW) \
-    BatchKernel{reinterpret_cast<const void*>(&direct_kernel<MODE, WALK, THREADS, MINW, true>), MODE, WALK, THREADS, MINW}
-#define TRT_DIRECT_MIS_PICK(MODE, WALK, THREADS, MINW) \
-    BatchKernel{reinterpret_cast<const void*>(&direct_mis_kernel<MODE, WALK, THREADS, MINW, true>), MODE, WALK, THREADS, MINW}
-// The PICK kernels (trt_direct_pick, trt_direct_mis_pick): the same shapes; the alias draw lives and dies ahead of the emitter record's
-// load.  Bounds by the same rule (profiles/direct_pick_resource_usage.txt).
-const BatchKernel kDirectPickKernels[] = {
-    TRT_DIRECT_PICK(MODE_LDS, WALK_FLAT, 256, 7),
-    TRT_DIRECT_PICK(MODE_LDS, WALK_LDS_STACK, 256, 8),
-    TRT_DIRECT_PICK(MODE_LDS, WALK_LDS_STACK, 768, 8),
-    TRT_DIRECT_PICK(MODE_LDS, WALK_REGS, 512, 7),
-    TRT_DIRECT_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 7),
-    TRT_DIRECT_PICK(MODE_GLOBAL, WALK_REGS, 256, 6),
-};
-const BatchKernel kDirectMisPickKernels[] = {
-    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5),
-    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 7),
-    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 7),
-    TRT_DIRECT_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5),
-    TRT_DIRECT_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 7),
-    TRT_DIRECT_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5),
-};
-#undef TRT_DIRECT_PICK
-#undef TRT_DIRECT_MIS_PICK
-static_assert(sizeof(kDirectMisKernels) == sizeof(kDirectKernels) && sizeof(kDirectPickKernels) == sizeof(kDirectKernels) &&
-              sizeof(kDirectMisPickKernels) == sizeof(kDirectKernels), "one weighted and one PICK instantiation per shape");
-constexpr size_t kDirectShapes = sizeof(kDirectKernels) / sizeof(kDirectKernels[0]);
-// The kernels of a query: [mis][pick].
-const BatchKernel* direct_kernels(bool mis, bool pick) {
-    return mis ? (pick ? kDirectMisPickKernels : kDirectMisKernels) : (pick ? kDirectPickKernels : kDirectKernels);
-}
+#undef TRT_DIRECT_TABLE
+#undef TRT_DIRECT_ROW
 
-// What a call asks of the device, after the checks.
-struct DirectCall {
+// What a call asks of the device, after the checks; the variant's fields are emitter_query.h's.
+struct DirectCall : EmitterVariant {
     RenderArgs ra;                   // of the path parameters: seed key, 1 / K, sample range, accumulate (radiance_check)
     uint32_t samples_per_item, first_stream;
     uint32_t n_emitters;
     float shadow_end;
-    bool mis = false;                // trt_direct_mis: the weighted kernels, with `heuristic`
-    uint32_t heuristic = 0u;
-    bool pick = false;               // trt_direct_pick / trt_direct_mis_pick: the PICK kernels, with an alias table (and `total_power`)
-    float total_power = 0.0f;
     bool nothing() const { return ra.sample_begin == ra.sample_end; }       // an empty sample range: no sample is drawn
 };
 
@@ -478,7 +440,7 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, direct_kernels(c.mis, c.pick), kDirectShapes, b);
+    const hipError_t e = batch_prepare(scd, n, kDirectKernels[c.pick][c.mis], kDirectShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     DirectArgs da{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
@@ -487,8 +449,12 @@ hipError_t launch_direct(const QueryScene& qs, const DirectCall& c, const float*
     DirectMisArgs ma{da, c.heuristic};
     DirectPickArgs pa{da, d_pick};
     DirectMisPickArgs mpa{ma, d_pick, c.total_power};
-    void* const query = c.mis ? (c.pick ? static_cast<void*>(&mpa) : static_cast<void*>(&ma)) : (c.pick ? static_cast<void*>(&pa) : static_cast<void*>(&da));
-    void* args[] = {&scd, query, &b.leaf_list, &b.nodes16};
+    void* args[] = {&scd, &da, &b.leaf_list, &b.nodes16};
+    switch ((c.pick ? 2 : 0) | (c.mis ? 1 : 0)) {                           // the kernel's own argument struct
+    case 1: args[1] = &ma; break;
+    case 2: args[1] = &pa; break;
+    case 3: args[1] = &mpa; break;
+    }
     return batch_launch(b, args, stream);
 }
 
@@ -509,42 +475,49 @@ int direct_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt
     c.shadow_end = p->shadow_end;
     return TRT_OK;
 }
-
 // trt_direct_mis' checks before any device work: trt_direct's on p->direct, then the heuristic and this struct's reserved words.
-int direct_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters,
-                     const trt_direct_mis_params* p, const float* radiance, DirectCall& c) {
+int direct_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_mis_params* p,
+                 const float* radiance, DirectCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     const int rc = direct_check(s, items, n, emitters, n_emitters, &p->direct, radiance, c);
-    if (rc != TRT_OK) return rc;
-    if (p->heuristic > TRT_MIS_POWER) return query_fail(TRT_ERR_INVALID_ARG, "heuristic must be TRT_MIS_BALANCE or TRT_MIS_POWER");
-    for (uint32_t r : p->reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
-    c.mis = true;
-    c.heuristic = p->heuristic;
-    return TRT_OK;
+    return rc != TRT_OK ? rc : emitter_mis_check(*p, c);
 }
 
-// The two forms after their checks, for the four queries alike: `c` says which kernels, `d_pick` / `pick` is the alias table of a PICK query.
-int direct_on_device(trt_scene* s, const DirectCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters,
-                     const trt_emitter_pick* d_pick, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    return sample_query_on_device(s, n, "direct-light query launch", [&](const QueryScene& qs) {
-        return launch_direct(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters),
-                             reinterpret_cast<const float*>(d_pick), d_radiance, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),
-                             static_cast<hipStream_t>(stream));
+constexpr EmitterLabels kDirectLabels{"direct-light query buffers", "direct-light query launch"};
+
+// The two forms of the four queries (emitter_query.h): the family's parameter check, then the query's steps over its tables, then the
+// launcher.  `steps` is the query's list below, `t.pick` / `t.total_power` what a PICK query was handed.
+template <class Params, size_t K>
+int direct_device(const EmitterStep (&steps)[K], trt_scene* s, const trt_ray* d_items, uint32_t n, const EmitterTables& t, const Params* p, float* d_radiance,
+                  float* d_moment2, uint64_t* d_counters, void* stream) {
+    DirectCall c;
+    const int rc = direct_check(s, d_items, n, t.emitters, t.n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    return emitter_query_on_device(s, c, steps, kDirectLabels, launch_direct, d_items, n, t, d_radiance, d_moment2, d_counters, stream);
+}
+template <class Params, size_t K>
+int direct_host(const EmitterStep (&steps)[K], trt_scene* s, const trt_ray* items, uint32_t n, const EmitterTables& t, const Params* p, float* radiance,
+                float* moment2, trt_stats* stats) {
+    return host_form([&]() -> int {
+        DirectCall c;
+        const int rc = direct_check(s, items, n, t.emitters, t.n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        return emitter_query_on_host(s, c, steps, kDirectLabels, launch_direct, items, n, t, radiance, moment2, stats);
     });
 }
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters | pick table, if any).
-int direct_on_host(trt_scene* s, const DirectCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick,
-                   uint32_t n_emitters, float* radiance, float* moment2, trt_stats* stats) {
-    const size_t sums = (size_t)n * 12u;
-    SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                 "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
-    if (c.pick) { h.table2 = pick; h.table2_b = (size_t)n_emitters * sizeof(trt_emitter_pick); h.table2_what = "hipMemcpy of the pick table"; }
-    return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "direct-light query buffers", "direct-light query launch", stats,
-                                [&](const QueryScene& qs, const SampleDev& d) {
-                                    return launch_direct(qs, c, d.items, n, d.table, d.table2, d.sums, d.sums2, d.counters, nullptr);
-                                });
+// How launch_direct would launch n items on this scene with the kernels of a query.
+int direct_plan(bool mis, bool pick, const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return batch_launch_plan(s, n, compute_units, kDirectKernels[pick][mis], kDirectShapes, out);
 }
+
+// THE ORDER OF EACH QUERY'S TABLE CHECKS (tinyrt.h), behind trt_direct's / trt_direct_mis' own.  The host form runs every step, the device
+// form the pointer's only: it cannot read a table, and the rules are the caller's to keep (the kernel's clamp keeps a wrong pick table's
+// reads inside the E records).  An empty batch reads no table either.
+constexpr EmitterStep kDirectSteps[] = {STEP_EMITTER_ENTRIES};
+constexpr EmitterStep kDirectMisSteps[] = {STEP_EMITTER_ENTRIES, STEP_TABLE_RULE};
+constexpr EmitterStep kDirectPickSteps[] = {STEP_PICK_POINTER, STEP_EMITTER_ENTRIES, STEP_PICK_ENTRIES};
+// the table rule BEFORE the pick records (trt_nee_mis_pick has them the other way round)
+constexpr EmitterStep kDirectMisPickSteps[] = {STEP_PICK_POINTER, STEP_EMITTER_ENTRIES, STEP_TABLE_RULE, STEP_PICK_ENTRIES, STEP_PICK_POWER};
 
 }  // namespace
 }  // namespace trt
@@ -560,28 +533,14 @@ void trt_direct_params_default(trt_direct_params* out) {
 
 int trt_direct_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters, const trt_direct_params* p,
                       float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::DirectCall c;
-    const int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_device(trt::kDirectSteps, s, d_items, n, {d_emitters, nullptr, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
-// The table's entries are checked where n > 0, ahead of any device work.
 int trt_direct(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_params* p,
                float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::DirectCall c;
-        int rc = trt::direct_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
-        if (rc != TRT_OK) return rc;
-        return trt::direct_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
-    });
+    return trt::direct_host(trt::kDirectSteps, s, items, n, {emitters, nullptr, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
-// How launch_direct would launch n items on this scene.
 int trt_direct_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectKernels, trt::kDirectShapes, out);
+    return trt::direct_plan(false, false, s, n, compute_units, out);
 }
 
 void trt_direct_mis_params_default(trt_direct_mis_params* out) {
@@ -591,34 +550,16 @@ void trt_direct_mis_params_default(trt_direct_mis_params* out) {
     out->heuristic = TRT_MIS_BALANCE;
 }
 
-// The device form cannot read the table: the table rule is the caller's to keep.
 int trt_direct_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters,
                           const trt_direct_mis_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::DirectCall c;
-    const int rc = trt::direct_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_device(trt::kDirectMisSteps, s, d_items, n, {d_emitters, nullptr, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
 int trt_direct_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_direct_mis_params* p,
                    float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::DirectCall c;
-        int rc = trt::direct_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-        }
-        return trt::direct_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
-    });
+    return trt::direct_host(trt::kDirectMisSteps, s, items, n, {emitters, nullptr, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
-// The weighted kernels' table: the same shapes, its own bounds.
 int trt_direct_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectMisKernels, trt::kDirectShapes, out);
+    return trt::direct_plan(true, false, s, n, compute_units, out);
 }
 
 // ---- the PICK queries: the emitter chosen by power (or the caller's weights) through an alias table ----
@@ -626,81 +567,30 @@ int trt_emitter_pick_build(const trt_emitter* emitters, uint32_t n_emitters, con
     return trt::host_form([&]() -> int { return trt::pick_build(emitters, n_emitters, weights, out, total); });
 }
 
-// The device form checks the pointer only: the kernel's clamp keeps a wrong table's reads inside the E records.
 int trt_direct_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
                            uint32_t n_emitters, const trt_direct_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::DirectCall c;
-    int rc = trt::direct_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    rc = trt::pick_pointer_check(n, d_pick);
-    if (rc != TRT_OK) return rc;
-    c.pick = true;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_device(trt::kDirectPickSteps, s, d_items, n, {d_emitters, d_pick, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
 int trt_direct_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
                     const trt_direct_params* p, float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::DirectCall c;
-        int rc = trt::direct_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::pick_pointer_check(n, pick);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_entries_check(pick, n_emitters);
-            if (rc != TRT_OK) return rc;
-        }
-        c.pick = true;
-        return trt::direct_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
-    });
+    return trt::direct_host(trt::kDirectPickSteps, s, items, n, {emitters, pick, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
 int trt_direct_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectPickKernels, trt::kDirectShapes, out);
+    return trt::direct_plan(false, true, s, n, compute_units, out);
 }
 
-// The device form can read neither table: both table rules are the caller's to keep.
 int trt_direct_mis_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
                                uint32_t n_emitters, const trt_direct_mis_params* p, float total_power, float* d_radiance, float* d_moment2,
                                uint64_t* d_counters, void* stream) {
-    trt::DirectCall c;
-    int rc = trt::direct_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    rc = trt::pick_pointer_check(n, d_pick);
-    if (rc != TRT_OK) return rc;
-    c.pick = true;
-    c.total_power = total_power;
-    return trt::direct_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+    return trt::direct_device(trt::kDirectMisPickSteps, s, d_items, n, {d_emitters, d_pick, n_emitters, total_power}, p, d_radiance, d_moment2, d_counters,
+                              stream);
 }
-
 int trt_direct_mis_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
                         const trt_direct_mis_params* p, float total_power, float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::DirectCall c;
-        int rc = trt::direct_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::pick_pointer_check(n, pick);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_entries_check(pick, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_power_check(emitters, pick, n_emitters, total_power);
-            if (rc != TRT_OK) return rc;
-        }
-        c.pick = true;
-        c.total_power = total_power;
-        return trt::direct_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
-    });
+    return trt::direct_host(trt::kDirectMisPickSteps, s, items, n, {emitters, pick, n_emitters, total_power}, p, radiance, moment2, stats);
 }
-
 int trt_direct_mis_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kDirectMisPickKernels, trt::kDirectShapes, out);
+    return trt::direct_plan(true, true, s, n, compute_units, out);
 }
 
 }  // extern "C"

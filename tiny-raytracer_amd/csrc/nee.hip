@@ -30,13 +30,14 @@
 // emitter), and a light the path reaches after a diffuse scatter at hit >= 2, which the plain kernel hides, adds its emission scaled by
 // wb = q(g) / (1 + q(g)) (mis_weight.h mis_hit_weight) in the branch where shade has ended the path: cold, since a light always ends it.  A lane
 // carries csh, the cosine of its last Lambertian scatter, besides.  The MIS = false instantiations are instruction for instruction what
-// they were without the parameter; the two entry points share their checks, launcher and both forms' bodies with trt_nee.
+// they were without the parameter; the host side of all four queries is emitter_query.h's, shared with direct.hip.
 //
 // trt_nee_pick / trt_nee_mis_pick (tinyrt.h) are the same kernel with PICK = true: every vertex draw goes through the alias table of
 // direct.hip's PICK queries (gather_draw.h AliasPick: one draw and two loads more), and the weighted hit takes the light's choice
-// probability from the hit itself (mis_weight.h, the overload with total_power).  The table's checks are emitter_pick.h's, the ones
-// direct.hip applies.  The PICK = false instantiations are instruction for instruction what they were.
+// probability from the hit itself (mis_weight.h, the overload with total_power).  The table's checks are emitter_pick.h's, in the order
+// of this unit's step lists (emitter_query.h).  The PICK = false instantiations are instruction for instruction what they were.
 #include "emitter_pick.h"
+#include "emitter_query.h"
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
@@ -275,105 +276,36 @@ __global__ __launch_bounds__(THREADS, MINW) void nee_kernel(SceneDev scd, Render
 
 namespace {
 
-#define TRT_NEE(MODE, WALK, THREADS, MINW, SOURCE) \
-    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, false>), MODE, WALK, THREADS, MINW}
-#define TRT_NEE_MIS(MODE, WALK, THREADS, MINW, SOURCE) \
-    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, true>), MODE, WALK, THREADS, MINW}
 // The (scene mode, walk, workgroup shape) set of the other batch units, with the register-slot fallback (query_plan.h), so that every
-// scene has a kernel; one set for rays as given, one for the drawn lobes, as radiance.hip has.  A lane carries what a lane of the gather
-// kernel carries plus the outstanding shadow ray (direction, t_max, colour) and two flags: the launch bounds are the highest at which
-// the instantiation uses no scratch memory and spills no vector register (profiles/nee_resource_usage.txt).  The plan reports the bound
-// (kernel_waves_per_simd).
-const BatchKernel kNeeRayKernels[] = {
-    TRT_NEE(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
-    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_RAYS),
-    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_RAYS),
-    TRT_NEE(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
-    TRT_NEE(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
-    TRT_NEE(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
+// scene has a kernel: the six shapes, written once.  A table is nee_kernel with one (SOURCE, MIS, PICK) over them; its launch bounds, one
+// per shape in this order, are all that a table says of its own, and the tables for rays as given and for the drawn lobes (as
+// radiance.hip has them) share theirs.  The plan reports the bound (kernel_waves_per_simd).
+#define TRT_NEE_ROW(SOURCE, MIS, PICK, MODE, WALK, THREADS, MINW) \
+    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, MIS, PICK>), MODE, WALK, THREADS, MINW}
+#define TRT_NEE_TABLE(SOURCE, MIS, PICK, LDS_FLAT, LDS_STACK_256, LDS_STACK_768, LDS_REGS, GLOBAL_COMPACT, GLOBAL_REGS)                                       \
+    {TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_LDS, WALK_FLAT, 256, LDS_FLAT), TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_LDS, WALK_LDS_STACK, 256, LDS_STACK_256),         \
+     TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_LDS, WALK_LDS_STACK, 768, LDS_STACK_768), TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_LDS, WALK_REGS, 512, LDS_REGS),         \
+     TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_GLOBAL, WALK_COMPACT, 256, GLOBAL_COMPACT), TRT_NEE_ROW(SOURCE, MIS, PICK, MODE_GLOBAL, WALK_REGS, 256, GLOBAL_REGS)}
+#define TRT_NEE_TABLES(MIS, PICK, ...) {TRT_NEE_TABLE(NEE_RAYS, MIS, PICK, __VA_ARGS__), TRT_NEE_TABLE(NEE_LOBE, MIS, PICK, __VA_ARGS__)}
+constexpr size_t kNeeShapes = 6;
+// The kernels of a query: [pick][mis][SOURCE].
+//  - plain: a lane carries what a lane of the gather kernel carries plus the outstanding shadow ray (direction, t_max, colour) and two
+//    flags: the launch bounds are the highest at which the instantiation uses no scratch memory and spills no vector register
+//    (profiles/nee_resource_usage.txt).
+//  - weighted (trt_nee_mis): a lane carries csh besides.  Bounds by the same rule, read per shape off both sources
+//    (profiles/nee_mis_resource_usage.txt).
+//  - PICK (trt_nee_pick, trt_nee_mis_pick): u1, q and the alias die before the emitter record is loaded, the table pointer is
+//    wave-uniform; bounds by the same rule, read per shape off both sources (profiles/nee_pick_resource_usage.txt).
+const BatchKernel kNeeKernels[2][2][2][kNeeShapes] = {
+    {TRT_NEE_TABLES(false, false, 5, 6, 6, 5, 5, 5), TRT_NEE_TABLES(true, false, 5, 5, 5, 5, 5, 5)},
+    {TRT_NEE_TABLES(false, true, 5, 6, 6, 5, 5, 5), TRT_NEE_TABLES(true, true, 5, 5, 5, 5, 5, 5)},
 };
-const BatchKernel kNeeLobeKernels[] = {
-    TRT_NEE(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
-    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_LOBE),
-    TRT_NEE(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_LOBE),
-    TRT_NEE(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
-    TRT_NEE(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
-    TRT_NEE(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
-};
-// The weighted kernels (trt_nee_mis): the same shapes; a lane carries csh besides.  Bounds by the same rule, read per shape off both
-// sources (profiles/nee_mis_resource_usage.txt).
-const BatchKernel kNeeMisRayKernels[] = {
-    TRT_NEE_MIS(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_RAYS),
-    TRT_NEE_MIS(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
-    TRT_NEE_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
-};
-const BatchKernel kNeeMisLobeKernels[] = {
-    TRT_NEE_MIS(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_LOBE),
-    TRT_NEE_MIS(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
-    TRT_NEE_MIS(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
-};
-#undef TRT_NEE
-#undef TRT_NEE_MIS
-#define TRT_NEE_PICK(MODE, WALK, THREADS, MINW, SOURCE) \
-    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, false, true>), MODE, WALK, THREADS, MINW}
-#define TRT_NEE_MIS_PICK(MODE, WALK, THREADS, MINW, SOURCE) \
-    BatchKernel{reinterpret_cast<const void*>(&nee_kernel<MODE, WALK, THREADS, MINW, SOURCE, true, true>), MODE, WALK, THREADS, MINW}
-// The PICK kernels (trt_nee_pick, trt_nee_mis_pick): the same shapes.  u1, q and the alias die before the emitter record is loaded, the
-// table pointer is wave-uniform; bounds by the same rule, read per shape off both sources (profiles/nee_pick_resource_usage.txt).
-const BatchKernel kNeePickRayKernels[] = {
-    TRT_NEE_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
-    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_RAYS),
-    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_RAYS),
-    TRT_NEE_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
-    TRT_NEE_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
-    TRT_NEE_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
-};
-const BatchKernel kNeePickLobeKernels[] = {
-    TRT_NEE_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
-    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 256, 6, NEE_LOBE),
-    TRT_NEE_PICK(MODE_LDS, WALK_LDS_STACK, 768, 6, NEE_LOBE),
-    TRT_NEE_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
-    TRT_NEE_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
-    TRT_NEE_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
-};
-const BatchKernel kNeeMisPickRayKernels[] = {
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_RAYS),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_RAYS),
-    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_RAYS),
-    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_RAYS),
-};
-const BatchKernel kNeeMisPickLobeKernels[] = {
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_FLAT, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_LDS_STACK, 768, 5, NEE_LOBE),
-    TRT_NEE_MIS_PICK(MODE_LDS, WALK_REGS, 512, 5, NEE_LOBE),
-    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_COMPACT, 256, 5, NEE_LOBE),
-    TRT_NEE_MIS_PICK(MODE_GLOBAL, WALK_REGS, 256, 5, NEE_LOBE),
-};
-#undef TRT_NEE_PICK
-#undef TRT_NEE_MIS_PICK
-constexpr size_t kNeeShapes = sizeof(kNeeRayKernels) / sizeof(kNeeRayKernels[0]);
-static_assert(sizeof(kNeeLobeKernels) == sizeof(kNeeRayKernels), "one lobe instantiation per shape");
-static_assert(sizeof(kNeeMisRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeeMisLobeKernels) == sizeof(kNeeRayKernels), "one weighted instantiation per shape and source");
-static_assert(sizeof(kNeePickRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeePickLobeKernels) == sizeof(kNeeRayKernels) &&
-              sizeof(kNeeMisPickRayKernels) == sizeof(kNeeRayKernels) && sizeof(kNeeMisPickLobeKernels) == sizeof(kNeeRayKernels),
-              "one PICK instantiation per shape, source and weighting");
-// The kernels of a query: [mis][pick][the items are rays].
-const BatchKernel* nee_kernels(bool mis, bool pick, bool rays) {
-    if (pick) return mis ? (rays ? kNeeMisPickRayKernels : kNeeMisPickLobeKernels) : (rays ? kNeePickRayKernels : kNeePickLobeKernels);
-    return mis ? (rays ? kNeeMisRayKernels : kNeeMisLobeKernels) : (rays ? kNeeRayKernels : kNeeLobeKernels);
-}
+#undef TRT_NEE_TABLES
+#undef TRT_NEE_TABLE
+#undef TRT_NEE_ROW
 
-// What a call asks of the device, after the checks.
-struct NeeCall {
+// What a call asks of the device, after the checks; the variant's fields are emitter_query.h's.
+struct NeeCall : EmitterVariant {
     RenderArgs ra;                   // of the path parameters (radiance_check)
     uint32_t samples_per_item, first_stream;
     uint32_t source;
@@ -381,10 +313,6 @@ struct NeeCall {
     uint32_t n_emitters;
     float shadow_end;
     uint32_t source_is_diffuse;
-    bool mis = false;                // trt_nee_mis: the weighted kernels, with `heuristic`
-    uint32_t heuristic = 0u;
-    bool pick = false;               // trt_nee_pick / trt_nee_mis_pick: the PICK kernels, with an alias table (and `total_power`)
-    float total_power = 0.0f;
     bool nothing() const { return ra.sample_begin == ra.sample_end || ra.max_bounces == 0u; }
 };
 
@@ -398,7 +326,7 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     }
     SceneDev scd = qs.scene;
     BatchLaunch b;
-    const hipError_t e = batch_prepare(scd, n, nee_kernels(c.mis, c.pick, c.source == TRT_PASSES_RAYS), kNeeShapes, b);
+    const hipError_t e = batch_prepare(scd, n, kNeeKernels[c.pick][c.mis][c.source == TRT_PASSES_RAYS ? NEE_RAYS : NEE_LOBE], kNeeShapes, b);
     if (e != hipSuccess) return e;
     const trt_query_plan& q = b.q;
     RenderArgs ra = c.ra;
@@ -406,7 +334,8 @@ hipError_t launch_nee(const QueryScene& qs, const NeeCall& c, const float* d_ite
     NeeArgs ga{d_items, d_emitters, d_radiance, d_moment2, d_counters, n, q.rays_per_wave, q.leaf_slots, q.stragglers, c.samples_per_item,
                c.first_stream, c.source, c.spread, c.n_emitters, c.shadow_end, c.source_is_diffuse, c.heuristic};
     NeePickArgs pa{ga, d_pick, c.total_power};
-    void* args[] = {&scd, &ra, c.pick ? static_cast<void*>(&pa) : static_cast<void*>(&ga), &b.leaf_list, &b.nodes16};
+    void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
+    if (c.pick) args[2] = &pa;                                              // the PICK kernels' own argument struct
     return batch_launch(b, args, stream);
 }
 
@@ -435,42 +364,50 @@ int nee_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_em
     c.source_is_diffuse = p->source_is_diffuse;
     return TRT_OK;
 }
-
 // trt_nee_mis' checks before any device work: trt_nee's on p->nee, then the heuristic and this struct's reserved words.
-int nee_mis_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
-                  const float* radiance, NeeCall& c) {
+int nee_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
+              const float* radiance, NeeCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     const int rc = nee_check(s, items, n, emitters, n_emitters, &p->nee, radiance, c);
-    if (rc != TRT_OK) return rc;
-    if (p->heuristic > TRT_MIS_POWER) return query_fail(TRT_ERR_INVALID_ARG, "heuristic must be TRT_MIS_BALANCE or TRT_MIS_POWER");
-    for (uint32_t r : p->reserved)
-        if (r != 0u) return query_fail(TRT_ERR_INVALID_ARG, "reserved words must be zero");
-    c.mis = true;
-    c.heuristic = p->heuristic;
-    return TRT_OK;
+    return rc != TRT_OK ? rc : emitter_mis_check(*p, c);
 }
 
-// The two forms after their checks, for the four queries alike: `c` says which kernels, `d_pick` / `pick` is the alias table of a PICK query.
-int nee_on_device(trt_scene* s, const NeeCall& c, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
-                  float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    return sample_query_on_device(s, n, "next-event query launch", [&](const QueryScene& qs) {
-        return launch_nee(qs, c, reinterpret_cast<const float*>(d_items), n, reinterpret_cast<const float*>(d_emitters),
-                          reinterpret_cast<const float*>(d_pick), d_radiance, d_moment2, reinterpret_cast<unsigned long long*>(d_counters),
-                          static_cast<hipStream_t>(stream));
+constexpr EmitterLabels kNeeLabels{"next-event query buffers", "next-event query launch"};
+
+// The two forms of the four queries (emitter_query.h): the family's parameter check, then the query's steps over its tables, then the
+// launcher.  `steps` is the query's list below, `t.pick` / `t.total_power` what a PICK query was handed.
+template <class Params, size_t K>
+int nee_device(const EmitterStep (&steps)[K], trt_scene* s, const trt_ray* d_items, uint32_t n, const EmitterTables& t, const Params* p, float* d_radiance,
+               float* d_moment2, uint64_t* d_counters, void* stream) {
+    NeeCall c;
+    const int rc = nee_check(s, d_items, n, t.emitters, t.n_emitters, p, d_radiance, c);
+    if (rc != TRT_OK) return rc;
+    return emitter_query_on_device(s, c, steps, kNeeLabels, launch_nee, d_items, n, t, d_radiance, d_moment2, d_counters, stream);
+}
+template <class Params, size_t K>
+int nee_host(const EmitterStep (&steps)[K], trt_scene* s, const trt_ray* items, uint32_t n, const EmitterTables& t, const Params* p, float* radiance,
+             float* moment2, trt_stats* stats) {
+    return host_form([&]() -> int {
+        NeeCall c;
+        const int rc = nee_check(s, items, n, t.emitters, t.n_emitters, p, radiance, c);
+        if (rc != TRT_OK) return rc;
+        return emitter_query_on_host(s, c, steps, kNeeLabels, launch_nee, items, n, t, radiance, moment2, stats);
     });
 }
-// Host buffers: staged by host_stage.h sample_query_on_host (items | table | sums | second moments, if wanted | counters | pick table, if any).
-int nee_on_host(trt_scene* s, const NeeCall& c, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick,
-                uint32_t n_emitters, float* radiance, float* moment2, trt_stats* stats) {
-    const size_t sums = (size_t)n * 12u;
-    SampleHost h{items, (size_t)n * sizeof(trt_ray), "hipMemcpy of the items", emitters, (size_t)n_emitters * sizeof(trt_emitter),
-                 "hipMemcpy of the emitters", radiance, sums, moment2, sums, "hipMemcpy of the second moments"};
-    if (c.pick) { h.table2 = pick; h.table2_b = (size_t)n_emitters * sizeof(trt_emitter_pick); h.table2_what = "hipMemcpy of the pick table"; }
-    return sample_query_on_host(s, n, h, c.ra.accumulate != 0u, c.nothing(), "next-event query buffers", "next-event query launch", stats,
-                                [&](const QueryScene& qs, const SampleDev& d) {
-                                    return launch_nee(qs, c, d.items, n, d.table, d.table2, d.sums, d.sums2, d.counters, nullptr);
-                                });
+// How launch_nee would launch n items on this scene with the kernels of a query: the two sources' tables share their shapes and bounds,
+// so the source does not enter.
+int nee_plan(bool mis, bool pick, const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
+    return batch_launch_plan(s, n, compute_units, kNeeKernels[pick][mis][NEE_LOBE], kNeeShapes, out);
 }
+
+// THE ORDER OF EACH QUERY'S TABLE CHECKS (tinyrt.h), behind trt_nee's / trt_nee_mis' own.  The host form runs every step, the device
+// form the pointer's only: it cannot read a table, and the rules are the caller's to keep (the kernel's clamp keeps a wrong pick table's
+// reads inside the E records).  An empty batch reads no table either.
+constexpr EmitterStep kNeeSteps[] = {STEP_EMITTER_ENTRIES};
+constexpr EmitterStep kNeeMisSteps[] = {STEP_EMITTER_ENTRIES, STEP_TABLE_RULE};
+constexpr EmitterStep kNeePickSteps[] = {STEP_PICK_POINTER, STEP_EMITTER_ENTRIES, STEP_PICK_ENTRIES};
+// the pick records BEFORE the table rule (trt_direct_mis_pick has them the other way round)
+constexpr EmitterStep kNeeMisPickSteps[] = {STEP_PICK_POINTER, STEP_EMITTER_ENTRIES, STEP_PICK_ENTRIES, STEP_TABLE_RULE, STEP_PICK_POWER};
 
 }  // namespace
 }  // namespace trt
@@ -487,28 +424,14 @@ void trt_nee_params_default(trt_nee_params* out) {
 
 int trt_nee_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters, const trt_nee_params* p,
                    float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::NeeCall c;
-    const int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_device(trt::kNeeSteps, s, d_items, n, {d_emitters, nullptr, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
-// The table's entries are checked where n > 0, ahead of any device work.
 int trt_nee(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_params* p, float* radiance,
             float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::NeeCall c;
-        int rc = trt::nee_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::emitter_entries_check(emitters, n == 0u ? 0u : n_emitters);
-        if (rc != TRT_OK) return rc;
-        return trt::nee_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
-    });
+    return trt::nee_host(trt::kNeeSteps, s, items, n, {emitters, nullptr, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
-// How launch_nee would launch n items on this scene: the two tables share their shapes and bounds, so the source does not enter.
 int trt_nee_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeLobeKernels, trt::kNeeShapes, out);
+    return trt::nee_plan(false, false, s, n, compute_units, out);
 }
 
 void trt_nee_mis_params_default(trt_nee_mis_params* out) {
@@ -518,113 +441,42 @@ void trt_nee_mis_params_default(trt_nee_mis_params* out) {
     out->heuristic = TRT_MIS_BALANCE;
 }
 
-// The device form cannot read the table: the table rule is the caller's to keep.
 int trt_nee_mis_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, uint32_t n_emitters,
                        const trt_nee_mis_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::NeeCall c;
-    const int rc = trt::nee_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, nullptr, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_device(trt::kNeeMisSteps, s, d_items, n, {d_emitters, nullptr, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
 int trt_nee_mis(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, uint32_t n_emitters, const trt_nee_mis_params* p,
                 float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::NeeCall c;
-        int rc = trt::nee_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-        }
-        return trt::nee_on_host(s, c, items, n, emitters, nullptr, n_emitters, radiance, moment2, stats);
-    });
+    return trt::nee_host(trt::kNeeMisSteps, s, items, n, {emitters, nullptr, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
-// The weighted kernels' table: the same shapes, its own bounds.
 int trt_nee_mis_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeMisLobeKernels, trt::kNeeShapes, out);
+    return trt::nee_plan(true, false, s, n, compute_units, out);
 }
 
 // ---- the PICK queries: the emitter of every vertex's shadow ray chosen by power (or the caller's weights) through an alias table ----
-// The device form checks the pointer only: the kernel's clamp keeps a wrong table's reads inside the E records.
 int trt_nee_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
                         uint32_t n_emitters, const trt_nee_params* p, float* d_radiance, float* d_moment2, uint64_t* d_counters, void* stream) {
-    trt::NeeCall c;
-    int rc = trt::nee_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    rc = trt::pick_pointer_check(n, d_pick);
-    if (rc != TRT_OK) return rc;
-    c.pick = true;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_device(trt::kNeePickSteps, s, d_items, n, {d_emitters, d_pick, n_emitters, 0.0f}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
 int trt_nee_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
                  const trt_nee_params* p, float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::NeeCall c;
-        int rc = trt::nee_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::pick_pointer_check(n, pick);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_entries_check(pick, n_emitters);
-            if (rc != TRT_OK) return rc;
-        }
-        c.pick = true;
-        return trt::nee_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
-    });
+    return trt::nee_host(trt::kNeePickSteps, s, items, n, {emitters, pick, n_emitters, 0.0f}, p, radiance, moment2, stats);
 }
-
-// The PICK kernels' tables: the same shapes, their own bounds.
 int trt_nee_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kNeePickLobeKernels, trt::kNeeShapes, out);
+    return trt::nee_plan(false, true, s, n, compute_units, out);
 }
 
-// The device form can read neither table: both table rules are the caller's to keep.
 int trt_nee_mis_pick_device(trt_scene* s, const trt_ray* d_items, uint32_t n, const trt_emitter* d_emitters, const trt_emitter_pick* d_pick,
                             uint32_t n_emitters, const trt_nee_mis_params* p, float total_power, float* d_radiance, float* d_moment2,
                             uint64_t* d_counters, void* stream) {
-    trt::NeeCall c;
-    int rc = trt::nee_mis_check(s, d_items, n, d_emitters, n_emitters, p, d_radiance, c);
-    if (rc != TRT_OK) return rc;
-    rc = trt::pick_pointer_check(n, d_pick);
-    if (rc != TRT_OK) return rc;
-    c.pick = true;
-    c.total_power = total_power;
-    return trt::nee_on_device(s, c, d_items, n, d_emitters, d_pick, d_radiance, d_moment2, d_counters, stream);
+    return trt::nee_device(trt::kNeeMisPickSteps, s, d_items, n, {d_emitters, d_pick, n_emitters, total_power}, p, d_radiance, d_moment2, d_counters, stream);
 }
-
 int trt_nee_mis_pick(trt_scene* s, const trt_ray* items, uint32_t n, const trt_emitter* emitters, const trt_emitter_pick* pick, uint32_t n_emitters,
                      const trt_nee_mis_params* p, float total_power, float* radiance, float* moment2, trt_stats* stats) {
-    return trt::host_form([&]() -> int {
-        trt::NeeCall c;
-        int rc = trt::nee_mis_check(s, items, n, emitters, n_emitters, p, radiance, c);
-        if (rc != TRT_OK) return rc;
-        rc = trt::pick_pointer_check(n, pick);
-        if (rc != TRT_OK) return rc;
-        if (n > 0u) {
-            rc = trt::emitter_entries_check(emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_entries_check(pick, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::nee_mis_table_check(s, emitters, n_emitters);
-            if (rc != TRT_OK) return rc;
-            rc = trt::pick_power_check(emitters, pick, n_emitters, total_power);
-            if (rc != TRT_OK) return rc;
-        }
-        c.pick = true;
-        c.total_power = total_power;
-        return trt::nee_on_host(s, c, items, n, emitters, pick, n_emitters, radiance, moment2, stats);
-    });
+    return trt::nee_host(trt::kNeeMisPickSteps, s, items, n, {emitters, pick, n_emitters, total_power}, p, radiance, moment2, stats);
 }
-
 int trt_nee_mis_pick_launch_plan(const trt_scene* s, uint32_t n, uint32_t compute_units, trt_query_plan* out) {
-    return trt::batch_launch_plan(s, n, compute_units, trt::kNeeMisPickLobeKernels, trt::kNeeShapes, out);
+    return trt::nee_plan(true, true, s, n, compute_units, out);
 }
 
 }  // extern "C"
