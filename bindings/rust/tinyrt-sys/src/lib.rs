@@ -295,6 +295,24 @@ pub struct trt_ambient_params {
     pub reserved: [u32; 7],
 }
 
+/// `enum trt_sample_source`: where the first ray of a sample of `trt_samples` comes from (0 - 2 are `enum trt_passes_source`).
+pub const TRT_SAMPLE_RAYS: u32 = 0;
+pub const TRT_SAMPLE_COSINE: u32 = 1;
+pub const TRT_SAMPLE_CONE: u32 = 2;
+pub const TRT_SAMPLE_SPHERE: u32 = 3;
+pub const TRT_SAMPLE_HEMISPHERE: u32 = 4;
+
+/// `trt_radiance_params` (accumulate stays 0), the source of the first ray and the cone's spread of `trt_samples` (96 bytes); `reserved`
+/// stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_samples_params {
+    pub path: trt_radiance_params,
+    pub source: u32,
+    pub spread: f32,
+    pub reserved: [u32; 6],
+}
+
 /// `enum trt_probe_domain`: the directions the first ray of a probe sample is drawn over.
 pub const TRT_PROBE_SPHERE: u32 = 1;
 pub const TRT_PROBE_HEMISPHERE: u32 = 2;
@@ -598,6 +616,15 @@ extern "C" {
     pub fn trt_probe_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_probe_params, d_sh: *mut f32,
                             d_counters: *mut u64, stream: *mut c_void) -> c_int;
     pub fn trt_probe_launch_plan(s: *const trt_scene, n: u32, bands: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_samples_params_default(out: *mut trt_samples_params);
+    pub fn trt_samples(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_samples_params, colors: *mut f32, directions: *mut f32,
+                       stats: *mut trt_stats) -> c_int;
+    pub fn trt_samples_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_samples_params, d_colors: *mut f32,
+                              d_directions: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_samples_launch_plan(s: *const trt_scene, n: u32, range_length: u32, compute_units: u32, out: *mut trt_query_plan) -> c_int;
+    pub fn trt_fold_samples(colors: *const f32, n: u32, p: *const trt_radiance_params, radiance: *mut f32, moment2: *mut f32) -> c_int;
+    pub fn trt_fold_samples_device(d_colors: *const f32, n: u32, p: *const trt_radiance_params, d_radiance: *mut f32, d_moment2: *mut f32,
+                                   stream: *mut c_void) -> c_int;
     pub fn trt_passes_params_default(out: *mut trt_passes_params);
     pub fn trt_passes(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_passes_params, passes: *mut f32, spent: *mut f32,
                       stats: *mut trt_stats) -> c_int;

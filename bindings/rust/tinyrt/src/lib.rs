@@ -128,6 +128,15 @@ pub enum ProbeDomain {
     Hemisphere,
 }
 
+/// Where `World::samples` takes the first ray of a sample from (`enum trt_sample_source`): the items are rays, surfels `World::gather`
+/// draws about, or points `World::probe` draws about.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum SampleSource {
+    Rays,
+    Lobe(Lobe),
+    Probe(ProbeDomain),
+}
+
 /// Where `World::passes` takes the first ray of a sample from (`enum trt_passes_source`): the items are rays, or surfels the device draws
 /// `World::gather`'s first rays about.
 #[derive(Clone, Copy, Debug, PartialEq)]
@@ -195,6 +204,24 @@ pub fn sphere_emitter(centre: Vec3, radius: Float, color: Vec3) -> sys::trt_emit
     let mut e = sys::trt_emitter::default();
     unsafe { sys::trt_emitter_init_sphere(&mut e, centre.raw(), radius, color.raw()) };
     e
+}
+
+/// The fold of `World::samples`' colours (`trt_fold_samples`; runs on the device, needs no scene): per item over all `samples_per_item`
+/// samples in order, `radiance += c / K` and `moment2 += c * c / K` in f32 - for the sources `Rays` and `Lobe` the sums `World::radiance` /
+/// `World::gather` return.  `colors` holds `samples_per_item * 3` floats per item.  Returns `(radiance, moment2)`, 3 floats per item each.
+pub fn fold_samples(colors: &[Float], samples_per_item: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+    let per_item = samples_per_item as usize * 3;
+    if per_item == 0 || colors.len() % per_item != 0 || colors.len() / per_item > u32::MAX as usize {
+        return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "colors holds n x samples_per_item x 3 floats".to_string() });
+    }
+    let n = colors.len() / per_item;
+    let mut params = sys::trt_radiance_params::default();
+    unsafe { sys::trt_radiance_params_default(&mut params) };
+    params.samples_per_ray = samples_per_item;
+    let mut radiance = vec![0.0 as Float; n * 3];
+    let mut moment2 = vec![0.0 as Float; n * 3];
+    check(unsafe { sys::trt_fold_samples(colors.as_ptr(), n as u32, &params, radiance.as_mut_ptr(), moment2.as_mut_ptr()) })?;
+    Ok((radiance, moment2))
 }
 
 pub struct World {
@@ -512,6 +539,43 @@ impl World {
             sys::trt_probe(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, sh.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok(sh)
+    }
+
+    /// Every sample's colour and first direction, unfolded (`trt_samples`): a sample to a GPU lane, where `radiance`, `gather` and `probe`
+    /// give the samples of an item one lane.  Sample `s` of item `i` runs on RNG stream `(seed, first_stream + i * samples_per_item + s, 0)`
+    /// from the first ray `source` names.  Returns `(colors, directions)`, each `samples_per_item * 3` floats per item, record
+    /// `i * samples_per_item + s`; `directions` holds the traced rays' stored directions.  `fold_samples` turns the colours of the sources
+    /// `Rays` and `Lobe` into `radiance` / `gather`'s sums.
+    pub fn samples(&mut self, items: &[[Float; 6]], samples_per_item: u32, source: SampleSource, max_bounces: u32, background: Vec3, seed: u32,
+                   first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_samples_params::default();
+        unsafe { sys::trt_samples_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.max_bounces = max_bounces;
+        params.path.background = background.raw();
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        let (source, spread) = match source {
+            SampleSource::Rays => (sys::TRT_SAMPLE_RAYS, 0.0),
+            SampleSource::Lobe(Lobe::Cosine) => (sys::TRT_SAMPLE_COSINE, 0.0),
+            SampleSource::Lobe(Lobe::Cone(spread)) => (sys::TRT_SAMPLE_CONE, spread),
+            SampleSource::Probe(ProbeDomain::Sphere) => (sys::TRT_SAMPLE_SPHERE, 0.0),
+            SampleSource::Probe(ProbeDomain::Hemisphere) => (sys::TRT_SAMPLE_HEMISPHERE, 0.0),
+        };
+        params.source = source;
+        params.spread = spread;
+        let floats = items.len() * samples_per_item as usize * 3;
+        let mut colors = vec![0.0 as Float; floats];
+        let mut directions = vec![0.0 as Float; floats];
+        check(unsafe {
+            sys::trt_samples(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, colors.as_mut_ptr(), directions.as_mut_ptr(),
+                             ptr::null_mut())
+        })?;
+        Ok((colors, directions))
     }
 
     /// The light `radiance` or `gather` folds into one colour, split by how each path ended and after how many scatters (`trt_passes`).

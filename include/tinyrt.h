@@ -56,7 +56,8 @@ extern "C" {
  *              trt_direct_mis, trt_direct_mis_device, trt_direct_mis_launch_plan; trt_emitter_pick, trt_emitter_pick_build,
  *              trt_direct_pick, trt_direct_pick_device, trt_direct_pick_launch_plan, trt_direct_mis_pick, trt_direct_mis_pick_device,
  *              trt_direct_mis_pick_launch_plan; trt_nee_pick, trt_nee_pick_device, trt_nee_pick_launch_plan, trt_nee_mis_pick,
- *              trt_nee_mis_pick_device, trt_nee_mis_pick_launch_plan. */
+ *              trt_nee_mis_pick_device, trt_nee_mis_pick_launch_plan; trt_sample_source, trt_samples_params, trt_samples_params_default,
+ *              trt_samples, trt_samples_device, trt_samples_launch_plan, trt_fold_samples, trt_fold_samples_device. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -1156,6 +1157,75 @@ int trt_nee_mis_pick_device(trt_scene *s, const trt_ray *d_items, uint32_t n, co
                             const trt_emitter_pick *d_pick, uint32_t n_emitters, const trt_nee_mis_params *p, float total_power,
                             float *d_radiance, float *d_moment2, uint64_t *d_counters, void *stream);
 int trt_nee_mis_pick_launch_plan(const trt_scene *s, uint32_t n, uint32_t compute_units, trt_query_plan *out);
+
+/* ---- Sample queries: every sample's colour and first direction, and the device fold of those records ----
+ * Every query above traces K samples per item and returns only their fold.  A caller with an estimator of its own (median of means, a
+ * clamp against fireflies, an outlier test, a histogram) or a projection of its own (more SH bands, an octahedral map, spherical
+ * Gaussians, moments) needs the samples; and the fold pins an item's K samples to one lane, so that the launch rule gives a wave 256
+ * items whatever K is.  A sample query gives every SAMPLE a lane, writes that sample's colour and on request its first ray's direction,
+ * and trt_fold_samples turns the colours into exactly the bytes trt_radiance / trt_gather would have written.
+ *  - Stream index.  K = path.samples_per_ray; [b, e) = [sample_begin, sample_end), sample_end == 0 meaning K; R = e - b.  Sample s of item i
+ *    has stream index j = first_stream + i * K + s: the numbering of every other query.
+ *  - First ray.  TRT_SAMPLE_RAYS: item i as given, as in trt_radiance.  COSINE, CONE: trt_gather's draw for that lobe and `spread`, bit
+ *    for bit.  SPHERE, HEMISPHERE: trt_probe's draw for that domain, bit for bit.  The last four draw on RNG (seed, j, 1).
+ *  - Colour.  c = CpuSampler::single_point_sampling (cpu.rs:39-65) for that ray on RNG (seed, j, 0) with budget max_bounces: exactly
+ *    what the folding queries fold for stream j.
+ *  - Outputs.  colors[3 * (i * K + s) ..] = c.  With `directions` not NULL, directions[3 * (i * K + s) ..] = the traced ray's stored
+ *    direction: RAYS: the item's direction as given; otherwise what Ray::new left (ray.rs:12-14), the d of the probe contract.  Both
+ *    buffers hold n x K x 3 f32 whatever the range.  Entries of samples outside [b, e) are never written, and no byte outside
+ *    [0, 12 n K) of either buffer is: calls over disjoint ranges fill one buffer, and a split by items (items [a, n) with
+ *    first_stream + a * K, the buffers advanced by 3 a K floats) leaves the bytes of one call.
+ *  - Nothing to trace.  An empty range touches nothing.  With max_bounces == 0 the colours of the range become +0, the colour the
+ *    reference returns; `directions` is not written, and samples / rays are counted as trt_gather counts them for that call: 0.
+ *  - stats / d_counters (samples and rays only): what trt_radiance / trt_gather / trt_probe report for the same items, range and
+ *    parameters.  kernel_ms and `d_counters` as in trt_radiance.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG: a NULL params; trt_radiance's own errors, applied to `path` with `colors` as the
+ *    required buffer; accumulate != 0 (a record is written, never added to); a source outside 0..4; with CONE a spread that is negative,
+ *    infinite or NaN; a non-zero reserved word; n * R > 2^32 - 1.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's buffers.
+ *    n == 0 succeeds and touches nothing, with or without a device.
+ *  - Order, coherence and concurrency.  The n * R samples of the call are numbered q = i' * R + s', and a wave works through a contiguous
+ *    run of q: the samples of an item travel together, then the next item's.  Nothing is sorted.  Concurrency as for the ray queries.
+ * trt_samples: HOST buffers, synchronous, staged as trt_gather's; a call that leaves records of the buffers alone (R < K, or
+ * max_bounces == 0) uploads the caller's buffers first, so what it does not write comes back as it was.
+ * trt_samples_device: buffers in HBM, asynchronous on `stream`; allocates nothing. */
+enum trt_sample_source { TRT_SAMPLE_RAYS = 0, TRT_SAMPLE_COSINE = 1, TRT_SAMPLE_CONE = 2,   /* = enum trt_passes_source */
+                         TRT_SAMPLE_SPHERE = 3, TRT_SAMPLE_HEMISPHERE = 4 };                /* trt_probe's two domains */
+typedef struct {
+    trt_radiance_params path;     /* K, max_bounces, background, seed, sample range, first_stream: trt_radiance's rules and errors;
+                                     accumulate must be 0 (TRT_ERR_INVALID_ARG): a record is written, never added to */
+    uint32_t source;              /* enum trt_sample_source */
+    float spread;                 /* CONE only: trt_gather's rule and error; not read otherwise */
+    uint32_t reserved[6];         /* zero */
+} trt_samples_params;             /* 96 B: offsets 0, 64, 68, 72 */
+void trt_samples_params_default(trt_samples_params *out);   /* path = trt_radiance_params_default, COSINE; NULL tolerated */
+int trt_samples(trt_scene *s, const trt_ray *items, uint32_t n, const trt_samples_params *p, float *colors, float *directions,
+                trt_stats *stats);
+int trt_samples_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_samples_params *p, float *d_colors,
+                       float *d_directions, uint64_t *d_counters, void *stream);
+/* How trt_samples[_device] launches n items with a range of range_length = R samples on this scene: trt_gather_launch_plan's rule and
+ * fields over the sample kernels' own table with n * R in the place of n - rays_per_wave = samples a wave owns, 256 or more once
+ * ceil(n * R / 256) exceeds wave_slots.  n * R > 2^32 - 1 is TRT_ERR_INVALID_ARG. */
+int trt_samples_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_length, uint32_t compute_units, trt_query_plan *out);
+/* The fold of sample records: for every item, over the samples of [b, e) in order, with inv_K = 1.0f / float(K), all f32, one IEEE
+ * operation per operator, nothing fused:
+ *   radiance.ch = radiance.ch + c.ch * inv_K;   moment2.ch = moment2.ch + (c.ch * c.ch) * inv_K
+ * where c = colors[3 * (i * K + s) ..].  Of `p` only samples_per_ray, sample_begin, sample_end and accumulate are read (and the reserved
+ * words, which must be zero).  The sums start from 0, or from the buffers with accumulate; `moment2` may be NULL.  An empty range zeroes
+ * the n entries unless accumulate.  `colors` holds n x K x 3 f32, `radiance` and `moment2` n x 3; no other byte is written.
+ * IDENTITY.  For source RAYS, COSINE or CONE, max_bounces > 0 and any split of [0, K) into ranges, trt_fold_samples over the records of
+ * trt_samples leaves in `radiance` / `moment2` the bytes trt_radiance / trt_gather leave for the same items and parameters (a split
+ * folded range by range with accumulate).  For SPHERE / HEMISPHERE the records and directions, folded by the probe fold above
+ * (t = b_k(d) * inv_K; sh[k].ch = sh[k].ch + c.ch * t, a sample whose direction or point has a NaN adding nothing), give trt_probe's
+ * bytes.  (Every number by its bits; a sum that is NaN is NaN in both, with a sign and payload that are not fixed.)  This is the K-aware
+ * route: the paths run a sample to a lane, and the serial chain the fold's order demands is a few operations per sample.
+ * No scene handle, like trt_variance.  The outputs must not overlap `colors`: the device form checks this from the sizes above
+ * (TRT_ERR_INVALID_ARG), as trt_denoise_device checks its buffers.  Errors, TRT_ERR_INVALID_ARG: a NULL `p`; K == 0 or a bad range; with
+ * n > 0 a NULL `colors` or `radiance`; a non-zero reserved word.  Then TRT_ERR_NO_DEVICE; n == 0 succeeds and touches nothing.
+ * trt_fold_samples: HOST buffers, synchronous (uploads, runs the device kernel, downloads; there is no CPU path).
+ * trt_fold_samples_device: buffers in HBM on the calling thread's current device, asynchronous on `stream`; allocates nothing. */
+int trt_fold_samples(const float *colors, uint32_t n, const trt_radiance_params *p, float *radiance, float *moment2);
+int trt_fold_samples_device(const float *d_colors, uint32_t n, const trt_radiance_params *p, float *d_radiance, float *d_moment2,
+                            void *stream);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

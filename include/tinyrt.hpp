@@ -236,6 +236,19 @@ public:
         sh.resize(items.size() * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);   // (bands out of range: trt_probe says so)
         check(trt_probe(get_bvh(), items.data(), (uint32_t)items.size(), &p, sh.data(), stats));
     }
+    // Every sample's colour and, with `directions`, its first ray's stored direction (trt_samples): a sample to a GPU lane where radiance(),
+    // gather() and probe() give the samples of an item one lane.  p.source says where the first ray comes from - TRT_SAMPLE_RAYS: the
+    // items are rays; COSINE, CONE: gather()'s draw about surfels; SPHERE, HEMISPHERE: probe()'s - and p.path the samples, the range
+    // (only samples [sample_begin, sample_end) are written) and the RNG numbering; accumulate must be 0.  Both vectors become
+    // items.size() x K x 3 floats, record i * K + s; what they held outside the range stays.  Start `p` from trt_samples_params_default.
+    void samples(const std::vector<trt_ray>& items, const trt_samples_params& p, std::vector<float>& colors, std::vector<float>* directions = nullptr,
+                 trt_stats* stats = nullptr) {
+        if (items.size() > 0xFFFFFFFFull) throw Error(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 items in one call");
+        const size_t floats = items.size() * (size_t)p.path.samples_per_ray * 3;
+        colors.resize(floats);
+        if (directions) directions->resize(floats);
+        check(trt_samples(get_bvh(), items.data(), (uint32_t)items.size(), &p, colors.data(), directions ? directions->data() : nullptr, stats));
+    }
     // The light radiance() or gather() folds into one colour, split by how each path ended and after how many scatters (trt_passes):
     // p.gather.lobe is the source of the first ray (TRT_PASSES_RAYS: the items are rays; TRT_PASSES_COSINE, TRT_PASSES_CONE: surfels,
     // gather()'s draws).  `sums` becomes 2 x p.depth_bins x 3 floats per item - the paths that ended at a light by depth bin, then those
@@ -279,6 +292,21 @@ private:
     trt_scene_options options_{};
     bool has_options_ = false;
 };
+
+// The fold of World::samples' colours (trt_fold_samples; runs on the device, no scene needed): per item over samples [p.sample_begin,
+// p.sample_end) of K = p.samples_per_ray in order, radiance += c / K and moment2 += c * c / K in f32 - for the sources RAYS, COSINE and CONE
+// the bytes World::radiance / World::gather return.  `colors` holds n x K x 3 floats; `radiance` (and `moment2`, if given) become n x 3
+// and continue the sums they hold when p.accumulate is set.  Of `p` nothing else is read.
+inline void fold_samples(const std::vector<float>& colors, const trt_radiance_params& p, std::vector<float>& radiance, std::vector<float>* moment2 = nullptr) {
+    const size_t per_item = (size_t)p.samples_per_ray * 3;
+    if (per_item == 0 || colors.size() % per_item != 0) throw Error(TRT_ERR_INVALID_ARG, "colors holds n x samples_per_ray x 3 floats");
+    const size_t n = colors.size() / per_item;
+    if (n > 0xFFFFFFFFull) throw Error(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 items in one call");
+    radiance.resize(n * 3);
+    if (moment2) moment2->resize(n * 3);
+    check(trt_fold_samples(colors.data(), (uint32_t)n, &p, radiance.data(), moment2 ? moment2->data() : nullptr));
+}
+
 
 // A scene compiled on the current device (trt_scene_create_on_device): the same bytes as World::get_bvh(), already resident there.
 // Owns its handle; render it through the C ABI (scene()).

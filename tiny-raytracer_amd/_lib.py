@@ -167,6 +167,14 @@ class ProbeParams(C.Structure):
     _fields_ = [("path", RadianceParams), ("domain", C.c_uint32), ("bands", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
+SAMPLE_RAYS, SAMPLE_COSINE, SAMPLE_CONE, SAMPLE_SPHERE, SAMPLE_HEMISPHERE = 0, 1, 2, 3, 4      # tinyrt.h enum trt_sample_source
+
+
+class SamplesParams(C.Structure):
+    """tinyrt.h trt_samples_params: trt_radiance_params (accumulate must be 0) and the source of a sample's first ray (96 bytes)."""
+    _fields_ = [("path", RadianceParams), ("source", C.c_uint32), ("spread", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
 PASSES_RAYS, PASSES_COSINE, PASSES_CONE = 0, 1, 2                           # tinyrt.h enum trt_passes_source (1, 2 = enum trt_lobe)
 
 
@@ -351,6 +359,13 @@ SIGNATURES = {
     "trt_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]),
     "trt_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_probe_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_samples_params_default": (None, [C.POINTER(SamplesParams)]),
+    "trt_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SamplesParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "trt_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SamplesParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "trt_samples_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
+    "trt_fold_samples": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p]),
+    "trt_fold_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_passes_params_default": (None, [C.POINTER(PassesParams)]),
     "trt_passes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "trt_passes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.c_void_p,

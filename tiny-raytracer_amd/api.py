@@ -536,6 +536,61 @@ class Scene:
         check(lib.trt_probe_launch_plan(self._h, int(n), int(bands), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    # ---- sample queries (tinyrt.h trt_samples): every sample's colour and first direction, a sample to a lane ----
+    SAMPLE_SOURCES = {"rays": _lib.SAMPLE_RAYS, "cosine": _lib.SAMPLE_COSINE, "cone": _lib.SAMPLE_CONE, "sphere": _lib.SAMPLE_SPHERE,
+                      "hemisphere": _lib.SAMPLE_HEMISPHERE}
+
+    @classmethod
+    def _samples_params(cls, samples_per_item, source="cosine", spread=0.0, **path):
+        if source not in cls.SAMPLE_SOURCES:
+            raise ValueError("source must be 'rays', 'cosine', 'cone', 'sphere' or 'hemisphere'")
+        p = _lib.SamplesParams()
+        lib.trt_samples_params_default(C.byref(p))
+        p.path = cls._radiance_params(samples_per_item, **path)
+        p.source, p.spread = cls.SAMPLE_SOURCES[source], float(spread)
+        return p
+
+    def samples(self, items, samples_per_item, source="cosine", spread=0.0, max_bounces=50, background=(0.0, 0.0, 0.0), seed=1, first_stream=0,
+                sample_begin=0, sample_end=None, colors=None, directions=False):
+        """trt_samples: the colour of EVERY sample of items float32 [n, 6], unfolded.  Sample s of item i, of samples_per_item = K, runs on
+        RNG stream (seed, first_stream + i * K + s, 0); its first ray is the item itself (source "rays", as radiance()), gather()'s draw
+        ("cosine", "cone" with `spread`) or probe()'s ("sphere", "hemisphere"), drawn on stream (.., 1).  Only samples [sample_begin,
+        sample_end) are traced and written (None: K): calls over disjoint ranges fill one buffer.  `colors`: float32 [n, K, 3] to write
+        into, None allocates zeros.  `directions`: True allocates float32 [n, K, 3] for the traced rays' stored directions, an array is
+        written into, False / None = not wanted.  Returns (colors[n, K, 3], directions or None, stats with samples and rays).
+        fold_samples() turns the colours into radiance() / gather()'s bytes, sh.project() colours and directions into probe()'s."""
+        r, _ = _rays_and_t_max(items, None)
+        n, k = len(r), int(samples_per_item)
+        p = self._samples_params(k, source, spread, max_bounces=max_bounces, background=background, seed=seed, first_stream=first_stream,
+                                 sample_begin=sample_begin, sample_end=sample_end)
+        if colors is None:
+            colors = np.zeros((n, k, 3), np.float32)
+        if directions is True:
+            directions = np.zeros((n, k, 3), np.float32)
+        elif directions is False:
+            directions = None
+        for a in (colors, directions):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, k, 3))
+        st = Stats()
+        check(lib.trt_samples(self._h, r.ctypes.data if n else None, n, C.byref(p), colors.ctypes.data if n else None,
+                              directions.ctypes.data if directions is not None and n else None, C.byref(st)))
+        return colors, directions, st.as_dict()
+
+    def samples_device(self, d_items_ptr, n, d_colors_ptr, d_directions_ptr=0, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue samples() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n x K x 12 bytes of colours and,
+        where wanted, of directions) on the current device; asynchronous on the stream, allocates nothing.  `params`: samples()'s
+        keywords, samples_per_item included."""
+        p = self._samples_params(**params)
+        check(lib.trt_samples_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_colors_ptr), C.c_void_p(d_directions_ptr),
+                                     C.c_void_p(d_counters_ptr), C.c_void_p(stream_ptr)))
+
+    def samples_plan(self, n, range_length=None, compute_units=0):
+        """trt_samples_launch_plan: how samples() launches n items with range_length samples each (None: 1) on this scene, as a dict with
+        gather_plan()'s fields; rays_per_wave = samples a wave owns."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_samples_launch_plan(self._h, int(n), 1 if range_length is None else int(range_length), int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     # ---- passes queries (tinyrt.h trt_passes): the gathered radiance split by the depth and the end of each path ----
     SOURCES = {"rays": _lib.PASSES_RAYS, "cosine": _lib.PASSES_COSINE, "cone": _lib.PASSES_CONE}
 
@@ -1001,6 +1056,45 @@ def variance_device(d_accum_ptr, d_moment2_ptr, npixels, samples_per_pixel, d_va
     """Enqueue variance() on buffers already in HBM (device pointers as integers; npixels floats out); asynchronous on the stream."""
     check(lib.trt_variance_device(C.c_void_p(d_accum_ptr), C.c_void_p(d_moment2_ptr), int(npixels), int(samples_per_pixel),
                                   C.c_void_p(d_variance_ptr), C.c_void_p(stream_ptr)))
+
+
+def _fold_params(samples_per_item, sample_begin=0, sample_end=0, accumulate=False):
+    p = _lib.RadianceParams()
+    lib.trt_radiance_params_default(C.byref(p))
+    p.samples_per_ray, p.sample_begin, p.sample_end, p.accumulate = int(samples_per_item), int(sample_begin), int(sample_end), 1 if accumulate else 0
+    return p
+
+
+def fold_samples(colors, samples_per_item, sample_begin=0, sample_end=0, radiance=None, moment2=None, accumulate=False):
+    """trt_fold_samples: Scene.samples()'s colours float32 [n, K, 3] folded per item over samples [sample_begin, sample_end) (0: K) in
+    order with the imager's rule, radiance += c / K and moment2 += c * c / K in f32 - for colours of source "rays", "cosine" or "cone" the
+    bytes Scene.radiance() / Scene.gather() return.  `radiance`, `moment2`: float32 [n, 3] to write or, with accumulate, to continue (the
+    fold of a later range; changed in place); radiance=None allocates one, moment2=None: True allocates one, None = not wanted.  Runs
+    on the device; there is no CPU path.  Returns (radiance[n, 3], moment2 or None)."""
+    c = np.ascontiguousarray(colors, np.float32)
+    k = int(samples_per_item)
+    if c.ndim != 3 or c.shape[1] != k or c.shape[2] != 3:
+        raise ValueError("colors must have the shape [n, samples_per_item, 3]")
+    n = c.shape[0]
+    if radiance is None:
+        radiance = np.zeros((n, 3), np.float32)
+    if moment2 is True:
+        moment2 = np.zeros((n, 3), np.float32)
+    for a in (radiance, moment2):
+        assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, 3))
+    p = _fold_params(k, sample_begin, sample_end, accumulate)
+    check(lib.trt_fold_samples(c.ctypes.data if n else None, n, C.byref(p), radiance.ctypes.data if n else None,
+                               moment2.ctypes.data if moment2 is not None and n else None))
+    return radiance, moment2
+
+
+def fold_samples_device(d_colors_ptr, n, samples_per_item, d_radiance_ptr, d_moment2_ptr=0, sample_begin=0, sample_end=0, accumulate=False,
+                        stream_ptr=0):
+    """Enqueue fold_samples() on buffers already in HBM (device pointers as integers: n x K x 12 bytes of colours, n x 12 bytes of sums
+    each; the sums must not overlap the colours); asynchronous on the stream, allocates nothing.  accumulate continues the sums."""
+    p = _fold_params(samples_per_item, sample_begin, sample_end, accumulate)
+    check(lib.trt_fold_samples_device(C.c_void_p(d_colors_ptr), int(n), C.byref(p), C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr),
+                                      C.c_void_p(stream_ptr)))
 
 
 def select_pixels(accum, moment2, samples_per_pixel, samples_done, rel_tol, abs_tol=0.0, candidates=None):

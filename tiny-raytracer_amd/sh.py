@@ -56,3 +56,27 @@ def irradiance(coeffs, normal, domain="sphere"):
     a = np.array([COSINE_LOBE[BAND_OF[k]] for k in range(count)])
     y = basis(normal, _bands_of(count)).astype(np.float64)
     return SOLID_ANGLE[domain] * (coeffs * (a * y)[..., None]).sum(axis=-2)
+
+
+def project(colors, directions, bands=3, begin=0, end=None, sh=None, points=None):
+    """float32 [n, bands ** 2, 3]: the probe fold of tinyrt.h over Scene.samples()'s records - colors and directions float32 [n, K, 3] of
+    source "sphere" or "hemisphere" - in numpy f32, one IEEE operation per operator: for samples [begin, end) in order (None: K)
+    t = b_k(d) * inv_K; sh[k].ch = sh[k].ch + c.ch * t, inv_K = 1 / K, from `sh` (not changed) or from 0.  A sample whose direction has a
+    NaN adds nothing; with `points` float32 [n, 3] (the items' points) neither does a sample of an item whose point has one - the rule
+    under which the result is Scene.probe()'s, byte for byte."""
+    colors, directions = np.asarray(colors, f32), np.asarray(directions, f32)
+    if colors.ndim != 3 or colors.shape[2] != 3 or directions.shape != colors.shape:
+        raise ValueError("colors and directions must have the same shape [n, K, 3]")
+    n, k = colors.shape[0], colors.shape[1]
+    end = k if end is None else end
+    inv = f32(1.0) / f32(k)
+    out = np.zeros((n, bands * bands, 3), f32) if sh is None else np.array(sh, f32)
+    dead = np.zeros(n, bool) if points is None else np.isnan(np.asarray(points, f32)).any(axis=-1)
+    with np.errstate(all="ignore"):
+        for s in range(begin, end):
+            t = basis(directions[:, s, :], bands) * inv                     # [n, C]
+            added = out + colors[:, s, None, :] * t[:, :, None]
+            folds = ~(np.isnan(directions[:, s, :]).any(axis=1) | dead)
+            out = np.where(folds[:, None, None], added, out)
+    assert out.dtype == f32
+    return out
