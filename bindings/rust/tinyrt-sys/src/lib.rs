@@ -366,6 +366,17 @@ pub struct trt_nee_mis_params {
     pub reserved: [u32; 7],
 }
 
+/// `trt_nee_mis_params` (accumulate stays 0; the heuristic is read only when `weighted` is 1), whether the sample is the weighted
+/// queries' and `trt_nee_mis_pick`'s `total_power`, for `trt_nee_samples` (192 bytes); `reserved` stays zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct trt_nee_samples_params {
+    pub query: trt_nee_mis_params,
+    pub weighted: u32,
+    pub total_power: f32,
+    pub reserved: [u32; 6],
+}
+
 /// One record of the alias table `trt_direct_pick` / `trt_direct_mis_pick` choose their emitter through (16 bytes): slot k keeps
 /// emitter k where the second draw is below `q`, else takes `alias`; `prob` is the probability with which emitter k is chosen.
 #[repr(C)]
@@ -625,6 +636,14 @@ extern "C" {
     pub fn trt_fold_samples(colors: *const f32, n: u32, p: *const trt_radiance_params, radiance: *mut f32, moment2: *mut f32) -> c_int;
     pub fn trt_fold_samples_device(d_colors: *const f32, n: u32, p: *const trt_radiance_params, d_radiance: *mut f32, d_moment2: *mut f32,
                                    stream: *mut c_void) -> c_int;
+    pub fn trt_nee_samples_params_default(out: *mut trt_nee_samples_params);
+    pub fn trt_nee_samples(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
+                           n_emitters: u32, p: *const trt_nee_samples_params, colors: *mut f32, directions: *mut f32, stats: *mut trt_stats) -> c_int;
+    pub fn trt_nee_samples_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, d_emitters: *const trt_emitter,
+                                  d_pick: *const trt_emitter_pick, n_emitters: u32, p: *const trt_nee_samples_params, d_colors: *mut f32,
+                                  d_directions: *mut f32, d_counters: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn trt_nee_samples_launch_plan(s: *const trt_scene, n: u32, range_length: u32, weighted: u32, pick: u32, compute_units: u32,
+                                       out: *mut trt_query_plan) -> c_int;
     pub fn trt_passes_params_default(out: *mut trt_passes_params);
     pub fn trt_passes(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_passes_params, passes: *mut f32, spent: *mut f32,
                       stats: *mut trt_stats) -> c_int;

@@ -718,6 +718,50 @@ impl World {
         Ok((radiance, moment2))
     }
 
+    /// Every sample's colour and first direction of the next-event queries, unfolded (`trt_nee_samples`): `samples` for `nee`, `nee_mis`,
+    /// `nee_pick` and `nee_mis_pick`.  `heuristic` (`None`: unweighted) and `pick` (`None`: the uniform choice; else the records and, for
+    /// the weighted sample, the total `pick_table` reported) select the sibling whose sample is written, bit for bit.  Returns
+    /// `(colors, directions)`, each `samples_per_item * 3` floats per item, record `i * samples_per_item + s`; `fold_samples` turns the
+    /// colours into the sibling's sums.
+    pub fn nee_samples(&mut self, items: &[[Float; 6]], emitters: &[sys::trt_emitter], pick: Option<(&[sys::trt_emitter_pick], Float)>,
+                       samples_per_item: u32, source: PassesSource, source_is_diffuse: bool, heuristic: Option<MisHeuristic>, shadow_end: Float,
+                       max_bounces: u32, background: Vec3, seed: u32, first_stream: u32) -> Result<(Vec<Float>, Vec<Float>), Error> {
+        if items.len() > u32::MAX as usize || emitters.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items or emitters in one call".to_string() });
+        }
+        if let Some((records, _)) = pick {
+            if records.len() != emitters.len() {
+                return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "the pick table needs one record per emitter".to_string() });
+            }
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_nee_samples_params::default();
+        unsafe { sys::trt_nee_samples_params_default(&mut params) };
+        params.query.nee = nee_params(samples_per_item, source, source_is_diffuse, shadow_end, max_bounces, background, seed, first_stream);
+        if let Some(h) = heuristic {
+            params.weighted = 1;
+            params.query.heuristic = match h {
+                MisHeuristic::Balance => sys::TRT_MIS_BALANCE,
+                MisHeuristic::Power => sys::TRT_MIS_POWER,
+            };
+        }
+        let pick_ptr = match pick {
+            Some((records, total)) => {
+                params.total_power = total;
+                records.as_ptr()
+            }
+            None => ptr::null(),
+        };
+        let floats = items.len() * samples_per_item as usize * 3;
+        let mut colors = vec![0.0 as Float; floats];
+        let mut directions = vec![0.0 as Float; floats];
+        check(unsafe {
+            sys::trt_nee_samples(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, emitters.as_ptr(), pick_ptr, emitters.len() as u32,
+                                 &params, colors.as_mut_ptr(), directions.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((colors, directions))
+    }
+
     /// Frees the device scratch (render workspaces, frame buffers) the compiled scene caches between renders.
     pub fn trim(&mut self) -> Result<(), Error> {
         if self.scene.is_null() {

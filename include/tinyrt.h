@@ -57,7 +57,9 @@ extern "C" {
  *              trt_direct_pick, trt_direct_pick_device, trt_direct_pick_launch_plan, trt_direct_mis_pick, trt_direct_mis_pick_device,
  *              trt_direct_mis_pick_launch_plan; trt_nee_pick, trt_nee_pick_device, trt_nee_pick_launch_plan, trt_nee_mis_pick,
  *              trt_nee_mis_pick_device, trt_nee_mis_pick_launch_plan; trt_sample_source, trt_samples_params, trt_samples_params_default,
- *              trt_samples, trt_samples_device, trt_samples_launch_plan, trt_fold_samples, trt_fold_samples_device. */
+ *              trt_samples, trt_samples_device, trt_samples_launch_plan, trt_fold_samples, trt_fold_samples_device;
+ *              trt_nee_samples_params, trt_nee_samples_params_default, trt_nee_samples, trt_nee_samples_device,
+ *              trt_nee_samples_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -1226,6 +1228,75 @@ int trt_samples_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_lengt
 int trt_fold_samples(const float *colors, uint32_t n, const trt_radiance_params *p, float *radiance, float *moment2);
 int trt_fold_samples_device(const float *d_colors, uint32_t n, const trt_radiance_params *p, float *d_radiance, float *d_moment2,
                             void *stream);
+
+/* ---- Sample-parallel next-event queries: every sample's colour of trt_nee / trt_nee_mis / trt_nee_pick / trt_nee_mis_pick ----
+ * The four next-event queries trace K samples per item and return only their fold, a lane owning an item for all K.  trt_nee_samples
+ * is to them what trt_samples is to trt_radiance / trt_gather: a lane owns one SAMPLE, the call writes that sample's colour and on
+ * request its first ray's direction, and trt_fold_samples turns the colours into the folding query's bytes.  A caller with a robust
+ * estimator of its own (median of means, a clamp against the 1 / d^2 tail) gets the samples; a caller that wants the sums gets them
+ * from a launch that fills the device whatever K is.
+ *  - Which query.  `weighted` and `pick` select the sibling: weighted == 0 and pick == NULL: trt_nee; weighted == 1 and pick == NULL:
+ *    trt_nee_mis; weighted == 0 and pick != NULL: trt_nee_pick; weighted == 1 and pick != NULL: trt_nee_mis_pick, whose `total_power`
+ *    argument is p->total_power.  p->query.nee is read always and means what it means to trt_nee; p->query.heuristic and
+ *    p->query.reserved are read only when weighted != 0; total_power only when weighted != 0 and pick != NULL.
+ *  - Stream index.  K = samples_per_ray of p->query.nee.gather.path; [b, e) = [sample_begin, sample_end), sample_end == 0 meaning K;
+ *    R = e - b.  Sample s of item i has stream index j = first_stream + i * K + s: the numbering of every other query.
+ *  - Colour.  colors[3 * (i * K + s) ..] = the colour the sibling folds for sample s of item i, BIT FOR BIT: the path on (seed, j, 0),
+ *    a drawn first ray on (seed, j, 1), the vertex draws on (seed, j, 2 + d), the hiding of diffusely reached lights, the last-vertex
+ *    rule, source_is_diffuse, shadow_end, the alias clamp, and the weights wl / wb with the weighted form's csh: all the sibling's.  The
+ *    sources are trt_nee's three (TRT_PASSES_RAYS, _COSINE, _CONE).
+ *  - Direction.  With `directions` not NULL, directions[3 * (i * K + s) ..] = the first ray's stored direction, as trt_samples writes it.
+ *  - Ranges.  Both buffers hold n x K x 3 f32 whatever the range.  Only the records of [b, e) are written, and no byte outside
+ *    [0, 12 n K) of either buffer is: calls over disjoint ranges fill one buffer, and a split by items (items [a, n) with
+ *    first_stream + a * K, the buffers advanced by 3 a K floats) leaves the bytes of one call.  An empty range touches nothing.  With
+ *    max_bounces == 0 the colours of the range become +0 and `directions` is not written; samples and rays are counted 0, as the
+ *    siblings count them.
+ *  - stats / d_counters (samples and rays only) count the n x R samples of the range; rays are the sibling's for the same range: the
+ *    path walks plus the shadow walks.  An empty shadow range and a dead sample walk nothing.  kernel_ms and `d_counters` as in trt_nee.
+ *  - Errors, before any device work, TRT_ERR_INVALID_ARG, IN THIS ORDER: a NULL `p`; (1) trt_nee's own errors in trt_nee's order,
+ *    applied to p->query.nee with `colors` as the required buffer, as far as its table size, shadow_end, source_is_diffuse and reserved
+ *    words; (2) accumulate != 0 (a record is written, never added to: trt_samples' rule and message); (3) weighted > 1; (4) when
+ *    weighted, trt_nee_mis' own fields: the heuristic, then p->query.reserved; (5) a non-zero word of p->reserved; (6) n * R > 2^32 - 1;
+ *    (7) the table checks of the sibling that (weighted, pick != NULL) selects, unchanged and in the sibling's order - trt_nee: the
+ *    emitter records; trt_nee_mis: the emitter records, the table rule; trt_nee_pick: the emitter records, the pick records;
+ *    trt_nee_mis_pick: the emitter records, the pick records, the table rule, total_power, prob by bits.  THE HOST FORM READS THE
+ *    TABLES; THE DEVICE FORM CHECKS ONLY WHAT THE SIBLINGS' DEVICE FORMS CHECK, and a wrong pick table's reads stay inside the E
+ *    records of either table, as theirs do.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's buffers.  n == 0 succeeds
+ *    and touches nothing, with or without a device.
+ *  - Order, coherence and concurrency as in trt_samples: the n * R samples are numbered q = i' * R + s', a wave works through a
+ *    contiguous run of q.
+ * IDENTITY.  For max_bounces > 0 and any split of [0, K) into ranges, trt_fold_samples over the records of trt_nee_samples leaves in
+ * `radiance` / `moment2` the bytes the folding query - trt_nee, trt_nee_mis, trt_nee_pick or trt_nee_mis_pick, by (weighted, pick) -
+ * leaves for the same arguments (a split folded range by range with accumulate), and stats agree.  Every number by its bits.  It holds
+ * because the next-event kernels' fold is trt_radiance's, operator for operator.  The n x K x 12 bytes of records are the caller's
+ * memory.  A split of the range folds part by part with accumulate into the same sums but does not shrink the buffer, which holds
+ * n x K records whatever the range; a caller short of memory splits by ITEMS, tracing and folding one chunk of items after the other
+ * through one buffer of chunk x K records.
+ * trt_nee_samples: HOST buffers, synchronous, staged as trt_samples' (items, colours, directions, counters) with the emitter table and
+ * the pick table in the call's one device allocation; a call that leaves records of the buffers alone (R < K, or max_bounces == 0)
+ * uploads the caller's buffers first, so what it does not write comes back as it was.
+ * trt_nee_samples_device: buffers and tables in HBM, asynchronous on `stream`; allocates nothing. */
+typedef struct trt_nee_samples_params {
+    trt_nee_mis_params query;     /* 160 B.  query.nee is read always and means what it means to trt_nee; query.heuristic and
+                                     query.reserved are read only when weighted != 0 (reserved must then be 0) */
+    uint32_t weighted;            /* 0: the sample of trt_nee / trt_nee_pick; 1: of trt_nee_mis / trt_nee_mis_pick */
+    float    total_power;         /* read only when weighted != 0 and pick != NULL (trt_nee_mis_pick's argument) */
+    uint32_t reserved[6];         /* zero */
+} trt_nee_samples_params;         /* 192 B: offsets 0, 160, 164, 168 */
+void trt_nee_samples_params_default(trt_nee_samples_params *out);   /* query = trt_nee_mis_params_default's, weighted 0, total_power 0;
+                                                                       NULL tolerated */
+int trt_nee_samples(trt_scene *s, const trt_ray *items, uint32_t n, const trt_emitter *emitters,
+                    const trt_emitter_pick *pick /* NULL: uniform choice */, uint32_t n_emitters, const trt_nee_samples_params *p,
+                    float *colors, float *directions /* NULL: not wanted */, trt_stats *stats);
+int trt_nee_samples_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_emitter *d_emitters,
+                           const trt_emitter_pick *d_pick, uint32_t n_emitters, const trt_nee_samples_params *p, float *d_colors,
+                           float *d_directions, uint64_t *d_counters, void *stream);
+/* How trt_nee_samples[_device] launches n items with a range of range_length = R samples on this scene: trt_nee_launch_plan's rule and
+ * fields over the sample-parallel next-event kernels' own table for (weighted, pick), each 0 or not, with n * R in the place of n -
+ * rays_per_wave = samples a wave owns, 256 or more once ceil(n * R / 256) exceeds wave_slots.  n * R > 2^32 - 1 is
+ * TRT_ERR_INVALID_ARG. */
+int trt_nee_samples_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_length, uint32_t weighted, uint32_t pick,
+                                uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Denoising a frame with its feature buffers: an edge-avoiding a-trous wavelet filter ----
  * Takes the frame as trt_render leaves it (`color`, 3 f32 per pixel, required) and the guides as trt_render_aov writes them (`albedo`

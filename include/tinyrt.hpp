@@ -249,6 +249,21 @@ public:
         if (directions) directions->resize(floats);
         check(trt_samples(get_bvh(), items.data(), (uint32_t)items.size(), &p, colors.data(), directions ? directions->data() : nullptr, stats));
     }
+    // Every sample's colour of the next-event queries (trt_nee_samples): samples() for nee(), nee_mis(), nee_pick() and nee_mis_pick().
+    // p.weighted and `pick` (nullptr: the uniform choice; else one record per emitter) select the sibling whose sample is written, bit
+    // for bit; p.query.nee is nee()'s parameter struct (accumulate must be 0), p.total_power nee_mis_pick()'s argument.  Both vectors
+    // become items.size() x K x 3 floats, record i * K + s; what they held outside the range stays.  fold_samples() turns the colours
+    // into the sibling's sums.  Start `p` from trt_nee_samples_params_default.
+    void nee_samples(const std::vector<trt_ray>& items, const std::vector<trt_emitter>& emitters, const std::vector<trt_emitter_pick>* pick,
+                     const trt_nee_samples_params& p, std::vector<float>& colors, std::vector<float>* directions = nullptr, trt_stats* stats = nullptr) {
+        if (items.size() > 0xFFFFFFFFull) throw Error(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 items in one call");
+        if (pick && pick->size() != emitters.size()) throw Error(TRT_ERR_INVALID_ARG, "pick holds one record per emitter");
+        const size_t floats = items.size() * (size_t)p.query.nee.gather.path.samples_per_ray * 3;
+        colors.resize(floats);
+        if (directions) directions->resize(floats);
+        check(trt_nee_samples(get_bvh(), items.data(), (uint32_t)items.size(), emitters.data(), pick ? pick->data() : nullptr, (uint32_t)emitters.size(), &p,
+                              colors.data(), directions ? directions->data() : nullptr, stats));
+    }
     // The light radiance() or gather() folds into one colour, split by how each path ended and after how many scatters (trt_passes):
     // p.gather.lobe is the source of the first ray (TRT_PASSES_RAYS: the items are rays; TRT_PASSES_COSINE, TRT_PASSES_CONE: surfels,
     // gather()'s draws).  `sums` becomes 2 x p.depth_bins x 3 floats per item - the paths that ended at a light by depth bin, then those

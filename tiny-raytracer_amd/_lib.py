@@ -198,6 +198,12 @@ class NeeMisParams(C.Structure):
     _fields_ = [("nee", NeeParams), ("heuristic", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class NeeSamplesParams(C.Structure):
+    """tinyrt.h trt_nee_samples_params: trt_nee_mis_params (accumulate must be 0; heuristic read only when weighted), whether the sample
+    is the weighted queries' and trt_nee_mis_pick's total_power (192 bytes)."""
+    _fields_ = [("query", NeeMisParams), ("weighted", C.c_uint32), ("total_power", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
 class DirectMisParams(C.Structure):
     """tinyrt.h trt_direct_mis_params: trt_direct_params and the heuristic that weights a shadow ray against a cosine-lobe ray from the
     surfel (128 bytes)."""
@@ -366,6 +372,12 @@ SIGNATURES = {
     "trt_samples_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_fold_samples": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p]),
     "trt_fold_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_nee_samples_params_default": (None, [C.POINTER(NeeSamplesParams)]),
+    "trt_nee_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeSamplesParams), C.c_void_p,
+                                  C.c_void_p, C.POINTER(Stats)]),
+    "trt_nee_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeSamplesParams),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_nee_samples_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_passes_params_default": (None, [C.POINTER(PassesParams)]),
     "trt_passes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "trt_passes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PassesParams), C.c_void_p, C.c_void_p, C.c_void_p,

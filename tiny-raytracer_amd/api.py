@@ -702,6 +702,78 @@ class Scene:
         n items on this scene, as a dict with gather_plan()'s fields."""
         return self._emitter_query_plan("nee", n, compute_units, mis, pick)
 
+    # ---- sample-parallel next-event queries (tinyrt.h trt_nee_samples): every sample's colour of nee(), a lane per sample ----
+    @classmethod
+    def _nee_samples_params(cls, samples_per_item, mis=None, total=None, **nee):
+        """A trt_nee_samples_params: nee()'s keywords (accumulate is not one), weighted where mis is given, total_power = total or 0."""
+        q = cls._nee_params(samples_per_item, mis=mis, **nee)
+        p = _lib.NeeSamplesParams()
+        lib.trt_nee_samples_params_default(C.byref(p))
+        if mis is None:
+            p.query.nee = q
+        else:
+            p.query, p.weighted = q, 1
+        p.total_power = 0.0 if total is None else float(total)
+        return p
+
+    def nee_samples(self, items, emitters, samples_per_item, source="cosine", spread=0.0, shadow_end=None, source_is_diffuse=False, max_bounces=50,
+                    background=(0.0, 0.0, 0.0), seed=1, first_stream=0, sample_begin=0, sample_end=None, mis=None, pick=None, colors=None,
+                    directions=False):
+        """trt_nee_samples: the colour of EVERY sample of nee(), unfolded, traced a sample to a lane.  Keyword meanings are nee()'s: mis
+        None | "balance" | "power", pick None or lights.pick_table(emitters) (with mis the (records, total) pair); together they choose
+        the sibling whose sample is written - nee(), its mis, its pick or its mis + pick form - bit for bit.  Only samples [sample_begin,
+        sample_end) are traced and written (None: K): calls over disjoint ranges fill one buffer.  `colors`, `directions` and the returns
+        as in samples(): (colors[n, K, 3], directions or None, stats with samples and rays = path segments plus shadow walks).
+        fold_samples() turns the colours into the sibling's radiance / moment2 bytes."""
+        r, _ = _rays_and_t_max(items, None)
+        n, k = len(r), int(samples_per_item)
+        e = self._emitter_table(emitters)
+        d_pick, total = None, None
+        if pick is not None:
+            pick, total = self._pick_and_total(pick, mis)
+            pk = np.ascontiguousarray(pick)
+            if pk.dtype != PICK_DTYPE or pk.shape != (len(e),):
+                raise ValueError("pick must be lights.PICK_DTYPE records, one per emitter")
+            d_pick = pk.ctypes.data if len(pk) else None
+        p = self._nee_samples_params(k, mis=mis, total=total, source=source, spread=spread, shadow_end=shadow_end, source_is_diffuse=source_is_diffuse,
+                                     max_bounces=max_bounces, background=background, seed=seed, first_stream=first_stream, sample_begin=sample_begin,
+                                     sample_end=sample_end)
+        if colors is None:
+            colors = np.zeros((n, k, 3), np.float32)
+        if directions is True:
+            directions = np.zeros((n, k, 3), np.float32)
+        elif directions is False:
+            directions = None
+        for a in (colors, directions):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, k, 3))
+        st = Stats()
+        check(lib.trt_nee_samples(self._h, r.ctypes.data if n else None, n, e.ctypes.data if len(e) else None, d_pick, len(e), C.byref(p),
+                                  colors.ctypes.data if n else None, directions.ctypes.data if directions is not None and n else None, C.byref(st)))
+        return colors, directions, st.as_dict()
+
+    def nee_samples_device(self, d_items_ptr, n, d_emitters_ptr, n_emitters, d_colors_ptr, d_directions_ptr=0, d_counters_ptr=0, stream_ptr=0,
+                           pick=None, **params):
+        """Enqueue nee_samples() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n_emitters x 80 bytes of
+        trt_emitter records, n x K x 12 bytes of colours and, where wanted, of directions) on the current device; asynchronous on the
+        stream, allocates nothing.  `params`: nee_samples()'s keywords, samples_per_item and mis included.  pick: the device pointer of
+        the n_emitters x 16 bytes of lights.pick_table's records, or with mis (pointer, total); the device form checks neither table."""
+        mis = params.pop("mis", None)
+        d_pick_ptr, total = None, None
+        if pick is not None:
+            d_pick_ptr, total = self._pick_and_total(pick, mis)
+        p = self._nee_samples_params(mis=mis, total=total, **params)
+        check(lib.trt_nee_samples_device(self._h, C.c_void_p(d_items_ptr), int(n), C.c_void_p(d_emitters_ptr), C.c_void_p(d_pick_ptr), int(n_emitters),
+                                         C.byref(p), C.c_void_p(d_colors_ptr), C.c_void_p(d_directions_ptr), C.c_void_p(d_counters_ptr),
+                                         C.c_void_p(stream_ptr)))
+
+    def nee_samples_plan(self, n, range_length=None, mis=None, pick=False, compute_units=0):
+        """trt_nee_samples_launch_plan: how nee_samples() launches n items with range_length samples each (None: 1) on this scene with the
+        kernels of (mis given, pick given), as a dict with gather_plan()'s fields; rays_per_wave = samples a wave owns."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_nee_samples_launch_plan(self._h, int(n), 1 if range_length is None else int(range_length), 0 if mis is None else 1,
+                                              0 if pick is None or pick is False else 1, int(compute_units), C.byref(plan)))
+        return plan.as_dict()
+
     def compact_nodes(self):
         """The culling tree as 16-byte nodes (f16 boxes rounded outward) if the scene is walked from global memory:
         (lo[n,3] float16, hi[n,3] float16, link[n] uint32), else None."""
