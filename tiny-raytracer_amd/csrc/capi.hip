@@ -122,6 +122,8 @@ struct Defaults {
     uint32_t flat_literal = 2;                    // TRT_FLAT_LITERAL: the lock-step kernel compiled per scene at run time (literal_kernel.h): 0 never, 1 at the first
                                                   // streamed render of the scene, unset (2): at the first render call of kLiteralAutoSamples samples or more
     bool flat_literal_test_fail = false;          // TRT_FLAT_LITERAL_TEST_FAIL=1: that compilation is handed an empty source (tests of the fallback)
+    uint32_t flat_literal_pairs = kLiteralIntervalPairs;   // TRT_FLAT_LITERAL_PAIRS (3 ... 8), TRT_FLAT_LITERAL_PLANES (0 ... 8): the registers of that kernel's
+    uint32_t flat_literal_planes = kLiteralPlaneRegs;      // interval cache (flat_literal.h); a value out of range leaves the built-in one; 3 and 0: no cache
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -148,6 +150,8 @@ const Defaults& defaults() {
         if (const char* e = env("TRT_NEAREST_FIRST")) x.nearest_first = atoi(e) != 0;
         if (const char* e = env("TRT_FLAT_LITERAL")) x.flat_literal = atoi(e) != 0 ? 1u : 0u;
         if (const char* e = env("TRT_FLAT_LITERAL_TEST_FAIL")) x.flat_literal_test_fail = atoi(e) != 0;
+        if (const char* e = env("TRT_FLAT_LITERAL_PAIRS")) { const int v = atoi(e); if (v >= 3 && v <= 8) x.flat_literal_pairs = (uint32_t)v; }
+        if (const char* e = env("TRT_FLAT_LITERAL_PLANES")) { const int v = atoi(e); if (v >= 0 && v <= 8 && *e >= '0' && *e <= '9') x.flat_literal_planes = (uint32_t)v; }
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -311,6 +315,9 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
             const uint64_t call_samples = (uint64_t)cam->width * rows * (ra.sample_end - ra.sample_begin);
             lit.wanted = defaults().flat_literal == 1u || call_samples >= kLiteralAutoSamples;
             lit.empty_source = defaults().flat_literal_test_fail;
+            // TRT_FLAT_REUSE=0 asks for every box in full: no cache either
+            lit.interval_pairs = defaults().flat_reuse ? defaults().flat_literal_pairs : 3u;
+            lit.plane_regs = defaults().flat_reuse ? defaults().flat_literal_planes : 0u;
         }
         const LiteralScope lit_scope(lit.slot ? &lit : nullptr);
         hipError_t le;

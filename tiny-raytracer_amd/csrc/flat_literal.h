@@ -146,6 +146,198 @@ inline bool flat_literal_asm(const void* leaf_list, uint32_t n_leaves, const uin
     return true;
 }
 
+// ---- the interval cache ----
+// flat_literal_asm keeps an interval only from leaf i-1 to leaf i: the rule of the run-time loop, which held three intervals and chose
+// per box with scalar branches.  A text written per scene can keep more, because which interval sits in which register is decided while
+// the text is written: flat_literal_cached_asm puts a CACHED STREAM in front of flat_literal_asm's text.
+//   * It is entered only at i == 0 - where every new ray starts - and runs the leaves in walk order to the end or to a stack-full exit.
+//     t_best is constant within one call of the block, so an x interval (folded with t_min / t_best) is as good at leaf 17 as at leaf 1.
+//   * `interval_pairs` register pairs hold intervals: (xe xx) (ye yx) (ze zx), then (c0 c1) (c2 c3) ...  Any pair holds any axis' interval;
+//     each leaf's v_max3 / v_min3 name the pairs that hold its three.  No moves.
+//   * An interval is found again only if both plane words are the earlier ones bit for bit, on the same axis, both finite (flat_reuse.h).
+//   * A pair is taken by farthest next use (optimal for a fixed sequence: Belady), ties by the lowest pair, never one the current leaf
+//     needs.  An empty pair, and one whose interval no later leaf uses, count as never used again.
+//   * `plane_regs` further registers (behind the pairs among c0 ...) hold single plane distances fl(fl(p - o) * inv): a finite plane that
+//     a LATER COMPUTED interval of the same axis names again is written there instead of t0 / t1 - the same two instructions on the same
+//     operands - and read from there.  Taken by farthest next use as well; a plane whose next use lies farther than every resident's goes
+//     through t0 / t1.  The interval's two instructions keep their operand order: the lo plane's distance, then the hi plane's.
+//   * The push, the link, the ballot behind every second leaf: as in flat_literal_asm, and the ballot's exit IS that text's exit (400 + k).
+// An entry at i > 0 (after a stack-full exit) goes to flat_literal_asm's text, which follows whole and unchanged behind label 1000: its
+// table, its fresh copies, its stream that reuses from leaf i-1 only.  Local labels of the new part: 1000, and 1200 + k for cached leaf k.
+// Operands beyond flat_literal_asm's: [c0] ... "=&v", FlatCacheStats::extra_operands of them.
+struct FlatCacheStats {
+    uint32_t intervals = 0;             // intervals the stream entered at i == 0 computes
+    uint32_t plane_distances = 0;       // plane distances it computes (two instructions each)
+    uint32_t evictions = 0;             // intervals dropped from a pair although a later leaf names them again
+    uint32_t far_reuses = 0;            // intervals read from a pair that leaf i-1 did not use on that axis (what flat_literal_asm cannot do)
+    uint32_t extra_operands = 0;        // [c0] ... the text names; 0: the text is flat_literal_asm's
+    bool cached = false;                // a cached stream was written
+};
+constexpr uint32_t kFlatCacheMinPairs = 3u, kFlatCacheMaxPairs = 8u, kFlatCacheMaxPlanes = 8u;
+constexpr uint32_t kFlatCacheMaxExtra = 2u * (kFlatCacheMaxPairs - 3u) + kFlatCacheMaxPlanes;
+
+// False - nothing written - where flat_literal_asm refuses, or for interval_pairs outside 3 ... 8 or plane_regs beyond 8.  The text is
+// flat_literal_asm's own, byte for byte, for (3, 0) and for a list on which the cached stream would compute no fewer intervals and no fewer
+// plane distances than the masks' schedule (then stats.cached is false and the counts are that schedule's).
+inline bool flat_literal_cached_asm(const void* leaf_list, uint32_t n_leaves, const uint32_t masks[3], uint32_t interval_pairs, uint32_t plane_regs,
+                                    std::string& out, FlatCacheStats& stats) {
+    using namespace flat_literal_detail;
+    if (interval_pairs < kFlatCacheMinPairs || interval_pairs > kFlatCacheMaxPairs || plane_regs > kFlatCacheMaxPlanes) return false;
+    std::string plain;
+    if (!flat_literal_asm(leaf_list, n_leaves, masks, plain)) return false;
+    const unsigned char* p = static_cast<const unsigned char*>(leaf_list);
+    const uint32_t n = n_leaves, kNever = 0xffffffffu;
+    uint32_t w[kFlatLiteralMaxLeaves][8];
+    for (uint32_t k = 0; k < n; k++) memcpy(w[k], p + 32u * (size_t)k, 32u);
+    auto finite = [](uint32_t b) { return (b & 0x7f800000u) != 0x7f800000u; };
+    auto shareable = [&](uint32_t k, int a) { return finite(w[k][a]) && finite(w[k][3 + a]); };
+    auto same = [&](uint32_t k, uint32_t j, int a) { return w[k][a] == w[j][a] && w[k][3 + a] == w[j][3 + a]; };
+    FlatCacheStats st;
+    // the masks' schedule, for the comparison and for the plain case
+    uint32_t plain_intervals = 0;
+    for (uint32_t k = 0; k < n; k++)
+        for (int a = 0; a < 3; a++) plain_intervals += (k == 0u || !(masks[a] & (1u << k))) ? 1u : 0u;
+    // ---- pass 1: which pair holds each leaf's three intervals, and which of them are computed there ----
+    struct Pair { bool used = false; int axis = 0; uint32_t leaf = 0; bool share = false; };       // the interval of `leaf` on `axis`
+    Pair pairs[kFlatCacheMaxPairs];
+    uint32_t slot_of[kFlatLiteralMaxLeaves][3];
+    bool computed[kFlatLiteralMaxLeaves][3];
+    // when q's interval is named next behind leaf `after`, in steps of one axis of one leaf (x, y, z of leaf 0, x of leaf 1 ...): no two
+    // intervals share a step, so only pairs that are never used again tie
+    auto next_use = [&](const Pair& q, uint32_t after) {
+        if (!q.used || !q.share) return kNever;
+        for (uint32_t j = after + 1u; j < n; j++) if (shareable(j, q.axis) && same(j, q.leaf, q.axis)) return 3u * j + (uint32_t)q.axis;
+        return kNever;
+    };
+    for (uint32_t k = 0; k < n; k++) {
+        bool needed[kFlatCacheMaxPairs] = {};
+        uint32_t found[3] = {kNever, kNever, kNever};
+        for (int a = 0; a < 3; a++) {                                                               // what is there is kept before anything is taken
+            if (!shareable(k, a)) continue;
+            for (uint32_t s = 0; s < interval_pairs; s++)
+                if (pairs[s].used && pairs[s].share && pairs[s].axis == a && same(k, pairs[s].leaf, a)) { found[a] = s; needed[s] = true; break; }
+        }
+        for (int a = 0; a < 3; a++) {
+            if (found[a] != kNever) {
+                slot_of[k][a] = found[a]; computed[k][a] = false;
+                if (k == 0u || !(masks[a] & (1u << k))) st.far_reuses++;
+                continue;
+            }
+            uint32_t best = kNever, best_use = 0;
+            for (uint32_t s = 0; s < interval_pairs; s++) {
+                if (needed[s]) continue;
+                const uint32_t u = next_use(pairs[s], k);
+                if (best == kNever || u > best_use) { best = s; best_use = u; }
+            }
+            if (best_use != kNever) st.evictions++;
+            pairs[best] = Pair{true, a, k, shareable(k, a)};
+            needed[best] = true;
+            slot_of[k][a] = best; computed[k][a] = true;
+            st.intervals++;
+        }
+    }
+    // ---- pass 2: where each plane distance of the computed intervals comes from ----
+    struct Use { uint32_t leaf; int axis; int hi; uint32_t bits; bool share; };
+    Use uses[6u * kFlatLiteralMaxLeaves];
+    uint32_t n_uses = 0;
+    for (uint32_t k = 0; k < n; k++)
+        for (int a = 0; a < 3; a++)
+            if (computed[k][a])
+                for (int h = 0; h < 2; h++) { const uint32_t b = w[k][3 * h + a]; uses[n_uses++] = Use{k, a, h, b, finite(b)}; }
+    auto plane_next = [&](int axis, uint32_t bits, uint32_t after) {
+        for (uint32_t j = after + 1u; j < n_uses; j++) if (uses[j].share && uses[j].axis == axis && uses[j].bits == bits) return j;
+        return kNever;
+    };
+    struct Plane { bool used = false; int axis = 0; uint32_t bits = 0; };
+    Plane planes[kFlatCacheMaxPlanes];
+    // per use: the register read (0 ... plane_regs - 1, or kNever: t0 / t1) and whether it is written here
+    uint32_t reg_of[6u * kFlatLiteralMaxLeaves];
+    bool written[6u * kFlatLiteralMaxLeaves];
+    for (uint32_t u = 0; u < n_uses; u++) {
+        reg_of[u] = kNever; written[u] = true;
+        if (!uses[u].share || plane_regs == 0u) { st.plane_distances++; continue; }
+        uint32_t hit = kNever;
+        for (uint32_t r = 0; r < plane_regs; r++) if (planes[r].used && planes[r].axis == uses[u].axis && planes[r].bits == uses[u].bits) { hit = r; break; }
+        if (hit != kNever) { reg_of[u] = hit; written[u] = false; continue; }
+        st.plane_distances++;
+        const uint32_t mine = plane_next(uses[u].axis, uses[u].bits, u);
+        if (mine == kNever) continue;
+        const uint32_t partner = uses[u].hi ? reg_of[u - 1u] : kNever;                              // the lo plane of this interval is read with this one
+        uint32_t best = kNever, best_use = 0;
+        for (uint32_t r = 0; r < plane_regs; r++) {
+            if (r == partner) continue;
+            const uint32_t v = planes[r].used ? plane_next(planes[r].axis, planes[r].bits, u) : kNever;
+            if (best == kNever || v > best_use) { best = r; best_use = v; }
+        }
+        if (best == kNever || best_use <= mine) continue;                                           // every resident is needed sooner
+        planes[best] = Plane{true, uses[u].axis, uses[u].bits};
+        reg_of[u] = best;
+    }
+    const bool gains = st.intervals < plain_intervals || st.plane_distances < 2u * plain_intervals;
+    if ((interval_pairs == kFlatCacheMinPairs && plane_regs == 0u) || !gains) {
+        stats = FlatCacheStats{};
+        stats.intervals = plain_intervals; stats.plane_distances = 2u * plain_intervals;
+        out.swap(plain);
+        return true;
+    }
+    // ---- the text ----
+    static const char* const o[3] = {"%[ox]", "%[oy]", "%[oz]"};
+    static const char* const inv[3] = {"%[ix]", "%[iy]", "%[iz]"};
+    static const char* const first_lo[3] = {"%[xe]", "%[ye]", "%[ze]"};
+    static const char* const first_hi[3] = {"%[xx]", "%[yx]", "%[zx]"};
+    auto c = [](uint32_t j) { return "%[c" + std::to_string(j) + "]"; };
+    auto pair_lo = [&](uint32_t s) { return s < 3u ? std::string(first_lo[s]) : c(2u * (s - 3u)); };
+    auto pair_hi = [&](uint32_t s) { return s < 3u ? std::string(first_hi[s]) : c(2u * (s - 3u) + 1u); };
+    auto plane_reg = [&](uint32_t r) { return c(2u * (interval_pairs - 3u) + r); };
+    std::string s;
+    s += "s_cmp_lg_u32 %[i], 0\n";
+    s += "s_cbranch_scc1 1000f\n";
+    uint32_t u = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        label(s, 1200u, k);
+        for (int a = 0; a < 3; a++) {
+            if (!computed[k][a]) continue;
+            std::string d[2];
+            for (int h = 0; h < 2; h++) {
+                d[h] = reg_of[u + h] != kNever ? plane_reg(reg_of[u + h]) : (h ? "%[t1]" : "%[t0]");
+                if (written[u + h]) { s += "v_sub_f32_e32 " + d[h] + ", "; hex(s, uses[u + h].bits); s += ", "; s += o[a]; s += "\n"; }
+            }
+            for (int h = 0; h < 2; h++)
+                if (written[u + h]) { s += "v_mul_f32_e32 " + d[h] + ", "; s += inv[a]; s += ", " + d[h] + "\n"; }
+            const std::string lo = pair_lo(slot_of[k][a]), hi = pair_hi(slot_of[k][a]);
+            if (a == 0) {
+                s += "v_med3_f32 " + lo + ", " + d[0] + ", " + d[1] + ", %[tmin]\n";
+                s += "v_med3_f32 " + hi + ", " + d[0] + ", " + d[1] + ", %[tb]\n";
+            } else {
+                s += "v_min_f32_e32 " + lo + ", " + d[0] + ", " + d[1] + "\n";
+                s += "v_max_f32_e32 " + hi + ", " + d[0] + ", " + d[1] + "\n";
+            }
+            u += 2u;
+        }
+        s += "v_max3_f32 %[st], " + pair_lo(slot_of[k][0]) + ", " + pair_lo(slot_of[k][1]) + ", " + pair_lo(slot_of[k][2]) + "\n";
+        s += "v_min3_f32 %[t0], " + pair_hi(slot_of[k][0]) + ", " + pair_hi(slot_of[k][1]) + ", " + pair_hi(slot_of[k][2]) + "\n";
+        s += "v_cmp_nle_f32_e32 vcc, %[t0], %[st]\n";
+        s += "s_and_saveexec_b64 %[m], vcc\n";
+        s += "v_mov_b32_e32 %[lk], "; hex(s, w[k][7]); s += "\n";
+        s += "ds_write2_b32 %[top], %[lk], %[st] offset1:1\n";
+        s += "v_add_u32_e32 %[top], 0x200, %[top]\n";
+        s += "s_mov_b64 exec, %[m]\n";
+        if ((k & 1u) && k + 1u < n) {
+            s += "v_cmp_gt_u32_e32 vcc, %[top], %[lim]\n";
+            s += "s_cbranch_vccnz "; ref(s, 400u, k + 1u, 'f'); s += "\n";
+        }
+    }
+    s += "s_mov_b32 %[i], "; hex(s, n); s += "\n";
+    s += "s_branch 990f\n";
+    s += "1000:\n";
+    s += plain;
+    st.extra_operands = 2u * (interval_pairs - 3u) + plane_regs;
+    st.cached = true;
+    stats = st;
+    out.swap(s);
+    return true;
+}
+
 // The same text as a C string literal, one quoted line per instruction, for a `#define NAME \` in the run-time compiled unit.
 inline std::string flat_literal_define(const std::string& name, const std::string& asm_text) {
     std::string d = "#define " + name + " \\\n";

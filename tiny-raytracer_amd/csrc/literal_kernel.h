@@ -30,6 +30,12 @@ struct LiteralKernel {
     }
 };
 
+// The interval cache of the scene's kernel: how many register pairs hold slab intervals and how many registers single plane distances.
+// Measured on Cornell (profiles/ic_flat_cache_ab.txt): every further pair and every further plane register gained, 3 / 4 / 5 /
+// 6 / 8 pairs and 8 pairs with 2 / 4 / 6 plane registers in one interleaved run; the 16 registers live only inside the box phase, below
+// the kernel's register peak (70 VGPRs at every setting).
+constexpr uint32_t kLiteralIntervalPairs = 8u, kLiteralPlaneRegs = 6u;
+
 // What a render says about its scene: the host copy of the leaf list (n_leaves x 32 bytes, walk order) and whether the scene should run
 // its own kernel now (TRT_FLAT_LITERAL: 0 never, 1 at the first streamed render, unset: at the first render large enough).
 struct LiteralRequest {
@@ -38,6 +44,8 @@ struct LiteralRequest {
     uint32_t n_leaves = 0;
     bool wanted = false;
     bool empty_source = false;               // TRT_FLAT_LITERAL_TEST_FAIL=1: the compiler is handed an empty source (tests of the fallback)
+    uint32_t interval_pairs = kLiteralIntervalPairs;   // the cached stream's registers (flat_literal.h flat_literal_cached_asm):
+    uint32_t plane_regs = kLiteralPlaneRegs;           //   TRT_FLAT_LITERAL_PAIRS 3 ... 8, TRT_FLAT_LITERAL_PLANES 0 ... 8; (3, 0): no cached stream
 };
 inline thread_local const LiteralRequest* t_literal_request = nullptr;
 class LiteralScope {

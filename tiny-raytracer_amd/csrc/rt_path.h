@@ -669,16 +669,44 @@ TRT_DEV float2* box_loop_flat(const Trav& tr, const V3& o, const float4* __restr
 // writes for the scene's leaf list - the same box steps unrolled over the leaves, planes and links as literals, the reuse schedule and the
 // pair loop resolved when the text was written.  Same contract: `i` in and out (even, or n), the lane's new stack top returned.  The leaf
 // list and the schedule are in the text, so neither is an argument; s[36:38] serve the jump of an entry at i > 0.
+// TRT_FLAT_LITERAL_EXTRA (written next to the text): how many further registers [c0] ... the text names - the interval pairs and plane
+// distances its cached stream keeps beyond the three intervals (flat_literal.h flat_literal_cached_asm); 0 or absent: none.
+#ifndef TRT_FLAT_LITERAL_EXTRA
+#define TRT_FLAT_LITERAL_EXTRA 0
+#endif
+#define TRT_FLC_0
+#define TRT_FLC_1 TRT_FLC_0, [c0] "=&v"(c[0])
+#define TRT_FLC_2 TRT_FLC_1, [c1] "=&v"(c[1])
+#define TRT_FLC_3 TRT_FLC_2, [c2] "=&v"(c[2])
+#define TRT_FLC_4 TRT_FLC_3, [c3] "=&v"(c[3])
+#define TRT_FLC_5 TRT_FLC_4, [c4] "=&v"(c[4])
+#define TRT_FLC_6 TRT_FLC_5, [c5] "=&v"(c[5])
+#define TRT_FLC_7 TRT_FLC_6, [c6] "=&v"(c[6])
+#define TRT_FLC_8 TRT_FLC_7, [c7] "=&v"(c[7])
+#define TRT_FLC_9 TRT_FLC_8, [c8] "=&v"(c[8])
+#define TRT_FLC_10 TRT_FLC_9, [c9] "=&v"(c[9])
+#define TRT_FLC_11 TRT_FLC_10, [c10] "=&v"(c[10])
+#define TRT_FLC_12 TRT_FLC_11, [c11] "=&v"(c[11])
+#define TRT_FLC_13 TRT_FLC_12, [c12] "=&v"(c[12])
+#define TRT_FLC_14 TRT_FLC_13, [c13] "=&v"(c[13])
+#define TRT_FLC_15 TRT_FLC_14, [c14] "=&v"(c[14])
+#define TRT_FLC_16 TRT_FLC_15, [c15] "=&v"(c[15])
+#define TRT_FLC_17 TRT_FLC_16, [c16] "=&v"(c[16])
+#define TRT_FLC_18 TRT_FLC_17, [c17] "=&v"(c[17])
+#define TRT_FLC_CAT2(a, b) a##b
+#define TRT_FLC_CAT(a, b) TRT_FLC_CAT2(a, b)
 TRT_DEV float2* box_loop_flat_literal(const Trav& tr, const V3& o, uint32_t& i, float2* stk, float2* limit) {
     const uint32_t stk_off = lds_offset(stk);
     uint32_t top = stk_off;
     const uint32_t lim = lds_offset(limit);
     unsigned long long m;
     float t0, t1, xe, xx, ye, yx, ze, zx, st, lk;
+    [[maybe_unused]] float c[18];
     asm volatile(
         TRT_FLAT_LITERAL_ASM
         : [i] "+s"(i), [top] "+v"(top), [m] "=&s"(m), [t0] "=&v"(t0), [t1] "=&v"(t1), [xe] "=&v"(xe), [xx] "=&v"(xx),
           [ye] "=&v"(ye), [yx] "=&v"(yx), [ze] "=&v"(ze), [zx] "=&v"(zx), [st] "=&v"(st), [lk] "=&v"(lk)
+          TRT_FLC_CAT(TRT_FLC_, TRT_FLAT_LITERAL_EXTRA)
         : [lim] "v"(lim), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(tr.inv.x), [iy] "v"(tr.inv.y),
           [iz] "v"(tr.inv.z), [tb] "v"(tr.t_best), [tmin] "s"(kTMin)
         : "vcc", "scc", "memory", "s36", "s37", "s38");

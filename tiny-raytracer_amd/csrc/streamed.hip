@@ -439,8 +439,9 @@ bool literal_build(LiteralKernel& slot, const LiteralRequest& rq, const FlatReus
     const uint32_t masks[3] = {reuse.x, reuse.y, reuse.z};
     std::string text, source;
     if (!rq.empty_source) {
-        if (!flat_literal_asm(rq.leaf_list, rq.n_leaves, masks, text)) { why = "leaf list refused"; return false; }
-        source = flat_literal_source(text);
+        FlatCacheStats cache;
+        if (!flat_literal_cached_asm(rq.leaf_list, rq.n_leaves, masks, rq.interval_pairs, rq.plane_regs, text, cache)) { why = "leaf list refused"; return false; }
+        source = flat_literal_source(text, cache.extra_operands);
     }
     FlatLiteralBuild built;
     if (!flat_literal_compile(source, minw, arch.c_str(), reinterpret_cast<const void*>(&hipModuleLoadData), built)) { why = "hiprtc: " + built.log; return false; }
