@@ -686,6 +686,8 @@ extern "C" {
     pub fn trt_dominant_kernel(s: *const trt_scene, cam: *const trt_camera, p: *const trt_render_params) -> *const c_char;
     pub fn trt_flat_literal_compilations() -> u64;
     pub fn trt_flat_literal_diagnostic() -> *const c_char;
+    pub fn trt_scene_facts(s: *const trt_scene) -> u32;
+    pub fn trt_flat_literal_facts() -> u32;
 
     pub fn trt_last_error() -> *const c_char;
     pub fn trt_device_count() -> c_int;

@@ -1438,6 +1438,17 @@ const char *trt_dominant_kernel(const trt_scene *s, const trt_camera *cam, const
  * the calling thread's until its next call). */
 uint64_t trt_flat_literal_compilations(void);
 const char *trt_flat_literal_diagnostic(void);
+/* What that kernel is told about its scene besides the planes (environment TRT_SCENE_FACTS: 0 nothing, 1 "no sphere" and the kinds as
+ * compile-time constants, unset or anything else: those and the straight-line shade of scenes with Lambertian and light quads only; bits
+ * 1 to 3 are reported and stay run-time switches in the kernel).  Each fact is claimed only
+ * where the packed scene proves it; the frame is the same, bit for bit, whatever is claimed.  One word: bit 0 no sphere, bit 1 every quad
+ * axis-exact (and no sphere), bit 2 the nearest-first leaf phase (with bit 1), bit 3 lazy colour, bit 4 the straight-line shade,
+ * bits 8 ... 11 the trt_material_kind values some primitive references (0: not claimed).  0 for NULL, a scene of more than 32 primitives
+ * and TRT_SCENE_FACTS=0.  Host only, needs no device. */
+uint32_t trt_scene_facts(const trt_scene *s);
+/* The same word for the unit this process compiled and loaded last: the facts its source was written with (0 before any, and for a
+ * unit compiled without facts).  After a scene's first streamed render with TRT_FLAT_LITERAL=1 it equals trt_scene_facts(scene). */
+uint32_t trt_flat_literal_facts(void);
 
 /* ---- library ---- */
 const char *trt_last_error(void);

@@ -414,6 +414,8 @@ SIGNATURES = {
     "trt_abi_version": (C.c_uint32, []),
     "trt_flat_literal_compilations": (C.c_uint64, []),
     "trt_flat_literal_diagnostic": (C.c_char_p, []),
+    "trt_scene_facts": (C.c_uint32, [C.c_void_p]),
+    "trt_flat_literal_facts": (C.c_uint32, []),
 }
 
 

@@ -30,6 +30,7 @@
 #include "scene.h"
 #include "scene_adopt.h"
 #include "scene_cache.h"
+#include "scene_facts.h"
 #include "scene_query.h"
 #include "stream_plan.h"
 
@@ -88,6 +89,7 @@ void timing_mark(hipStream_t stream, bool begin) {
 struct trt_scene {
     SceneHost host;
     FlatReuse flat_reuse{};                       // the lock-step leaf walk's reuse schedule (flat_reuse.h) and axis-exact-quads switch (axis_quads.h), derived once from host.blob
+    SceneFacts facts;                             // what the scene's own kernel may be told about it (scene_facts.h), derived with flat_reuse; TRT_SCENE_FACTS=0: nothing
     std::vector<uint32_t> geo_index;              // ray queries: geometry insertion index of sphere k at [k], of quad k at [n_spheres + k] (the kernels know a
                                                   // primitive as kind bit | index within its kind); derived once from the reference tree, outside the packed scene
     SceneCache cache;                             // what the scene keeps on its devices (scene_cache.h); destroyed with the handle
@@ -124,6 +126,8 @@ struct Defaults {
     bool flat_literal_test_fail = false;          // TRT_FLAT_LITERAL_TEST_FAIL=1: that compilation is handed an empty source (tests of the fallback)
     uint32_t flat_literal_pairs = kLiteralIntervalPairs;   // TRT_FLAT_LITERAL_PAIRS (3 ... 8), TRT_FLAT_LITERAL_PLANES (0 ... 8): the registers of that kernel's
     uint32_t flat_literal_planes = kLiteralPlaneRegs;      // interval cache (flat_literal.h); a value out of range leaves the built-in one; 3 and 0: no cache
+    uint32_t scene_facts = SCENE_FACTS_ALL;       // TRT_SCENE_FACTS: what that kernel is told about its scene (scene_facts.h): 0 nothing, 1 the facts as constants,
+                                                  // anything else and unset: those and the straight-line shade (A/B runs, tests)
 };
 const Defaults& defaults() {
     static const Defaults d = [] {
@@ -152,6 +156,12 @@ const Defaults& defaults() {
         if (const char* e = env("TRT_FLAT_LITERAL_TEST_FAIL")) x.flat_literal_test_fail = atoi(e) != 0;
         if (const char* e = env("TRT_FLAT_LITERAL_PAIRS")) { const int v = atoi(e); if (v >= 3 && v <= 8) x.flat_literal_pairs = (uint32_t)v; }
         if (const char* e = env("TRT_FLAT_LITERAL_PLANES")) { const int v = atoi(e); if (v >= 0 && v <= 8 && *e >= '0' && *e <= '9') x.flat_literal_planes = (uint32_t)v; }
+        if (const char* e = env("TRT_SCENE_FACTS")) {                      // "0" and "1" as numbers; anything else, text included: all
+            char* end = nullptr;
+            const long v = strtol(e, &end, 10);
+            const bool number = end != e && *end == '\0';
+            x.scene_facts = (number && v == 0) ? SCENE_FACTS_NONE : (number && v == 1) ? SCENE_FACTS_CONSTANTS : SCENE_FACTS_ALL;
+        }
         if (const char* e = env("TRT_COMPACT_NODES")) o.compact_nodes = atoi(e) ? 1 : 0;
         if (const char* e = env("TRT_SCRATCH_CAP_MB")) o.scratch_cap_bytes = (uint64_t)strtoull(e, nullptr, 10) << 20;
         return x;
@@ -318,6 +328,7 @@ int enqueue_render(trt_scene* s, const trt_camera* cam, const trt_render_params*
             // TRT_FLAT_REUSE=0 asks for every box in full: no cache either
             lit.interval_pairs = defaults().flat_reuse ? defaults().flat_literal_pairs : 3u;
             lit.plane_regs = defaults().flat_reuse ? defaults().flat_literal_planes : 0u;
+            lit.facts = s->facts;
         }
         const LiteralScope lit_scope(lit.slot ? &lit : nullptr);
         hipError_t le;
@@ -356,6 +367,15 @@ void set_flat_reuse(trt_scene* s) {
                                            have_quads ? s->host.blob.data() + 16u * (size_t)L.off_quad : nullptr, L.n_quads, L.n_spheres, aq,
                                            defaults().nearest_first, planes);
     s->flat_reuse = FlatReuse{m[0], m[1], m[2], aq, nf, planes[0], planes[1], planes[2]};
+    // ... and what the kernel compiled for this scene may take as constants (scene_facts.h), from the same host copy
+    const size_t kend = 4u * ((size_t)L.off_material_kind + L.n_materials), smend = 4u * ((size_t)L.off_sphere_mat + L.n_spheres);
+    const bool have_mats = have && s->host.blob.size() >= kend && s->host.blob.size() >= smend && (L.n_quads == 0u || have_quads);
+    s->facts = have_mats ? scene_facts_derive(s->host.blob.data() + 16u * (size_t)L.off_leaf_list, L.n_leaves,
+                                              have_quads ? s->host.blob.data() + 16u * (size_t)L.off_quad : nullptr, L.n_quads, L.n_spheres,
+                                              reinterpret_cast<const uint32_t*>(s->host.blob.data()) + L.off_sphere_mat,
+                                              reinterpret_cast<const uint32_t*>(s->host.blob.data()) + L.off_material_kind, L.n_materials, aq, nf,
+                                              L.lazy_color, defaults().scene_facts)
+                           : SceneFacts{};
 }
 
 // The per-kind -> insertion-index table of the ray queries, from what both scene compilers leave on the handle: leaf i of the reference tree's
@@ -592,6 +612,8 @@ int trt_scene_get_compact_nodes(const trt_scene* s, uint32_t* words4, uint32_t c
         if (!(words4[4u * (size_t)i + 3u] & 0x80000000u)) words4[4u * (size_t)i + 3u] >>= 4;
     return TRT_OK;
 }
+uint32_t trt_scene_facts(const trt_scene* s) { return s ? s->facts.word() : 0u; }
+
 int trt_scene_get_packed(const trt_scene* s, uint8_t* bytes, uint32_t cap) {
     if (!s || !bytes) return fail(TRT_ERR_INVALID_ARG, "null argument");
     const uint32_t n = s->host.layout.blob_bytes;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "flat_literal.h"
+#include "scene_facts.h"
 
 namespace trt {
 
@@ -84,10 +85,11 @@ struct FlatLiteralBuild {
     std::string log;                 // why not, or the compiler's remarks
 };
 
-// The source of the unit for this asm text (flat_literal_asm, or flat_literal_cached_asm with the `extra_operands` of its statistics).
-inline std::string flat_literal_source(const std::string& asm_text, uint32_t extra_operands = 0u) {
-    return flat_literal_define("TRT_FLAT_LITERAL_ASM", asm_text) + "#define TRT_FLAT_LITERAL_EXTRA " + std::to_string(extra_operands) +
-           "\n#include \"stream_pool.h\"\n";
+// The source of the unit for this asm text (flat_literal_asm, or flat_literal_cached_asm with the `extra_operands` of its statistics) and
+// these scene facts (scene_facts.h; none: the text is the one without them, byte for byte).
+inline std::string flat_literal_source(const std::string& asm_text, uint32_t extra_operands = 0u, const SceneFacts& facts = SceneFacts{}) {
+    return flat_literal_define("TRT_FLAT_LITERAL_ASM", asm_text) + "#define TRT_FLAT_LITERAL_EXTRA " + std::to_string(extra_operands) + "\n" +
+           scene_facts_defines(facts) + "#include \"stream_pool.h\"\n";
 }
 
 // stream_pool_kernel<MODE_LDS, false, minw, 256, WALK_FLAT, true> with this box phase, for `arch` ("gfx950"), with the library's flags.

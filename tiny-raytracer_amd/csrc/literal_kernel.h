@@ -9,6 +9,8 @@
 #include <condition_variable>
 #include <mutex>
 
+#include "scene_facts.h"
+
 namespace trt {
 
 // One scene's run-time compiled kernel on one device.  UNTRIED -> COMPILING (one thread; the others wait) -> READY or FAILED, for good: a
@@ -21,6 +23,7 @@ struct LiteralKernel {
     void* module = nullptr;                  // hipModule_t
     void* function = nullptr;                // hipFunction_t
     int minw = 0;                            // the launch bound it was instantiated with (stream_plan.h: the plan's row)
+    SceneFacts facts;                        // the scene facts it was compiled with (scene_facts.h): a launch with other facts does not take it
     void (*unload)(void* module) = nullptr;  // set by the unit that loaded it
     // Call with no render of the scene in flight on the device (SceneCache's destructor has waited for them).
     void release() {
@@ -46,6 +49,7 @@ struct LiteralRequest {
     bool empty_source = false;               // TRT_FLAT_LITERAL_TEST_FAIL=1: the compiler is handed an empty source (tests of the fallback)
     uint32_t interval_pairs = kLiteralIntervalPairs;   // the cached stream's registers (flat_literal.h flat_literal_cached_asm):
     uint32_t plane_regs = kLiteralPlaneRegs;           //   TRT_FLAT_LITERAL_PAIRS 3 ... 8, TRT_FLAT_LITERAL_PLANES 0 ... 8; (3, 0): no cached stream
+    SceneFacts facts;                        // what the handle has derived about the scene (scene_facts.h; TRT_SCENE_FACTS=0: nothing)
 };
 inline thread_local const LiteralRequest* t_literal_request = nullptr;
 class LiteralScope {

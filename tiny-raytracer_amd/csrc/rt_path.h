@@ -16,6 +16,29 @@ namespace trt {
 extern __shared__ float4 g_lds[];          // dynamic LDS: [scene copy (LDS variants)] [backend-private area]
 
 // ------------------------------------------------------------------------------------------------
+// Scene facts (scene_facts.h): what the unit compiled at run time for ONE scene is told about it, as #defines in front of its include of
+// stream_pool.h.  No define - every unit built ahead of time - knows nothing: each constant below is then false (kinds: any), every
+// `if constexpr` on it takes the general side, and the kernels are the ones written without this block.  A fact is true for the whole
+// scene, so a constant replaces a test whose outcome the host has proved, never a value: the frame is the same bit for bit.
+// The three read here are properties of the SCENE (what its primitives and materials are), true in whatever kernel a unit instantiates.
+// The axis-exact and nearest-first switches, which also depend on what the KERNEL did to its LDS records, stay run-time flags: as
+// constants, with the material-kind guards in shade_body, they measured +0.8 %, under the A/B's threshold, and were taken out.
+// ------------------------------------------------------------------------------------------------
+#ifndef TRT_FACT_NO_SPHERE
+#define TRT_FACT_NO_SPHERE 0
+#endif
+#ifndef TRT_FACT_KINDS
+#define TRT_FACT_KINDS 0
+#endif
+#ifndef TRT_FACT_STRAIGHT_SHADE
+#define TRT_FACT_STRAIGHT_SHADE 0
+#endif
+constexpr bool kFactNoSphere = TRT_FACT_NO_SPHERE != 0;                      // every primitive reference carries PRIM_QUAD_BIT
+constexpr uint32_t kFactKinds = TRT_FACT_KINDS;                              // bit k: trt_material_kind k is referenced; 0: unknown
+constexpr bool kFactStraightShade = kFactNoSphere && TRT_FACT_STRAIGHT_SHADE != 0;     // quads of Lambertian and Light materials only, lazy colour: shade_straight
+constexpr bool fact_kind_possible(uint32_t kind) { return kFactKinds == 0u || ((kFactKinds >> kind) & 1u) != 0u; }
+
+// ------------------------------------------------------------------------------------------------
 // Scene access: LDS copy or global blob, same element offsets (scene.h).
 // ------------------------------------------------------------------------------------------------
 // MODE_GLOBAL / MODE_LDS: stream_plan.h, with the launch rule that chooses between them.
@@ -212,7 +235,7 @@ TRT_DEV uint32_t trav_box_step(const SceneAcc<MODE>& sc, const Ray& ray, Trav& t
 template <int MODE, bool STATS, bool COLD = false>
 TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint32_t leaf, Counters<STATS>& ctr, uint32_t axis_quads = 0u) {
     const uint32_t idx = leaf & PRIM_INDEX_MASK;
-    if (axis_quads != 0u && (leaf & PRIM_QUAD_BIT)) {
+    if (axis_quads != 0u && (kFactNoSphere || (leaf & PRIM_QUAD_BIT))) {
         // Axis-exact quads (axis_quads.h has the argument and its case table): alpha = fl(w_a dot(p, A)), beta = fl(w_a dot(p, B)) are the
         // generic test's dot(cross(p, v), w) and dot(cross(u, p), w) up to the sign of a zero, and a non-finite p is rejected by both
         // forms.  Elements 2 and 3 of the record are (A.xyz, w_a) (B.xyz, 0) here; 0, 1 and 4 are the packed ones (shade_hit reads them).
@@ -232,7 +255,7 @@ TRT_DEV void trav_leaf(const SceneAcc<MODE>& sc, const Ray& ray, Trav& tr, uint3
             tr.t_best = t;
             tr.prim_best = leaf;
         }
-    } else if (leaf & PRIM_QUAD_BIT) {                                 // Quad::hit, quad.rs:33-54
+    } else if (kFactNoSphere || (leaf & PRIM_QUAD_BIT)) {              // Quad::hit, quad.rs:33-54
         if constexpr (STATS) ctr.quad_plane++;
         // Branch-free: all five planes are requested at once and the inside test is evaluated whatever the plane stage says.
         // Nearly every quad whose box still passes also passes the plane stage (Cornell: 1.08 plane tests and 0.97 inside
@@ -1182,7 +1205,7 @@ TRT_DEV bool closest_hit_resume(const SceneAcc<MODE>& sc, const Ray& ray, Trav& 
 template <int MODE>
 TRT_DEV uint32_t prim_material(const SceneAcc<MODE>& sc, uint32_t prim) {
     const uint32_t idx = prim & PRIM_INDEX_MASK;
-    return (prim & PRIM_QUAD_BIT) ? __float_as_uint(sc.quad(1, idx).w) : sc.sphere_material(idx);
+    return (kFactNoSphere || (prim & PRIM_QUAD_BIT)) ? __float_as_uint(sc.quad(1, idx).w) : sc.sphere_material(idx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1226,7 +1249,7 @@ TRT_DEV bool shade_body(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float 
     V3 normal;
     bool front_face;
     uint32_t mat;
-    if (prim & PRIM_QUAD_BIT) {
+    if (kFactNoSphere || (prim & PRIM_QUAD_BIT)) {
         float4 q0 = sc.quad(0, idx), q1 = sc.quad(1, idx), q4 = sc.quad(4, idx);
         front_face = dot(p.ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;        // outward normal = n, un-normalised (quad.rs:45)
         V3 nu = v3(q4.y, q4.z, q4.w);                                  // n.normalized(), precomputed on the host
@@ -1302,6 +1325,60 @@ TRT_DEV bool shade_hit(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t
 template <int MODE, bool STATS>
 TRT_DEV bool shade_hit_info(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background, Counters<STATS>& ctr, ShadeInfo& info) {
     return shade_body<MODE, STATS, false, true>(sc, p, prim, t, background, ctr, &info);
+}
+
+// shade_hit<MODE, false, true> for a scene whose primitives reference Lambertian and Light materials only (kFactStraightShade: the unit
+// compiled for one scene, stream_pool.h), as ONE straight-line body that updates the path in place.  Every lane - hit or miss, light or
+// not - runs the Lambertian scatter; `ended` is miss, kind == LIGHT or a spent budget.
+//   WHAT IS DEAD.  Where this returns true the caller stores p.color and drops the path; the lane's next path comes from the pool take,
+//   which assigns p.ray, p.rng, p.color, p.atten and p.remain before anything reads them (stream_pool.h), and n_samples, n_rays and
+//   out_idx are not touched here.  So for a lane that ends, only p.color is observable, and the ray, generator, attenuation and budget this
+//   body leaves behind are read by nobody: a light lane may draw its three random numbers and scatter, a miss lane may run the arithmetic
+//   on primitive 0's record with t = +inf.  shade_body returns early on those lanes instead, and the compiler has to merge the states of
+//   its exits with register copies (28 v_mov_b32 on the hit path of a round, 12 more for the miss exit).
+//   WHAT IS THE SAME.  For a lane that goes on (Lambertian hit, budget left) every operation of shade_body's Lambertian path, on the same
+//   operands, in the same order: HitRecord, the three draws, normal + unit vector, the near-zero test, atten * albedo, Ray::new, remain - 1.
+//   p.color (LAZY): +0 for a hit that is not a light; 0 + atten * albedo at a light, with the attenuation of BEFORE the hit - which is the
+//   product the Lambertian path forms as the new attenuation, the same multiplication on the same operands; 0 + atten * background on a
+//   miss, where shade_body leaves the attenuation alone and this body may spoil it (dead).  The sums with +0 stay (they turn a -0
+//   product into +0, as shade_body's do).  No observable value depends on a dead register: the colour of a lane that goes on is
+//   indeterminate and is overwritten, by this body or by the take, before the one place that reads a colour - the store under `ended`.
+template <int MODE>
+TRT_DEV bool shade_straight(const SceneAcc<MODE>& sc, Path& p, uint32_t prim, float t, V3 background) {
+    const bool miss = prim == PRIM_NONE;
+    static_assert(!kFactStraightShade || kFactNoSphere, "the straight-line shade is claimed for scenes of quads only (scene_facts.h)");
+    const uint32_t idx = miss ? 0u : (prim & PRIM_INDEX_MASK);     // a miss lane reads quad 0's record: values nobody uses, addresses inside the scene
+    const V3 point = ray_at(p.ray, t);
+    const float4 q0 = sc.quad(0, idx), q1 = sc.quad(1, idx), q4 = sc.quad(4, idx);
+    const bool front_face = dot(p.ray.d, v3(q0.x, q0.y, q0.z)) < 0.0f;
+    const V3 nu = v3(q4.y, q4.z, q4.w);
+    const V3 normal = front_face ? nu : -nu;
+    const uint32_t mat = __float_as_uint(q1.w);
+    const float4 m = sc.material(mat);
+    const bool light = fact_kind_possible(TRT_LIGHT) && sc.material_kind(mat) == TRT_LIGHT;
+    const V3 in_sphere = random_in_unit_sphere_unit(p.rng);
+    V3 dir = normal + normalized(in_sphere);
+    if (near_zero(dir)) dir = normal;
+    // ONE product serves the three exits: a miss lane multiplies by the background instead of the albedo, so the new attenuation IS
+    // atten * background there and atten * albedo at a light - what the colour is made of - and no exit needs the old attenuation again
+    // (kept alive for the miss exit it cost three copies at the round's end)
+    const V3 factor = miss ? background : v3(m.x, m.y, m.z);
+    p.atten = p.atten * factor;
+    // (the hit point and the direction are both complete here, before the normalisation: the old ray is dead from this line on and the new
+    // one is written over it; left to itself the scheduler formed the point last and kept both rays alive, six copies at the round's end)
+    V3 origin = point;
+    asm volatile("" : "+v"(origin.x), "+v"(origin.y), "+v"(origin.z), "+v"(dir.x), "+v"(dir.y), "+v"(dir.z));
+    p.ray = ray_new(origin, dir);
+    p.remain -= 1u;
+    const bool lit = miss | light;
+    const bool ended = lit | (p.remain == 0u);
+    // The colour is written on EVERY lane, so that it is not carried from round to round (assigned under `ended` alone it stayed live
+    // from the pool take on, three registers through the box phase: 72 VGPRs for 70): the lanes that store it get 0 + the product or +0,
+    // the others a value that is left indeterminate - whatever the registers hold, no instruction - and that nobody reads.
+    V3 c = v3(__builtin_nondeterministic_value(0.0f), __builtin_nondeterministic_value(0.0f), __builtin_nondeterministic_value(0.0f));
+    if (ended) c = lit ? v3(0.0f, 0.0f, 0.0f) + p.atten : v3(0.0f, 0.0f, 0.0f);
+    p.color = c;
+    return ended;
 }
 
 // SamplePointGenerator::generate body (pointgen.rs:41-43) + Camera::get_ray (camera.rs:58-66)

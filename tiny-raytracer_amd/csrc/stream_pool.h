@@ -168,7 +168,11 @@ __global__ __launch_bounds__(THREADS, MINW) void stream_pool_kernel(SceneDev scd
                 n_rays++;
                 float t;
                 const uint32_t prim = closest_hit<MODE, STATS, WALK>(sc, p.ray, STATS && ra.ref_tree != 0u, t, ctr, ra.leaf_slots, leaf_stack, leaf_list, nodes16, flat_reuse);
-                if (shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr)) {
+                bool ended;
+                // (the unit compiled for a scene of Lambertian and light quads: one straight-line body, the path updated in place - rt_path.h)
+                if constexpr (kFactStraightShade && !STATS && LAZY) ended = shade_straight<MODE>(sc, p, prim, t, background);
+                else ended = shade_hit<MODE, STATS, LAZY>(sc, p, prim, t, background, ctr);
+                if (ended) {
                     radiance_store(kernarg_reload<float*>(offsetof(StreamKernargs, colors)), out_idx, p.color);       // the pointer: as the refill arguments
                     has_path = false;
                 }

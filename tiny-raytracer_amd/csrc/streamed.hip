@@ -418,6 +418,7 @@ static_assert(sizeof(kStreamKernelFns) / sizeof(kStreamKernelFns[0]) == kStreamK
 std::mutex g_literal_mu;
 unsigned long long g_literal_compilations = 0;
 std::string g_literal_diagnostic;
+uint32_t g_literal_facts_word = 0;          // SceneFacts::word() of the unit compiled and loaded last (trt_flat_literal_facts)
 thread_local std::string t_literal_diagnostic_copy;
 
 void literal_unload(void* module) {
@@ -438,10 +439,11 @@ bool literal_build(LiteralKernel& slot, const LiteralRequest& rq, const FlatReus
     arch = arch.substr(0, arch.find(':'));                                          // "gfx950:sramecc+:xnack-" -> "gfx950"
     const uint32_t masks[3] = {reuse.x, reuse.y, reuse.z};
     std::string text, source;
+    const SceneFacts unit_facts = rq.empty_source ? SceneFacts{} : rq.facts;       // what the source below is written with, and nothing else
     if (!rq.empty_source) {
         FlatCacheStats cache;
         if (!flat_literal_cached_asm(rq.leaf_list, rq.n_leaves, masks, rq.interval_pairs, rq.plane_regs, text, cache)) { why = "leaf list refused"; return false; }
-        source = flat_literal_source(text, cache.extra_operands);
+        source = flat_literal_source(text, cache.extra_operands, unit_facts);
     }
     FlatLiteralBuild built;
     if (!flat_literal_compile(source, minw, arch.c_str(), reinterpret_cast<const void*>(&hipModuleLoadData), built)) { why = "hiprtc: " + built.log; return false; }
@@ -455,7 +457,11 @@ bool literal_build(LiteralKernel& slot, const LiteralRequest& rq, const FlatReus
         why = std::string("module load: ") + hipGetErrorString(e);
         return false;
     }
-    slot.module = mod; slot.function = fn; slot.minw = minw; slot.unload = &literal_unload;
+    slot.module = mod; slot.function = fn; slot.minw = minw; slot.facts = unit_facts; slot.unload = &literal_unload;
+    {
+        std::lock_guard<std::mutex> lock(g_literal_mu);
+        g_literal_facts_word = unit_facts.word();
+    }
     return true;
 }
 
@@ -485,7 +491,7 @@ hipFunction_t literal_kernel_for(const StreamLaunchPlan& pl, const RenderArgs& r
         slot.state = ok ? LiteralKernel::READY : LiteralKernel::FAILED;
         slot.cv.notify_all();
     }
-    if (slot.state != LiteralKernel::READY || slot.minw != pl.kernel_minw) return nullptr;
+    if (slot.state != LiteralKernel::READY || slot.minw != pl.kernel_minw || slot.facts != rq->facts) return nullptr;
     return static_cast<hipFunction_t>(slot.function);
 }
 
@@ -612,6 +618,10 @@ int trt_variance_device(const float* d_accum, const float* d_moment2, uint32_t n
 uint64_t trt_flat_literal_compilations(void) {
     std::lock_guard<std::mutex> lock(trt::g_literal_mu);
     return trt::g_literal_compilations;
+}
+uint32_t trt_flat_literal_facts(void) {
+    std::lock_guard<std::mutex> lock(trt::g_literal_mu);
+    return trt::g_literal_facts_word;
 }
 const char* trt_flat_literal_diagnostic(void) {
     std::lock_guard<std::mutex> lock(trt::g_literal_mu);
