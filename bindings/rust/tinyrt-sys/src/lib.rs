@@ -636,6 +636,16 @@ extern "C" {
     pub fn trt_fold_samples(colors: *const f32, n: u32, p: *const trt_radiance_params, radiance: *mut f32, moment2: *mut f32) -> c_int;
     pub fn trt_fold_samples_device(d_colors: *const f32, n: u32, p: *const trt_radiance_params, d_radiance: *mut f32, d_moment2: *mut f32,
                                    stream: *mut c_void) -> c_int;
+    pub fn trt_project_samples(colors: *const f32, directions: *const f32, items: *const trt_ray, n: u32, p: *const trt_probe_params,
+                               sh: *mut f32) -> c_int;
+    pub fn trt_project_samples_device(d_colors: *const f32, d_directions: *const f32, d_items: *const trt_ray, n: u32,
+                                      p: *const trt_probe_params, d_sh: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn trt_probe_parallel(s: *mut trt_scene, items: *const trt_ray, n: u32, p: *const trt_probe_params, sh: *mut f32,
+                              stats: *mut trt_stats, record_bytes: u64) -> c_int;
+    pub fn trt_probe_parallel_device(s: *mut trt_scene, d_items: *const trt_ray, n: u32, p: *const trt_probe_params, d_sh: *mut f32,
+                                     d_counters: *mut u64, d_records: *mut c_void, record_bytes: u64, stream: *mut c_void) -> c_int;
+    pub fn trt_probe_parallel_launch_plan(s: *const trt_scene, n: u32, range_length: u32, compute_units: u32,
+                                          out: *mut trt_query_plan) -> c_int;
     pub fn trt_nee_samples_params_default(out: *mut trt_nee_samples_params);
     pub fn trt_nee_samples(s: *mut trt_scene, items: *const trt_ray, n: u32, emitters: *const trt_emitter, pick: *const trt_emitter_pick,
                            n_emitters: u32, p: *const trt_nee_samples_params, colors: *mut f32, directions: *mut f32, stats: *mut trt_stats) -> c_int;

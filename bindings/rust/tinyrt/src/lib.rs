@@ -224,6 +224,35 @@ pub fn fold_samples(colors: &[Float], samples_per_item: u32) -> Result<(Vec<Floa
     Ok((radiance, moment2))
 }
 
+/// The probe fold of `World::samples`' colours and directions for `SampleSource::Probe` (`trt_project_samples`; runs on the device, needs
+/// no scene): per item over all `samples_per_item` samples in order, `sh[k] += c * (Y_k(d) / K)` in f32 for the `bands * bands` real
+/// spherical harmonics.  A sample whose direction has a NaN adds nothing; with `items` (the probes) neither does a sample of an item
+/// whose point has one - then the result is `World::probe`'s, byte for byte.  Returns `bands * bands * 3` floats per item.
+pub fn project_samples(colors: &[Float], directions: &[Float], samples_per_item: u32, bands: u32, items: Option<&[[Float; 6]]>)
+                       -> Result<Vec<Float>, Error> {
+    let per_item = samples_per_item as usize * 3;
+    if per_item == 0 || colors.len() % per_item != 0 || colors.len() / per_item > u32::MAX as usize || directions.len() != colors.len() {
+        return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "colors and directions hold n x samples_per_item x 3 floats each".to_string() });
+    }
+    let n = colors.len() / per_item;
+    if !(1..=3).contains(&bands) {
+        return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "bands must be 1, 2 or 3".to_string() });
+    }
+    if let Some(items) = items {
+        if items.len() != n {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "items holds one probe per item".to_string() });
+        }
+    }
+    let mut params = sys::trt_probe_params::default();
+    unsafe { sys::trt_probe_params_default(&mut params) };
+    params.path.samples_per_ray = samples_per_item;
+    params.bands = bands;
+    let mut sh = vec![0.0 as Float; n * (bands * bands) as usize * 3];
+    let items_ptr = items.map_or(ptr::null(), |i| i.as_ptr() as *const sys::trt_ray);
+    check(unsafe { sys::trt_project_samples(colors.as_ptr(), directions.as_ptr(), items_ptr, n as u32, &params, sh.as_mut_ptr()) })?;
+    Ok(sh)
+}
+
 pub struct World {
     handle: *mut sys::trt_world,
     scene: *mut sys::trt_scene, // World::get_bvh(), cached until the world changes
@@ -537,6 +566,38 @@ impl World {
         let mut sh = vec![0.0 as Float; items.len() * (bands * bands) as usize * 3];
         check(unsafe {
             sys::trt_probe(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, sh.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok(sh)
+    }
+
+    /// `probe` with a launch that fills the device whatever `samples_per_item` is (`trt_probe_parallel`): the same arguments and the same
+    /// coefficients, bit for bit.  The paths run a sample to a GPU lane into a record buffer of the call's own and the records are
+    /// folded on the device, in chunks of `min(n, record_bytes / (24 K))` items; `record_bytes = 0` takes the library's default.
+    pub fn probe_parallel(&mut self, items: &[[Float; 6]], samples_per_item: u32, bands: u32, domain: ProbeDomain, max_bounces: u32,
+                          background: Vec3, seed: u32, first_stream: u32, record_bytes: u64) -> Result<Vec<Float>, Error> {
+        if items.len() > u32::MAX as usize {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "more than 2^32 - 1 items in one call".to_string() });
+        }
+        if !(1..=3).contains(&bands) {
+            return Err(Error { code: sys::TRT_ERR_INVALID_ARG, message: "bands must be 1, 2 or 3".to_string() });
+        }
+        let scene = self.get_bvh()?;
+        let mut params = sys::trt_probe_params::default();
+        unsafe { sys::trt_probe_params_default(&mut params) };
+        params.path.samples_per_ray = samples_per_item;
+        params.path.max_bounces = max_bounces;
+        params.path.background = background.raw();
+        params.path.seed = seed;
+        params.path.first_stream = first_stream;
+        params.bands = bands;
+        params.domain = match domain {
+            ProbeDomain::Sphere => sys::TRT_PROBE_SPHERE,
+            ProbeDomain::Hemisphere => sys::TRT_PROBE_HEMISPHERE,
+        };
+        let mut sh = vec![0.0 as Float; items.len() * (bands * bands) as usize * 3];
+        check(unsafe {
+            sys::trt_probe_parallel(scene, items.as_ptr() as *const sys::trt_ray, items.len() as u32, &params, sh.as_mut_ptr(), ptr::null_mut(),
+                                    record_bytes)
         })?;
         Ok(sh)
     }

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Bake light probes: a G x G grid of points in the horizontal plane y = 50 of the Cornell box, the radiance arriving at each projected
 onto 9 spherical-harmonic coefficients per channel -> probes.png.
-   python examples/bake_probes.py [G K] [--export]
+   python examples/bake_probes.py [G K] [--export] [--parallel]
 Scene.probe (trt_probe) does it on the device: for every one of K samples it draws a direction uniformly over the sphere, traces its path
 and adds colour * Y_k(direction) / K to the probe's coefficients; 24 bytes per probe go up and 108 come down.  Each probe is drawn as a
 small white diffuse ball seen from the open front of the box and lit by sh.irradiance of its own coefficients - the irradiance about the
 normal, over pi: what a dynamic object placed there would look like.  Far probes are at the top, the red wall's side on the left.
 --export bakes through the sample-parallel route instead - Scene.samples_device (trt_samples_device, source "sphere") leaves every
 sample's colour and direction in HBM, a sample to a lane where Scene.probe gives the K samples of a probe one lane, and sh.project folds
-them on the host - and asserts that the coefficients are Scene.probe's, bit for bit.  Needs torch for the device buffers."""
+them on the host - and asserts that the coefficients are Scene.probe's, bit for bit.  Needs torch for the device buffers.
+--parallel bakes the same probes through Scene.probe_parallel (trt_probe_parallel) as well - the same sample-parallel paths with the
+projection on the device too, in one call with host buffers - asserts the coefficients equal to Scene.probe's by their bits and prints
+both kernel times: few probes with many samples (say 4 4096) are where it pays."""
 import os
 import sys
 import time
@@ -19,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tinyrt_amd as trt
 
 export = "--export" in sys.argv[1:]
-argv = [a for a in sys.argv[1:] if a != "--export"]
+parallel = "--parallel" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a not in ("--export", "--parallel")]
 grid, spp = (int(a) for a in argv[:2]) if len(argv) >= 2 else (8, 256)
 TILE = 48                                                                    # pixels per ball
 desc = trt.scenes.cornell(2, 2)                                              # the camera of the description is not used
@@ -54,6 +58,14 @@ if export:
     print(f"--export: {n * spp} samples on {q['waves']} waves (Scene.probe: {scene.probe_plan(n)['waves']}), kernel {a.elapsed_time(b):.1f} ms "
           f"against {st['kernel_ms']:.1f} ms; projected on the host, the coefficients are Scene.probe's bit for bit")
     coeffs = exported
+if parallel:
+    baked, stp = scene.probe_parallel(items, spp, bands=3, domain="sphere", max_bounces=20, background=desc["background"])
+    same = np.where(np.isnan(coeffs), np.isnan(baked), baked.view(np.uint32) == coeffs.view(np.uint32))
+    assert same.all() and stp["rays"] == st["rays"] and stp["samples"] == st["samples"], "Scene.probe_parallel's coefficients are not Scene.probe's"
+    q = scene.probe_parallel_plan(len(items), spp)
+    print(f"--parallel: {len(items) * spp} samples on {q['waves']} waves (Scene.probe: {scene.probe_plan(len(items))['waves']}), kernels "
+          f"{stp['kernel_ms']:.1f} ms against Scene.probe's {st['kernel_ms']:.1f} ms; the coefficients are Scene.probe's bit for bit")
+    coeffs = baked
 # the normals of a ball seen along +z: image x is world x, image y (up) is world y, and the visible side faces the viewer at -z
 p = (np.arange(TILE) + 0.5) / TILE * 2.0 - 1.0
 nx, ny = np.meshgrid(p, -p)

@@ -59,7 +59,8 @@ extern "C" {
  *              trt_nee_mis_pick_device, trt_nee_mis_pick_launch_plan; trt_sample_source, trt_samples_params, trt_samples_params_default,
  *              trt_samples, trt_samples_device, trt_samples_launch_plan, trt_fold_samples, trt_fold_samples_device;
  *              trt_nee_samples_params, trt_nee_samples_params_default, trt_nee_samples, trt_nee_samples_device,
- *              trt_nee_samples_launch_plan. */
+ *              trt_nee_samples_launch_plan; trt_project_samples, trt_project_samples_device, trt_probe_parallel,
+ *              trt_probe_parallel_device, trt_probe_parallel_launch_plan. */
 
 enum trt_status {
     TRT_OK = 0,
@@ -1218,7 +1219,7 @@ int trt_samples_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_lengt
  * trt_samples leaves in `radiance` / `moment2` the bytes trt_radiance / trt_gather leave for the same items and parameters (a split
  * folded range by range with accumulate).  For SPHERE / HEMISPHERE the records and directions, folded by the probe fold above
  * (t = b_k(d) * inv_K; sh[k].ch = sh[k].ch + c.ch * t, a sample whose direction or point has a NaN adding nothing), give trt_probe's
- * bytes.  (Every number by its bits; a sum that is NaN is NaN in both, with a sign and payload that are not fixed.)  This is the K-aware
+ * bytes: trt_project_samples below is that fold on the device.  (Every number by its bits; a sum that is NaN is NaN in both, with a sign and payload that are not fixed.)  This is the K-aware
  * route: the paths run a sample to a lane, and the serial chain the fold's order demands is a few operations per sample.
  * No scene handle, like trt_variance.  The outputs must not overlap `colors`: the device form checks this from the sizes above
  * (TRT_ERR_INVALID_ARG), as trt_denoise_device checks its buffers.  Errors, TRT_ERR_INVALID_ARG: a NULL `p`; K == 0 or a bad range; with
@@ -1228,6 +1229,62 @@ int trt_samples_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_lengt
 int trt_fold_samples(const float *colors, uint32_t n, const trt_radiance_params *p, float *radiance, float *moment2);
 int trt_fold_samples_device(const float *d_colors, uint32_t n, const trt_radiance_params *p, float *d_radiance, float *d_moment2,
                             void *stream);
+/* The PROBE fold of sample records: what trt_fold_samples is to trt_radiance / trt_gather, for trt_probe.  For every item, over the
+ * samples of [b, e) in order, with inv_K = 1.0f / float(K), c = colors[3 * (i * K + s) ..], d = directions[3 * (i * K + s) ..] and the
+ * basis b_k(d) exactly as the probe contract above parenthesises it:
+ *   t = b_k * inv_K;   sh[k].ch = sh[k].ch + c.ch * t        for k < C = bands * bands
+ * all f32, one IEEE operation per operator, nothing fused.
+ *  - Fields read.  Of `p` only path.samples_per_ray (K), path.sample_begin, path.sample_end (0 = K), path.accumulate and bands (1..3) are
+ *    read, and both reserved arrays, which must be zero.  `domain` is not read, nor any other field of `path`.
+ *  - A sample that adds nothing.  A sample whose d has a NaN component adds nothing, neither 0 nor NaN.  With `items` not NULL (n x
+ *    trt_ray; only items[i].origin, the point, is read) every sample of an item whose point has a NaN component adds nothing either:
+ *    the rule under which the result is trt_probe's.  `items` may be NULL.  An item none of whose samples folds keeps the exact bits of
+ *    its prior sums with accumulate, -0 and a NaN's payload included - no arithmetic touches them; without accumulate it is +0.
+ *  - Layout.  `colors` and `directions` hold n x K x 3 f32 and are read only; `sh` holds n x C x 3 f32, item-major, then coefficient,
+ *    then channel, and the bytes of coefficient k do not depend on `bands`.  The sums start from 0, or from `sh` with accumulate.  An
+ *    empty range zeroes [0, 12 C n) unless accumulate, which touches nothing.  No byte outside [0, 12 C n) of `sh` is written.
+ *  - IDENTITY.  For source SPHERE or HEMISPHERE, max_bounces > 0 and any split of [0, K) into ranges, trt_project_samples over the
+ *    colours and directions of trt_samples, with the items, leaves in `sh` the bytes trt_probe leaves for the same items and parameters
+ *    (a split folded range by range with accumulate; a NaN sum is NaN in both, with a sign and payload that are not fixed).
+ *  - Errors, before any device work, all TRT_ERR_INVALID_ARG, in this order: a NULL `p`; K == 0 or a bad range; `bands` outside 1..3; a
+ *    non-zero reserved word; with n > 0 a NULL `colors`, `directions` or `sh`.  The device form then refuses an `sh` that overlaps either
+ *    record buffer (from the sizes above, as trt_fold_samples_device).  Then TRT_ERR_NO_DEVICE; n == 0 succeeds and touches nothing,
+ *    with or without a device.
+ * No scene handle, like trt_fold_samples.
+ * trt_project_samples: HOST buffers, synchronous (uploads, runs the device kernel, downloads; there is no CPU path).
+ * trt_project_samples_device: buffers in HBM on the calling thread's current device, asynchronous on `stream`; allocates nothing. */
+int trt_project_samples(const float *colors, const float *directions, const trt_ray *items, uint32_t n, const trt_probe_params *p,
+                        float *sh);
+int trt_project_samples_device(const float *d_colors, const float *d_directions, const trt_ray *d_items, uint32_t n,
+                               const trt_probe_params *p, float *d_sh, void *stream);
+/* trt_probe's contract with a launch that fills the device whatever K is: the paths run a sample to a lane (trt_samples' kernels for
+ * SPHERE / HEMISPHERE, with directions) into a record buffer and trt_project_samples folds the records.
+ *  - Results.  `sh`, stats.samples / d_counters[samples] and stats.rays / d_counters[rays] are trt_probe's, bit for bit, for the same
+ *    arguments: sample ranges, accumulate, first_stream, both split invariances, the NaN rules and "nothing to trace" (an empty range
+ *    or max_bounces == 0: zero unless accumulate, and no sample launch) included.
+ *  - Chunks.  With K = path.samples_per_ray and R the range's length, the call runs chunks of
+ *      m = min(n, record_bytes / (24 K), (2^32 - 1) / R)
+ *    items: the sample kernels for items [a, a + m) on the streams from first_stream + a K, then the projection of those records into
+ *    rows [a, a + m) of `sh` with the caller's accumulate.  Within the record buffer a chunk's colours come first (12 K bytes per item
+ *    of the chunk), then its directions.  No byte of the record buffer beyond 24 K m is touched.
+ *  - Errors, TRT_ERR_INVALID_ARG before any device work: trt_probe's, in trt_probe's order; then, with n > 0, m == 0 (the message says
+ *    how many bytes one item needs); for the device form a NULL `d_records`, and a `d_sh` that overlaps the 24 K m bytes of the record
+ *    buffer.  Then TRT_ERR_NO_DEVICE, then TRT_ERR_OOM for the host form's buffers.  n == 0 succeeds and touches nothing.
+ * trt_probe_parallel: HOST buffers, synchronous, staged as trt_probe's.  The record buffer is the call's own, allocated with its staging
+ *   (24 K m bytes) and freed by it.  record_bytes == 0 means the library's default: 96 MiB - the records of 4 Mi samples, eight times
+ *   the 524 288 samples that fill the wave slots of a 256-CU device at the sample kernels' 8 waves per SIMD, so that a chunk's launch has a
+ *   tail of several rounds to even out - or one item's 24 K bytes where that is more.  Chosen by that reasoning, not swept.  kernel_ms
+ *   covers all launches of the call, from the first to the last.
+ * trt_probe_parallel_device: buffers in HBM, `d_records` the caller's scratch of record_bytes bytes; allocates nothing, and everything is
+ *   enqueued on `stream` in order. */
+int trt_probe_parallel(trt_scene *s, const trt_ray *items, uint32_t n, const trt_probe_params *p, float *sh, trt_stats *stats,
+                       uint64_t record_bytes);
+int trt_probe_parallel_device(trt_scene *s, const trt_ray *d_items, uint32_t n, const trt_probe_params *p, float *d_sh,
+                              uint64_t *d_counters, void *d_records, uint64_t record_bytes, void *stream);
+/* How trt_probe_parallel[_device] launches the sample kernels of ONE chunk of n items with a range of range_length = R samples: exactly
+ * trt_samples_launch_plan's answer for (n, R), errors included.  (The projection behind it is a lane per item, or a wave per item where
+ * R >= 64 and n <= 4096.) */
+int trt_probe_parallel_launch_plan(const trt_scene *s, uint32_t n, uint32_t range_length, uint32_t compute_units, trt_query_plan *out);
 
 /* ---- Sample-parallel next-event queries: every sample's colour of trt_nee / trt_nee_mis / trt_nee_pick / trt_nee_mis_pick ----
  * The four next-event queries trace K samples per item and return only their fold, a lane owning an item for all K.  trt_nee_samples

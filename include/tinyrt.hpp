@@ -236,6 +236,16 @@ public:
         sh.resize(items.size() * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);   // (bands out of range: trt_probe says so)
         check(trt_probe(get_bvh(), items.data(), (uint32_t)items.size(), &p, sh.data(), stats));
     }
+    // probe() with a launch that fills the device whatever K is (trt_probe_parallel): the same arguments, the same `sh` and the same
+    // samples and rays in `stats`, bit for bit.  The paths run a sample to a GPU lane into a record buffer of the call's own and
+    // project_samples' kernels fold the records, in chunks of min(n, record_bytes / (24 K)) items; record_bytes = 0 takes the
+    // library's default (96 MiB, or one item's 24 K bytes where that is more), a buffer that holds no item is an error.
+    void probe_parallel(const std::vector<trt_ray>& items, const trt_probe_params& p, std::vector<float>& sh, trt_stats* stats = nullptr,
+                        uint64_t record_bytes = 0) {
+        if (items.size() > 0xFFFFFFFFull) throw Error(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 items in one call");
+        sh.resize(items.size() * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);   // (bands out of range: trt_probe_parallel says so)
+        check(trt_probe_parallel(get_bvh(), items.data(), (uint32_t)items.size(), &p, sh.data(), stats, record_bytes));
+    }
     // Every sample's colour and, with `directions`, its first ray's stored direction (trt_samples): a sample to a GPU lane where radiance(),
     // gather() and probe() give the samples of an item one lane.  p.source says where the first ray comes from - TRT_SAMPLE_RAYS: the
     // items are rays; COSINE, CONE: gather()'s draw about surfels; SPHERE, HEMISPHERE: probe()'s - and p.path the samples, the range
@@ -320,6 +330,24 @@ inline void fold_samples(const std::vector<float>& colors, const trt_radiance_pa
     radiance.resize(n * 3);
     if (moment2) moment2->resize(n * 3);
     check(trt_fold_samples(colors.data(), (uint32_t)n, &p, radiance.data(), moment2 ? moment2->data() : nullptr));
+}
+
+// The probe fold of World::samples' colours and directions for the sources SPHERE and HEMISPHERE (trt_project_samples; runs on the
+// device, no scene needed): per item over samples [p.path.sample_begin, p.path.sample_end) of K = p.path.samples_per_ray in order,
+// sh[k] += c * (Y_k(d) / K) in f32 for the p.bands^2 real spherical harmonics.  A sample whose direction has a NaN adds nothing; with
+// `items` (the probes, one per item) neither does any sample of an item whose point has one - then `sh` is World::probe's, byte for
+// byte.  `sh` becomes n x p.bands^2 x 3 floats and continues the sums it holds when p.path.accumulate is set.  Of `p` only K, the
+// range, accumulate and bands are read.
+inline void project_samples(const std::vector<float>& colors, const std::vector<float>& directions, const trt_probe_params& p, std::vector<float>& sh,
+                            const std::vector<trt_ray>* items = nullptr) {
+    const size_t per_item = (size_t)p.path.samples_per_ray * 3;
+    if (per_item == 0 || colors.size() % per_item != 0 || directions.size() != colors.size())
+        throw Error(TRT_ERR_INVALID_ARG, "colors and directions hold n x samples_per_ray x 3 floats each");
+    const size_t n = colors.size() / per_item;
+    if (n > 0xFFFFFFFFull) throw Error(TRT_ERR_INVALID_ARG, "more than 2^32 - 1 items in one call");
+    if (items && items->size() != n) throw Error(TRT_ERR_INVALID_ARG, "items holds one probe per item");
+    sh.resize(n * (p.bands <= 3u ? (size_t)p.bands * p.bands : 0u) * 3);                  // (bands out of range: trt_project_samples says so)
+    check(trt_project_samples(colors.data(), directions.data(), items ? items->data() : nullptr, (uint32_t)n, &p, sh.data()));
 }
 
 

@@ -7,7 +7,7 @@ from . import bake, lights, passes, scenes, sh  # noqa: F401
 from ._lib import (BACKEND_AUTO, BACKEND_MEGAKERNEL, BACKEND_STREAMED, BACKEND_WAVEFRONT, DIELECTRIC, LAMBERTIAN, LIGHT, METAL, CameraPOD,  # noqa: F401
                    Hit, Material, Ray, RenderParams, SampledColor, SamplePoint, SceneOptions, Stats, TinyRTError, Tuning, Vec3, lib)
 from .api import (AOV_CHANNELS, HIT_DTYPE, Camera, Dielectric, Image, Lambertian, Light, Metal, Quad, Renderer, Scene, Sphere, World,  # noqa: F401
-                  denoise, denoise_color, denoise_device, denoise_params, denoise_scratch_bytes, fold_samples, fold_samples_device, sample_batch, scene_options, select_pixels, select_pixels_device, select_scratch_bytes, tonemap_u8_device, tuning, variance,
+                  denoise, denoise_color, denoise_device, denoise_params, denoise_scratch_bytes, fold_samples, fold_samples_device, project_samples, project_samples_device, sample_batch, scene_options, select_pixels, select_pixels_device, select_scratch_bytes, tonemap_u8_device, tuning, variance,
                   variance_device)
 
 _MATERIAL_CTORS = {LAMBERTIAN: lambda a, p: Lambertian(a), METAL: Metal, DIELECTRIC: Dielectric,

@@ -372,6 +372,12 @@ SIGNATURES = {
     "trt_samples_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_fold_samples": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p]),
     "trt_fold_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trt_project_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p]),
+    "trt_project_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p]),
+    "trt_probe_parallel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats), C.c_uint64]),
+    "trt_probe_parallel_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.c_void_p]),
+    "trt_probe_parallel_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(QueryPlan)]),
     "trt_nee_samples_params_default": (None, [C.POINTER(NeeSamplesParams)]),
     "trt_nee_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(NeeSamplesParams), C.c_void_p,
                                   C.c_void_p, C.POINTER(Stats)]),

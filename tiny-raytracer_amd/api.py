@@ -536,6 +536,41 @@ class Scene:
         check(lib.trt_probe_launch_plan(self._h, int(n), int(bands), int(compute_units), C.byref(plan)))
         return plan.as_dict()
 
+    def probe_parallel(self, items, samples_per_item, bands=3, domain="sphere", max_bounces=50, background=(0.0, 0.0, 0.0), seed=1,
+                       first_stream=0, sample_begin=0, sample_end=None, accumulate=False, sh=None, record_bytes=0):
+        """trt_probe_parallel: probe()'s arguments and probe()'s results, bit for bit, from a launch that fills the device whatever K is -
+        the paths run a sample to a lane into a record buffer of the call's own and project_samples() folds the records, in chunks of
+        min(n, record_bytes // (24 K)) items.  record_bytes = 0: the library's default (96 MiB, or one item's 24 K bytes where that is
+        more); a buffer that holds no item is refused.  Returns (sh[n, C, 3], stats with samples and rays)."""
+        r, _ = _rays_and_t_max(items, None)
+        n = len(r)
+        p = self._probe_params(samples_per_item, bands, domain, max_bounces=max_bounces, background=background, seed=seed, first_stream=first_stream,
+                               sample_begin=sample_begin, sample_end=sample_end, accumulate=accumulate)
+        coeffs = int(bands) ** 2
+        if sh is None:
+            sh = np.zeros((n, coeffs, 3), np.float32)
+        assert sh.dtype == np.float32 and sh.flags.c_contiguous and sh.shape == (n, coeffs, 3)
+        st = Stats()
+        check(lib.trt_probe_parallel(self._h, r.ctypes.data if n else None, n, C.byref(p), sh.ctypes.data if n else None, C.byref(st),
+                                     int(record_bytes)))
+        return sh, st.as_dict()
+
+    def probe_parallel_device(self, d_items_ptr, n, d_sh_ptr, d_records_ptr, record_bytes, d_counters_ptr=0, stream_ptr=0, **params):
+        """Enqueue probe_parallel() on buffers already in HBM (device pointers as integers: n x 24 bytes of items, n x bands ** 2 x 12
+        bytes of sums, record_bytes bytes of scratch for the records, which the sums must not overlap) on the current device;
+        asynchronous on the stream, allocates nothing.  `params`: probe()'s keywords, samples_per_item included."""
+        p = self._probe_params(**params)
+        check(lib.trt_probe_parallel_device(self._h, C.c_void_p(d_items_ptr), int(n), C.byref(p), C.c_void_p(d_sh_ptr), C.c_void_p(d_counters_ptr),
+                                            C.c_void_p(d_records_ptr), int(record_bytes), C.c_void_p(stream_ptr)))
+
+    def probe_parallel_plan(self, n, range_length=None, compute_units=0):
+        """trt_probe_parallel_launch_plan: how probe_parallel() launches the sample kernels of one chunk of n items with range_length
+        samples each (None: 1) on this scene - samples_plan()'s answer."""
+        plan = _lib.QueryPlan()
+        check(lib.trt_probe_parallel_launch_plan(self._h, int(n), 1 if range_length is None else int(range_length), int(compute_units),
+                                                 C.byref(plan)))
+        return plan.as_dict()
+
     # ---- sample queries (tinyrt.h trt_samples): every sample's colour and first direction, a sample to a lane ----
     SAMPLE_SOURCES = {"rays": _lib.SAMPLE_RAYS, "cosine": _lib.SAMPLE_COSINE, "cone": _lib.SAMPLE_CONE, "sphere": _lib.SAMPLE_SPHERE,
                       "hemisphere": _lib.SAMPLE_HEMISPHERE}
@@ -1167,6 +1202,48 @@ def fold_samples_device(d_colors_ptr, n, samples_per_item, d_radiance_ptr, d_mom
     p = _fold_params(samples_per_item, sample_begin, sample_end, accumulate)
     check(lib.trt_fold_samples_device(C.c_void_p(d_colors_ptr), int(n), C.byref(p), C.c_void_p(d_radiance_ptr), C.c_void_p(d_moment2_ptr),
                                       C.c_void_p(stream_ptr)))
+
+
+def _project_params(samples_per_item, bands=3, sample_begin=0, sample_end=0, accumulate=False):
+    p = _lib.ProbeParams()
+    lib.trt_probe_params_default(C.byref(p))
+    p.path = _fold_params(samples_per_item, sample_begin, sample_end, accumulate)
+    p.bands = int(bands)
+    return p
+
+
+def project_samples(colors, directions, bands=3, sample_begin=0, sample_end=0, sh=None, accumulate=False, items=None):
+    """trt_project_samples: Scene.samples()'s colours and directions float32 [n, K, 3] of source "sphere" or "hemisphere" folded per item
+    over samples [sample_begin, sample_end) (0: K) in order against the bands ** 2 = C real spherical harmonics of tiny-raytracer_amd.sh,
+    sh[k] += c * (Y_k(d) / K) in f32 - with `items` float32 [n, 6] (the probes; a sample of an item whose point has a NaN adds nothing,
+    as one whose direction has) the bytes Scene.probe() returns.  `sh`: float32 [n, C, 3] to write or, with accumulate, to continue
+    (changed in place); None allocates one.  Runs on the device; there is no CPU path (sh.project() is the numpy restatement).  Returns
+    sh[n, C, 3]."""
+    c, d = np.ascontiguousarray(colors, np.float32), np.ascontiguousarray(directions, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3 or d.shape != c.shape:
+        raise ValueError("colors and directions must have the same shape [n, K, 3]")
+    n, k = c.shape[0], c.shape[1]
+    coeffs = int(bands) ** 2
+    if sh is None:
+        sh = np.zeros((n, coeffs, 3), np.float32)
+    assert sh.dtype == np.float32 and sh.flags.c_contiguous and sh.shape == (n, coeffs, 3)
+    if items is not None:
+        items = np.ascontiguousarray(items, np.float32)
+        assert items.shape == (n, 6)
+    p = _project_params(k, bands, sample_begin, sample_end, accumulate)
+    check(lib.trt_project_samples(c.ctypes.data if n else None, d.ctypes.data if n else None, items.ctypes.data if items is not None and n else None,
+                                  n, C.byref(p), sh.ctypes.data if n else None))
+    return sh
+
+
+def project_samples_device(d_colors_ptr, d_directions_ptr, n, samples_per_item, d_sh_ptr, bands=3, sample_begin=0, sample_end=0, accumulate=False,
+                           d_items_ptr=0, stream_ptr=0):
+    """Enqueue project_samples() on buffers already in HBM (device pointers as integers: n x K x 12 bytes of colours and of directions,
+    n x bands ** 2 x 12 bytes of sums, which must overlap neither; n x 24 bytes of items or 0); asynchronous on the stream, allocates
+    nothing.  accumulate continues the sums."""
+    p = _project_params(samples_per_item, bands, sample_begin, sample_end, accumulate)
+    check(lib.trt_project_samples_device(C.c_void_p(d_colors_ptr), C.c_void_p(d_directions_ptr), C.c_void_p(d_items_ptr), int(n), C.byref(p),
+                                         C.c_void_p(d_sh_ptr), C.c_void_p(stream_ptr)))
 
 
 def select_pixels(accum, moment2, samples_per_pixel, samples_done, rel_tol, abs_tol=0.0, candidates=None):

@@ -19,9 +19,11 @@
 #include "gather_draw.h"
 #include "host_stage.h"
 #include "kernels.h"
+#include "probe_call.h"
 #include "query_plan.h"
 #include "rt_path.h"
 #include "scene_query.h"
+#include "sh_basis.h"
 #include "wave_run.h"
 
 namespace trt {
@@ -41,24 +43,12 @@ struct ProbeArgs {
     uint32_t coeffs;                 // coefficients stored per item, bands^2: 1, 4 or 9, at most the kernel's NC
 };
 
-// The fold of one sample (tinyrt.h): the real SH basis in the graphics convention at d, each product and sum one f32 operation in the
-// header's parenthesisation.  NC = 4 evaluates bands 0 and 1 only.
+// The fold of one sample (tinyrt.h): the real SH basis in the graphics convention at d (sh_basis.h, the one copy), each product and sum
+// one f32 operation in the header's parenthesisation.  NC = 4 evaluates bands 0 and 1 only.
 template <int NC>
 TRT_DEV void probe_fold(float (&acc)[3 * NC], const V3& d, const V3& c, float inv_k) {
-    const float c0 = 0.282094792f, c1 = 0.488602512f, c2 = 1.092548431f, c3 = 0.315391565f, c4 = 0.546274215f;
-    const float x = d.x, y = d.y, z = d.z;
     float b[NC];
-    b[0] = c0;
-    b[1] = c1 * y;
-    b[2] = c1 * z;
-    b[3] = c1 * x;
-    if constexpr (NC > 4) {
-        b[4] = c2 * (x * y);
-        b[5] = c2 * (y * z);
-        b[6] = c3 * ((3.0f * (z * z)) - 1.0f);
-        b[7] = c2 * (x * z);
-        b[8] = c4 * ((x * x) - (y * y));
-    }
+    sh_basis<NC>(b, d);
 #pragma unroll
     for (int k = 0; k < NC; k++) {
         const float t = b[k] * inv_k;
@@ -209,15 +199,6 @@ constexpr size_t kProbeShapes = sizeof(kProbeKernels9) / sizeof(kProbeKernels9[0
 static_assert(sizeof(kProbeKernels4) == sizeof(kProbeKernels9), "one instantiation per shape and coefficient count");
 const BatchKernel* probe_table(uint32_t bands) { return bands == 3u ? kProbeKernels9 : kProbeKernels4; }
 
-// What a call asks of the device, after the checks.
-struct ProbeCall {
-    RenderArgs ra;                   // of the path parameters (radiance_check)
-    uint32_t samples_per_item, first_stream;
-    uint32_t hemisphere, bands;
-    uint32_t coeffs() const { return bands * bands; }
-    bool nothing() const { return ra.sample_begin == ra.sample_end || ra.max_bounces == 0u; }
-};
-
 hipError_t launch_probe(const QueryScene& qs, const ProbeCall& c, const float* d_items, uint32_t n, float* d_sh, unsigned long long* d_counters,
                         hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -238,7 +219,10 @@ hipError_t launch_probe(const QueryScene& qs, const ProbeCall& c, const float* d
     return batch_launch(b, args, stream);
 }
 
-// What both forms check before any device work: trt_radiance's rules on p->path (radiance.hip radiance_check), then this struct's fields.
+}  // namespace
+
+// What both forms check before any device work (probe_call.h: project.hip's trt_probe_parallel applies the same): trt_radiance's rules
+// on p->path (radiance.hip radiance_check), then this struct's fields.
 int probe_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_probe_params* p, const float* sh, ProbeCall& c) {
     if (!p) return query_fail(TRT_ERR_INVALID_ARG, "null argument");
     const int rc = radiance_check(s, items, n, &p->path, sh, c.ra);
@@ -255,7 +239,6 @@ int probe_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_
     return TRT_OK;
 }
 
-}  // namespace
 }  // namespace trt
 
 extern "C" {

@@ -29,6 +29,7 @@
 #include "query_plan.h"
 #include "rt_path.h"
 #include "sample_index.h"
+#include "samples_call.h"
 #include "scene_query.h"
 #include "wave_run.h"
 
@@ -290,15 +291,9 @@ const BatchKernel kSamplesKernels[] = {
 #undef TRT_SAMPLES
 constexpr size_t kSamplesShapes = sizeof(kSamplesKernels) / sizeof(kSamplesKernels[0]);
 
-// What a call asks of the device, after the checks.
-struct SamplesCall {
-    RenderArgs ra;                   // of the path parameters (radiance_check)
-    uint32_t samples_per_item, first_stream;
-    uint32_t source;
-    float spread;
-    uint32_t range() const { return ra.sample_end - ra.sample_begin; }
-};
+}  // namespace
 
+// The launch of a call after the checks (samples_call.h: project.hip's trt_probe_parallel launches its chunks through it).
 hipError_t launch_samples(const QueryScene& qs, const SamplesCall& c, const float* d_items, uint32_t n, float* d_colors, float* d_directions,
                           unsigned long long* d_counters, hipStream_t stream) {
     const uint32_t R = c.range();
@@ -321,6 +316,8 @@ hipError_t launch_samples(const QueryScene& qs, const SamplesCall& c, const floa
     void* args[] = {&scd, &ra, &ga, &b.leaf_list, &b.nodes16};
     return batch_launch(b, args, stream);
 }
+
+namespace {
 
 // What both forms check before any device work: trt_radiance's rules on p->path (radiance.hip radiance_check), then this struct's fields.
 int samples_check(const trt_scene* s, const trt_ray* items, uint32_t n, const trt_samples_params* p, const float* colors, SamplesCall& c) {
@@ -378,11 +375,6 @@ hipError_t launch_fold(const FoldCall& c, const float* d_colors, uint32_t n, flo
     if (fold_by_wave(n, R)) hipLaunchKernelGGL(fold_wave_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, fa);
     else hipLaunchKernelGGL(fold_tile_kernel, dim3((uint32_t)(((unsigned long long)n + 255ull) / 256ull)), dim3(256), 0, stream, fa);
     return hipGetLastError();
-}
-
-bool ranges_overlap(const void* a, unsigned long long a_bytes, const void* b, unsigned long long b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 }  // namespace
